@@ -13,14 +13,14 @@ runs between two towers (step = tower + scan; measured) (mi_pipel
 The query runs as the two-stage EXACT search (a byte mirror of the rows prefilters, the fp32
 rows decide: ids and distance bits of the single pass; --prefilter 1 = the bf16
 mirror, --no-prefilter = one pass over the fp32 rows, which is also what `roofline_knn` times);
-the run itself checks that both modes return the same ids and distance bits (`two_stage_equal`).
+with --full the run checks that both modes return the same ids and distance bits (`two_stage_equal`).
 
 N > 1 (BASELINE config 5, one process per GPU): every rank embeds its own batch (replicas, no
 collective) and owns its own 10M-row shard of an N x 10M table; each query's per-shard top-k
 (12 k bytes) stays on the device, is all-gathered over RCCL in one collective and merged
 identically on every rank (image_search_amd.search.ShardExchange) — weak scaling.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher starts its own N ranks (a child
@@ -28,8 +28,15 @@ identically on every rank (image_search_amd.search.ShardExchange) — weak scali
 When the box has fewer GPUs than ranks (a rehearsal) the ranks share GPU 0 and exchange over gloo.
 
 Rank 0 prints ONE JSON line.  `value` is whole-job images/s over the timed region
-(ViT + query); the per-phase rates (HIP events on the launch stream) are under
-"vit" and "knn", each with the roofline of its dominant kernel.
+(ViT + query), `ms_per_step` the time of one timed step; "vit" is the forward's time inside
+the timed region (HIP events on the ingest stream).  A plain run does only that: set-up,
+warm-up, the timed steps.  --full adds everything else, each behind the timed steps: the same
+steps with the single-pass query, the kNN kernel alone and the two-stage check ("knn"),
+the rooflines, other BASELINE configs, the one-process sharded probe, the CPU baseline and,
+with N > 1, the check that every rank merged the same lists.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0): the k ids (float64)
+and distances of its query and the embeddings of its batch, as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -72,8 +79,11 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--rows", type=int, default=10_000_000, help="table rows per GPU")
     ap.add_argument("--k", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="skip the BASELINE config 1 / 2 sub-lines")
+    ap.add_argument("--full", action="store_true", help="behind the timed steps, also measure and check everything beyond the "
+                    "headline figure (single-pass query, kNN kernel alone, rooflines, other configs, sharded probe, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra-configs", action="store_true", help="with --full: skip the BASELINE config 1 / 2 sub-lines")
     ap.add_argument("--front-overlap", type=int, default=None, choices=(0, 1), help="A/B: option front_overlap of the model (the next forward's "
                     "patch gather + patch GEMM on the copy stream, under the current forward)")
     ap.add_argument("--serial", action="store_true", help="A/B: synchronise after every step (no cross-step overlap)")
@@ -85,7 +95,10 @@ def parse_args(argv=None):
                     "mi_pipeline_create_sharded — as a child of the N = 1 run; prints one JSON object")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: launch, rendezvous, the exchange + merge over fake per-rank lists "
                                                           "(what the CPU test of the self-launch path runs)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args) -> int:
@@ -157,7 +170,7 @@ def gemm_in_situ(batch):
         return dict(head, refused="no gemm_bf16_pp_kernel<6> rows in the profile")
     per_forward_ms = ns / forwards / 1e6
     flop = batch * 257 * 2.0 * (3 * 1024 * 1024 + 1024 * 1024 + 2 * 4096 * 1024) * 23   # the 23 full layers the kernel runs
-    return dict(head, command="MI_CLIP_PARTS=1 rocprofv3 --kernel-trace --stats -- python3 bench.py (tools/round_profile.sh)",
+    return dict(head, command="MI_CLIP_PARTS=1 rocprofv3 --kernel-trace --stats -- python3 bench.py --full (tools/round_profile.sh)",
                 gemm_ms_per_forward=round(per_forward_ms, 3), forwards_in_profile=round(forwards, 1),
                 TFLOP_per_s=round(flop / (per_forward_ms * 1e-3) / 1e12, 1),
                 frac=round(flop / (per_forward_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
@@ -542,7 +555,7 @@ def main():
     pipe = Pipeline(model, table)
     lag = 0 if args.serial else 1           # results of query i are consumed while query i+1 scans
     ex = ShardExchange(args.k, depth=4) if world > 1 else None
-    merged, pending = [], []
+    merged, pending, last = [], [], {}
 
     def consume(leave):
         """host side of the exchange, `leave` queries behind the scan"""
@@ -564,7 +577,8 @@ def main():
         if ex is not None and ex.on_device:
             ex.query(pipe, queries[i % n_q])
         else:
-            pending.append(pipe.query(queries[i % n_q], args.k))
+            last["query"] = pipe.query(queries[i % n_q], args.k)   # filled in by the sync that delivers it
+            pending.append(last["query"])
         if args.serial:
             pipe.sync()
         consume(lag)
@@ -599,10 +613,20 @@ def main():
     elapsed = timed(args.warmup, args.steps)
     n_f, ms_f, n_s, ms_s = pipe.stats()
     n_merged = len(merged)
+    if args.dump_outputs and rank == 0:
+        # the last timed step: its query's k results (N > 1: the merged lists every rank receives) and its batch's rows
+        last_ids, last_dist = merged[-1] if world > 1 else last["query"]
+        emb = table.rows(len(table) - args.batch, args.batch)
+        if emb.nbytes > 48 << 20:   # the dump stays under 64 MB: a fixed, seeded sample of the rows
+            emb = emb[np.sort(np.random.default_rng(0).choice(args.batch, (48 << 20) // emb[0].nbytes, replace=False))]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("knn_ids", last_ids.astype(np.float64)), ("knn_distances", last_dist.astype(np.float32)),
+                        ("embeddings", emb)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     # The same steps once more with the query as ONE pass over the fp32 rows (the kernel that carries the kNN roofline
     # credit): `value_single_pass_query`.  Behind the headline loop, never inside it; the table was reserved for these rows too.
     elapsed_single = None
-    if not args.no_prefilter:
+    if args.full and not args.no_prefilter:
         table.set_option("prefilter", 0)
         step(total_steps)
         finish()
@@ -612,7 +636,7 @@ def main():
     ms_vit = ms_f / max(n_f, 1)          # HIP events on the ingest stream around each forward, timed region only
     ms_knn_overlapped = ms_s / max(n_s, 1)
     exchange_check = None
-    if world > 1:
+    if args.full and world > 1:
         # every rank must hold the same merged lists, each sorted and made of ids of all shards' ranges
         mine = np.stack([np.concatenate([m[0].view(np.uint8), m[1].view(np.uint8)]) for m in merged]) if merged else np.zeros((0, 1), np.uint8)
         g = [None] * world
@@ -625,7 +649,7 @@ def main():
 
     extra = {}
     two_stage_equal = None
-    if rank == 0:
+    if args.full and rank == 0:
         # ---- the kNN kernel by itself (same table): HIP events on the launch stream --------------
         stream = torch.cuda.Stream()
         d_q = torch.from_numpy(queries).cuda()
@@ -662,7 +686,7 @@ def main():
                 log("[bench] the two-stage search and the single pass DISAGREE on the timed queries")
     pipe.close()
 
-    if rank == 0 and world == 1 and not args.no_extra_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_extra_configs:
         # BASELINE config 3 (1 M rows; k = 10 and the reference's k = 1000) and config 2 (fp32 b = 32)
         rows_total = len(table)
         t1m = EmbeddingTable(768, local)
@@ -769,21 +793,12 @@ def main():
     failed = False
     if rank == 0:
         imgs = world * args.batch * args.steps
-        executed = VIT_FLOP_PER_IMAGE - VIT_FLOP_SKIPPED_PER_IMAGE
-        tf_exec = args.batch * executed / (ms_vit * 1e-3) / 1e12
-        tf_alg = args.batch * VIT_FLOP_PER_IMAGE / (ms_vit * 1e-3) / 1e12
-        knn_gbs = len(table) * 768 * 4 / (ms_knn * 1e-3) / 1e9
-        pmc, pmc_refused = pmc_traffic(args)
-        traffic_ok = pmc is not None
-        pmc = pmc or {}
         out = {
             "metric": METRIC,
             "value": round(imgs / elapsed, 2),
             "unit": "images/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "value_single_pass_query": round(imgs / elapsed_single, 2) if elapsed_single else None,
-            "ms_per_step_single_pass_query": round(elapsed_single / args.steps * 1e3, 3) if elapsed_single else None,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "bf16", "data": "synthetic",
             "config": {"workload": f"BASELINE config 4: per step, H2D of a pinned batch of {args.batch} 224x224x3 f32 images -> bf16 ViT-L/14 "
@@ -804,61 +819,73 @@ def main():
                        "backend": backend if world > 1 else None, "ranks_share_one_gpu": bool(shared_gpu)},
             "vit": {"images_per_sec": round(world * args.batch / (ms_vit * 1e-3), 1), "ms_per_batch": round(ms_vit, 3),
                     "note": "HIP events on the ingest stream around each forward of the timed region (one forward at a time on the ingest stream)"},
-            "knn": {"queries_per_sec": round(1e3 / (ms_knn_two or ms_knn), 2), "ms_per_query": round(ms_knn_two or ms_knn, 4),
-                    "ms_per_query_in_the_pipeline": round(ms_knn_overlapped, 4),
-                    "ms_per_query_single_pass": round(ms_knn, 4),
-                    "mode": "single pass over the fp32 rows" if args.no_prefilter else
-                            f"two-stage exact ({'byte' if args.prefilter == 2 else 'bf16'} mirror prefilter + fp32 re-evaluation)",
-                    "two_stage_equal": two_stage_equal, "fell_back": bool(pref_fell_back),
-                    "rows_searched_per_sec": round(world * len(table) / ((ms_knn_two or ms_knn) * 1e-3), 0), "dtype": "f32"},
-            "roofline": {"bound": "mfma", "kernel": "ViT-L/14 forward (gemm_bf16_pp_kernel x 96 with the LayerNorms and residual adds in its epilogues + "
-                                                    "attention, two half-chunk streams)",
-                         "achieved": round(tf_exec, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(tf_exec / PEAK_BF16_TFLOPS, 4),
-                         "traffic": pmc.get("vit_hbm_bytes") if traffic_ok else None,
-                         "traffic_source": "profiles/pmc_latest.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command "
-                                           "(tools/round_profile.sh), NOT an observation of this run; fabric-side bytes incl. Infinity-Cache hits"
-                                           + ("" if traffic_ok else f"; REFUSED: {pmc_refused}"),
-                         "from_profile": {"note": "read from committed profiles, not observed by this run; each entry is refused (no numbers) "
-                                                  "when its stamp does not match the kernel sources and batch of this run",
-                                          "gemm_in_situ": gemm_in_situ(args.batch)},
-                         "executed_gflop_per_image": round(executed / 1e9, 2),
-                         "algorithmic_gflop_per_image": round(VIT_FLOP_PER_IMAGE / 1e9, 2),
-                         "frac_on_algorithmic_flops": round(tf_alg / PEAK_BF16_TFLOPS, 4),
-                         "note": "achieved/frac count the FLOPs this implementation EXECUTES (the last layer runs on the CLS rows only: "
-                                 "3.5 % of the algorithmic 162.03 GFLOP/image are dead rows of the reference graph, output bit-identical); "
-                                 "the algorithmic-count fraction is beside it"},
-            "roofline_knn": {"bound": "hbm", "kernel": "knn_scan_kernel<12,WaveTopReg> (+2 merge launches), alone on the chip",
-                             "achieved": round(knn_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                             "frac": round(knn_gbs / PEAK_HBM_GBS, 4),
-                             "traffic": pmc.get("knn_scan_hbm_bytes") if traffic_ok else None,
-                             "traffic_source": "profiles/pmc_latest.json (separate --pmc passes of this command, not this run)",
-                             "note": "the single-pass scan over the fp32 rows: algorithmic bytes = rows x 768 x 4"},
         }
-        if ms_knn_two:
-            row_bytes = 768 + 12 if args.prefilter == 2 else 768 * 2 + 4      # mirror row + its per-row floats
-            two_bytes = len(table) * (row_bytes + 4 * 5 + (4 if args.prefilter == 2 else 0))  # + the coarse keys written once and read four times (+ the bound factors in the collect)
-            out["roofline_knn"]["two_stage"] = {
-                "ms_per_query": round(ms_knn_two, 4), "bytes_read_and_written": two_bytes,
-                "GB_per_s_of_those_bytes": round(two_bytes / (ms_knn_two * 1e-3) / 1e9, 1),
-                "frac_of_hbm_peak_on_those_bytes": round(two_bytes / (ms_knn_two * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
-                "speedup_over_single_pass": round(ms_knn / ms_knn_two, 3),
-                "rows_re_evaluated_last_query": pref_cand, "fell_back_to_single_pass": pref_fell_back,
-                "equal_to_single_pass": two_stage_equal,
-                "traffic_stage1": pmc.get("knn_two_stage_stage1_hbm_bytes") if traffic_ok and args.prefilter == 2 else None}
-        if exchange_check is not None:
-            out["exchange"] = exchange_check
-            failed = failed or not (exchange_check["identical_on_every_rank"] and exchange_check["sorted"]
-                                    and exchange_check["queries_merged"] == args.steps)
-        if extra:
-            out["other_configs"] = extra
-        if world == 1 and not args.no_extra_configs:
-            # the ONE-process form (mi_knn_sharded + mi_pipeline_create_sharded) over every GPU this process can see, as a
-            # child with its own deadline; on a one-GPU box: two shards and two replicas on GPU 0
-            out.setdefault("other_configs", {})["one_process_sharded"] = run_sharded_probe(args, wpath, ms_knn_two or ms_knn)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(weights, cfg)
-        failed = failed or two_stage_equal is False
+        if args.full:
+            executed = VIT_FLOP_PER_IMAGE - VIT_FLOP_SKIPPED_PER_IMAGE
+            tf_exec = args.batch * executed / (ms_vit * 1e-3) / 1e12
+            tf_alg = args.batch * VIT_FLOP_PER_IMAGE / (ms_vit * 1e-3) / 1e12
+            knn_gbs = len(table) * 768 * 4 / (ms_knn * 1e-3) / 1e9
+            pmc, pmc_refused = pmc_traffic(args)
+            traffic_ok = pmc is not None
+            pmc = pmc or {}
+            out.update({
+                "value_single_pass_query": round(imgs / elapsed_single, 2) if elapsed_single else None,
+                "ms_per_step_single_pass_query": round(elapsed_single / args.steps * 1e3, 3) if elapsed_single else None,
+                "knn": {"queries_per_sec": round(1e3 / (ms_knn_two or ms_knn), 2), "ms_per_query": round(ms_knn_two or ms_knn, 4),
+                        "ms_per_query_in_the_pipeline": round(ms_knn_overlapped, 4),
+                        "ms_per_query_single_pass": round(ms_knn, 4),
+                        "mode": "single pass over the fp32 rows" if args.no_prefilter else
+                                f"two-stage exact ({'byte' if args.prefilter == 2 else 'bf16'} mirror prefilter + fp32 re-evaluation)",
+                        "two_stage_equal": two_stage_equal, "fell_back": bool(pref_fell_back),
+                        "rows_searched_per_sec": round(world * len(table) / ((ms_knn_two or ms_knn) * 1e-3), 0), "dtype": "f32"},
+                "roofline": {"bound": "mfma", "kernel": "ViT-L/14 forward (gemm_bf16_pp_kernel x 96 with the LayerNorms and residual adds in its epilogues + "
+                                                        "attention, two half-chunk streams)",
+                             "achieved": round(tf_exec, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                             "frac": round(tf_exec / PEAK_BF16_TFLOPS, 4),
+                             "traffic": pmc.get("vit_hbm_bytes") if traffic_ok else None,
+                             "traffic_source": "profiles/pmc_latest.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command "
+                                               "(tools/round_profile.sh), NOT an observation of this run; fabric-side bytes incl. Infinity-Cache hits"
+                                               + ("" if traffic_ok else f"; REFUSED: {pmc_refused}"),
+                             "from_profile": {"note": "read from committed profiles, not observed by this run; each entry is refused (no numbers) "
+                                                      "when its stamp does not match the kernel sources and batch of this run",
+                                              "gemm_in_situ": gemm_in_situ(args.batch)},
+                             "executed_gflop_per_image": round(executed / 1e9, 2),
+                             "algorithmic_gflop_per_image": round(VIT_FLOP_PER_IMAGE / 1e9, 2),
+                             "frac_on_algorithmic_flops": round(tf_alg / PEAK_BF16_TFLOPS, 4),
+                             "note": "achieved/frac count the FLOPs this implementation EXECUTES (the last layer runs on the CLS rows only: "
+                                     "3.5 % of the algorithmic 162.03 GFLOP/image are dead rows of the reference graph, output bit-identical); "
+                                     "the algorithmic-count fraction is beside it"},
+                "roofline_knn": {"bound": "hbm", "kernel": "knn_scan_kernel<12,WaveTopReg> (+2 merge launches), alone on the chip",
+                                 "achieved": round(knn_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                 "frac": round(knn_gbs / PEAK_HBM_GBS, 4),
+                                 "traffic": pmc.get("knn_scan_hbm_bytes") if traffic_ok else None,
+                                 "traffic_source": "profiles/pmc_latest.json (separate --pmc passes of this command, not this run)",
+                                 "note": "the single-pass scan over the fp32 rows: algorithmic bytes = rows x 768 x 4"},
+            })
+            if ms_knn_two:
+                row_bytes = 768 + 12 if args.prefilter == 2 else 768 * 2 + 4      # mirror row + its per-row floats
+                two_bytes = len(table) * (row_bytes + 4 * 5 + (4 if args.prefilter == 2 else 0))  # + the coarse keys written once and read four times (+ the bound factors in the collect)
+                out["roofline_knn"]["two_stage"] = {
+                    "ms_per_query": round(ms_knn_two, 4), "bytes_read_and_written": two_bytes,
+                    "GB_per_s_of_those_bytes": round(two_bytes / (ms_knn_two * 1e-3) / 1e9, 1),
+                    "frac_of_hbm_peak_on_those_bytes": round(two_bytes / (ms_knn_two * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+                    "speedup_over_single_pass": round(ms_knn / ms_knn_two, 3),
+                    "rows_re_evaluated_last_query": pref_cand, "fell_back_to_single_pass": pref_fell_back,
+                    "equal_to_single_pass": two_stage_equal,
+                    "traffic_stage1": pmc.get("knn_two_stage_stage1_hbm_bytes") if traffic_ok and args.prefilter == 2 else None}
+            if exchange_check is not None:
+                out["exchange"] = exchange_check
+                failed = failed or not (exchange_check["identical_on_every_rank"] and exchange_check["sorted"]
+                                        and exchange_check["queries_merged"] == args.steps)
+            if extra:
+                out["other_configs"] = extra
+            if world == 1 and not args.no_extra_configs:
+                # the ONE-process form (mi_knn_sharded + mi_pipeline_create_sharded) over every GPU this process can see, as a
+                # child with its own deadline; on a one-GPU box: two shards and two replicas on GPU 0
+                out.setdefault("other_configs", {})["one_process_sharded"] = run_sharded_probe(args, wpath, ms_knn_two or ms_knn)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(weights, cfg)
+            failed = failed or two_stage_equal is False
         print(json.dumps(out), flush=True)
 
     model.close()

@@ -1,9 +1,9 @@
 """Builds profiles/pmc_latest.json (what bench.py reports as roofline.traffic) from two rocprofv3
-counter passes of the default bench, collected separately as the guide prescribes:
+counter passes of the full bench, collected separately as the guide prescribes:
 
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace -d gpurun_out/pmc_f -o f --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace -d gpurun_out/pmc_w -o w --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-  python tools/pmc_collect.py gpurun_out/pmc_f gpurun_out/pmc_w
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace -d DIR_F -o f --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace -d DIR_W -o w --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+  python tools/pmc_collect.py DIR_F DIR_W
 
 gfx950 corrections: FETCH_SIZE counts 64 B per 128-B request (x2); both counters are in KiB (x1024)."""
 import collections, csv, glob, json, os, sys
@@ -38,7 +38,7 @@ vit = [k for k in pk if "mi::" in k and "knn" not in k and "gen_f32" not in k]
 forwards = next(v["launches"] for k, v in pk.items() if "head_kernel" in k) / 2  # two half-chunk streams per forward
 vit_bytes = sum(pk[k]["launches"] * (pk[k]["fetch_bytes_per_launch_x2"] + (pk[k]["write_bytes_per_launch"] or 0)) for k in vit) / forwards
 out = {
-    "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline (two passes)",
+    "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline (two passes)",
     "correction": "FETCH_SIZE x2 (gfx950 counts 64 B per 128-B request), x1024 B; WRITE_SIZE x1024 B",
     "rows": 10000000, "batch": 256,
     "knn_scan_hbm_bytes": scan["fetch_bytes_per_launch_x2"] + (scan["write_bytes_per_launch"] or 0),

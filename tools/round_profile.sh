@@ -14,12 +14,12 @@ step() {  # name, seconds, command...
 }
 step pytest 900 bash -c "python -m pytest tests -q -m gpu -x > $OUT/pytest.log 2>&1; tail -3 $OUT/pytest.log"
 step text 120 bash -c "python tools/text_check.py > $OUT/text_check.txt 2>&1; tail -7 $OUT/text_check.txt"
-step bench 400 bash -c "python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.json"
+step bench 400 bash -c "python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.json"
 [ "${2:-}" = quick ] && exit 0
-step prof2 300 bash -c "rocprofv3 --kernel-trace --stats -d $OUT/prof2 -o b --output-format csv -- python3 bench.py --no-cpu-baseline --no-extra-configs > $OUT/prof2.log 2>&1; python tools/prof_stats.py $OUT/prof2 12"
-step prof1 300 bash -c "MI_CLIP_PARTS=1 rocprofv3 --kernel-trace --stats -d $OUT/prof1 -o b --output-format csv -- python3 bench.py --no-cpu-baseline --no-extra-configs > $OUT/prof1.log 2>&1; python tools/prof_stats.py $OUT/prof1 12"
-step pmcf 300 bash -c "rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_f -o f --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $OUT/pmcf.log 2>&1"
-step pmcw 300 bash -c "rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_w -o w --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $OUT/pmcw.log 2>&1"
+step prof2 300 bash -c "rocprofv3 --kernel-trace --stats -d $OUT/prof2 -o b --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-extra-configs > $OUT/prof2.log 2>&1; python tools/prof_stats.py $OUT/prof2 12"
+step prof1 300 bash -c "MI_CLIP_PARTS=1 rocprofv3 --kernel-trace --stats -d $OUT/prof1 -o b --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-extra-configs > $OUT/prof1.log 2>&1; python tools/prof_stats.py $OUT/prof1 12"
+step pmcf 300 bash -c "rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_f -o f --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $OUT/pmcf.log 2>&1"
+step pmcw 300 bash -c "rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_w -o w --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $OUT/pmcw.log 2>&1"
 step pmc 60 bash -c "python tools/pmc_collect.py $OUT/pmc_f $OUT/pmc_w > $OUT/pmc.json 2>&1; cp profiles/pmc_latest.json $OUT/pmc_latest.json; head -20 $OUT/pmc.json"
 step textprof 200 bash -c "rocprofv3 --kernel-trace --stats -d $OUT/proft -o t --output-format csv -- python3 tools/text_profile.py > $OUT/proft.log 2>&1; python tools/prof_stats.py $OUT/proft 12"
 # what goes into profiles/ (cp gpurun_out/$R/commit/* profiles/), stamped HERE with the fingerprint of the sources that were measured
