@@ -34,7 +34,10 @@ inline uint16_t f32_to_bf16_host(float f) {  // round to nearest even, NaN stays
 
 namespace {
 
-size_t esize(const mi_clip* m) { return m->precision == MI_PRECISION_F32 ? 4 : 2; }
+bool is_x3(const mi_clip* m) { return m->precision == MI_PRECISION_BF16X3; }
+// bytes per activation element; MI_PRECISION_BF16X3 keeps fp32 rows (residual, q|k|v, patch embedding) or hi | lo bf16
+// pairs (LayerNorm outputs, attention context, fc1 output): 4 bytes per logical element either way
+size_t esize(const mi_clip* m) { return m->precision == MI_PRECISION_F32 || is_x3(m) ? 4 : 2; }
 
 size_t pad256(size_t v) { return (v + 255) / 256 * 256; }
 
@@ -42,7 +45,7 @@ size_t pad256(size_t v) { return (v + 255) / 256 * 256; }
 // option "qkv_pad" elements (default 128 = 256 bytes; a multiple of 64 so that the GEMM epilogue still stores whole
 // 128-byte lines): dense 6 144-byte rows put a head's K / V / q pieces on few memory channels and cost that kernel 15-20 %.
 bool attn32_applies(const mi_clip* m) {
-    return m->precision != MI_PRECISION_F32 && m->attn_ver >= 2 && !m->text && m->S > 64 && m->S <= 288;
+    return m->precision == MI_PRECISION_BF16 && m->attn_ver >= 2 && !m->text && m->S > 64 && m->S <= 288;
 }
 size_t qkv_pitch(const mi_clip* m) { return (size_t)3 * m->D + (attn32_applies(m) ? (size_t)m->qkv_pad : 0); }
 // Option "qkv_layout" = 1: q|k|v as head-major planes [3][H][Mp][64] instead of token rows — the persistent GEMM's epilogue
@@ -71,13 +74,38 @@ float* upload_f32(mi_clip* m, const std::vector<float>& h) {
 // GEMM operand in the model's precision; dup_k > 0: every row of k = dup_k values is stored twice, [W | W]
 // (the operand of a GEMM whose activations arrive as hi | lo halves, MI_PRECISION_BF16_SPLIT)
 void* upload_mat(mi_clip* m, const std::vector<float>& h, size_t dup_k = 0) {
-    if (m->precision == MI_PRECISION_F32) return upload_f32(m, h);
+    if (m->precision == MI_PRECISION_F32 || is_x3(m)) return upload_f32(m, h);
     std::vector<uint16_t> b(h.size() * (dup_k ? 2 : 1));
     if (dup_k) {
         for (size_t r = 0; r < h.size() / dup_k; ++r)
             for (size_t c = 0; c < dup_k; ++c) b[r * 2 * dup_k + c] = b[r * 2 * dup_k + dup_k + c] = f32_to_bf16_host(h[r * dup_k + c]);
     } else
     for (size_t i = 0; i < h.size(); ++i) b[i] = f32_to_bf16_host(h[i]);
+    uint16_t* d = dalloc<uint16_t>(m, b.size(), m->allocs);
+    HIP_CHECK(hipMemcpy(d, b.data(), b.size() * 2, hipMemcpyHostToDevice));
+    return d;
+}
+
+// rows of k fp32 values -> rows [hi | lo] of 2k bf16, hi = bf16(v), lo = bf16(v - hi) (MI_PRECISION_BF16X3 operands);
+// rows_pad >= rows: the padding rows are zeros
+std::vector<uint16_t> split_rows_x3(const float* h, size_t rows, size_t k, size_t rows_pad) {
+    std::vector<uint16_t> b(rows_pad * 2 * k, 0);
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t c = 0; c < k; ++c) {
+            const float v = h[r * k + c];
+            const uint16_t hi = f32_to_bf16_host(v);
+            uint32_t u = (uint32_t)hi << 16;
+            float hv;
+            std::memcpy(&hv, &u, 4);
+            b[r * 2 * k + c] = hi;
+            b[r * 2 * k + k + c] = f32_to_bf16_host(v - hv);
+        }
+    return b;
+}
+
+// an encoder linear of a MI_PRECISION_BF16X3 handle: W [N][k] as rows [W_hi | W_lo] (4 bytes per weight, as fp32)
+void* upload_x3(mi_clip* m, const std::vector<float>& h, size_t k) {
+    const std::vector<uint16_t> b = split_rows_x3(h.data(), h.size() / k, k, h.size() / k);
     uint16_t* d = dalloc<uint16_t>(m, b.size(), m->allocs);
     HIP_CHECK(hipMemcpy(d, b.data(), b.size() * 2, hipMemcpyHostToDevice));
     return d;
@@ -199,6 +227,10 @@ void load_weights(mi_clip* m, const char* path) {
         fail(MI_ERR_UNSUPPORTED, "hidden %d with %d heads: the attention kernels are built for head_dim 64", m->D, m->H);
     if (m->D % 128 != 0 || m->FF % 128 != 0)
         fail(MI_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of 128", m->D, m->FF);
+    // the three-pass GEMM is the persistent 256x256 kernel only, and the attention the exact-f32 MFMA kernel: no fallbacks
+    if (is_x3(m) && (m->D % 256 != 0 || m->FF % 256 != 0 || m->S > 272))
+        fail(MI_ERR_UNSUPPORTED, "MI_PRECISION_BF16X3 needs hidden (%d) and intermediate (%d) sizes that are multiples of 256 and at most 272 tokens (%d)",
+             m->D, m->FF, m->S);
     const int K = 3 * m->patch * m->patch;
     m->Kp = (K + 63) / 64 * 64;
 
@@ -252,16 +284,18 @@ void load_layers(mi_clip* m, WeightFile& st, const std::string& v) {
             wqkv.insert(wqkv.end(), w.begin(), w.end());
             bqkv.insert(bqkv.end(), b.begin(), b.end());
         }
-        ly.wqkv = upload_mat(m, wqkv, m->split_ln ? (size_t)D : 0);
+        // an encoder linear: [W_hi | W_lo] rows (BF16X3), [W | W] rows (BF16_SPLIT's q/k/v and fc1), or W as the precision has it
+        auto linear = [&](const std::vector<float>& w, int k, bool dup) { return is_x3(m) ? upload_x3(m, w, (size_t)k) : upload_mat(m, w, dup ? (size_t)k : 0); };
+        ly.wqkv = linear(wqkv, D, m->split_ln);
         ly.bqkv = upload_f32(m, bqkv);
         {
             std::vector<float> wo = st.read(p + "self_attn.out_proj.weight", (int64_t)D * D), bo = st.read(p + "self_attn.out_proj.bias", D);
             if (m->ln_center) center_writer(wo, bo, D, D);
-            ly.wo = upload_mat(m, wo);
+            ly.wo = linear(wo, D, false);
             ly.bo = upload_f32(m, bo);
         }
         const std::vector<float> w1 = st.read(p + "mlp.fc1.weight", (int64_t)FF * D), b1 = st.read(p + "mlp.fc1.bias", FF);
-        ly.w1 = upload_mat(m, w1, m->split_ln ? (size_t)D : 0);
+        ly.w1 = linear(w1, D, m->split_ln);
         ly.b1 = upload_f32(m, b1);
         if (m->fold_ready) {  // (the last layer folds LN1 only: behind its attention it works on the CLS rows, forward())
             fold_ln(m, wqkv, bqkv, st.read(p + "layer_norm1.weight", D), st.read(p + "layer_norm1.bias", D), 3 * D, D, &ly.wqkv_f, &ly.cqkv, &ly.bqkv_f);
@@ -270,7 +304,7 @@ void load_layers(mi_clip* m, WeightFile& st, const std::string& v) {
         {
             std::vector<float> w2 = st.read(p + "mlp.fc2.weight", (int64_t)D * FF), b2 = st.read(p + "mlp.fc2.bias", D);
             if (m->ln_center) center_writer(w2, b2, D, FF);
-            ly.w2 = upload_mat(m, w2);
+            ly.w2 = linear(w2, FF, false);
             ly.b2 = upload_f32(m, b2);
         }
     }
@@ -301,7 +335,7 @@ void ensure_workspace(mi_clip* m, size_t n) {
     m->d_in = (float*)bytes(n * px * 4);
     m->d_in2 = (float*)bytes(n * px * 4);  // mi_clip_embed: upload of chunk i+1 under the forward of chunk i
     m->d_rgb = (uint8_t*)bytes(n * px);
-    const int sets = (m->precision == MI_PRECISION_BF16) ? std::max(1, m->parts) : 1;
+    const int sets = (m->precision == MI_PRECISION_BF16 || is_x3(m)) ? std::max(1, m->parts) : 1;
     for (int a = 0; a < sets; ++a) {
         const size_t na = a == 0 ? n : (n + 1) / 2;
         const size_t Ma = pad256(na * m->S), Pa = pad256(na * (m->S - 1));
@@ -312,15 +346,19 @@ void ensure_workspace(mi_clip* m, size_t n) {
         m->act[a].y = bytes(Ma * m->D * es * (m->split_ln ? 2 : 1));
         m->act[a].qkv = bytes(Ma * qkv_pitch(m) * es);
         m->act[a].h = bytes(Ma * m->FF * es);
-        m->act[a].delta = (bf16_t*)bytes(Ma * m->D * 2);
-        m->act[a].delta2 = (bf16_t*)bytes(Ma * m->D * 2);
+        if (!is_x3(m)) {   // the deferred residual adds of the bf16 tower (BF16X3 adds in the GEMM epilogue)
+            m->act[a].delta = (bf16_t*)bytes(Ma * m->D * 2);
+            m->act[a].delta2 = (bf16_t*)bytes(Ma * m->D * 2);
+        }
         const size_t Ca = pad256(na);
         m->act[a].c_ctx = bytes(Ca * m->D * es);
         m->act[a].c_y = bytes(Ca * m->D * es * (m->split_ln ? 2 : 1));
         m->act[a].c_h = bytes(Ca * m->FF * es);
         m->act[a].c_x = (float*)bytes(Ca * m->D * 4);
-        m->act[a].c_d1 = (bf16_t*)bytes(Ca * m->D * 2);
-        m->act[a].c_d2 = (bf16_t*)bytes(Ca * m->D * 2);
+        if (!is_x3(m)) {
+            m->act[a].c_d1 = (bf16_t*)bytes(Ca * m->D * 2);
+            m->act[a].c_d2 = (bf16_t*)bytes(Ca * m->D * 2);
+        }
         if (m->fold_ready) {
             m->act[a].part = (float*)bytes(Ma * (size_t)(m->D / 32) * 8);
             m->act[a].stats = (float*)bytes(Ma * 8);
@@ -366,11 +404,12 @@ void gemm_p(int precision, const void* X, const void* W, const float* bias, void
 }
 
 // the persistent 256x256 kernel (gemm_bf16_pp_kernel): shapes it takes, and its launch
-bool pp_shape_ok(size_t Mp, int N, int K, int ldo) {
-    return N % 256 == 0 && K % 64 == 0 && K >= 128 && Mp * (size_t)K * 2 < (1ull << 32) && Mp * (size_t)ldo * 2 < (1ull << 32) &&
-           (size_t)N * K * 2 < (1ull << 32);
+// kb: bytes per K element of an operand row (4: the hi | lo rows of MI_PRECISION_BF16X3); ob: bytes per output element
+bool pp_shape_ok(size_t Mp, int N, int K, int ldo, size_t kb = 2, size_t ob = 2) {
+    return N % 256 == 0 && K % 64 == 0 && K >= 128 && Mp * (size_t)K * kb < (1ull << 32) && Mp * (size_t)ldo * ob < (1ull << 32) &&
+           (size_t)N * K * kb < (1ull << 32);
 }
-template <int EPI>
+template <int EPI, bool X3 = false>
 void launch_pp(mi_clip* m, const void* X, const void* W, const float* bias, void* out, size_t Mp, int N, int K, int ldo,
                const PpFold& fold, hipStream_t s) {
     constexpr bool LNF = EPI == EPI_LNF || EPI == EPI_LNF_QGELU;
@@ -385,13 +424,13 @@ void launch_pp(mi_clip* m, const void* X, const void* W, const float* bias, void
     const int order = fits(m->gemm_order) ? m->gemm_order : (m->gemm_order > 0 && fits(4)) ? 4 : 0;
     // option "store_nt" (default 1): the plain output stores with the nt cache policy; EPI_RESID24 has none of them
     if (EPI == EPI_RESID24 || m->store_nt) {
-        auto kern = gemm_bf16_pp_kernel<EPI, bf16_t, true>;
+        auto kern = gemm_bf16_pp_kernel<EPI, bf16_t, true, X3>;
         static DevOnce once;
         allow_lds_once(once, kern, LDS);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, s, (const bf16_t*)X, (const bf16_t*)W, bias, out, (int)Mp, N, K, ldo,
                            n_tiles, n_full, order, fold);
     } else {
-        auto kern = gemm_bf16_pp_kernel<EPI, bf16_t, (EPI == EPI_RESID24)>;
+        auto kern = gemm_bf16_pp_kernel<EPI, bf16_t, (EPI == EPI_RESID24), X3>;
         static DevOnce once;
         allow_lds_once(once, kern, LDS);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, s, (const bf16_t*)X, (const bf16_t*)W, bias, out, (int)Mp, N, K, ldo,
@@ -405,6 +444,21 @@ void launch_pp(mi_clip* m, const void* X, const void* W, const float* bias, void
 template <int EPI>
 void gemm(mi_clip* m, const void* X, const void* W, const float* bias, void* out, size_t Mrows, int N, int K, int ldo,
           hipStream_t s, uint32_t col_stride = 64) {
+    if (is_x3(m)) {
+        if constexpr (EPI == EPI_STORE_F32) {   // the patch embedding stays fp32 (0.2 % of the FLOPs)
+            gemm_p<EPI>(MI_PRECISION_F32, X, W, bias, out, Mrows, N, K, ldo, s);
+        } else if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_QGELU || EPI == EPI_BIAS_RESID) {
+            // X [Mrows][2K] and W [N][2K] as hi | lo rows; K and ldo count logical columns (QGELU: the pair's pitch is 2 ldo)
+            const size_t Mp = pad256(Mrows);
+            const int ldo_e = EPI == EPI_BIAS_QGELU ? 2 * ldo : ldo;
+            if (col_stride != 64 || !pp_shape_ok(Mp, N, K, ldo_e, 4, EPI == EPI_BIAS_QGELU ? 2 : 4))
+                fail(MI_ERR_UNSUPPORTED, "MI_PRECISION_BF16X3: GEMM [%zu x %d x %d] is not one of the persistent kernel's shapes", Mrows, N, K);
+            launch_pp<EPI, true>(m, X, W, bias, out, Mp, N, K, ldo_e, PpFold(), s);
+        } else {
+            fail(MI_ERR_INVALID, "MI_PRECISION_BF16X3 has no epilogue %d", EPI);
+        }
+        return;
+    }
     if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_QGELU) {
         const size_t Mp = pad256(Mrows);
         if (m->precision == MI_PRECISION_BF16 && pp_shape_ok(Mp, N, K, col_stride == 64 ? ldo : N)) {
@@ -438,7 +492,7 @@ void gemm(mi_clip* m, const void* X, const void* W, const float* bias, void* out
 void layer_norm(mi_clip* m, float* x, const bf16_t* d1, const bf16_t* d2, bool write_back, void* y, const float* w,
                 const float* b, size_t rows, hipStream_t s, size_t x_lo = 0) {
     const unsigned blocks = (unsigned)((rows + 3) / 4);
-    const int split = m->split_ln ? 1 : 0, y_ld = m->D * (1 + split);
+    const int split = (m->split_ln || is_x3(m)) ? 1 : 0, y_ld = m->D * (1 + split);
     if (m->precision == MI_PRECISION_F32) {
         MI_LN_DISPATCH(m->D, hipLaunchKernelGGL((ln_kernel<float, VEC, NT, true>), dim3(blocks), dim3(256), 0, s, x, d1, d2, (float*)y, w, b, (int)rows, m->eps, y_ld, 0));
     } else if (write_back) {
@@ -461,7 +515,19 @@ void attention(mi_clip* m, const void* qkv, void* ctx, size_t n, hipStream_t s, 
         head_stride = (uint32_t)(hm_rows * 64);
         sel_stride = (uint32_t)((size_t)m->H * hm_rows * 64);
     }
-    if (m->precision == MI_PRECISION_F32) {
+    if (is_x3(m)) {   // exact-f32 attention on the fp32 q|k|v; ctx as hi | lo bf16 pairs (pitch 2D), out_proj's X
+        if (m->S > 272) fail(MI_ERR_UNSUPPORTED, "MI_PRECISION_BF16X3 attention is built for up to 272 tokens (got %d)", m->S);
+#define MI_ATTNX(SP)                                                                                                    \
+    {                                                                                                                   \
+        static DevOnce once;                                                                                            \
+        allow_lds_once(once, attn_f32_mfma_kernel<SP, true>, attnf_lds_bytes(SP));                                      \
+        hipLaunchKernelGGL((attn_f32_mfma_kernel<SP, true>), dim3((unsigned)(n * m->H)), dim3(512), attnf_lds_bytes(SP), s, (const float*)qkv, (float*)ctx, m->S, m->D, m->H, 0, first_tile_only ? 1 : 0); \
+    }
+        if (m->S <= 80) MI_ATTNX(80)
+        else if (m->S <= 208) MI_ATTNX(208)
+        else MI_ATTNX(272)
+#undef MI_ATTNX
+    } else if (m->precision == MI_PRECISION_F32) {
         if (m->S <= 272 && m->attn_f32_mfma) {   // on the matrix pipe (exact-f32 MFMA), one workgroup per (image, head)
 #define MI_ATTNF(SP)                                                                                                    \
     {                                                                                                                   \
@@ -575,7 +641,7 @@ void forward(mi_clip* m, const float* d_img, size_t n, float* d_out, hipStream_t
     const size_t px = (size_t)m->image * m->image * 3;
     const bool deferred = m->precision == MI_PRECISION_BF16;
     const int Kln = m->split_ln ? 2 * D : D;  // K of the GEMMs fed by a LayerNorm (q/k/v, fc1): hi | lo halves when split
-    const int parts = (deferred && m->parts > 1 && n >= 32) ? m->parts : 1;
+    const int parts = ((deferred || is_x3(m)) && m->parts > 1 && n >= 32) ? m->parts : 1;
     struct Part { size_t n, M, P; const float* img; float* out; hipStream_t s; mi_clip::Act* a; const bf16_t *p1, *p2; size_t xlo; } pt[4];
     const bool fold = deferred && fold_applies(m, (n / parts + 1) * (size_t)S);
     // the residual stream as 24-bit floats in two planes (option "x24"; bf16 tower, D a multiple of 256, no hi + lo LayerNorm outputs)
@@ -608,7 +674,7 @@ void forward(mi_clip* m, const float* d_img, size_t n, float* d_out, hipStream_t
         // patch embedding: gather -> GEMM [P,Kp] x [D,Kp]^T -> f32
         const size_t total = q.P * 3 * (size_t)m->patch;  // one thread per patch-row segment
         const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 65535 * 4);
-        if (m->precision == MI_PRECISION_F32)
+        if (m->precision == MI_PRECISION_F32 || is_x3(m))
             hipLaunchKernelGGL((im2col_kernel<float>), dim3(blocks), dim3(256), 0, fs, q.img, (float*)q.a->col, (int)q.n, m->grid, m->patch, m->image, m->Kp);
         else if (m->im2col_rows && m->image % 4 == 0 && (3 * m->patch * m->patch) % 4 == 0 && m->Kp % 4 == 0 && (size_t)3 * m->patch * m->image * 4 <= 64 * 1024)
             hipLaunchKernelGGL(im2col_rows_kernel, dim3((unsigned)(q.n * m->grid)), dim3(256), (size_t)3 * m->patch * m->image * 4, fs, q.img,
@@ -1013,6 +1079,7 @@ int mi_clip_set_option(mi_clip* m, const char* key, int value) {
         } else if (k == "qkv_layout") {   // takes effect with the next forward (every forward rewrites q|k|v)
             if (value < 0 || value > 1) fail(MI_ERR_INVALID, "qkv_layout must be 0 (token rows) or 1 (head-major planes)");
             if (m->text) fail(MI_ERR_INVALID, "the text tower's qkv rows are dense");
+            if (value == 1 && is_x3(m)) fail(MI_ERR_UNSUPPORTED, "qkv_layout: MI_PRECISION_BF16X3 keeps q|k|v as fp32 token rows");
             m->qkv_layout = value;
         } else if (k == "attn_order") {
             if (value < 0 || value > 1) fail(MI_ERR_INVALID, "attn_order must be 0 or 1");
@@ -1028,7 +1095,10 @@ int mi_clip_set_option(mi_clip* m, const char* key, int value) {
         else if (k == "text_fuse") m->text_fuse = value != 0;
         else if (k == "attn_f32_mfma") m->attn_f32_mfma = value != 0;
         else if (k == "ln_nt") m->ln_nt = value & 3;
-        else if (k == "x24") m->x24 = value != 0;   // takes effect with the next forward (every forward rewrites the residual stream)
+        else if (k == "x24") {   // takes effect with the next forward (every forward rewrites the residual stream)
+            if (value != 0 && is_x3(m)) fail(MI_ERR_UNSUPPORTED, "x24: the MI_PRECISION_BF16X3 residual stream is fp32");
+            m->x24 = value != 0;
+        }
         else if (k == "ln_fold") {   // takes effect with the next forward (every forward rewrites the residual stream)
             if (value != 0 && !m->fold_ready)
                 fail(MI_ERR_UNSUPPORTED, "ln_fold needs the bf16 image tower with hidden and intermediate sizes that are multiples of 256 and at least two layers");
@@ -1057,8 +1127,9 @@ int mi_clip_load(const char* weights_path, int device, int precision, mi_clip** 
         if (!out) fail(MI_ERR_INVALID, "out is null");
         *out = nullptr;
         if (!weights_path) fail(MI_ERR_INVALID, "weights_path is null");
-        if (precision != MI_PRECISION_F32 && precision != MI_PRECISION_BF16 && precision != MI_PRECISION_BF16_SPLIT)
-            fail(MI_ERR_INVALID, "precision %d: use MI_PRECISION_F32 (0), MI_PRECISION_BF16 (1) or MI_PRECISION_BF16_SPLIT (2)", precision);
+        if (precision != MI_PRECISION_F32 && precision != MI_PRECISION_BF16 && precision != MI_PRECISION_BF16_SPLIT &&
+            precision != MI_PRECISION_BF16X3)
+            fail(MI_ERR_INVALID, "precision %d: use MI_PRECISION_F32 (0), MI_PRECISION_BF16 (1), MI_PRECISION_BF16_SPLIT (2) or MI_PRECISION_BF16X3 (3)", precision);
         DeviceGuard g(device);
         m = new mi_clip();
         m->device = device;
@@ -1077,6 +1148,7 @@ int mi_clip_load(const char* weights_path, int device, int precision, mi_clip** 
         if (const char* e = std::getenv("MI_CLIP_IM2COL")) m->im2col_rows = std::atoi(e) != 0;
         if (const char* e = std::getenv("MI_CLIP_LN_NT")) m->ln_nt = std::atoi(e) & 3;
         if (const char* e = std::getenv("MI_CLIP_X24")) m->x24 = std::atoi(e) != 0;
+        if (m->precision == MI_PRECISION_BF16X3) m->x24 = false;   // no effect there; an explicit option 1 is refused
         if (const char* e = std::getenv("MI_CLIP_LN_CENTER")) m->ln_center = std::atoi(e) != 0;   // fixed at load: it shapes the weights
         if (const char* e = std::getenv("MI_CLIP_QKV_LAYOUT")) m->qkv_layout = std::atoi(e) == 1 ? 1 : 0;
         if (const char* e = std::getenv("MI_CLIP_FRONT_OVERLAP")) m->front_overlap = std::atoi(e) != 0;
@@ -1360,11 +1432,63 @@ struct Scratch {
 };
 }  // namespace
 
+namespace {
+// MI_PRECISION_BF16X3: x and w are split into hi | lo rows on the way in, the three-pass persistent GEMM runs, and the
+// output comes back fp32 (EPI_BIAS, EPI_BIAS_RESID) or as its hi | lo pair widened to hi + lo (EPI_BIAS_QGELU)
+void op_linear_x3(int device, int epilogue, const float* x, const float* w, const float* bias, float* out, size_t m_rows, int n, int k) {
+    if (epilogue != EPI_BIAS && epilogue != EPI_BIAS_QGELU && epilogue != EPI_BIAS_RESID)
+        fail(MI_ERR_INVALID, "MI_PRECISION_BF16X3: epilogue %d (EPI_BIAS, EPI_BIAS_QGELU or EPI_BIAS_RESID)", epilogue);
+    const size_t mp = pad256(m_rows);
+    const bool pair = epilogue == EPI_BIAS_QGELU;
+    if (!pp_shape_ok(mp, n, k, pair ? 2 * n : n, 4, pair ? 2 : 4))
+        fail(MI_ERR_UNSUPPORTED, "MI_PRECISION_BF16X3: shape [%zu x %d x %d] is not one of the persistent GEMM's", m_rows, n, k);
+    DeviceGuard g(device);
+    Scratch sc;
+    const std::vector<uint16_t> xs = split_rows_x3(x, m_rows, (size_t)k, mp), ws = split_rows_x3(w, (size_t)n, (size_t)k, (size_t)n);
+    void* dx = sc.bytes(xs.size() * 2);
+    void* dw = sc.bytes(ws.size() * 2);
+    HIP_CHECK(hipMemcpy(dx, xs.data(), xs.size() * 2, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dw, ws.data(), ws.size() * 2, hipMemcpyHostToDevice));
+    float* db = (float*)sc.up(MI_PRECISION_F32, bias, 1, n, 1);
+    void* dout = pair ? sc.bytes(mp * (size_t)n * 4) : sc.up(MI_PRECISION_F32, out, m_rows, n, mp);
+    mi_clip mm;
+    mm.precision = MI_PRECISION_BF16X3;
+    hipDeviceProp_t prop;
+    HIP_CHECK(hipGetDeviceProperties(&prop, device));
+    mm.n_cu = prop.multiProcessorCount;
+    if (const char* e = std::getenv("MI_OP_GRID")) mm.n_cu = std::max(1, std::atoi(e));
+    if (const char* e = std::getenv("MI_OP_GEMM_ORDER")) mm.gemm_order = std::max(0, std::min(16, std::atoi(e)));
+    if (const char* e = std::getenv("MI_GEMM_SPLIT")) mm.split_tail = std::atoi(e) != 0;
+    if (const char* e = std::getenv("MI_OP_STORE_NT")) mm.store_nt = std::atoi(e) != 0;
+    switch (epilogue) {
+        case EPI_BIAS: gemm<EPI_BIAS>(&mm, dx, dw, db, dout, m_rows, n, k, n, nullptr); break;
+        case EPI_BIAS_QGELU: gemm<EPI_BIAS_QGELU>(&mm, dx, dw, db, dout, m_rows, n, k, n, nullptr); break;
+        default: gemm<EPI_BIAS_RESID>(&mm, dx, dw, db, dout, m_rows, n, k, n, nullptr); break;
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    if (!pair) {
+        HIP_CHECK(hipMemcpy(out, dout, m_rows * (size_t)n * 4, hipMemcpyDeviceToHost));
+        return;
+    }
+    std::vector<uint16_t> h(m_rows * (size_t)n * 2);
+    HIP_CHECK(hipMemcpy(h.data(), dout, h.size() * 2, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < m_rows; ++r)
+        for (size_t c = 0; c < (size_t)n; ++c) {
+            const uint32_t uh = (uint32_t)h[r * 2 * n + c] << 16, ul = (uint32_t)h[r * 2 * n + n + c] << 16;
+            float fh, fl;
+            std::memcpy(&fh, &uh, 4);
+            std::memcpy(&fl, &ul, 4);
+            out[r * n + c] = fh + fl;
+        }
+}
+}  // namespace
+
 int mi_op_linear(int device, int precision, int epilogue, const float* x, const float* w, const float* bias,
                  float* out, size_t m_rows, int n, int k) {
     return guarded([&] {
         if (!x || !w || !out) fail(MI_ERR_INVALID, "null buffer");
         if (epilogue != EPI_STORE_F32 && !bias) fail(MI_ERR_INVALID, "bias is null");
+        if (precision == MI_PRECISION_BF16X3) { op_linear_x3(device, epilogue, x, w, bias, out, m_rows, n, k); return; }
         DeviceGuard g(device);
         Scratch sc;
         const size_t mp = pad256(m_rows);
@@ -1488,6 +1612,7 @@ int mi_op_attention(int device, int precision, const float* qkv, float* ctx, siz
     return guarded([&] {
         if (!qkv || !ctx) fail(MI_ERR_INVALID, "null buffer");
         if (d != heads * 64) fail(MI_ERR_UNSUPPORTED, "head_dim must be 64");
+        if (precision == MI_PRECISION_BF16X3) fail(MI_ERR_UNSUPPORTED, "no attention op for MI_PRECISION_BF16X3 (the tower's is the fp32 kernel)");
         DeviceGuard g(device);
         Scratch sc;
         mi_clip m;
@@ -1551,6 +1676,7 @@ int mi_op_layernorm(int device, int precision, const float* x, const float* w, c
                     int d, float eps) {
     return guarded([&] {
         if (!x || !w || !b || !y) fail(MI_ERR_INVALID, "null buffer");
+        if (precision == MI_PRECISION_BF16X3) fail(MI_ERR_UNSUPPORTED, "no LayerNorm op for MI_PRECISION_BF16X3");
         DeviceGuard g(device);
         Scratch sc;
         mi_clip m;

@@ -1242,18 +1242,32 @@ __global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__
 #endif
 // STORE_NT: the plain output stores (every epilogue but EPI_RESID24) carry the nt cache policy (MI_PP_STORE_AUX_* above);
 // 0 = default policy, the A/B partner of option "store_nt".
-template <int EPI, typename TO, bool STORE_NT = true>
+// X3 (MI_PRECISION_BF16X3): X and W rows are [hi | lo] bf16 pairs, hi = bf16(v), lo = bf16(v - hi), row pitch 2K.  The K
+// walk runs over 3K / 64 tiles: pass p = kt / (K / 64) stages the planes (X, W) = (hi, hi), (lo, hi), (hi, lo) into the
+// same LDS images, and everything lands in ONE accumulator — only the source offset of a half-tile changes.  Epilogues:
+//   EPI_BIAS        acc + bias as fp32 rows (q|k|v, read by the fp32 attention)
+//   EPI_BIAS_QGELU  quick_gelu(acc + bias) as a hi | lo bf16 pair, pitch ldo = 2N (fc1: fc2's X)
+//   EPI_BIAS_RESID  x += acc + bias, fp32, in place (out_proj, fc2: the residual stream)
+// The fp32 / pair outputs are twice the bf16 bytes: they go through the same 18 KiB of patches in two rounds per 16 rows
+// (32 fp32 columns, or the hi plane then the lo plane), so the LDS budget is the bf16 kernel's.
+template <int EPI, typename TO, bool STORE_NT = true, bool X3 = false>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(const bf16_t* __restrict__ X,
                                                               const bf16_t* __restrict__ W,
                                                               const float* __restrict__ bias,
                                                               void* __restrict__ out, int M, int N, int K, int ldo,
                                                               int n_tiles, int n_full, int order, const PpFold fold = PpFold()) {
-    static_assert(EPI == EPI_BIAS || EPI == EPI_BIAS_QGELU || EPI == EPI_LNF || EPI == EPI_LNF_QGELU || EPI == EPI_RESID24,
+    static_assert(EPI == EPI_BIAS || EPI == EPI_BIAS_QGELU || EPI == EPI_LNF || EPI == EPI_LNF_QGELU || EPI == EPI_RESID24 ||
+                      (X3 && EPI == EPI_BIAS_RESID),
                   "the persistent form stores bf16 with bias");
+    static_assert(!X3 || EPI == EPI_BIAS || EPI == EPI_BIAS_QGELU || EPI == EPI_BIAS_RESID, "the three-pass form's epilogues");
     static_assert(sizeof(TO) == 2, "bf16 output");
     constexpr bool LNF = EPI == EPI_LNF || EPI == EPI_LNF_QGELU;   // LayerNorm folded into this linear (PpFold::cvec, stats)
     constexpr bool RES = EPI == EPI_RESID24;                        // residual add + row sums in the epilogue (PpFold::xlo, part)
     constexpr bool GELU = EPI == EPI_BIAS_QGELU || EPI == EPI_LNF_QGELU;
+    constexpr bool F32O = X3 && EPI != EPI_BIAS_QGELU;              // fp32 output rows (X3 q|k|v, X3 residual)
+    constexpr bool RESF = X3 && EPI == EPI_BIAS_RESID;              // ... added in place to what the rows hold
+    constexpr bool SPLITO = X3 && EPI == EPI_BIAS_QGELU;            // hi | lo bf16 output pair (lo plane N columns behind hi)
+    constexpr uint32_t OB = F32O ? 4u : 2u;                         // bytes per output element
     // per wave behind the patches: 256 B bias [+ 256 B c + 1 KiB {rstd, -mean rstd} of the wave's 128 rows]
     constexpr int AUX = LNF ? 1536 : 256;
     constexpr int AUX_OPS = LNF ? 3 : 1;   // LDS-DMA instructions of stage_aux
@@ -1266,11 +1280,19 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(const bf16_t* __re
     const int lb = (int)xcd_remap(blockIdx.x, G);
     PP_CLOCK_BEGIN
 
-    const uint32_t Kb = (uint32_t)K * 2;
+    const uint32_t Kb = (uint32_t)K * (X3 ? 4u : 2u);   // operand row pitch in bytes (X3: hi | lo)
+    const int nk1 = K / 64;                            // K tiles of one pass
     const rsrc_t xr = make_rsrc(X, (uint32_t)M * Kb);
     const rsrc_t wr = make_rsrc(W, (uint32_t)N * Kb);
     const uint32_t cs = fold.col_stride;
-    const rsrc_t orr = make_rsrc(out, cs == 64u ? (uint32_t)M * (uint32_t)ldo * (uint32_t)sizeof(TO) : (uint32_t)(N / 64) * cs * (uint32_t)sizeof(TO));
+    const rsrc_t orr = make_rsrc(out, cs == 64u ? (uint32_t)M * (uint32_t)ldo * OB : (uint32_t)(N / 64) * cs * OB);
+    // byte offset of K tile kt inside an operand row (X3: pass kt / nk1 picks the hi or lo plane of X and of W)
+    auto k_off = [&](int kt, bool is_x) -> uint32_t {
+        if constexpr (!X3) return (uint32_t)kt * 128u;
+        const int pass = kt >= 2 * nk1 ? 2 : kt >= nk1 ? 1 : 0;
+        const bool lo = is_x ? pass == 1 : pass == 2;
+        return (uint32_t)(kt - pass * nk1) * 128u + (lo ? (uint32_t)K * 2u : 0u);
+    };
     const rsrc_t br = make_rsrc(bias, (uint32_t)N * 4u);
     const int rr = lane >> 3, p = lane & 7;
     const uint32_t x_lane = (uint32_t)rr * Kb + 16 * (p ^ rr);
@@ -1281,7 +1303,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(const bf16_t* __re
         const bool is_x = (j == 0 || j == 3);
         const int h = (j >= 2) ? 1 : 0;
         unsigned char* dst = smem + buf * 65536 + (is_x ? 0 : 32768) + h * 16384 + wave * 2048;
-        const uint32_t so = (is_x ? xs + x_wave + 64u * h * Kb : ws + w_wave + 32u * h * Kb) + (uint32_t)kt * 128u;
+        const uint32_t so = (is_x ? xs + x_wave + 64u * h * Kb : ws + w_wave + 32u * h * Kb) + k_off(kt, is_x);
         if (is_x) {
             glds16_buf_aux<MI_PP_X_AUX>(xr, x_lane, so, dst);
             glds16_buf_aux<MI_PP_X_AUX>(xr, x_lane, so + 8u * Kb, dst + 1024);
@@ -1336,7 +1358,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(const bf16_t* __re
 
     // position in the flattened (tile, K tile) stream of this workgroup
     struct Pos { uint32_t xs, ws; int kt, tile, tm, tn; bool ok; };
-    const int nk = K / 64;
+    const int nk = X3 ? 3 * nk1 : nk1;
     // visit index -> tile.  order == 0: row-major (an XCD's 32 concurrent tiles = 32 / nt row panels x ALL nt weight tiles:
     // every XCD streams the whole W every round).  order = np > 0 (nt % np == 0): the complete rounds of an XCD are made
     // contiguous (its visits r * G + lb become c * R * per + r * per + lb % per), and the sequence walks column groups of np
@@ -1381,7 +1403,25 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(const bf16_t* __re
 #endif
     constexpr int RES_P = MI_RES_P;
     // vector-memory instructions an epilogue leaves in the queue behind the operand DMA of the phase it runs in
-    constexpr int EPI_OPS = RES ? 2 * RES_P + 4 : 16;
+    constexpr int EPI_OPS = RES ? 2 * RES_P + 4 : X3 ? 32 : 16;   // X3: two rounds of 16 stores (RESF: + 32 loads ahead of them)
+    // X3 fp32 rows: lane -> row (lane >> 3) of an 8-row step, fp32 columns 4 (lane & 7) .. + 3 of a 32-column round
+    const uint32_t o_lane32 = ((uint32_t)(wm * 128 + (lane >> 3)) * (uint32_t)ldo + (uint32_t)wn * 64u + (uint32_t)(4 * (lane & 7))) * 4u;
+    // hi | lo pair of one output row: the lo plane starts N bf16 columns behind the hi plane
+    const uint32_t lo_plane = (uint32_t)N * 2u;
+    // X3: 16 rows x 64 columns of v (fp32) -> the LDS patch as bf16 of the hi (h = 0) or the lo (h = 1) plane
+    auto patch_pair = [&](const v4f* vv, int nv, int h) {
+#pragma unroll
+        for (int ni = 0; ni < nv; ++ni) {
+            v2u pk;
+            pk.x = pack2bf(vv[ni][0], vv[ni][1]);
+            pk.y = pack2bf(vv[ni][2], vv[ni][3]);
+            if (h) {
+                pk.x = pack2bf(vv[ni][0] - __uint_as_float(pk.x << 16), vv[ni][1] - __uint_as_float(pk.x & 0xffff0000u));
+                pk.y = pack2bf(vv[ni][2] - __uint_as_float(pk.y << 16), vv[ni][3] - __uint_as_float(pk.y & 0xffff0000u));
+            }
+            *reinterpret_cast<v2u*>(patch + l15 * 144 + (ni * 16 + 4 * g) * 2) = pk;
+        }
+    };
     // bias (or the folded LayerNorm) + activation + bf16 + 128-byte row segments through the wave's LDS patch; clears acc
     auto epilogue = [&](int tm, int tn) {
         __builtin_amdgcn_sched_barrier(0);
@@ -1393,6 +1433,77 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(const bf16_t* __re
         if constexpr (LNF) {
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) cv[ni] = *reinterpret_cast<const v4f*>(bias_lds + 256 + (ni * 16 + 4 * g) * 4);
+        }
+        if constexpr (F32O) {
+            // step st = (mi, round r, j): rows mi * 16 + j * 8 + (lane >> 3), fp32 columns 32 r + 4 (lane & 7) .. + 3
+            const uint32_t t32 = ((uint32_t)tm * 256u * (uint32_t)ldo + (uint32_t)tn * 256u) * 4u;
+            auto so32 = [&](int st) {
+                return t32 + (uint32_t)((st >> 2) * 16 + (st & 1) * 8) * (uint32_t)ldo * 4u + (uint32_t)((st >> 1) & 1) * 128u;
+            };
+            v4u xq[RES_P];   // RESF: the old rows of the next RES_P steps, in flight
+            if constexpr (RESF) {
+#pragma unroll
+                for (int st = 0; st < RES_P; ++st) { xq[st] = __builtin_amdgcn_raw_buffer_load_b128(orr, o_lane32, so32(st), MI_PP_RES_LOAD_AUX); __builtin_amdgcn_sched_barrier(0); }
+            }
+#pragma unroll
+            for (int mi = 0; mi < 8; ++mi) {
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+#pragma unroll
+                    for (int n2 = 0; n2 < 2; ++n2) {
+                        const int ni = 2 * r + n2;
+                        const v4f v = acc[ni][mi] + bv[ni];
+                        acc[ni][mi] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+                        *reinterpret_cast<v4f*>(patch + l15 * 144 + (n2 * 16 + 4 * g) * 4) = v;
+                    }
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const int st = 4 * mi + 2 * r + j;
+                        v4u d = *reinterpret_cast<const v4u*>(patch + (j * 8 + (lane >> 3)) * 144 + (lane & 7) * 16);
+                        if constexpr (RESF) {
+                            // x + (acc + bias): the fp32 path's EPI_BIAS_RESID
+                            d = __builtin_bit_cast(v4u, __builtin_bit_cast(v4f, xq[st % RES_P]) + __builtin_bit_cast(v4f, d));
+                            buffer_store_b128_aux<MI_PP_STORE_AUX_RES>(d, orr, o_lane32, so32(st));
+                            if (st + RES_P < 32) xq[st % RES_P] = __builtin_amdgcn_raw_buffer_load_b128(orr, o_lane32, so32(st + RES_P), MI_PP_RES_LOAD_AUX);
+                        } else {
+                            buffer_store_b128_aux<STORE_NT ? MI_PP_STORE_AUX_QKV : 0>(d, orr, o_lane32, so32(st));
+                        }
+                    }
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            return;
+        }
+        if constexpr (SPLITO) {
+#pragma unroll
+            for (int mi = 0; mi < 8; ++mi) {
+                v4f vv[4];
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni) {
+                    vv[ni] = acc[ni][mi] + bv[ni];
+                    acc[ni][mi] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) vv[ni][c] = quick_gelu<true>(vv[ni][c]);
+                }
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    patch_pair(vv, 4, h);
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const v4u d = *reinterpret_cast<const v4u*>(patch + (j * 8 + (lane >> 3)) * 144 + (lane & 7) * 16);
+                        const uint32_t so = o_tile + (uint32_t)(mi * 16 + j * 8) * (uint32_t)ldo * 2u + (h ? lo_plane : 0u);
+                        buffer_store_b128_aux<STORE_NT ? MI_PP_STORE_AUX_H : 0>(d, orr, o_lane, so);
+                    }
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            return;
         }
         v4u hq[RES_P];
         v2u lq[RES_P];
@@ -1553,7 +1664,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(const bf16_t* __re
     auto stage_task = [&](int slot, uint32_t xs, uint32_t ws, int kt) {
         unsigned char* dx = smem + (slot & 1) * 65536 + (slot >> 1) * 16384 + wave * 2048;
         unsigned char* dw = dx + 32768;
-        const uint32_t sx = xs + x_wave + (uint32_t)kt * 128u, sw = ws + w_wave + (uint32_t)kt * 128u;
+        const uint32_t sx = xs + x_wave + k_off(kt, true), sw = ws + w_wave + k_off(kt, false);
         glds16_buf_aux<MI_PP_X_AUX>(xr, x_lane, sx, dx);
         glds16_buf_aux<MI_PP_X_AUX>(xr, x_lane, sx + 8u * Kb, dx + 1024);
         glds16_buf_aux<MI_PP_W_AUX>(wr, x_lane, sw, dw);
@@ -1592,6 +1703,67 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(const bf16_t* __re
         }
         const uint32_t q_tile = ((uint32_t)ttm * 256u * (uint32_t)ldo + (uint32_t)ttn * 4u * cs) * 2u;
         const uint32_t q_lane = ((uint32_t)(wm * 128 + 64 * mh + (lane >> 2)) * (uint32_t)ldo + (uint32_t)wn * cs + (uint32_t)(32 * nh + 8 * (lane & 3))) * 2u;
+        if constexpr (F32O) {   // the task's 64 rows x 32 fp32 columns: per 16 rows, two 8-row steps of 128-byte row segments
+            const uint32_t q32_tile = ((uint32_t)ttm * 256u * (uint32_t)ldo + (uint32_t)ttn * 256u) * 4u;
+            const uint32_t q32_lane = ((uint32_t)(wm * 128 + 64 * mh + (lane >> 3)) * (uint32_t)ldo + (uint32_t)(wn * 64 + 32 * nh + 4 * (lane & 7))) * 4u;
+            v4u xo[8];
+            if constexpr (RESF) {
+#pragma unroll
+                for (int st = 0; st < 8; ++st)
+                    xo[st] = __builtin_amdgcn_raw_buffer_load_b128(orr, q32_lane, q32_tile + (uint32_t)(st * 8) * (uint32_t)ldo * 4u, MI_PP_RES_LOAD_AUX);
+            }
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) {
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) {
+                    const v4f v = acc[ni][mi] + bq[ni];
+                    acc[ni][mi] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+                    *reinterpret_cast<v4f*>(patch + l15 * 144 + (ni * 16 + 4 * g) * 4) = v;
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int st = 2 * mi + j;
+                    v4u d = *reinterpret_cast<const v4u*>(patch + (j * 8 + (lane >> 3)) * 144 + (lane & 7) * 16);
+                    const uint32_t so = q32_tile + (uint32_t)(st * 8) * (uint32_t)ldo * 4u;
+                    if constexpr (RESF) {
+                        d = __builtin_bit_cast(v4u, __builtin_bit_cast(v4f, xo[st]) + __builtin_bit_cast(v4f, d));
+                        buffer_store_b128_aux<MI_PP_STORE_AUX_RES>(d, orr, q32_lane, so);
+                    } else {
+                        buffer_store_b128_aux<STORE_NT ? MI_PP_STORE_AUX_QKV : 0>(d, orr, q32_lane, so);
+                    }
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            continue;
+        }
+        if constexpr (SPLITO) {
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) {
+                v4f vv[2];
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) {
+                    vv[ni] = acc[ni][mi] + bq[ni];
+                    acc[ni][mi] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) vv[ni][c] = quick_gelu<true>(vv[ni][c]);
+                }
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    patch_pair(vv, 2, h);
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+                    const v4u d = *reinterpret_cast<const v4u*>(patch + (lane >> 2) * 144 + (lane & 3) * 16);
+                    const uint32_t so = q_tile + (uint32_t)(mi * 16) * (uint32_t)ldo * 2u + (h ? lo_plane : 0u);
+                    buffer_store_b128_aux<STORE_NT ? MI_PP_STORE_AUX_H : 0>(d, orr, q_lane, so);
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            continue;
+        }
         v4u hq[4];
         v2u lq[4];
         if constexpr (RES) {   // the old planes of the task's four 16-row steps
@@ -1750,6 +1922,8 @@ __device__ __forceinline__ float xmax_rows(float v) {
 //   O^T = V^T P^T: for the same reason key slot (e, g) of an MFMA means key 16T + 4g + e, so the B operand is the lane's OWN
 //                 p[T][e] — P never moves — and A = V[16T + 4g + e][16dt + l15];  o[dt][e'] = O[query l15][16dt + 4g + e']
 // causal / q_tiles as attn_f32_kernel (q_tiles counts 16-query tiles here).
+// SPLIT (MI_PRECISION_BF16X3): ctx goes out as hi | lo bf16 pairs, row pitch 2D (hi = bf16(c), lo = bf16(c - hi)), the X
+// operand of the three-pass out_proj; the values split are the fp32 ones the plain form stores.
 __device__ __forceinline__ float xsum_rows(float v) {
     const unsigned u = __float_as_uint(v);
     const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
@@ -1760,7 +1934,7 @@ __device__ __forceinline__ float xsum_rows(float v) {
 }
 constexpr int ATTNF_PITCH = 68;
 constexpr int attnf_lds_bytes(int s_pad) { return 2 * s_pad * ATTNF_PITCH * 4; }
-template <int S_PAD>
+template <int S_PAD, bool SPLIT = false>
 __global__ __launch_bounds__(512) void attn_f32_mfma_kernel(const float* __restrict__ qkv, float* __restrict__ ctx, int S, int D, int H,
                                                             int causal, int q_tiles) {
     constexpr int NKT = S_PAD / 16;
@@ -1850,7 +2024,20 @@ __global__ __launch_bounds__(512) void attn_f32_mfma_kernel(const float* __restr
                 }
             }
         }
-        if (qi < S) {
+        if (qi < S && SPLIT) {
+            bf16_t* dst = reinterpret_cast<bf16_t*>(ctx) + ((size_t)b * S + qi) * 2 * D + hh * 64 + 4 * g;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                const v4f t = {o[dt][0] / l, o[dt][1] / l, o[dt][2] / l, o[dt][3] / l};
+                v2u hi, lo;
+                hi.x = pack2bf(t[0], t[1]);
+                hi.y = pack2bf(t[2], t[3]);
+                lo.x = pack2bf(t[0] - __uint_as_float(hi.x << 16), t[1] - __uint_as_float(hi.x & 0xffff0000u));
+                lo.y = pack2bf(t[2] - __uint_as_float(hi.y << 16), t[3] - __uint_as_float(hi.y & 0xffff0000u));
+                *reinterpret_cast<v2u*>(dst + 16 * dt) = hi;
+                *reinterpret_cast<v2u*>(dst + D + 16 * dt) = lo;
+            }
+        } else if (qi < S) {
             float* dst = ctx + ((size_t)b * S + qi) * D + hh * 64 + 4 * g;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {

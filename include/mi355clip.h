@@ -54,6 +54,8 @@ extern "C" {
 #define MI_PRECISION_BF16 1 /* bf16 MFMA operands, fp32 accumulate + fp32 residual stream */
 #define MI_PRECISION_BF16_SPLIT 2 /* as BF16, but every LayerNorm output feeds its GEMM as a hi + lo bf16 pair (K = 2D
                                    * against [W | W]): for towers whose LayerNorm outputs carry outlier channels */
+#define MI_PRECISION_BF16X3 3 /* image tower only: every encoder GEMM as three bf16 MFMA passes over hi + lo halves of both
+                               * operands (x_hi w_hi + x_lo w_hi + x_hi w_lo), fp32 attention and residual: within 1e-4 */
 
 #define MI_KNN_NO_ID UINT64_MAX /* id written for missing results (fewer than k rows) */
 
