@@ -52,6 +52,8 @@ SYMBOLS = {
     "mi_knn_get_rows": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp]),
     "mi_knn_save": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_knn_load": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
+    "mi_knn_delete": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_u64p]),
+    "mi_knn_deleted": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_u64p]),
     "mi_knn_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, c_vp]),
     "mi_knn_search_batched_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, c_vp]),
@@ -74,6 +76,8 @@ SYMBOLS = {
     "mi_knn_sharded_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_sharded_save": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_knn_sharded_load": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
+    "mi_knn_sharded_delete": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_u64p]),
+    "mi_knn_sharded_deleted": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_u64p]),
     "mi_knn_sharded_place": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32),
                                             c_u64p]),
     "mi_knn_sharded_id": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, c_u64p]),
@@ -85,6 +89,8 @@ SYMBOLS = {
     "mi_index_existing": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, c_vp]),
     "mi_index_insert": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_char_p), c_vp, ctypes.c_size_t, c_u64p]),
     "mi_index_adopt": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t]),
+    "mi_index_live_paths": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_index_remove": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, c_u64p]),
     "mi_index_rows_of": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, c_vp, ctypes.c_size_t,
                                         ctypes.POINTER(ctypes.c_size_t)]),
     "mi_index_path": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,

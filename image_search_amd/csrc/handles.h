@@ -184,6 +184,14 @@ struct mi_knn {
     // table must wait for them).  An append only ever writes rows beyond `rows`, so it does not wait
     // for searches in flight: ingest and query streams overlap.
     mi::WorkOrder writes, reads;
+    // Deleted rows (mi_knn_delete): they keep their ids and storage, every search leaves them out.  `dead` = the deleted
+    // local rows, ascending; d_tomb = the same as a bitmap (one bit per row, sized by `cap`, carried over by grow()),
+    // d_dead = the same rows on the device in deletion order (what a two-stage search walks after stage 1).  With `dead`
+    // empty every search runs the code that ran before deletions existed.
+    std::vector<uint32_t> dead;
+    uint64_t* d_tomb = nullptr;
+    uint32_t* d_dead = nullptr;
+    size_t tomb_words = 0, dead_cap = 0;
     std::mutex mu;
 };
 

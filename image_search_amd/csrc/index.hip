@@ -5,6 +5,7 @@
 //   db.insert("image").content(rows)                                   server/src/clip.rs:125-137   mi_index_insert
 //   SELECT id, image_path, embedding FROM image WHERE image_path IN $p server/src/search.rs:43-58   mi_index_rows_of
 //   refine + SELECT id, image_path, knn() ... <|K|> $reference         server/src/search.rs:20-110  mi_index_search
+//   DELETE FROM image WHERE image_path IN $paths                                                    mi_index_remove
 // Row id = insertion ordinal; like the reference's table there is no uniqueness constraint on image_path (the scan
 // loop filters first), a path may own several rows and lookups return all of them in id order.
 // Persistence: `<dir>/embedding.miknn` (mi_knn_save) and `<dir>/image_path.bin`, each written to a temporary name,
@@ -33,15 +34,17 @@ struct mi_index {
     uint32_t dim = 0;
     std::string media_dir;  // the server's media directory: "media/..." in requests maps onto it (search.rs:35-40)
     std::vector<std::string> paths;                            // row id -> image_path
-    std::unordered_map<std::string, std::vector<uint64_t>> rows_of;  // image_path -> row ids, ascending
+    std::unordered_map<std::string, std::vector<uint64_t>> rows_of;  // image_path -> row ids, ascending (live rows only)
+    std::vector<uint8_t> removed;                              // row id -> deleted by mi_index_remove (the table's tombstones)
     std::mutex mu;
 };
 
 namespace {
 
-void add_path(mi_index* ix, const std::string& p) {
-    ix->rows_of[p].push_back(ix->paths.size());
+void add_path(mi_index* ix, const std::string& p, bool removed = false) {
+    if (!removed) ix->rows_of[p].push_back(ix->paths.size());
     ix->paths.push_back(p);
+    ix->removed.push_back(removed ? 1 : 0);
 }
 
 // "media/x.jpg" as the client names it -> the path the row was stored under (search.rs:35-40: only such names are looked up)
@@ -176,6 +179,7 @@ int mi_index_path(mi_index* ix, uint64_t id, int web, char* buf, size_t cap, siz
         if (!ix) fail(MI_ERR_INVALID, "null index handle");
         std::lock_guard<std::mutex> l(ix->mu);
         if (id >= ix->paths.size()) fail(MI_ERR_INVALID, "id %llu out of range (%zu rows)", (unsigned long long)id, ix->paths.size());
+        if (ix->removed[id]) fail(MI_ERR_INVALID, "row %llu was removed (mi_index_remove)", (unsigned long long)id);
         std::string p = ix->paths[id];
         // search.rs:104-109: what goes back to the client is relative to "media/"
         if (web && !ix->media_dir.empty() && p.compare(0, ix->media_dir.size(), ix->media_dir) == 0) p = "media/" + p.substr(ix->media_dir.size());
@@ -312,7 +316,54 @@ int mi_index_load(mi_index* ix, const char* dir) {
         if (rows < paths.size()) fail(MI_ERR_IO, "%s: %llu embeddings for %zu paths", dir, (unsigned long long)rows, paths.size());
         if (rows > paths.size()) knn_truncate(ix->table, paths.size());  // under the table's own lock; rows beyond are rewritten by later inserts
         ix->media_dir = media;
-        for (const auto& p : paths) add_path(ix, p);
+        // the removed rows are the table's deleted ones (saved in embedding.miknn): no lookup finds them
+        uint64_t n_dead = 0;
+        std::vector<uint64_t> dead;
+        if (mi_knn_deleted(ix->table, nullptr, 0, &n_dead) != MI_OK) fail(MI_ERR_INVALID, "%s", mi_last_error());
+        dead.resize(n_dead);
+        if (n_dead && mi_knn_deleted(ix->table, dead.data(), n_dead, &n_dead) != MI_OK) fail(MI_ERR_INVALID, "%s", mi_last_error());
+        std::vector<uint8_t> gone(paths.size(), 0);
+        for (uint64_t id : dead)
+            if (id < gone.size()) gone[id] = 1;
+        for (size_t i = 0; i < paths.size(); ++i) add_path(ix, paths[i], gone[i] != 0);
+    });
+}
+
+// every image_path that still has a row, once each, NUL-terminated one after the other (the prune of a scan compares them
+// with what the walk found); *needed = bytes of the whole list, at most `cap` are written (whole paths only)
+int mi_index_live_paths(mi_index* ix, char* buf, size_t cap, size_t* needed) {
+    return guarded([&] {
+        if (!ix || !needed) fail(MI_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> l(ix->mu);
+        size_t total = 0, at = 0;
+        for (const auto& kv : ix->rows_of) {
+            const size_t n = kv.first.size() + 1;
+            if (buf && at + n <= cap) { std::memcpy(buf + at, kv.first.c_str(), n); at += n; }
+            total += n;
+        }
+        *needed = total;
+    });
+}
+
+// DELETE FROM image WHERE image_path IN $paths: the rows go from the table (mi_knn_delete, ids stay) and from the lookups
+int mi_index_remove(mi_index* ix, const char* const* paths, size_t n, uint64_t* removed_rows) {
+    return guarded([&] {
+        if (!ix || (n && !paths)) fail(MI_ERR_INVALID, "null argument");
+        if (removed_rows) *removed_rows = 0;
+        std::lock_guard<std::mutex> l(ix->mu);
+        std::vector<uint64_t> ids;
+        for (size_t i = 0; i < n; ++i) {
+            if (!paths[i]) fail(MI_ERR_INVALID, "path %zu is null", i);
+            auto it = ix->rows_of.find(paths[i]);
+            if (it != ix->rows_of.end()) ids.insert(ids.end(), it->second.begin(), it->second.end());
+        }
+        if (ids.empty()) return;
+        uint64_t newly = 0;
+        const int e = mi_knn_delete(ix->table, ids.data(), ids.size(), &newly);  // the rows first: a failure changes nothing
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        for (uint64_t id : ids) ix->removed[id] = 1;
+        for (size_t i = 0; i < n; ++i) ix->rows_of.erase(paths[i]);
+        if (removed_rows) *removed_rows = newly;
     });
 }
 

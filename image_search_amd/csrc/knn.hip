@@ -7,6 +7,7 @@
 #include <cstring>
 #include <unistd.h>
 
+#include <iterator>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -51,6 +52,73 @@ hipStream_t own_stream(mi_knn* t) {
     return t->stream;
 }
 
+// ---- deleted rows (handles.h: dead, d_tomb, d_dead) -------------------------------------------------------------
+// the bitmap the kernels consult, or nullptr: a table without deletions runs the kernels it ran before they existed
+const uint64_t* tomb_of(const mi_knn* t) { return t->dead.empty() ? nullptr : t->d_tomb; }
+
+// the bitmap covers `cap` rows (the words it gains are zero); nothing in flight may use the old one
+void tomb_fit(mi_knn* t) {
+    const size_t want = (size_t)((t->cap + 63) / 64);
+    if (t->tomb_words >= want && t->d_tomb) return;
+    t->writes.sync();
+    t->reads.sync();
+    uint64_t* nb = nullptr;
+    HIP_CHECK(hipMalloc((void**)&nb, std::max<size_t>(want, 1) * sizeof(uint64_t)));
+    HIP_CHECK(hipMemset(nb, 0, std::max<size_t>(want, 1) * sizeof(uint64_t)));
+    if (t->d_tomb) {
+        HIP_CHECK(hipMemcpy(nb, t->d_tomb, t->tomb_words * sizeof(uint64_t), hipMemcpyDeviceToDevice));
+        HIP_CHECK(hipFree(t->d_tomb));
+    }
+    t->d_tomb = nb;
+    t->tomb_words = std::max<size_t>(want, 1);
+}
+
+// `rows` (sorted, none deleted yet) join the deleted rows: device list and bitmap on `s`, then the host list
+void tomb_add(mi_knn* t, const std::vector<uint32_t>& rows, hipStream_t s) {
+    if (rows.empty()) return;
+    tomb_fit(t);
+    const size_t have = t->dead.size();
+    // (grown geometrically: a caller that deletes one row per call must not copy the whole list each time)
+    const size_t want = have + rows.size();
+    ensure_keep(t, (void**)&t->d_dead, &t->dead_cap, want > t->dead_cap ? std::max(want, 2 * t->dead_cap) : want, sizeof(uint32_t), have);
+    HIP_CHECK(hipMemcpyAsync(t->d_dead + have, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    const uint32_t n = (uint32_t)rows.size();
+    hipLaunchKernelGGL(knn_tomb_set_kernel, dim3(std::max(1u, std::min<uint32_t>((n + 255) / 256, (uint32_t)t->n_cu * 4))), dim3(256), 0, s,
+                       t->d_dead + have, n, (unsigned long long*)t->d_tomb);
+    HIP_CHECK(hipGetLastError());
+    std::vector<uint32_t> merged(have + rows.size());
+    std::merge(t->dead.begin(), t->dead.end(), rows.begin(), rows.end(), merged.begin());
+    t->dead.swap(merged);
+}
+
+// the device side rebuilt from the host list (after a truncation or a load); waits for the handle's work in flight
+void tomb_rebuild(mi_knn* t) {
+    if (!t->d_tomb && t->dead.empty()) return;
+    tomb_fit(t);
+    t->writes.sync();
+    t->reads.sync();
+    HIP_CHECK(hipMemset(t->d_tomb, 0, t->tomb_words * sizeof(uint64_t)));
+    std::vector<uint32_t> rows;
+    rows.swap(t->dead);
+    tomb_add(t, rows, own_stream(t));
+    HIP_CHECK(hipStreamSynchronize(t->stream));
+}
+
+// id -> local row of this table (its own id space: base, and the block-cyclic map of a shard); false if it holds no such row
+bool local_of(const mi_knn* t, uint64_t id, uint64_t* local) {
+    if (id < t->base) return false;
+    const uint64_t off = id - t->base;
+    uint64_t l = off;
+    if (t->cyc_n > 1 && t->cyc_block) {
+        const uint64_t b = off / t->cyc_block;
+        if (b % t->cyc_n != t->cyc_rank) return false;
+        l = (b / t->cyc_n) * t->cyc_block + off % t->cyc_block;
+    }
+    if (l >= t->rows) return false;
+    *local = l;
+    return true;
+}
+
 void grow(mi_knn* t, uint64_t want_rows) {
     if (want_rows <= t->cap) return;
     uint64_t ncap = std::max<uint64_t>(want_rows, t->cap + t->cap / 2);
@@ -69,6 +137,7 @@ void grow(mi_knn* t, uint64_t want_rows) {
     if (t->table) HIP_CHECK(hipFree(t->table));
     t->table = nt;
     t->cap = ncap;
+    if (t->d_tomb) tomb_fit(t);  // the deletion bitmap keeps one bit per row of capacity
 }
 
 template <class K>
@@ -83,9 +152,16 @@ template <class Top>
 void launch_scan(mi_knn* t, const float* d_q, uint32_t k, const uint64_t* lo, uint64_t* cand, uint32_t blocks,
                  hipStream_t s, const uint32_t* run_if = nullptr, uint32_t gy = 1, QGroup qg = QGroup{}) {
     const size_t lds = (size_t)4 * Top::LDS_KEYS * sizeof(uint64_t);
+    const uint64_t* tomb = tomb_of(t);
     switch (t->dim / 64) {
 #define MI_CASE(NCH)                                                                                   \
     case NCH:                                                                                          \
+        if (tomb) {                                                                                    \
+            allow_lds(knn_scan_kernel<NCH, Top, 0, true>, lds);                                        \
+            hipLaunchKernelGGL((knn_scan_kernel<NCH, Top, 0, true>), dim3(blocks, gy), dim3(256), lds, s, \
+                               t->table, t->rows, d_q, k, lo, cand, (uint32_t*)nullptr, run_if, qg, tomb); \
+            break;                                                                                     \
+        }                                                                                              \
         allow_lds(knn_scan_kernel<NCH, Top>, lds);                                                     \
         hipLaunchKernelGGL((knn_scan_kernel<NCH, Top>), dim3(blocks, gy), dim3(256), lds, s, t->table, \
                            t->rows, d_q, k, lo, cand, (uint32_t*)nullptr, run_if, qg);                 \
@@ -283,6 +359,15 @@ uint32_t* prefilter_pass(mi_knn* t, const float* d_q, uint32_t k, hipStream_t s,
     static const uint32_t ring8_bpc = [] { const char* e = std::getenv("MI_KNN_RING_BPC"); return e ? (uint32_t)std::max(1, std::atoi(e)) : 2u; }();  // A/B
     const float e0 = 4.1f * (float)(t->dim + 8) * 0x1p-24f + 2e-6f;  // fp32 summations, norms, divisions
     const float eps = 0x1p-8f + e0;                                  // bf16: 8 significant bits, unit roundoff 2^-8
+    // deleted rows: behind stage 1 their keys (and sampled keys) become 0xFFFFFFFF; the collect leaves them out
+    const uint64_t* tomb = tomb_of(t);
+    auto kill_keys = [&] {
+        if (!tomb) return;
+        const uint32_t nd = (uint32_t)t->dead.size();
+        hipLaunchKernelGGL(knn_tomb_keys_kernel, dim3(std::max(1u, std::min<uint32_t>((nd + 255) / 256, (uint32_t)t->n_cu * 4))), dim3(256), 0, s,
+                           t->d_dead, nd, t->rows, t->d_keys32, (uint64_t)t->cap, gy, sample_shift ? t->d_skeys : (uint32_t*)nullptr,
+                           sample_stride, sample_shift, tile_rows);
+    };
     if (bytes) {
         uint8_t* m8 = reinterpret_cast<uint8_t*>(t->d_mirror);
         const uint32_t* keys_q = t->d_keys32;   // query y: + y * cap (QGroup)
@@ -312,11 +397,12 @@ uint32_t* prefilter_pass(mi_knn* t, const float* d_q, uint32_t k, hipStream_t s,
                                sample_shift ? t->d_skeys : (uint32_t*)nullptr, sample_shift);                            \
         else                                                                                                             \
             launch_coarse8_batched<NCH>(t, m8, d_q, e0, nq_batch, blocks, s, sample_shift, sample_stride);               \
+        kill_keys();                                                                                                     \
         for (int p = 0; p < 3; ++p)                                                                                      \
             hipLaunchKernelGGL(knn_select_hist_kernel, dim3(hbh, gy), dim3(256), 0, s, keys_h, n_h, k, p, t->d_sel, states, \
                                (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, qgh, 0);    \
         hipLaunchKernelGGL(knn_prefilter_collect8_kernel, dim3(hb, gy), dim3(256), 0, s, keys_q, t->d_cfac8, t->rows, k, \
-                           t->d_sel, states, t->d_rho8, e0, PREF_CAP, t->d_pref_rows, flags, qg);                        \
+                           t->d_sel, states, t->d_rho8, e0, PREF_CAP, t->d_pref_rows, flags, qg, tomb);                  \
         hipLaunchKernelGGL((knn_rescore_kernel<NCH>), dim3(t->n_cu * (gy > 1 ? 2 : 8), gy), dim3(256), 0, s, t->table, d_q, \
                            t->d_pref_rows, flags, PREF_CAP, key32, qg);                                                  \
         break;
@@ -337,10 +423,11 @@ uint32_t* prefilter_pass(mi_knn* t, const float* d_q, uint32_t k, hipStream_t s,
         }                                                                                                                \
         hipLaunchKernelGGL((knn_scan_coarse_kernel<NCH>), dim3(blocks), dim3(256), 0, s, t->d_mirror, t->d_xx, t->rows,  \
                            d_q, t->d_keys32);                                                                            \
+        kill_keys();                                                                                                     \
         for (int p = 0; p < 3; ++p)                                                                                      \
             hipLaunchKernelGGL(knn_select_hist_kernel, dim3(hb), dim3(256), 0, s, t->d_keys32, t->rows, k, p, t->d_sel, states); \
         hipLaunchKernelGGL(knn_prefilter_collect_kernel, dim3(hb), dim3(256), 0, s, t->d_keys32, t->rows, k, t->d_sel,   \
-                           states, 2.0f * eps, PREF_CAP, t->d_pref_rows, flags);                                         \
+                           states, 2.0f * eps, PREF_CAP, t->d_pref_rows, flags, tomb);                                   \
         hipLaunchKernelGGL((knn_rescore_kernel<NCH>), dim3(t->n_cu * 8), dim3(256), 0, s, t->table, d_q, t->d_pref_rows, \
                            flags, PREF_CAP, key32);                                                                      \
         break;
@@ -373,6 +460,8 @@ void select_pass(mi_knn* t, const float* d_q, uint32_t k, uint64_t* keys_out, hi
     ensure(t, (void**)&t->d_sel, &t->sel_cap, (size_t)SEL_WORDS * gy, sizeof(uint32_t));
     ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)4096 * gy, sizeof(uint64_t));
     HIP_CHECK(hipMemsetAsync(t->d_sel, 0, (size_t)SEL_WORDS * gy * sizeof(uint32_t), s));
+    const uint64_t* tomb = tomb_of(t);
+    const uint64_t n_dead = t->dead.size();
     switch (t->dim / 64) {
 #define MI_CASE(NCH)                                                                                          \
     case NCH:                                                                                                 \
@@ -384,14 +473,22 @@ void select_pass(mi_knn* t, const float* d_q, uint32_t k, uint64_t* keys_out, hi
         default: fail(MI_ERR_UNSUPPORTED, "dim %u: built for dim/64 in {1,2,4,8,12,16}", t->dim);
     }
     HIP_CHECK(hipGetLastError());
+    // deleted rows: the scan above is the one a table without deletions runs; their keys then become 0xFFFFFFFF (O(deleted)
+    // work) and the selects below leave those keys out
+    if (tomb) {
+        const uint32_t nd = (uint32_t)t->dead.size();
+        hipLaunchKernelGGL(knn_tomb_keys_kernel, dim3(std::max(1u, std::min<uint32_t>((nd + 255) / 256, (uint32_t)t->n_cu * 4))), dim3(256), 0, s,
+                           t->d_dead, nd, t->rows, t->d_keys32, (uint64_t)t->cap, gy, (uint32_t*)nullptr, (uint64_t)0, 0, 64u);
+        HIP_CHECK(hipGetLastError());
+    }
     const uint32_t hb = (uint32_t)std::min<uint64_t>((uint64_t)t->n_cu * 8, (t->rows + 255) / 256);
     uint32_t* count = t->d_sel + 6 * SEL_BINS;
     SelState* states = reinterpret_cast<SelState*>(t->d_sel + 6 * SEL_BINS + 4);  // 6 states of 24 bytes behind the counter
     for (int p = 0; p < 6; ++p)
         hipLaunchKernelGGL(knn_select_hist_kernel, dim3(hb, gy), dim3(256), 0, s, t->d_keys32, t->rows, k, p, t->d_sel, states, run_if,
-                           (const uint32_t*)nullptr, (const uint32_t*)nullptr, qg, 0);
+                           (const uint32_t*)nullptr, (const uint32_t*)nullptr, qg, 0, tomb, n_dead);
     hipLaunchKernelGGL(knn_select_collect_kernel, dim3(hb, gy), dim3(256), 0, s, t->d_keys32, t->rows, k, t->d_sel, states, t->d_cand, count, run_if,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, qg, 0);
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, qg, 0, tomb, n_dead);
     hipLaunchKernelGGL(knn_select_sort_kernel, dim3(1, gy), dim3(1024), 0, s, t->d_cand, count, k, keys_out, run_if, qg);
     HIP_CHECK(hipGetLastError());
 }
@@ -534,7 +631,9 @@ void search_one(mi_knn* t, const float* d_q, uint32_t k, uint64_t* d_idx, float*
         if (t->pref_adaptive) pref_record(t, s);
         return;
     }
-    if (k > 64 && k <= 4096 && t->select_path) {
+    // a table with deleted rows takes the radix select for k <= 64 too: the scan with the bitmap in it (knn_scan_kernel
+    // TOMB) measured 13 % slower than the plain scan the select path runs
+    if ((k > 64 || tomb_of(t)) && k <= 4096 && t->select_path) {
         select_pass(t, d_q, k, t->d_keys, s);
         hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, 1), dim3(256), 0, s, t->d_keys, k, id_map(t),
                            d_idx, d_dist, (size_t)0, (size_t)0);
@@ -558,8 +657,12 @@ template <int NQ>
 void launch_batched(mi_knn* t, const float* d_q, uint32_t k, uint64_t* cand, uint32_t blocks, hipStream_t s) {
     switch (t->dim / 64) {
         case 12:
-            hipLaunchKernelGGL((knn_scan_batched_kernel<12, NQ>), dim3(blocks), dim3(256), 0, s, t->table, t->rows,
-                               d_q, k, cand);
+            if (const uint64_t* tomb = tomb_of(t))
+                hipLaunchKernelGGL((knn_scan_batched_kernel<12, NQ, true>), dim3(blocks), dim3(256), 0, s, t->table, t->rows,
+                                   d_q, k, cand, tomb);
+            else
+                hipLaunchKernelGGL((knn_scan_batched_kernel<12, NQ>), dim3(blocks), dim3(256), 0, s, t->table, t->rows,
+                                   d_q, k, cand);
             break;
         default: fail(MI_ERR_UNSUPPORTED, "batched search is built for dim 768 (got %u)", t->dim);
     }
@@ -632,6 +735,13 @@ void knn_truncate(mi_knn* t, uint64_t rows) {
     if (rows >= t->rows) return;
     t->rows = rows;
     t->mirror_rows = std::min(t->mirror_rows, rows);
+    // the rows beyond are forgotten, their tombstones with them (a later append reuses those rows, live)
+    const auto cut = std::lower_bound(t->dead.begin(), t->dead.end(), (uint32_t)std::min<uint64_t>(rows, 0xFFFFFFFFull));
+    if (cut != t->dead.end()) {
+        t->dead.erase(cut, t->dead.end());
+        DeviceGuard g(t->device);
+        tomb_rebuild(t);
+    }
 }
 void knn_merge_lists_device(const uint64_t* d_idx_in, const float* d_dist_in, uint32_t lists, uint32_t nq, uint32_t k,
                             size_t idx_stride, size_t dist_stride, uint64_t* d_idx, float* d_dist, hipStream_t s) {
@@ -676,7 +786,7 @@ void mi_knn_free(mi_knn* t) {
     for (void* p : {(void*)t->table, (void*)t->d_q, (void*)t->d_cand, (void*)t->d_tmp, (void*)t->d_keys,
                     (void*)t->d_idx, (void*)t->d_dist, (void*)t->d_keys32, (void*)t->d_sel, (void*)t->d_mirror,
                     (void*)t->d_xx, (void*)t->d_pref_rows, (void*)t->d_pref_keys, (void*)t->d_pref_flag, (void*)t->d_scale8,
-                    (void*)t->d_cfac8, (void*)t->d_rho8, (void*)t->d_g8, (void*)t->d_digits, (void*)t->d_qs, (void*)t->d_skeys})
+                    (void*)t->d_cfac8, (void*)t->d_rho8, (void*)t->d_g8, (void*)t->d_digits, (void*)t->d_qs, (void*)t->d_skeys, (void*)t->d_tomb, (void*)t->d_dead})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : t->pref_ev)
         if (e) (void)hipEventDestroy(e);
@@ -856,10 +966,58 @@ int mi_knn_get_rows(mi_knn* t, uint64_t first, uint64_t n, float* out) {
     });
 }
 
+// ---- deleted rows: DELETE FROM image WHERE id IN $ids (what the reference's database does for a removed image) ----
+int mi_knn_delete(mi_knn* t, const uint64_t* ids, uint64_t n, uint64_t* newly) {
+    return guarded([&] {
+        if (!t) fail(MI_ERR_INVALID, "null table handle");
+        if (newly) *newly = 0;
+        if (n == 0) return;
+        if (!ids) fail(MI_ERR_INVALID, "ids is null");
+        std::lock_guard<std::mutex> l(t->mu);
+        // every id is checked before anything changes: a call with one bad id deletes nothing
+        std::vector<uint32_t> rows((size_t)n);
+        for (uint64_t i = 0; i < n; ++i) {
+            uint64_t local = 0;
+            if (!local_of(t, ids[i], &local))
+                fail(MI_ERR_INVALID, "id %llu is not a row of this table (base %llu, %llu rows)", (unsigned long long)ids[i],
+                     (unsigned long long)t->base, (unsigned long long)t->rows);
+            rows[i] = (uint32_t)local;
+        }
+        std::sort(rows.begin(), rows.end());
+        rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+        std::vector<uint32_t> fresh;
+        std::set_difference(rows.begin(), rows.end(), t->dead.begin(), t->dead.end(), std::back_inserter(fresh));
+        if (fresh.empty()) return;  // already deleted: nothing to do
+        DeviceGuard g(t->device);
+        hipStream_t s = own_stream(t);
+        // a write that changes what searches read: it waits for the searches enqueued before it (any stream), and every
+        // search enqueued after it waits for it (writes)
+        t->writes.begin(s);
+        t->reads.begin(s);
+        tomb_add(t, fresh, s);
+        t->writes.end(s);
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (newly) *newly = fresh.size();
+    });
+}
+
+int mi_knn_deleted(mi_knn* t, uint64_t* ids, uint64_t cap, uint64_t* count) {
+    return guarded([&] {
+        if (!t || !count) fail(MI_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> l(t->mu);
+        *count = t->dead.size();
+        if (!ids) return;
+        const IdMap m = id_map(t);  // monotone in the local row: ascending rows give ascending ids
+        for (uint64_t i = 0; i < std::min<uint64_t>(cap, t->dead.size()); ++i) ids[i] = id_of_local(m, t->dead[i]);
+    });
+}
+
 // ---- persistence of a shard: what SurrealDB's storage does for
 // `image.embedding` (server/src/clip.rs:125-137).  File = 32-byte header {"MIKNNv01", u32 dim,
 // u32 reserved, u64 rows, u64 base} + rows*dim little-endian f32, streamed through a 64 MiB
-// pinned buffer so that neither side needs the table in host memory.
+// pinned buffer so that neither side needs the table in host memory.  A table with deleted rows writes "MIKNNv02":
+// the same header and rows, then u64 count + count u64 local rows, ascending (an older library refuses such a file
+// instead of bringing the deleted rows back); without deletions the file is the MIKNNv01 file, byte for byte.
 namespace {
 struct KnnFileHeader { char magic[8]; uint32_t dim, reserved; uint64_t rows, base; };
 static_assert(sizeof(KnnFileHeader) == 32, "header layout");
@@ -890,7 +1048,7 @@ int mi_knn_save(mi_knn* t, const char* path) {
             File f(tmp.c_str(), "wb");
             if (!f.f) fail(MI_ERR_IO, "cannot create %s", tmp.c_str());
             KnnFileHeader h{};
-            std::memcpy(h.magic, "MIKNNv01", 8);
+            std::memcpy(h.magic, t->dead.empty() ? "MIKNNv01" : "MIKNNv02", 8);
             h.dim = t->dim; h.rows = t->rows; h.base = t->base;
             if (std::fwrite(&h, sizeof h, 1, f.f) != 1) fail(MI_ERR_IO, "write to %s failed", tmp.c_str());
             const size_t total = (size_t)t->rows * t->dim * sizeof(float);
@@ -903,6 +1061,12 @@ int mi_knn_save(mi_knn* t, const char* path) {
                     HIP_CHECK(hipStreamSynchronize(t->stream));
                     if (std::fwrite(buf.p, 1, n, f.f) != n) fail(MI_ERR_IO, "write to %s failed (disk full?)", tmp.c_str());
                 }
+            }
+            if (!t->dead.empty()) {
+                const uint64_t cnt = t->dead.size();
+                std::vector<uint64_t> rows(t->dead.begin(), t->dead.end());
+                if (std::fwrite(&cnt, 8, 1, f.f) != 1 || std::fwrite(rows.data(), 8, rows.size(), f.f) != rows.size())
+                    fail(MI_ERR_IO, "write to %s failed (disk full?)", tmp.c_str());
             }
             if (std::fflush(f.f) != 0 || fsync(fileno(f.f)) != 0) fail(MI_ERR_IO, "flush of %s failed", tmp.c_str());
             FILE* fp = f.f;
@@ -929,8 +1093,9 @@ int mi_knn_load(mi_knn* t, const char* path) {
         File f(path, "rb");
         if (!f.f) fail(MI_ERR_IO, "cannot open %s", path);
         KnnFileHeader h{};
-        if (std::fread(&h, sizeof h, 1, f.f) != 1 || std::memcmp(h.magic, "MIKNNv01", 8) != 0)
-            fail(MI_ERR_IO, "%s is not a MIKNNv01 shard file", path);
+        if (std::fread(&h, sizeof h, 1, f.f) != 1 || (std::memcmp(h.magic, "MIKNNv01", 8) != 0 && std::memcmp(h.magic, "MIKNNv02", 8) != 0))
+            fail(MI_ERR_IO, "%s is not a MIKNNv01 / MIKNNv02 shard file", path);
+        const bool v2 = std::memcmp(h.magic, "MIKNNv02", 8) == 0;
         if (h.dim != t->dim) fail(MI_ERR_INVALID, "%s holds dim %u rows, the table has dim %u", path, h.dim, t->dim);
         if (t->rows == 0) t->base = h.base;  // an empty table takes the shard's id range
         else if (h.base != t->base + t->rows)
@@ -938,6 +1103,7 @@ int mi_knn_load(mi_knn* t, const char* path) {
                  (unsigned long long)h.base, (unsigned long long)t->base, (unsigned long long)t->rows);
         const size_t total = (size_t)h.rows * t->dim * sizeof(float);
         if (total == 0) return;
+        if (t->rows + h.rows > 0xFFFFFFFFull) fail(MI_ERR_UNSUPPORTED, "a shard holds at most 2^32-1 rows");
         grow(t, t->rows + h.rows);
         PinnedBuf buf(std::min(total, IO_CHUNK));
         char* dst = (char*)(t->table + t->rows * t->dim);
@@ -947,7 +1113,24 @@ int mi_knn_load(mi_knn* t, const char* path) {
             HIP_CHECK(hipMemcpyAsync(dst + off, buf.p, n, hipMemcpyHostToDevice, t->stream));
             HIP_CHECK(hipStreamSynchronize(t->stream));
         }
+        // MIKNNv02: the file's deleted rows, read (and checked) before anything of the file counts
+        std::vector<uint32_t> dead;
+        if (v2) {
+            uint64_t cnt = 0;
+            if (std::fread(&cnt, 8, 1, f.f) != 1 || cnt > h.rows) fail(MI_ERR_IO, "%s: truncated or corrupt list of deleted rows", path);
+            std::vector<uint64_t> rows((size_t)cnt);
+            if (cnt && std::fread(rows.data(), 8, (size_t)cnt, f.f) != (size_t)cnt) fail(MI_ERR_IO, "%s is truncated", path);
+            dead.reserve((size_t)cnt);
+            for (uint64_t i = 0; i < cnt; ++i) {
+                if (rows[i] >= h.rows || (i && rows[i] <= rows[i - 1])) fail(MI_ERR_IO, "%s: corrupt list of deleted rows", path);
+                dead.push_back((uint32_t)(t->rows + rows[i]));  // the file's rows continue the table
+            }
+        }
         t->rows += h.rows;
+        if (!dead.empty()) {
+            tomb_add(t, dead, t->stream);
+            HIP_CHECK(hipStreamSynchronize(t->stream));
+        }
     });
 }
 

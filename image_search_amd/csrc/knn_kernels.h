@@ -241,13 +241,17 @@ struct QGroup {
 // KEYS = 0: per-wave top-k lists into cand.  KEYS = 1: no selection here, every row's 32-bit distance key goes to
 // all_keys (one 256-byte store per tile: +2 % on the scan; holding the keys of 8 tiles in LDS and flushing them
 // together was measured at +17 %) for knn_select_* below.
-template <int NCH, class Top, int KEYS = 0>
+// TOMB (a table with deleted rows, mi_knn_delete; KEYS = 0 only — the select path fixes the keys of deleted rows after the
+// plain scan, knn_tomb_keys_kernel): tomb[tile] is the tile's 64-bit word of the deletion bitmap; a deleted row's key is
+// KEY_MAX, as for a row beyond the table.  TOMB = false is the code that ran before deletions existed.
+template <int NCH, class Top, int KEYS = 0, bool TOMB = false>
 __global__ __launch_bounds__(256, 2) void knn_scan_kernel(const float* __restrict__ table, uint64_t n_rows,
                                                        const float* __restrict__ q, uint32_t k,
                                                        const uint64_t* __restrict__ lo_ptr,
                                                        uint64_t* __restrict__ cand,
                                                        uint32_t* __restrict__ all_keys = nullptr,
-                                                       const uint32_t* __restrict__ run_if = nullptr, QGroup qg = QGroup{}) {
+                                                       const uint32_t* __restrict__ run_if = nullptr, QGroup qg = QGroup{},
+                                                       const uint64_t* __restrict__ tomb = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int DIM = NCH * 64;
     // query blockIdx.y of a group that shares this launch (QGroup: all strides 0 for a single query)
@@ -303,13 +307,19 @@ __global__ __launch_bounds__(256, 2) void knn_scan_kernel(const float* __restric
             load_row(xa, row0 + (it + 2 < 16 ? it + 2 : 15));
             reduce_row(xb, it + 1);
         }
+        // (the tile's bitmap word after its rows; wherever it is read, hipcc schedules the row loop of this variant differently
+        // from the plain one — 114 against 136 VGPRs at NCH 12 — and it measured 13 % slower at 10 M rows: DESIGN.md 5.13)
+        uint64_t dead_w = 0;
+        if constexpr (TOMB) dead_w = tomb[tile];
         const uint64_t r = (tile << 6) + lane;
         const float dist = 1.0f - mydot / (sq * sqrtf(myxx));
+        const bool dead = TOMB && ((dead_w >> lane) & 1ull);
         if constexpr (KEYS == 1) {
+            static_assert(!TOMB, "the select path fixes deleted keys after the scan");
             if (r < n_rows) all_keys[r] = dist_to_u32(dist);
             continue;
         }
-        uint64_t key = r < n_rows ? make_key(dist, (uint32_t)r) : KEY_MAX;
+        uint64_t key = (r < n_rows && !dead) ? make_key(dist, (uint32_t)r) : KEY_MAX;
         if (use_lo && key <= lo) key = KEY_MAX;
         top.offer(key);
     }
@@ -328,6 +338,13 @@ __global__ __launch_bounds__(256, 2) void knn_scan_kernel(const float* __restric
 // is shared by more rows than fit (exact duplicates).  Then one pass collects the keys <= the k-th and one block
 // sorts them.  Independent of the insertion order and of k.
 constexpr int SEL_BINS = 2048;
+// A deleted row's 32-bit key is 0xFFFFFFFF, the key of a NaN distance; among those keys the row digits break ties, so a
+// deleted row must leave the histograms and the collect altogether (ranked last it would still displace a live NaN row).
+// key = (distance key << 32) | row; the bitmap is consulted only for keys equal to 0xFFFFFFFF.
+__device__ __forceinline__ bool tomb_dead(const uint64_t* __restrict__ tomb, uint64_t key) {
+    const uint32_t row = (uint32_t)key;
+    return (uint32_t)(key >> 32) == 0xFFFFFFFFu && ((tomb[row >> 6] >> (row & 63)) & 1ull);
+}
 __device__ __forceinline__ int sel_shift(int p) { return p == 0 ? 53 : p == 1 ? 42 : p == 2 ? 32 : p == 3 ? 21 : p == 4 ? 10 : 0; }
 __device__ __forceinline__ uint32_t sel_mask(int p) { return (p == 2 || p == 5) ? 0x3FFu : 0x7FFu; }
 
@@ -389,7 +406,8 @@ __global__ __launch_bounds__(256) void knn_select_hist_kernel(const uint32_t* __
                                                               const uint32_t* __restrict__ run_if = nullptr,
                                                               const uint32_t* __restrict__ n_dev = nullptr,
                                                               const uint32_t* __restrict__ row_of = nullptr, QGroup qg = QGroup{},
-                                                              int keys_are_rows = 0) {
+                                                              int keys_are_rows = 0, const uint64_t* __restrict__ tomb = nullptr,
+                                                              uint64_t n_dead = 0) {
     __shared__ uint32_t lh[SEL_BINS];
     // query blockIdx.y of a group (QGroup); keys_are_rows: `keys` are the candidates' exact keys (they live behind the rows)
     keys += (size_t)blockIdx.y * (keys_are_rows ? qg.rows : qg.keys);
@@ -400,7 +418,7 @@ __global__ __launch_bounds__(256) void knn_select_hist_kernel(const uint32_t* __
     if (row_of) row_of += (size_t)blockIdx.y * qg.rows;
     if (run_if && *run_if == 0u) return;
     if (n_dev) n_rows = min(n_rows, (uint64_t)*n_dev);
-    const SelState st = sel_advance(hist, states, p, k, n_rows);
+    const SelState st = sel_advance(hist, states, p, k, n_rows - n_dead);
     if (st.done) return;
     for (int j = threadIdx.x; j < SEL_BINS; j += 256) lh[j] = 0;
     __syncthreads();
@@ -408,6 +426,7 @@ __global__ __launch_bounds__(256) void knn_select_hist_kernel(const uint32_t* __
     const uint32_t mk = sel_mask(p);
     const uint64_t hi_mask = p == 0 ? 0ull : ~0ull << sel_shift(p - 1);
     auto count_key = [&](uint64_t key, bool live) {
+        if (tomb && live) live = !tomb_dead(tomb, key);
         const bool hit = live && (key & hi_mask) == st.prefix;
         const uint32_t bin = (uint32_t)(key >> sh) & mk;
         // cosine distances of a corpus crowd into a handful of leading digits: when every hit of the wave falls into
@@ -454,7 +473,8 @@ __global__ __launch_bounds__(256) void knn_select_collect_kernel(const uint32_t*
                                                                  const uint32_t* __restrict__ run_if = nullptr,
                                                                  const uint32_t* __restrict__ n_dev = nullptr,
                                                                  const uint32_t* __restrict__ row_of = nullptr, QGroup qg = QGroup{},
-                                                                 int keys_are_rows = 0) {
+                                                                 int keys_are_rows = 0, const uint64_t* __restrict__ tomb = nullptr,
+                                                                 uint64_t n_dead = 0) {
     keys += (size_t)blockIdx.y * (keys_are_rows ? qg.rows : qg.keys);
     hist += (size_t)blockIdx.y * qg.sel;
     states = reinterpret_cast<SelState*>(reinterpret_cast<uint32_t*>(states) + (size_t)blockIdx.y * qg.sel);
@@ -465,14 +485,14 @@ __global__ __launch_bounds__(256) void knn_select_collect_kernel(const uint32_t*
     if (row_of) row_of += (size_t)blockIdx.y * qg.rows;
     if (run_if && *run_if == 0u) return;
     if (n_dev) n_rows = min(n_rows, (uint64_t)*n_dev);
-    const SelState st = sel_advance(hist, states, 6, k, n_rows);
+    const SelState st = sel_advance(hist, states, 6, k, n_rows - n_dead);
     // the k-th key: the chosen digits; when a whole group was taken its lower digits are free (all ones);
     // fewer rows than k: every key
     uint64_t T = KEY_MAX;
-    if (n_rows >= k) T = st.fixed == 6 ? st.prefix : (st.prefix | ((1ull << sel_shift(st.fixed - 1)) - 1ull));
+    if (n_rows - n_dead >= k) T = st.fixed == 6 ? st.prefix : (st.prefix | ((1ull << sel_shift(st.fixed - 1)) - 1ull));
     for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (uint64_t)gridDim.x * 256) {
         const uint64_t key = ((uint64_t)keys[r] << 32) | (row_of ? row_of[r] : (uint32_t)r);
-        if (key <= T) {
+        if (key <= T && !(tomb && tomb_dead(tomb, key))) {
             const uint32_t at = atomicAdd(count, 1u);
             if (at < k) out[at] = key;
         }
@@ -636,7 +656,7 @@ __global__ __launch_bounds__(256, 2) void knn_scan_coarse_kernel(const uint16_t*
 __global__ __launch_bounds__(256) void knn_prefilter_collect_kernel(const uint32_t* __restrict__ keys, uint64_t n_rows, uint32_t k,
                                                                     const uint32_t* __restrict__ hist, SelState* __restrict__ states,
                                                                     float band, uint32_t cap, uint32_t* __restrict__ cand_rows,
-                                                                    uint32_t* __restrict__ count) {
+                                                                    uint32_t* __restrict__ count, const uint64_t* __restrict__ tomb = nullptr) {
     const SelState st = sel_advance(hist, states, 3, k, n_rows);
     uint32_t B = 0xFFFFFFFFu;  // fewer rows than k, or a NaN at rank k: everything
     if (n_rows >= k && st.fixed >= 1) {
@@ -650,7 +670,7 @@ __global__ __launch_bounds__(256) void knn_prefilter_collect_kernel(const uint32
     for (uint64_t r0 = (uint64_t)blockIdx.x * 256 + (threadIdx.x & ~63u); r0 < n_rows; r0 += stride) {
         const uint64_t r = r0 + (threadIdx.x & 63);
         const uint32_t key = r < n_rows ? keys[r] : 0xFFFFFFFFu;
-        const bool take = r < n_rows && (key <= B || key == PREF_MARK);
+        const bool take = r < n_rows && (key <= B || key == PREF_MARK) && !(tomb && tomb_dead(tomb, ((uint64_t)key << 32) | r));
         const unsigned long long m = __ballot(take);
         if (m == 0ull) continue;
         uint32_t base = 0;
@@ -1154,7 +1174,8 @@ __global__ __launch_bounds__(256) void knn_prefilter_collect8_kernel(const uint3
                                                                      uint64_t n_rows, uint32_t k, const uint32_t* __restrict__ hist,
                                                                      SelState* __restrict__ states, const float* __restrict__ rho_ptr,
                                                                      float e0, uint32_t cap, uint32_t* __restrict__ cand_rows,
-                                                                     uint32_t* __restrict__ count, QGroup qg = QGroup{}) {
+                                                                     uint32_t* __restrict__ count, QGroup qg = QGroup{},
+                                                                     const uint64_t* __restrict__ tomb = nullptr) {
     keys += (size_t)blockIdx.y * qg.keys;
     hist += (size_t)blockIdx.y * qg.sel;
     states = reinterpret_cast<SelState*>(reinterpret_cast<uint32_t*>(states) + (size_t)blockIdx.y * qg.sel);
@@ -1177,6 +1198,7 @@ __global__ __launch_bounds__(256) void knn_prefilter_collect8_kernel(const uint3
         if (r < n_rows) {
             const uint32_t key = keys[r];
             take = key == PREF_MARK || key == 0xFFFFFFFFu || !(u32_to_dist(key) - 2.0f * (cfac[r] * rho + e0) > tau);
+            if (tomb && tomb_dead(tomb, ((uint64_t)key << 32) | r)) take = false;   // a deleted row is never a candidate
         }
         const unsigned long long m = __ballot(take);
         if (m == 0ull) continue;
@@ -1235,10 +1257,12 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
 
 // Q queries in one pass over the table (throughput variant).  Same per-row
 // arithmetic per query, so results equal Q single-query scans.  q: [NQ][dim].
-template <int NCH, int NQ>
+// TOMB: deleted rows (the deletion bitmap, one word per tile) offer KEY_MAX, as in knn_scan_kernel
+template <int NCH, int NQ, bool TOMB = false>
 __global__ __launch_bounds__(256) void knn_scan_batched_kernel(const float* __restrict__ table, uint64_t n_rows,
                                                                const float* __restrict__ q, uint32_t k,
-                                                               uint64_t* __restrict__ cand /*[NQ][waves][k]*/) {
+                                                               uint64_t* __restrict__ cand /*[NQ][waves][k]*/,
+                                                               const uint64_t* __restrict__ tomb = nullptr) {
     constexpr int DIM = NCH * 64;
     __shared__ __attribute__((aligned(16))) float qs[NQ * DIM];
     const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
@@ -1265,6 +1289,8 @@ __global__ __launch_bounds__(256) void knn_scan_batched_kernel(const float* __re
     const uint64_t n_tiles = (n_rows + 63) >> 6;
     for (uint64_t tile = wave; tile < n_tiles; tile += n_waves) {
         float mydot[NQ], myxx = 1.0f;
+        uint64_t dead_w = 0;
+        if constexpr (TOMB) dead_w = tomb[tile];
 #pragma unroll
         for (int u = 0; u < NQ; ++u) mydot[u] = 0.0f;
         const uint64_t row0 = (tile << 6) + 16 * g;
@@ -1300,14 +1326,43 @@ __global__ __launch_bounds__(256) void knn_scan_batched_kernel(const float* __re
         }
         const uint64_t r = (tile << 6) + lane;
         const float sx = sqrtf(myxx);
+        const bool dead = TOMB && ((dead_w >> lane) & 1ull);
 #pragma unroll
         for (int u = 0; u < NQ; ++u) {
             const float dist = 1.0f - mydot[u] / (sq[u] * sx);
-            top[u].offer(r < n_rows ? make_key(dist, (uint32_t)r) : KEY_MAX);
+            top[u].offer((r < n_rows && !dead) ? make_key(dist, (uint32_t)r) : KEY_MAX);
         }
     }
 #pragma unroll
     for (int u = 0; u < NQ; ++u) top[u].store(cand + ((size_t)u * n_waves + wave) * k);
+}
+
+// ---- deleted rows (mi_knn_delete) ----------------------------------------------------
+// rows[0, n) into the deletion bitmap (one bit per row, a 64-bit word per 64-row tile)
+__global__ __launch_bounds__(256) void knn_tomb_set_kernel(const uint32_t* __restrict__ rows, uint32_t n,
+                                                           unsigned long long* __restrict__ bitmap) {
+    for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256)
+        atomicOr(&bitmap[rows[j] >> 6], 1ull << (rows[j] & 63));
+}
+// Behind stage 1 of a two-stage search (and behind the select path's scan: its exact keys, no sample): every deleted row's key becomes 0xFFFFFFFF (rank last, never a mark) in each
+// of the gy queries' key arrays (stride key_stride), and, where the row's tile is sampled (every 2^sample_shift-th tile of
+// tile_rows rows, stored compactly: knn_scan_coarse8_kernel / knn_scan_coarse8_mfma_kernel), in the sampled keys too.  The
+// collect kernels then leave 0xFFFFFFFF keys of deleted rows out, so such a row neither tightens the threshold nor becomes
+// a candidate.
+__global__ __launch_bounds__(256) void knn_tomb_keys_kernel(const uint32_t* __restrict__ dead, uint32_t n_dead, uint64_t n_rows,
+                                                            uint32_t* __restrict__ keys, uint64_t key_stride, uint32_t gy,
+                                                            uint32_t* __restrict__ skeys, uint64_t skey_stride, int sample_shift,
+                                                            uint32_t tile_rows) {
+    for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < n_dead; j += gridDim.x * 256) {
+        const uint64_t r = dead[j];
+        if (r >= n_rows) continue;
+        for (uint32_t y = 0; y < gy; ++y) keys[y * key_stride + r] = 0xFFFFFFFFu;
+        if (!skeys) continue;
+        const uint64_t tile = r / tile_rows;
+        if ((tile & ((1ull << sample_shift) - 1)) != 0) continue;
+        const uint64_t at = (tile >> sample_shift) * tile_rows + r % tile_rows;
+        for (uint32_t y = 0; y < gy; ++y) skeys[y * skey_stride + at] = 0xFFFFFFFFu;
+    }
 }
 
 // ---- tree reduction of candidate lists ----------------------------------------------

@@ -554,6 +554,69 @@ int mi_knn_sharded_sync(mi_knn_sharded* t) {
     });
 }
 
+}  // extern "C"
+
+// ---- deleted rows: every shard is an mi_knn whose ids are the global ones (base 0, the block-cyclic map) ------------
+namespace {
+// t->mu held: every id checked first (a call with one bad id deletes nothing), then each shard takes its own ids
+uint64_t delete_locked(mi_knn_sharded* t, const uint64_t* ids, uint64_t n) {
+    std::vector<std::vector<uint64_t>> per(t->n());
+    for (uint64_t i = 0; i < n; ++i) {
+        if (ids[i] >= t->rows)
+            fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)ids[i], (unsigned long long)t->rows);
+        uint32_t s; uint64_t local;
+        sharded_place(t, ids[i], &s, &local);
+        per[s].push_back(ids[i]);
+    }
+    uint64_t newly = 0;
+    for (uint32_t s = 0; s < t->n(); ++s) {
+        if (per[s].empty()) continue;
+        uint64_t m = 0;
+        const int e = mi_knn_delete(t->shard[s], per[s].data(), per[s].size(), &m);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        newly += m;
+    }
+    return newly;
+}
+// t->mu held: the deleted global ids, ascending
+std::vector<uint64_t> deleted_locked(mi_knn_sharded* t) {
+    std::vector<uint64_t> all;
+    for (mi_knn* sh : t->shard) {
+        uint64_t c = 0;
+        if (mi_knn_deleted(sh, nullptr, 0, &c) != MI_OK) fail(MI_ERR_INVALID, "%s", mi_last_error());
+        const size_t at = all.size();
+        all.resize(at + c);
+        if (c && mi_knn_deleted(sh, all.data() + at, c, &c) != MI_OK) fail(MI_ERR_INVALID, "%s", mi_last_error());
+    }
+    std::sort(all.begin(), all.end());
+    return all;
+}
+}  // namespace
+
+extern "C" {
+
+int mi_knn_sharded_delete(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint64_t* newly) {
+    return guarded([&] {
+        if (!t) fail(MI_ERR_INVALID, "null table handle");
+        if (newly) *newly = 0;
+        if (n == 0) return;
+        if (!ids) fail(MI_ERR_INVALID, "ids is null");
+        std::lock_guard<std::mutex> l(t->mu);
+        const uint64_t m = delete_locked(t, ids, n);
+        if (newly) *newly = m;
+    });
+}
+
+int mi_knn_sharded_deleted(mi_knn_sharded* t, uint64_t* ids, uint64_t cap, uint64_t* count) {
+    return guarded([&] {
+        if (!t || !count) fail(MI_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> l(t->mu);
+        const std::vector<uint64_t> all = deleted_locked(t);
+        *count = all.size();
+        if (ids) std::copy(all.begin(), all.begin() + std::min<uint64_t>(cap, all.size()), ids);
+    });
+}
+
 // Every row of `src` into the EMPTY `dst` (another shard count, device set or block size) without leaving the devices:
 // src's blocks are walked in global order and each contiguous run is routed by append_device_locked — a device-to-device
 // copy when source and destination shard share a GPU, hipMemcpyPeerAsync over xGMI otherwise.  src is unchanged.
@@ -584,6 +647,8 @@ int mi_knn_sharded_rebalance(mi_knn_sharded* dst, mi_knn_sharded* src) {
                 DeviceGuard g(from->device);
                 if (from->stream) HIP_CHECK(hipStreamSynchronize(from->stream));
             }
+            const std::vector<uint64_t> dead = deleted_locked(src);  // global ids: the same rows in the new layout
+            if (!dead.empty()) delete_locked(dst, dead.data(), dead.size());
         } catch (...) {
             dst->rows = 0;
             roll_back(dst);
@@ -592,8 +657,8 @@ int mi_knn_sharded_rebalance(mi_knn_sharded* dst, mi_knn_sharded* src) {
     });
 }
 
-// Persistence: one MIKNNv01 file per shard and GENERATION, `<prefix>.g<gen>.<s>of<n>.miknn`, plus the manifest
-// `<prefix>.shards` (text: n, block, rows, dim, gen) written last through a temporary + fsync + rename.  Until that rename
+// Persistence: one shard file per shard and GENERATION, `<prefix>.g<gen>.<s>of<n>.miknn` (mi_knn_save: MIKNNv01, or
+// MIKNNv02 for a shard with deleted rows), plus the manifest `<prefix>.shards` (text: n, block, rows, dim, gen) written last through a temporary + fsync + rename.  Until that rename
 // the previous generation's files are untouched and still named by the previous manifest; afterwards they are deleted.
 int mi_knn_sharded_save(mi_knn_sharded* t, const char* prefix) {
     return guarded([&] {
@@ -677,6 +742,25 @@ int mi_knn_sharded_load(mi_knn_sharded* t, const char* prefix) {
             if (!fs[s]) fail(MI_ERR_IO, "cannot open %s", file_of(s).c_str());
         }
         std::vector<float> buf((size_t)ob * t->dim);
+        // the deleted rows of each old shard (MIKNNv02 trailer behind its rows), as global ids
+        std::vector<uint64_t> dead;
+        for (unsigned s = 0; s < on; ++s) {
+            char hdr[32];
+            if (std::fread(hdr, 1, 32, fs[s]) != 32 || (std::memcmp(hdr, "MIKNNv01", 8) != 0 && std::memcmp(hdr, "MIKNNv02", 8) != 0))
+                fail(MI_ERR_IO, "%s is not a MIKNNv01 / MIKNNv02 shard file", file_of(s).c_str());
+            if (std::memcmp(hdr, "MIKNNv02", 8) != 0) continue;
+            uint64_t srows = 0, cnt = 0;
+            std::memcpy(&srows, hdr + 16, 8);
+            if (fseeko(fs[s], (off_t)(32 + srows * t->dim * 4), SEEK_SET) != 0 || std::fread(&cnt, 8, 1, fs[s]) != 1 || cnt > srows)
+                fail(MI_ERR_IO, "%s: truncated or corrupt list of deleted rows", file_of(s).c_str());
+            std::vector<uint64_t> rows((size_t)cnt);
+            if (cnt && std::fread(rows.data(), 8, (size_t)cnt, fs[s]) != (size_t)cnt) fail(MI_ERR_IO, "%s is truncated", file_of(s).c_str());
+            for (uint64_t local : rows) {
+                const uint64_t g = ((local / ob) * on + s) * ob + local % ob;   // the old layout's block-cyclic map
+                if (local >= srows || g >= orows) fail(MI_ERR_IO, "%s: corrupt list of deleted rows", file_of(s).c_str());
+                dead.push_back(g);
+            }
+        }
         try {
             for (uint64_t r = 0; r < orows; r += ob) {
                 const uint64_t len = std::min<uint64_t>(ob, orows - r), blk = r / ob;
@@ -686,6 +770,10 @@ int mi_knn_sharded_load(mi_knn_sharded* t, const char* prefix) {
                     std::fread(buf.data(), 4, (size_t)len * t->dim, fs[s]) != (size_t)len * t->dim)
                     fail(MI_ERR_IO, "%s is truncated", file_of(s).c_str());
                 const int e = mi_knn_sharded_append(t, buf.data(), len, nullptr);
+                if (e != MI_OK) fail(e, "%s", mi_last_error());
+            }
+            if (!dead.empty()) {
+                const int e = mi_knn_sharded_delete(t, dead.data(), dead.size(), nullptr);
                 if (e != MI_OK) fail(e, "%s", mi_last_error());
             }
         } catch (...) {

@@ -117,6 +117,15 @@ class EmbeddingTable {
     ~EmbeddingTable() { mi_knn_free(h_); }
     void insert(const std::vector<float>& rows) { check(mi_knn_append(h_, rows.data(), rows.size() / dim_)); }
     uint64_t size() const { uint64_t n = 0; check(mi_knn_size(h_, &n)); return n; }
+    // DELETE FROM image WHERE id IN $ids: returns the rows that were live; ids stay, searches leave the rows out
+    uint64_t remove_ids(const std::vector<uint64_t>& ids) { uint64_t n = 0; check(mi_knn_delete(h_, ids.data(), ids.size(), &n)); return n; }
+    std::vector<uint64_t> deleted() const {
+        uint64_t n = 0;
+        check(mi_knn_deleted(h_, nullptr, 0, &n));
+        std::vector<uint64_t> v(n);
+        if (n) check(mi_knn_deleted(h_, v.data(), n, &n));
+        return v;
+    }
     // what the database's storage did for the reference: one file per shard
     void save(const std::string& path) const { check(mi_knn_save(h_, path.c_str())); }
     void load(const std::string& path) { check(mi_knn_load(h_, path.c_str())); }
@@ -150,6 +159,13 @@ class ImageIndex {
     ~ImageIndex() { mi_index_free(h_); }
     mi_index* handle() const { return h_; }
     uint64_t size() const { uint64_t n = 0; check(mi_index_size(h_, &n)); return n; }
+    // DELETE FROM image WHERE image_path IN $paths: returns the rows removed
+    uint64_t remove(const std::vector<std::string>& paths) {
+        const auto p = ptrs(paths);
+        uint64_t n = 0;
+        check(mi_index_remove(h_, p.data(), p.size(), &n));
+        return n;
+    }
     // SELECT image_path FROM image WHERE image_path IN $paths  (server/src/clip.rs:74-83)
     std::vector<bool> existing(const std::vector<std::string>& paths) const {
         std::vector<uint8_t> e(paths.size());
@@ -205,6 +221,15 @@ class ShardedTable {
         return first;
     }
     uint64_t size() const { uint64_t n = 0; check(mi_knn_sharded_info(h_, &n, nullptr, nullptr, nullptr)); return n; }
+    // DELETE FROM image WHERE id IN $ids on global ids
+    uint64_t remove_ids(const std::vector<uint64_t>& ids) { uint64_t n = 0; check(mi_knn_sharded_delete(h_, ids.data(), ids.size(), &n)); return n; }
+    std::vector<uint64_t> deleted() const {
+        uint64_t n = 0;
+        check(mi_knn_sharded_deleted(h_, nullptr, 0, &n));
+        std::vector<uint64_t> v(n);
+        if (n) check(mi_knn_sharded_deleted(h_, v.data(), n, &n));
+        return v;
+    }
     void set_option(const std::string& key, int value) { check(mi_knn_sharded_set_option(h_, key.c_str(), value)); }
     // {searches, ncclAllGather calls, transport copies, device merges} issued so far
     std::vector<uint64_t> stats() const { std::vector<uint64_t> v(4); check(mi_knn_sharded_stats(h_, v.data())); return v; }

@@ -119,6 +119,15 @@ class EmbeddingTable:
         check(lib().mi_knn_get_rows(self._h, first, n, out.ctypes.data))
         return out
 
+    def delete(self, ids) -> int:
+        """`DELETE FROM image WHERE id IN $ids` (mi_knn_delete): the rows keep their ids and storage, no later search
+        returns them.  All ids must be rows of the table (else nothing changes).  Returns the rows that were live."""
+        return _delete(lib().mi_knn_delete, self._h, ids)
+
+    def deleted(self) -> np.ndarray:
+        """ids of the deleted rows, ascending (mi_knn_deleted)"""
+        return _deleted(lib().mi_knn_deleted, self._h)
+
     def knn(self, reference: np.ndarray, k: int = K_REFERENCE):
         """`WHERE embedding <|k|> $reference` (search.rs:70-77): (ids, cosine distances),
         ascending distance then id.  reference: [dim] or [nq,dim]."""
@@ -133,6 +142,22 @@ class EmbeddingTable:
     def knn_device(self, d_q: int, nq: int, k: int, d_idx: int, d_dist: int, stream: int = 0, batched: bool = False):
         fn = lib().mi_knn_search_batched_device if batched else lib().mi_knn_search_device
         check(fn(self._h, d_q, nq, k, d_idx, d_dist, stream))
+
+
+def _delete(fn, h, ids) -> int:
+    a = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
+    newly = ctypes.c_uint64()
+    check(fn(h, a.ctypes.data if a.size else None, a.size, ctypes.byref(newly)))
+    return newly.value
+
+
+def _deleted(fn, h) -> np.ndarray:
+    n = ctypes.c_uint64()
+    check(fn(h, None, 0, ctypes.byref(n)))
+    out = np.empty(n.value, np.uint64)
+    if n.value:
+        check(fn(h, out.ctypes.data, n.value, ctypes.byref(n)))
+    return out
 
 
 class PinnedBuffer:
@@ -334,6 +359,13 @@ class ShardedTable:
         check(lib().mi_knn_sharded_search(self._h, q.ctypes.data, q.shape[0], k, idx.ctypes.data, dist.ctypes.data))
         return (idx[0], dist[0]) if single else (idx, dist)
 
+    def delete(self, ids) -> int:
+        """EmbeddingTable.delete on global ids (mi_knn_sharded_delete)"""
+        return _delete(lib().mi_knn_sharded_delete, self._h, ids)
+
+    def deleted(self) -> np.ndarray:
+        return _deleted(lib().mi_knn_sharded_deleted, self._h)
+
     def save(self, prefix: str):
         check(lib().mi_knn_sharded_save(self._h, prefix.encode()))
 
@@ -469,6 +501,7 @@ class ImageIndex:
       `db.insert("image").content(rows)`                                     -> insert()
       `SELECT id, image_path, embedding FROM image WHERE image_path IN $p`   -> embeddings_of()
       `SELECT id, image_path, knn() FROM image WHERE embedding <|K|> $ref`   -> web_search_text()
+      `DELETE FROM image WHERE image_path IN $paths`                         -> remove()
     kept across restarts by save / load (what the database did for the reference)."""
 
     def __init__(self, dim: int = 768, device: int = 0, media_dir: str = ""):
@@ -501,7 +534,9 @@ class ImageIndex:
 
     @property
     def paths(self) -> list:
-        return [self.path(i) for i in range(len(self))]
+        """image_path by row id; None for a removed row"""
+        gone = set(int(i) for i in self.table.deleted())
+        return [None if i in gone else self.path(i) for i in range(len(self))]
 
     def existing(self, paths: Sequence[str]) -> set:
         """clip.rs:74-83: which of `paths` already have a row."""
@@ -520,6 +555,22 @@ class ImageIndex:
         first = ctypes.c_uint64()
         check(lib().mi_index_insert(self._h, _cstrs(paths), e.ctypes.data, len(paths), ctypes.byref(first)))
         return first.value
+
+    def remove(self, paths: Sequence[str]) -> int:
+        """`DELETE FROM image WHERE image_path IN $paths` (mi_index_remove): every row of each path; paths without rows
+        are ignored.  Returns the rows removed."""
+        paths = list(paths)
+        n = ctypes.c_uint64()
+        check(lib().mi_index_remove(self._h, _cstrs(paths), len(paths), ctypes.byref(n)))
+        return n.value
+
+    def live_paths(self) -> set:
+        """the image_path of every row that has not been removed (mi_index_live_paths: one call)"""
+        need = ctypes.c_size_t()
+        check(lib().mi_index_live_paths(self._h, None, 0, ctypes.byref(need)))
+        buf = ctypes.create_string_buffer(max(need.value, 1))
+        check(lib().mi_index_live_paths(self._h, buf, need.value, ctypes.byref(need)))
+        return {p.decode() for p in buf.raw[:need.value].split(b"\0") if p}
 
     def adopt(self, paths: Sequence[str]):
         """Paths for rows the fused pipeline has just written into `self.table` (mi_index_adopt)."""
@@ -581,23 +632,16 @@ def decode_rgb8(path: str) -> np.ndarray:
         return np.asarray(im.convert("RGB"), np.uint8)
 
 
-def embed_all_images_in_dir(model, index: ImageIndex, media_dir: str, image_chunk_size: int = 500, decode=None,
-                            shuffle_seed=None) -> int:
-    """clip.rs:42-151: walk `media_dir` (following links), keep the allow-listed extensions, shuffle,
-    and per chunk: skip paths that already have a row, decode, embed (resize + normalise + tower on
-    the device: Model.forward_images), insert.  A crash loses at most one chunk; a rerun resumes.
-    `decode(path) -> RGB8 [H,W,3]` defaults to Pillow; files that fail to decode are logged and
-    skipped TOGETHER WITH their path (the reference zips the unfiltered path list with the
-    surviving embeddings, clip.rs:125-134, which shifts paths after a failure).  Returns rows added."""
-    import logging
+def _image_files(media_dir: str, errors=None) -> list:
+    """the scan's walk (clip.rs:42-60): every allow-listed file under media_dir, following links, each directory once.
+    errors (a list, optional) collects what the walk could not look into — an unreadable directory, a link whose target is
+    gone (an unmounted folder looks just like that) — so that a prune does not take what it could not see for deleted."""
     import os
-    import random
     from .clip import is_image_path
-    if decode is None:
-        decode = decode_rgb8
     paths = []
     seen_dirs = set()
-    for root, dirs, files in os.walk(media_dir, followlinks=True):
+    note = errors.append if errors is not None else (lambda e: None)
+    for root, dirs, files in os.walk(media_dir, followlinks=True, onerror=note):
         # WalkDir::follow_links detects cycles; os.walk does not: never descend into a directory twice
         st = os.stat(root)
         seen_dirs.add((st.st_dev, st.st_ino))
@@ -605,7 +649,8 @@ def embed_all_images_in_dir(model, index: ImageIndex, media_dir: str, image_chun
         for d in dirs:
             try:
                 sd = os.stat(os.path.join(root, d))
-            except OSError:
+            except OSError as err:
+                note(err)
                 continue
             if (sd.st_dev, sd.st_ino) not in seen_dirs:
                 seen_dirs.add((sd.st_dev, sd.st_ino))
@@ -613,8 +658,50 @@ def embed_all_images_in_dir(model, index: ImageIndex, media_dir: str, image_chun
         dirs[:] = keep
         for name in files:
             p = os.path.join(root, name)
-            if os.path.isfile(p) and is_image_path(p):
+            if os.path.islink(p) and not os.path.exists(p):
+                note(OSError(f"dangling link {p}"))
+            elif os.path.isfile(p) and is_image_path(p):
                 paths.append(p)
+    return paths
+
+
+def prune_missing_images(index, media_dir: str, found=None) -> int:
+    """Remove (ImageIndex.remove) the rows whose stored path lies under `media_dir` and is no longer an allow-listed
+    file there: deleted photos, and the old paths of moved or renamed folders.  `found`: the walk's paths if the caller
+    has them (embed_all_images_in_dir), else the directory is walked here.  Rows of paths outside media_dir are kept.
+    A walk that could not see everything (an unreadable directory, a dangling link: _image_files) removes nothing and
+    raises OSError — a folder that is briefly unmounted must not lose its rows.  Returns the rows removed."""
+    if found is None:
+        errors = []
+        found = _image_files(media_dir, errors)
+        if errors:
+            raise OSError(f"the walk of {media_dir} was incomplete ({errors[0]}); nothing was removed")
+    found = set(found)
+    prefix = media_dir.rstrip("/") + "/"
+    stale = sorted(p for p in index.live_paths() if p.startswith(prefix) and p not in found)
+    return index.remove(stale) if stale else 0
+
+
+def embed_all_images_in_dir(model, index: ImageIndex, media_dir: str, image_chunk_size: int = 500, decode=None,
+                            shuffle_seed=None, prune: bool = False) -> int:
+    """clip.rs:42-151: walk `media_dir` (following links), keep the allow-listed extensions, shuffle,
+    and per chunk: skip paths that already have a row, decode, embed (resize + normalise + tower on
+    the device: Model.forward_images), insert.  A crash loses at most one chunk; a rerun resumes.
+    `decode(path) -> RGB8 [H,W,3]` defaults to Pillow; files that fail to decode are logged and
+    skipped TOGETHER WITH their path (the reference zips the unfiltered path list with the
+    surviving embeddings, clip.rs:125-134, which shifts paths after a failure).  prune=True first removes the rows of
+    files that are gone from media_dir (prune_missing_images; the reference only ever adds).  Returns rows added."""
+    import logging
+    import random
+    if decode is None:
+        decode = decode_rgb8
+    errors = []
+    paths = _image_files(media_dir, errors)
+    if prune:
+        if errors:  # what the walk could not see is not gone: no prune this time
+            logging.getLogger(__name__).error("walk of %s incomplete (%s): rows not pruned", media_dir, errors[0])
+        else:
+            prune_missing_images(index, media_dir, paths)
     random.Random(shuffle_seed).shuffle(paths)
     added = 0
     for c0 in range(0, len(paths), image_chunk_size):

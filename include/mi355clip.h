@@ -286,6 +286,17 @@ int mi_knn_get_rows(mi_knn* t, uint64_t first, uint64_t n, float* out);
 int mi_knn_save(mi_knn* t, const char* path);
 int mi_knn_load(mi_knn* t, const char* path);
 
+/* Replaces `DELETE FROM image WHERE id IN $ids` (the row removal the reference's database offers; the scan of
+ * server/src/clip.rs:42-151 only ever adds).  ids are the table's own (base + ordinal; on a shard borrowed through
+ * mi_knn_sharded_shard: the ids its searches report).  A deleted row keeps its id and its storage (mi_knn_size counts it,
+ * mi_knn_get_rows returns it) and no later search returns it; searches enqueued before the call may.  Deleting a deleted
+ * row does nothing; an id that is not a row of the table fails the whole call (MI_ERR_INVALID) and nothing changes.
+ * *newly (may be NULL) = rows that were live before the call.  mi_knn_save writes "MIKNNv02" files (the rows, then the
+ * deleted rows) for a table with deletions, the MIKNNv01 file otherwise; mi_knn_load reads both. */
+int mi_knn_delete(mi_knn* t, const uint64_t* ids, uint64_t n, uint64_t* newly);
+/* *count = deleted rows; the first min(cap, count) of their ids, ascending, into ids (may be NULL) */
+int mi_knn_deleted(mi_knn* t, uint64_t* ids, uint64_t cap, uint64_t* count);
+
 /* Replaces `SELECT id, image_path, vector::distance::knn() FROM image WHERE
  * embedding <|K|> $reference` (server/src/search.rs:70-86; K = 1000 there).
  * For each of nq queries (q: [nq,dim] host f32): the k rows of this shard with the
@@ -358,6 +369,10 @@ int mi_knn_sharded_sync(mi_knn_sharded* t);
  * (and leaves it empty on failure) and re-deals the blocks when the shard count or block size differ from the saved ones. */
 int mi_knn_sharded_save(mi_knn_sharded* t, const char* prefix);
 int mi_knn_sharded_load(mi_knn_sharded* t, const char* prefix);
+/* mi_knn_delete / mi_knn_deleted on global ids (`DELETE FROM image WHERE id IN $ids` over the whole table); save, load
+ * (any shard count and block size) and rebalance carry the deletions */
+int mi_knn_sharded_delete(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint64_t* newly);
+int mi_knn_sharded_deleted(mi_knn_sharded* t, uint64_t* ids, uint64_t cap, uint64_t* count);
 /* Change the layout of a LIVE table: every row of `src` into the empty `dst` (another shard count, device set or block
  * size), block by block, device to device — a plain copy where source and destination shard share a GPU,
  * hipMemcpyPeerAsync over xGMI where they do not; nothing passes through the host.  src is unchanged. */
@@ -472,6 +487,16 @@ int mi_index_search(mi_index* ix, const float* text_embedding, const char* const
  * last: after a crash the directory holds a consistent index (at worst the one before the save). */
 int mi_index_save(mi_index* ix, const char* dir);
 int mi_index_load(mi_index* ix, const char* dir); /* into an empty index */
+/* Replaces `DELETE FROM image WHERE image_path IN $paths`: every row of each path (a path may own several) is deleted
+ * (mi_knn_delete on mi_index_table).  Afterwards mi_index_existing reports 0 for the path (a later scan re-embeds a file
+ * that comes back under it, as a new row), mi_index_rows_of and mi_index_search leave its rows out, and mi_index_path of
+ * such a row fails with MI_ERR_INVALID.  Paths without rows are ignored.  *removed_rows (may be NULL) = rows deleted.
+ * The removal is saved with the embedding file (MIKNNv02); the path file is unchanged. */
+int mi_index_remove(mi_index* ix, const char* const* paths, size_t n, uint64_t* removed_rows);
+/* every image_path that has a row that was not removed, once each, as consecutive NUL-terminated strings; *needed = bytes
+ * of the whole list, whole paths up to `cap` bytes are written (buf may be NULL) — what a scan's prune compares with the
+ * files it found (search.py prune_missing_images) */
+int mi_index_live_paths(mi_index* ix, char* buf, size_t cap, size_t* needed);
 
 /* ------------------------------------------------------------ query refinement */
 
