@@ -57,6 +57,7 @@ SYMBOLS = {
     "mi_knn_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, c_vp]),
     "mi_knn_search_batched_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, c_vp]),
+    "mi_knn_search_filtered": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, ctypes.c_uint64, c_vp, c_vp]),
     "mi_knn_sharded_create": (ctypes.c_int, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_uint32,
                                              ctypes.POINTER(c_vp)]),
     "mi_knn_sharded_free": (None, [c_vp]),
@@ -78,6 +79,8 @@ SYMBOLS = {
     "mi_knn_sharded_load": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_knn_sharded_delete": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_u64p]),
     "mi_knn_sharded_deleted": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_u64p]),
+    "mi_knn_sharded_search_filtered": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, ctypes.c_uint64, c_vp,
+                                                      c_vp]),
     "mi_knn_sharded_place": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32),
                                             c_u64p]),
     "mi_knn_sharded_id": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, c_u64p]),
@@ -97,6 +100,9 @@ SYMBOLS = {
                                      ctypes.POINTER(ctypes.c_size_t)]),
     "mi_index_search": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_uint32, c_vp, c_vp,
                                        ctypes.POINTER(ctypes.c_uint32)]),
+    "mi_index_search_within": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t,
+                                              ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_uint32, c_vp, c_vp,
+                                              ctypes.POINTER(ctypes.c_uint32)]),
     "mi_index_save": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_index_load": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_knn_merge": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),

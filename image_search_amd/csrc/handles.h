@@ -192,6 +192,13 @@ struct mi_knn {
     uint64_t* d_tomb = nullptr;
     uint32_t* d_dead = nullptr;
     size_t tomb_words = 0, dead_cap = 0;
+    // Filtered search (mi_knn_search_filtered): the filter's live local rows, ascending — n_flist of them in pinned host
+    // memory, what the upload reads (kept until the next filtered search: every filtered entry point waits for its results),
+    // and the device copy.
+    uint32_t* h_flist = nullptr;
+    size_t n_flist = 0, h_flist_cap = 0;
+    uint32_t* d_flist = nullptr;
+    size_t flist_cap = 0;
     std::mutex mu;
 };
 
@@ -268,12 +275,16 @@ void knn_grow(mi_knn* t, uint64_t want_rows);       // may reallocate: waits for
 void knn_search_one(mi_knn* t, const float* d_q, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s);
 void knn_search_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s);  // nq queries in groups that share their passes; results [nq][k]
 void knn_truncate(mi_knn* t, uint64_t rows);        // forget the rows behind `rows` (a failed multi-shard append / load rolls back)
+// the filtered search of nq queries (contiguous at d_q) over the ids (every one a row of t: checked by the caller), on s
+void knn_search_filtered_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, const uint64_t* ids, uint64_t n_ids,
+                              uint64_t* d_idx, float* d_dist, hipStream_t s);   // t->mu held, device selected
 // list l of query u: ids at d_idx_in + l * idx_stride + u * k, distances at d_dist_in + l * dist_stride + u * k (elements)
 void knn_merge_lists_device(const uint64_t* d_idx_in, const float* d_dist_in, uint32_t lists, uint32_t nq, uint32_t k,
                             size_t idx_stride, size_t dist_stride, uint64_t* d_idx, float* d_dist, hipStream_t s);   // caller has the device selected
 // sharded.hip
 void sharded_place(const mi_knn_sharded* t, uint64_t r, uint32_t* s, uint64_t* local);
 uint64_t sharded_rows_of(const mi_knn_sharded* t, uint64_t total, uint32_t s);  // rows shard s holds when the table holds `total`
-void sharded_search_enqueue(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, uint64_t* idx, float* dist);  // t->mu held
+void sharded_search_enqueue(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, uint64_t* idx, float* dist,
+                            const std::vector<std::vector<uint64_t>>* filter = nullptr);  // t->mu held
 void sharded_deliver_all(mi_knn_sharded* t);                                    // t->mu held
 }  // namespace mi

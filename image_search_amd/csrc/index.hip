@@ -5,6 +5,7 @@
 //   db.insert("image").content(rows)                                   server/src/clip.rs:125-137   mi_index_insert
 //   SELECT id, image_path, embedding FROM image WHERE image_path IN $p server/src/search.rs:43-58   mi_index_rows_of
 //   refine + SELECT id, image_path, knn() ... <|K|> $reference         server/src/search.rs:20-110  mi_index_search
+//   ... AND string::starts_with(image_path, $folder) (a pre-filter)                                 mi_index_search_within
 //   DELETE FROM image WHERE image_path IN $paths                                                    mi_index_remove
 // Row id = insertion ordinal; like the reference's table there is no uniqueness constraint on image_path (the scan
 // loop filters first), a path may own several rows and lookups return all of them in id order.
@@ -20,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <set>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -35,6 +37,7 @@ struct mi_index {
     std::string media_dir;  // the server's media directory: "media/..." in requests maps onto it (search.rs:35-40)
     std::vector<std::string> paths;                            // row id -> image_path
     std::unordered_map<std::string, std::vector<uint64_t>> rows_of;  // image_path -> row ids, ascending (live rows only)
+    std::set<std::string> live;                                // the keys of rows_of, ordered: a folder is one range of it
     std::vector<uint8_t> removed;                              // row id -> deleted by mi_index_remove (the table's tombstones)
     std::mutex mu;
 };
@@ -42,7 +45,10 @@ struct mi_index {
 namespace {
 
 void add_path(mi_index* ix, const std::string& p, bool removed = false) {
-    if (!removed) ix->rows_of[p].push_back(ix->paths.size());
+    if (!removed) {
+        ix->rows_of[p].push_back(ix->paths.size());
+        ix->live.insert(p);
+    }
     ix->paths.push_back(p);
     ix->removed.push_back(removed ? 1 : 0);
 }
@@ -52,6 +58,42 @@ bool to_disk(const mi_index* ix, const char* web, std::string* out) {
     if (std::strncmp(web, "media/", 6) != 0) return false;
     *out = ix->media_dir + (web + 6);
     return true;
+}
+
+// the query of web_search_text: the text vector, refined with the marked images found in the table (search.rs:35-67)
+std::vector<float> refined_query(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref) {
+    std::vector<uint64_t> marked;
+    {
+        std::lock_guard<std::mutex> l(ix->mu);
+        for (size_t i = 0; i < n_ref; ++i) {
+            std::string disk;
+            if (!referenced_images[i] || !to_disk(ix, referenced_images[i], &disk)) continue;  // search.rs:35-40
+            auto it = ix->rows_of.find(disk);
+            if (it != ix->rows_of.end()) marked.insert(marked.end(), it->second.begin(), it->second.end());
+        }
+    }
+    std::sort(marked.begin(), marked.end());
+    marked.erase(std::unique(marked.begin(), marked.end()), marked.end());
+    std::vector<float> query(text_embedding, text_embedding + ix->dim);
+    if (!marked.empty()) {  // search.rs:59-67
+        std::vector<float> sel(marked.size() * ix->dim);
+        std::vector<const float*> ptr(marked.size());
+        for (size_t i = 0; i < marked.size(); ++i) {
+            const int e = mi_knn_get_rows(ix->table, marked[i], 1, &sel[i * ix->dim]);
+            if (e != MI_OK) fail(e, "%s", mi_last_error());
+            ptr[i] = &sel[i * ix->dim];
+        }
+        const int e = mi_refine(text_embedding, ptr.data(), ptr.size(), ix->dim, query.data());
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+    }
+    return query;
+}
+
+// results in front of the MI_KNN_NO_ID padding
+uint32_t hits(const uint64_t* idx, uint32_t k) {
+    uint32_t n = 0;
+    while (n < k && idx[n] != MI_KNN_NO_ID) ++n;
+    return n;
 }
 
 void write_all(int fd, const void* p, size_t n, const char* what) {
@@ -198,37 +240,40 @@ int mi_index_search(mi_index* ix, const float* text_embedding, const char* const
                     uint64_t* idx, float* dist, uint32_t* n_found) {
     return guarded([&] {
         if (!ix || !text_embedding || !idx || !dist || (n_ref && !referenced_images)) fail(MI_ERR_INVALID, "null argument");
-        std::vector<uint64_t> marked;
-        {
-            std::lock_guard<std::mutex> l(ix->mu);
-            for (size_t i = 0; i < n_ref; ++i) {
-                std::string disk;
-                if (!referenced_images[i] || !to_disk(ix, referenced_images[i], &disk)) continue;  // search.rs:35-40
-                auto it = ix->rows_of.find(disk);
-                if (it != ix->rows_of.end()) marked.insert(marked.end(), it->second.begin(), it->second.end());
-            }
-        }
-        std::sort(marked.begin(), marked.end());
-        marked.erase(std::unique(marked.begin(), marked.end()), marked.end());
-        std::vector<float> query(text_embedding, text_embedding + ix->dim);
-        if (!marked.empty()) {  // search.rs:59-67
-            std::vector<float> sel(marked.size() * ix->dim);
-            std::vector<const float*> ptr(marked.size());
-            for (size_t i = 0; i < marked.size(); ++i) {
-                const int e = mi_knn_get_rows(ix->table, marked[i], 1, &sel[i * ix->dim]);
-                if (e != MI_OK) fail(e, "%s", mi_last_error());
-                ptr[i] = &sel[i * ix->dim];
-            }
-            const int e = mi_refine(text_embedding, ptr.data(), ptr.size(), ix->dim, query.data());
-            if (e != MI_OK) fail(e, "%s", mi_last_error());
-        }
+        const std::vector<float> query = refined_query(ix, text_embedding, referenced_images, n_ref);
         const int e = mi_knn_search(ix->table, query.data(), 1, k, idx, dist);
         if (e != MI_OK) fail(e, "%s", mi_last_error());
-        if (n_found) {
-            uint32_t n = 0;
-            while (n < k && idx[n] != MI_KNN_NO_ID) ++n;
-            *n_found = n;
+        if (n_found) *n_found = hits(idx, k);
+    });
+}
+
+// ... among the rows under `folders` (client names, whole path components): each folder is one range of the ordered live
+// paths, found by lower_bound; the search is mi_knn_search_filtered over those rows
+int mi_index_search_within(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
+                           const char* const* folders, size_t n_folders, uint32_t k, uint64_t* idx, float* dist,
+                           uint32_t* n_found) {
+    return guarded([&] {
+        if (!ix || !text_embedding || !idx || !dist || (n_ref && !referenced_images) || (n_folders && !folders))
+            fail(MI_ERR_INVALID, "null argument");
+        std::vector<uint64_t> ids;
+        {
+            std::lock_guard<std::mutex> l(ix->mu);
+            for (size_t i = 0; i < n_folders; ++i) {
+                if (!folders[i]) fail(MI_ERR_INVALID, "folder %zu is null", i);
+                std::string prefix;
+                if (!to_disk(ix, folders[i], &prefix)) continue;  // not under "media/": matches nothing
+                // "media/" is the media directory itself; any deeper folder matches whole components: "<dir>/"
+                if (prefix.size() > ix->media_dir.size() && prefix.back() != '/') prefix += '/';
+                for (auto it = ix->live.lower_bound(prefix); it != ix->live.end() && it->compare(0, prefix.size(), prefix) == 0; ++it) {
+                    const std::vector<uint64_t>& r = ix->rows_of.at(*it);
+                    ids.insert(ids.end(), r.begin(), r.end());
+                }
+            }
         }
+        const std::vector<float> query = refined_query(ix, text_embedding, referenced_images, n_ref);
+        const int e = mi_knn_search_filtered(ix->table, query.data(), 1, k, ids.data(), ids.size(), idx, dist);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        if (n_found) *n_found = hits(idx, k);
     });
 }
 
@@ -362,7 +407,10 @@ int mi_index_remove(mi_index* ix, const char* const* paths, size_t n, uint64_t* 
         const int e = mi_knn_delete(ix->table, ids.data(), ids.size(), &newly);  // the rows first: a failure changes nothing
         if (e != MI_OK) fail(e, "%s", mi_last_error());
         for (uint64_t id : ids) ix->removed[id] = 1;
-        for (size_t i = 0; i < n; ++i) ix->rows_of.erase(paths[i]);
+        for (size_t i = 0; i < n; ++i) {
+            ix->rows_of.erase(paths[i]);
+            ix->live.erase(paths[i]);
+        }
         if (removed_rows) *removed_rows = newly;
     });
 }

@@ -184,6 +184,10 @@ void launch_merge(const uint64_t* in, uint32_t n_lists, uint32_t k, uint32_t lpb
     HIP_CHECK(hipGetLastError());
 }
 
+template <class Top>
+void reduce_wave_lists(mi_knn* t, uint32_t lists, uint32_t kp, uint64_t* keys_out, hipStream_t s, const uint32_t* run_if,
+                       uint32_t gy, const QGroup& qg);
+
 // One pass: the kp <= 1024 smallest keys (> *lo if lo) of the shard, ascending, into keys_out[0..kp).
 // gy > 1 (register lists only): the same pass for a group of gy queries (contiguous at d_q) in the same launches, query y
 // gated by run_if[y * qg.flags], its keys to keys_out + y * qg.out
@@ -198,6 +202,13 @@ void one_pass(mi_knn* t, const float* d_q, uint32_t kp, const uint64_t* lo, uint
     ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)lists * kp * gy, sizeof(uint64_t));
     qg.lists = (uint64_t)lists * kp;
     launch_scan<Top>(t, d_q, kp, lo, t->d_cand, blocks, s, run_if, gy, qg);
+    reduce_wave_lists<Top>(t, lists, kp, keys_out, s, run_if, gy, qg);
+}
+
+// the per-wave lists in t->d_cand (lists x kp keys per query) -> the kp smallest keys, ascending, into keys_out
+template <class Top>
+void reduce_wave_lists(mi_knn* t, uint32_t lists, uint32_t kp, uint64_t* keys_out, hipStream_t s, const uint32_t* run_if,
+                       uint32_t gy, const QGroup& qg) {
     if constexpr (Top::LDS_KEYS != 0) {
         // k > 64: block-cooperative tree, 16 lists per block per level, ping-pong between d_tmp halves
         constexpr uint32_t LPB = 16;
@@ -719,9 +730,203 @@ void search_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t*
         u += b;
     }
 }
+
+// ---- filtered search (mi_knn_search_filtered): the k nearest among chosen rows ------------------------------------------
+// The filter goes to the device as its live local rows, ascending (t->d_flist); knn_scan_gather_kernel reads only those rows.
+constexpr uint32_t FILTER_K_MAX = 4096;
+
+// room for `want` rows in the pinned host list (its old contents are not kept; nothing in flight reads it: every filtered
+// entry point has waited for its results before it returned)
+uint32_t* flist_reserve(mi_knn* t, size_t want) {
+    if (want > t->h_flist_cap) {
+        if (t->h_flist) HIP_CHECK(hipHostFree(t->h_flist));
+        t->h_flist = nullptr;
+        t->h_flist_cap = 0;
+        const size_t cap = std::max(want, (size_t)4096);
+        HIP_CHECK(hipHostMalloc((void**)&t->h_flist, cap * sizeof(uint32_t), hipHostMallocPortable));
+        t->h_flist_cap = cap;
+    }
+    return t->h_flist;
+}
+
+// ids -> t->h_flist [0, n_flist): the local rows they name, ascending, once each, deleted rows left out; MI_ERR_INVALID (and
+// the list untouched) when an id is not a row of the table
+void filter_rows(mi_knn* t, const uint64_t* ids, uint64_t n_ids) {
+    std::vector<uint32_t> rows((size_t)n_ids);
+    for (uint64_t i = 0; i < n_ids; ++i) {
+        uint64_t local = 0;
+        if (!local_of(t, ids[i], &local))
+            fail(MI_ERR_INVALID, "id %llu is not a row of this table (base %llu, %llu rows)", (unsigned long long)ids[i],
+                 (unsigned long long)t->base, (unsigned long long)t->rows);
+        rows[i] = (uint32_t)local;
+    }
+    // From rows / 1024 ids on, a bitmap over the rows (zeroed, marked, emitted: O(rows / 64 + n_ids)) instead of a sort
+    // (O(n_ids log n_ids)): at 10 M rows the sort took 4 ms for 10^5 scattered ids and 570 ms for 10^7.
+    if (n_ids >= t->rows / 1024) {
+        std::vector<uint64_t> bits((size_t)((t->rows + 63) / 64), 0ull);
+        for (const uint32_t r : rows) bits[r >> 6] |= 1ull << (r & 63);
+        for (const uint32_t r : t->dead)
+            if (r < t->rows) bits[r >> 6] &= ~(1ull << (r & 63));
+        size_t n = 0;
+        for (const uint64_t b : bits) n += (size_t)__builtin_popcountll(b);
+        uint32_t* out = flist_reserve(t, n);
+        size_t at = 0;
+        for (size_t w = 0; w < bits.size(); ++w)
+            for (uint64_t b = bits[w]; b; b &= b - 1) out[at++] = (uint32_t)(w * 64 + (uint64_t)__builtin_ctzll(b));
+        t->n_flist = n;
+        return;
+    }
+    std::sort(rows.begin(), rows.end());
+    rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+    uint32_t* out = flist_reserve(t, rows.size());
+    t->n_flist = (size_t)(std::set_difference(rows.begin(), rows.end(), t->dead.begin(), t->dead.end(), out) - out);
+}
+
+// grid of a gathered pass over n entries (as one_pass over n rows)
+uint32_t gather_blocks(const mi_knn* t, uint32_t n, uint32_t bpc) {
+    const uint64_t n_tiles = ((uint64_t)n + 63) / 64;
+    return std::max(1u, (uint32_t)std::min<uint64_t>((uint64_t)t->n_cu * bpc, (n_tiles + 3) / 4));
+}
+
+// the kp <= 1024 smallest keys of the n entries, ascending, into keys_out: per-wave lists (Top) and the single pass's merge tree
+template <class Top>
+void gather_lists(mi_knn* t, const float* d_q, uint32_t n, uint32_t kp, uint64_t* keys_out, hipStream_t s) {
+    const uint32_t blocks = gather_blocks(t, n, Top::LDS_KEYS == 0 ? 4 : (Top::KP <= 256 ? 4 : 2)), lists = blocks * 4;
+    ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)lists * kp, sizeof(uint64_t));
+    const size_t lds = (size_t)4 * Top::LDS_KEYS * sizeof(uint64_t);
+    switch (t->dim / 64) {
+#define MI_CASE(NCH)                                                                                                    \
+    case NCH:                                                                                                           \
+        allow_lds(knn_scan_gather_kernel<NCH, Top>, lds);                                                               \
+        hipLaunchKernelGGL((knn_scan_gather_kernel<NCH, Top>), dim3(blocks), dim3(256), lds, s, t->table, t->d_flist, n, d_q, kp, \
+                           t->d_cand, (uint32_t*)nullptr);                                                              \
+        break;
+        MI_CASE(1) MI_CASE(2) MI_CASE(4) MI_CASE(8) MI_CASE(12) MI_CASE(16)
+#undef MI_CASE
+        default: fail(MI_ERR_UNSUPPORTED, "dim %u: built for dim/64 in {1,2,4,8,12,16}", t->dim);
+    }
+    HIP_CHECK(hipGetLastError());
+    QGroup qg;
+    qg.lists = (uint64_t)lists * kp;
+    reduce_wave_lists<Top>(t, lists, kp, keys_out, s, nullptr, 1, qg);
+}
+
+// the k <= 4096 smallest keys of the n entries, ascending, into keys_out: one distance key per entry, the radix select over
+// (key, position), then positions back to rows
+void gather_select(mi_knn* t, const float* d_q, uint32_t n, uint32_t k, uint64_t* keys_out, hipStream_t s) {
+    ensure(t, (void**)&t->d_keys32, &t->keys32_cap, (size_t)n, sizeof(uint32_t));
+    ensure(t, (void**)&t->d_sel, &t->sel_cap, (size_t)SEL_WORDS, sizeof(uint32_t));
+    ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)4096, sizeof(uint64_t));
+    HIP_CHECK(hipMemsetAsync(t->d_sel, 0, (size_t)SEL_WORDS * sizeof(uint32_t), s));
+    const uint32_t blocks = gather_blocks(t, n, 4);
+    switch (t->dim / 64) {
+#define MI_CASE(NCH)                                                                                                    \
+    case NCH:                                                                                                           \
+        hipLaunchKernelGGL((knn_scan_gather_kernel<NCH, WaveTopReg, 1>), dim3(blocks), dim3(256), 0, s, t->table, t->d_flist, n, \
+                           d_q, k, (uint64_t*)nullptr, t->d_keys32);                                                    \
+        break;
+        MI_CASE(1) MI_CASE(2) MI_CASE(4) MI_CASE(8) MI_CASE(12) MI_CASE(16)
+#undef MI_CASE
+        default: fail(MI_ERR_UNSUPPORTED, "dim %u: built for dim/64 in {1,2,4,8,12,16}", t->dim);
+    }
+    HIP_CHECK(hipGetLastError());
+    const uint32_t hb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)t->n_cu * 8, ((uint64_t)n + 255) / 256));
+    uint32_t* count = t->d_sel + 6 * SEL_BINS;
+    SelState* states = reinterpret_cast<SelState*>(t->d_sel + 6 * SEL_BINS + 4);
+    for (int p = 0; p < 6; ++p)
+        hipLaunchKernelGGL(knn_select_hist_kernel, dim3(hb), dim3(256), 0, s, t->d_keys32, (uint64_t)n, k, p, t->d_sel, states);
+    hipLaunchKernelGGL(knn_select_collect_kernel, dim3(hb), dim3(256), 0, s, t->d_keys32, (uint64_t)n, k, t->d_sel, states, t->d_cand, count);
+    hipLaunchKernelGGL(knn_select_sort_kernel, dim3(1), dim3(1024), 0, s, t->d_cand, count, k, keys_out);
+    hipLaunchKernelGGL(knn_gather_rows_kernel, dim3((k + 255) / 256), dim3(256), 0, s, keys_out, k, t->d_flist);
+    HIP_CHECK(hipGetLastError());
+}
+
+// Per-wave lists or the radix select for 64 < k <= 1024: the lists pay while a wave sees many more entries than k (most of
+// its offers then fail the threshold test); near k entries per wave nearly everything passes and the merge tree of
+// waves x k keys costs more than the select's passes over n compact keys.  Rule: lists when every wave of the full grid
+// sees at least 16 k entries (k = 100: n >= 3.3 M entries on 256 CUs).  A handle made with MI_KNN_SELECT=0 (the single
+// pass's A/B hook) takes the lists for every k <= 1024.  The lists are WaveTopLds<1024> for every 64 < k <= 1024: the gathered
+// scan with WaveTopLds<256> takes 154 VGPRs at dim 768 (3 waves per SIMD against the 4 of knn_scan_kernel<12, WaveTopLds<256>>,
+// and 112 bytes of scratch when held to 4); with WaveTopLds<1024> it takes 160 VGPRs, the 3 waves of the scan's own form.
+bool filter_takes_lists(const mi_knn* t, uint32_t n, uint32_t k) {
+    if (k <= 64) return true;
+    if (k > 1024) return false;
+    if (!t->select_path) return true;
+    const uint64_t waves = 4ull * t->n_cu * 2;
+    return (uint64_t)n >= 16ull * k * waves;
+}
+
+void filtered_one(mi_knn* t, const float* d_q, uint32_t n, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
+    if (n == 0) {  // nothing qualifies: k "none" entries
+        hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, 1), dim3(256), 0, s, (const uint64_t*)nullptr, k, id_map(t),
+                           d_idx, d_dist, (size_t)0, (size_t)0);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
+    ensure(t, (void**)&t->d_keys, &t->keys_cap, (size_t)FILTER_K_MAX, sizeof(uint64_t));
+    if (!filter_takes_lists(t, n, k)) gather_select(t, d_q, n, k, t->d_keys, s);
+    else if (k <= 64) gather_lists<WaveTopReg>(t, d_q, n, k, t->d_keys, s);
+    else gather_lists<WaveTopLds<1024>>(t, d_q, n, k, t->d_keys, s);
+    hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, 1), dim3(256), 0, s, t->d_keys, k, id_map(t), d_idx, d_dist,
+                       (size_t)0, (size_t)0);
+    HIP_CHECK(hipGetLastError());
+}
+
+// nq in {2, 4, 8} queries over one filter, k <= 64, dim 768: one gathered pass (knn_scan_gather_batched_kernel)
+void filtered_batched(mi_knn* t, const float* d_q, uint32_t nq, uint32_t n, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
+    const uint32_t blocks = gather_blocks(t, n, 2), lists = blocks * 4;
+    ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)nq * lists * k, sizeof(uint64_t));
+    ensure(t, (void**)&t->d_keys, &t->keys_cap, (size_t)std::max<uint32_t>(FILTER_K_MAX, nq * k), sizeof(uint64_t));
+    if (nq == 2)
+        hipLaunchKernelGGL((knn_scan_gather_batched_kernel<12, 2>), dim3(blocks), dim3(256), 0, s, t->table, t->d_flist, n, d_q, k, t->d_cand);
+    else if (nq == 4)
+        hipLaunchKernelGGL((knn_scan_gather_batched_kernel<12, 4>), dim3(blocks), dim3(256), 0, s, t->table, t->d_flist, n, d_q, k, t->d_cand);
+    else
+        hipLaunchKernelGGL((knn_scan_gather_batched_kernel<12, 8>), dim3(blocks), dim3(256), 0, s, t->table, t->d_flist, n, d_q, k, t->d_cand);
+    HIP_CHECK(hipGetLastError());
+    const size_t cstride = (size_t)lists * k;
+    if (lists <= 64) {
+        launch_merge<WaveTopReg>(t->d_cand, lists, k, lists, t->d_keys, nq, cstride, k, s);
+    } else {
+        const uint32_t lpb = 32, mid = (lists + lpb - 1) / lpb;
+        ensure(t, (void**)&t->d_tmp, &t->tmp_keys, (size_t)nq * mid * k, sizeof(uint64_t));
+        launch_merge<WaveTopReg>(t->d_cand, lists, k, lpb, t->d_tmp, nq, cstride, (size_t)mid * k, s);
+        launch_merge<WaveTopReg>(t->d_tmp, mid, k, mid, t->d_keys, nq, (size_t)mid * k, k, s);
+    }
+    hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, nq), dim3(256), 0, s, t->d_keys, k, id_map(t), d_idx, d_dist,
+                       (size_t)k, (size_t)k);
+    HIP_CHECK(hipGetLastError());
+}
+
+// the list to the device, once per call, from pinned memory (untouched until the call has waited for its results)
+void upload_filter(mi_knn* t, hipStream_t s) {
+    const size_t n = t->n_flist;
+    if (n == 0) return;
+    ensure(t, (void**)&t->d_flist, &t->flist_cap, n, sizeof(uint32_t));
+    HIP_CHECK(hipMemcpyAsync(t->d_flist, t->h_flist, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+}
+
+// nq queries (contiguous at d_q) over the uploaded filter, in groups of 8 / 4 / 2 (k <= 64, dim 768) or one by one
+void filtered_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
+    const uint32_t n = (uint32_t)t->n_flist;
+    uint32_t u = 0;
+    while (u < nq) {
+        const uint32_t left = nq - u;
+        const uint32_t b = (k <= 64 && n && t->dim == 768) ? (left >= 8 ? 8 : left >= 4 ? 4 : left >= 2 ? 2 : 1) : 1;
+        if (b == 1) filtered_one(t, d_q + (size_t)u * t->dim, n, k, d_idx + (size_t)u * k, d_dist + (size_t)u * k, s);
+        else filtered_batched(t, d_q + (size_t)u * t->dim, b, n, k, d_idx + (size_t)u * k, d_dist + (size_t)u * k, s);
+        u += b;
+    }
+}
 }  // namespace
 
 namespace mi {
+void knn_search_filtered_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, const uint64_t* ids, uint64_t n_ids,
+                              uint64_t* d_idx, float* d_dist, hipStream_t s) {
+    filter_rows(t, ids, n_ids);
+    upload_filter(t, s);
+    filtered_many(t, d_q, nq, k, d_idx, d_dist, s);
+}
 hipStream_t knn_own_stream(mi_knn* t) { return own_stream(t); }
 void knn_search_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
     search_many(t, d_q, nq, k, d_idx, d_dist, s);
@@ -786,11 +991,13 @@ void mi_knn_free(mi_knn* t) {
     for (void* p : {(void*)t->table, (void*)t->d_q, (void*)t->d_cand, (void*)t->d_tmp, (void*)t->d_keys,
                     (void*)t->d_idx, (void*)t->d_dist, (void*)t->d_keys32, (void*)t->d_sel, (void*)t->d_mirror,
                     (void*)t->d_xx, (void*)t->d_pref_rows, (void*)t->d_pref_keys, (void*)t->d_pref_flag, (void*)t->d_scale8,
-                    (void*)t->d_cfac8, (void*)t->d_rho8, (void*)t->d_g8, (void*)t->d_digits, (void*)t->d_qs, (void*)t->d_skeys, (void*)t->d_tomb, (void*)t->d_dead})
+                    (void*)t->d_cfac8, (void*)t->d_rho8, (void*)t->d_g8, (void*)t->d_digits, (void*)t->d_qs, (void*)t->d_skeys, (void*)t->d_tomb, (void*)t->d_dead,
+                    (void*)t->d_flist})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : t->pref_ev)
         if (e) (void)hipEventDestroy(e);
     if (t->h_pref_ring) (void)hipHostFree(t->h_pref_ring);
+    if (t->h_flist) (void)hipHostFree(t->h_flist);
     delete t;
 }
 
@@ -1209,6 +1416,40 @@ int mi_knn_search(mi_knn* t, const float* q, uint32_t nq, uint32_t k, uint64_t* 
                 else search_batched(t, t->d_q + (size_t)u * t->dim, b, k, t->d_idx + (size_t)u * k, t->d_dist + (size_t)u * k, t->stream);
                 u += b;
             }
+            HIP_CHECK(hipMemcpyAsync(idx + (size_t)u0 * k, t->d_idx, (size_t)ng * k * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                                     t->stream));
+            HIP_CHECK(hipMemcpyAsync(dist + (size_t)u0 * k, t->d_dist, (size_t)ng * k * sizeof(float), hipMemcpyDeviceToHost,
+                                     t->stream));
+            HIP_CHECK(hipStreamSynchronize(t->stream));
+        }
+        t->reads.pending = false;
+    });
+}
+
+// k nearest among the rows the ids name (WHERE embedding <|K|> $reference AND id IN $ids, a pre-filter): the result of a
+// search over a table that holds only the filter's live rows under their own ids
+int mi_knn_search_filtered(mi_knn* t, const float* q, uint32_t nq, uint32_t k, const uint64_t* ids, uint64_t n_ids, uint64_t* idx,
+                           float* dist) {
+    return guarded([&] {
+        check_search_args(t, q, nq, k, idx, dist);
+        if (k > FILTER_K_MAX) fail(MI_ERR_UNSUPPORTED, "a filtered search takes k <= %u (got %u)", FILTER_K_MAX, k);
+        if (n_ids && !ids) fail(MI_ERR_INVALID, "ids is null");
+        std::lock_guard<std::mutex> l(t->mu);
+        filter_rows(t, ids, n_ids);  // every id checked before anything runs
+        if (nq == 0) return;
+        DeviceGuard g(t->device);
+        own_stream(t);
+        constexpr uint32_t GROUP = 16;
+        ensure(t, (void**)&t->d_idx, &t->idx_cap, (size_t)GROUP * k, sizeof(uint64_t));
+        ensure(t, (void**)&t->d_dist, &t->dist_cap, (size_t)GROUP * k, sizeof(float));
+        t->writes.begin(t->stream);
+        t->reads.begin(t->stream);
+        upload_filter(t, t->stream);
+        for (uint32_t u0 = 0; u0 < nq; u0 += GROUP) {
+            const uint32_t ng = std::min(GROUP, nq - u0);
+            HIP_CHECK(hipMemcpyAsync(t->d_q, q + (size_t)u0 * t->dim, (size_t)ng * t->dim * sizeof(float),
+                                     hipMemcpyHostToDevice, t->stream));
+            filtered_many(t, t->d_q, ng, k, t->d_idx, t->d_dist, t->stream);
             HIP_CHECK(hipMemcpyAsync(idx + (size_t)u0 * k, t->d_idx, (size_t)ng * k * sizeof(uint64_t), hipMemcpyDeviceToHost,
                                      t->stream));
             HIP_CHECK(hipMemcpyAsync(dist + (size_t)u0 * k, t->d_dist, (size_t)ng * k * sizeof(float), hipMemcpyDeviceToHost,

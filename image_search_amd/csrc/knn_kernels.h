@@ -1337,6 +1337,174 @@ __global__ __launch_bounds__(256) void knn_scan_batched_kernel(const float* __re
     for (int u = 0; u < NQ; ++u) top[u].store(cand + ((size_t)u * n_waves + wave) * k);
 }
 
+// ---- filtered search (mi_knn_search_filtered): a gathered scan over chosen rows -------------------------------------
+// list[0, n): the filter's live local rows, ascending, once each (the host removes duplicates and deleted rows).  The
+// geometry of knn_scan_kernel with a wave's tile = 64 consecutive LIST ENTRIES: in step it the 16-lane group g streams row
+// list[64 tile + 16 g + it] with the same f32x4 nt loads (a row is dim / 64 fully used 256-byte segments), two row buffers
+// in flight, RowAcc, row16_sum and the same distance expression — an entry's distance has the bits the single pass gives its
+// row.  Lane L reads entry 64 tile + L of the list (one 256-byte load per tile, issued a tile ahead) and the groups take
+// their rows from it by __shfl.  Entries past n repeat the last entry's row and offer KEY_MAX.
+// KEYS = 0: make_key(dist, row) into the per-wave list (Top); knn_merge_kernel / knn_merge_block_kernel and
+// knn_finalize_kernel as for the single pass.  KEYS = 1: entry e's 32-bit distance key to all_keys[e]; the radix select runs
+// over the n compact keys with the entry's POSITION as the low word (the list ascends, so (distance, position) orders as
+// (distance, row)), and knn_gather_rows_kernel puts the rows back.
+// A kernel of its own, not a template flag of knn_scan_kernel: a one-word change to that body moved hipcc's schedule
+// of it and cost 13 %.  No deleted rows reach it, so it has no bitmap.
+template <int NCH, class Top, int KEYS = 0>
+__global__ __launch_bounds__(256, 2) void knn_scan_gather_kernel(const float* __restrict__ table, const uint32_t* __restrict__ list,
+                                                              uint32_t n, const float* __restrict__ q, uint32_t k,
+                                                              uint64_t* __restrict__ cand, uint32_t* __restrict__ all_keys) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int DIM = NCH * 64;
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    const int i = lane & 15, g = lane >> 4;
+    const uint32_t wave = blockIdx.x * 4 + wib, n_waves = gridDim.x * 4;
+
+    f32x4 qf[NCH];
+#pragma unroll
+    for (int t = 0; t < NCH; ++t) qf[t] = *reinterpret_cast<const f32x4*>(q + 64 * t + 4 * i);
+    float sq;  // sqrt(q.q), same summation order as a row
+    {
+        RowAcc<NCH> a; a.zero();
+#pragma unroll
+        for (int t = 0; t < NCH; ++t) a.step(qf[t], qf[t]);
+        sq = sqrtf(a.sumsq());
+    }
+    Top top;
+    top.init(reinterpret_cast<uint64_t*>(smem) + (size_t)wib * Top::LDS_KEYS, k, lane);
+
+    const uint32_t n_tiles = (n + 63) >> 6;
+    auto entry_row = [&](uint32_t tile) {
+        const uint64_t e = ((uint64_t)tile << 6) + lane;
+        return list[e < n ? e : n - 1];
+    };
+    auto load_row = [&](f32x4 (&x)[NCH], uint32_t r) {
+        const f32x4* p = reinterpret_cast<const f32x4*>(table + (uint64_t)r * DIM) + i;
+#pragma unroll
+        for (int t = 0; t < NCH; ++t) x[t] = __builtin_nontemporal_load(p + 16 * t);
+    };
+    uint32_t next = wave < n_tiles ? entry_row(wave) : 0u;
+    for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
+        const uint32_t myrow = next;  // the row of this lane's entry
+        if (tile + n_waves < n_tiles) next = entry_row(tile + n_waves);
+        auto row_at = [&](int it) { return (uint32_t)__shfl((int)myrow, 16 * g + it, 64); };
+        float mydot = 0.0f, myxx = 1.0f;
+        auto reduce_row = [&](const f32x4 (&x)[NCH], int it) {
+            RowAcc<NCH> a; a.zero();
+#pragma unroll
+            for (int t = 0; t < NCH; ++t) a.step(qf[t], x[t]);
+            const float d = a.dot(), s = a.sumsq();
+            if (i == it) { mydot = d; myxx = s; }
+        };
+        f32x4 xa[NCH], xb[NCH];
+        load_row(xa, row_at(0));
+#pragma unroll 1
+        for (int it = 0; it < 16; it += 2) {
+            load_row(xb, row_at(it + 1));
+            reduce_row(xa, it);
+            load_row(xa, row_at(it + 2 < 16 ? it + 2 : 15));
+            reduce_row(xb, it + 1);
+        }
+        const uint64_t e = ((uint64_t)tile << 6) + lane;
+        const float dist = 1.0f - mydot / (sq * sqrtf(myxx));
+        if constexpr (KEYS == 1) {
+            if (e < n) all_keys[e] = dist_to_u32(dist);
+            continue;
+        }
+        top.offer(e < n ? make_key(dist, myrow) : KEY_MAX);
+    }
+    if constexpr (KEYS != 0) return;
+    top.finish();
+    top.store(cand + (size_t)wave * k);
+}
+
+// NQ queries over one filter in one gathered pass (knn_scan_batched_kernel over list entries instead of rows; k <= 64):
+// the same per-(row, query) arithmetic, so results equal NQ single filtered searches.  cand: [NQ][waves][k].
+template <int NCH, int NQ>
+__global__ __launch_bounds__(256) void knn_scan_gather_batched_kernel(const float* __restrict__ table, const uint32_t* __restrict__ list,
+                                                                      uint32_t n, const float* __restrict__ q, uint32_t k,
+                                                                      uint64_t* __restrict__ cand) {
+    constexpr int DIM = NCH * 64;
+    __shared__ __attribute__((aligned(16))) float qs[NQ * DIM];
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    const int i = lane & 15, g = lane >> 4;
+    const uint32_t wave = blockIdx.x * 4 + wib, n_waves = gridDim.x * 4;
+    for (int j = threadIdx.x; j < NQ * DIM; j += 256) qs[j] = q[j];
+    __syncthreads();
+
+    float sq[NQ];
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+        RowAcc<NCH> a; a.zero();
+#pragma unroll
+        for (int t = 0; t < NCH; ++t) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(&qs[u * DIM + 64 * t + 4 * i]);
+            a.step(v, v);
+        }
+        sq[u] = sqrtf(a.sumsq());
+    }
+    WaveTopReg top[NQ];
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) top[u].init(nullptr, k, lane);
+
+    const uint32_t n_tiles = (n + 63) >> 6;
+    auto entry_row = [&](uint32_t tile) {
+        const uint64_t e = ((uint64_t)tile << 6) + lane;
+        return list[e < n ? e : n - 1];
+    };
+    for (uint32_t tile = wave; tile < n_tiles; tile += n_waves) {
+        const uint32_t myrow = entry_row(tile);  // (no prefetch a tile ahead here: at NQ = 8 its two registers cost scratch)
+        float mydot[NQ], myxx = 1.0f;
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) mydot[u] = 0.0f;
+        for (int it = 0; it < 16; ++it) {
+            const uint32_t r = (uint32_t)__shfl((int)myrow, 16 * g + it, 64);
+            const f32x4* p = reinterpret_cast<const f32x4*>(table + (uint64_t)r * DIM) + i;
+            f32x4 x[NCH];
+#pragma unroll
+            for (int t = 0; t < NCH; ++t) x[t] = __builtin_nontemporal_load(p + 16 * t);
+            float s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+#pragma unroll
+            for (int t = 0; t < NCH; ++t) {
+                s0 = __builtin_fmaf(x[t].x, x[t].x, s0); s1 = __builtin_fmaf(x[t].y, x[t].y, s1);
+                s2 = __builtin_fmaf(x[t].z, x[t].z, s2); s3 = __builtin_fmaf(x[t].w, x[t].w, s3);
+            }
+            const float s = row16_sum((s0 + s1) + (s2 + s3));
+            if (i == it) myxx = s;
+#pragma unroll
+            for (int u = 0; u < NQ; ++u) {
+                float d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+#pragma unroll
+                for (int t = 0; t < NCH; ++t) {
+                    // volatile: an LDS read per use, as in knn_scan_batched_kernel
+                    const f32x4 v = *reinterpret_cast<const volatile f32x4*>(&qs[u * DIM + 64 * t + 4 * i]);
+                    d0 = __builtin_fmaf(v.x, x[t].x, d0); d1 = __builtin_fmaf(v.y, x[t].y, d1);
+                    d2 = __builtin_fmaf(v.z, x[t].z, d2); d3 = __builtin_fmaf(v.w, x[t].w, d3);
+                }
+                const float d = row16_sum((d0 + d1) + (d2 + d3));
+                if (i == it) mydot[u] = d;
+            }
+        }
+        const uint64_t e = ((uint64_t)tile << 6) + lane;
+        const float sx = sqrtf(myxx);
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) {
+            const float dist = 1.0f - mydot[u] / (sq[u] * sx);
+            top[u].offer(e < n ? make_key(dist, myrow) : KEY_MAX);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) top[u].store(cand + ((size_t)u * n_waves + wave) * k);
+}
+
+// behind the radix select of a filtered search: keys (distance << 32 | list position) -> (distance << 32 | list[position])
+__global__ void knn_gather_rows_kernel(uint64_t* __restrict__ keys, uint32_t k, const uint32_t* __restrict__ list) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    const uint64_t key = keys[j];
+    if (key != KEY_MAX) keys[j] = (key & 0xFFFFFFFF00000000ull) | list[(uint32_t)key];
+}
+
 // ---- deleted rows (mi_knn_delete) ----------------------------------------------------
 // rows[0, n) into the deletion bitmap (one bit per row, a 64-bit word per 64-row tile)
 __global__ __launch_bounds__(256) void knn_tomb_set_kernel(const uint32_t* __restrict__ rows, uint32_t n,

@@ -258,7 +258,9 @@ void sharded_deliver_all(mi_knn_sharded* t) {
 // A shard's answer is ONE packed record [nq*k x u64 id | nq*k x f32 distance], padded to 16 bytes: the scan writes both
 // halves in place, the exchange moves it as one piece — one ncclAllGather of bytes per shard (or one copy) — the merge
 // kernel reads the gathered records where they lie, and the merged record goes to the host in one copy.
-void sharded_search_enqueue(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, uint64_t* idx, float* dist) {
+// filter (nullable): a filtered search (mi_knn_sharded_search_filtered), filter[s] = the global ids shard s holds
+void sharded_search_enqueue(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, uint64_t* idx, float* dist,
+                            const std::vector<std::vector<uint64_t>>* filter) {
     const uint32_t n = t->n();
     const size_t per = (size_t)nq * k;                        // results per shard
     const size_t rec = (per * 12 + 15) / 16 * 16;             // bytes of one shard's packed record
@@ -287,7 +289,11 @@ void sharded_search_enqueue(mi_knn_sharded* t, const float* q, uint32_t nq, uint
         sh->writes.begin(st);
         sh->reads.begin(st);
         // several queries per call share their passes over the shard (groups of up to 16 through the two-stage search)
-        knn_search_many(sh, (const float*)sl.d_q[s].p, nq, k, rec_idx(sl.d_rec[s].p), rec_dist(sl.d_rec[s].p), st);
+        if (filter)  // the shard's gathered search over its own ids (none: a no-id record)
+            knn_search_filtered_many(sh, (const float*)sl.d_q[s].p, nq, k, (*filter)[s].data(), (*filter)[s].size(),
+                                     rec_idx(sl.d_rec[s].p), rec_dist(sl.d_rec[s].p), st);
+        else
+            knn_search_many(sh, (const float*)sl.d_q[s].p, nq, k, rec_idx(sl.d_rec[s].p), rec_dist(sl.d_rec[s].p), st);
         sh->reads.end(st);
     }
     mi_knn* first = t->shard[0];
@@ -543,6 +549,29 @@ int mi_knn_sharded_search_async(mi_knn_sharded* t, const float* q, uint32_t nq, 
         if (nq == 0) return;
         std::lock_guard<std::mutex> l(t->mu);
         sharded_search_enqueue(t, q, nq, k, idx, dist);
+    });
+}
+
+// the filtered search on global ids: split by the block-cyclic placement, each shard's gathered search, the usual exchange and
+// merge; waits for the results (every shard's filter stays in its handle until then)
+int mi_knn_sharded_search_filtered(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, const uint64_t* ids, uint64_t n_ids,
+                                   uint64_t* idx, float* dist) {
+    return guarded([&] {
+        check_sharded_search(t, q, nq, k, idx, dist);
+        if (k > 4096) fail(MI_ERR_UNSUPPORTED, "a filtered search takes k <= 4096 (got %u)", k);
+        if (n_ids && !ids) fail(MI_ERR_INVALID, "ids is null");
+        std::lock_guard<std::mutex> l(t->mu);
+        std::vector<std::vector<uint64_t>> per(t->n());
+        for (uint64_t i = 0; i < n_ids; ++i) {  // every id checked before anything runs
+            if (ids[i] >= t->rows)
+                fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)ids[i], (unsigned long long)t->rows);
+            uint32_t s; uint64_t local;
+            sharded_place(t, ids[i], &s, &local);
+            per[s].push_back(ids[i]);
+        }
+        if (nq == 0) return;
+        sharded_search_enqueue(t, q, nq, k, idx, dist, &per);
+        sharded_deliver_all(t);
     });
 }
 

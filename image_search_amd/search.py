@@ -12,7 +12,7 @@ and merged identically on every rank.
 from __future__ import annotations
 
 import ctypes
-from typing import Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -128,15 +128,22 @@ class EmbeddingTable:
         """ids of the deleted rows, ascending (mi_knn_deleted)"""
         return _deleted(lib().mi_knn_deleted, self._h)
 
-    def knn(self, reference: np.ndarray, k: int = K_REFERENCE):
+    def knn(self, reference: np.ndarray, k: int = K_REFERENCE, within=None):
         """`WHERE embedding <|k|> $reference` (search.rs:70-77): (ids, cosine distances),
-        ascending distance then id.  reference: [dim] or [nq,dim]."""
+        ascending distance then id.  reference: [dim] or [nq,dim].
+        within: ids (any order, duplicates allowed): the k nearest among those rows only
+        (mi_knn_search_filtered; deleted rows left out, k <= 4096)."""
         q = _f32(reference)
         single = q.ndim == 1
         q = q.reshape(-1, self.dim)
         idx = np.empty((q.shape[0], k), np.uint64)
         dist = np.empty((q.shape[0], k), np.float32)
-        check(lib().mi_knn_search(self._h, q.ctypes.data, q.shape[0], k, idx.ctypes.data, dist.ctypes.data))
+        if within is None:
+            check(lib().mi_knn_search(self._h, q.ctypes.data, q.shape[0], k, idx.ctypes.data, dist.ctypes.data))
+        else:
+            ids = _ids(within)
+            check(lib().mi_knn_search_filtered(self._h, q.ctypes.data, q.shape[0], k, ids.ctypes.data if ids.size else None,
+                                               ids.size, idx.ctypes.data, dist.ctypes.data))
         return (idx[0], dist[0]) if single else (idx, dist)
 
     def knn_device(self, d_q: int, nq: int, k: int, d_idx: int, d_dist: int, stream: int = 0, batched: bool = False):
@@ -144,8 +151,12 @@ class EmbeddingTable:
         check(fn(self._h, d_q, nq, k, d_idx, d_dist, stream))
 
 
+def _ids(ids) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
+
+
 def _delete(fn, h, ids) -> int:
-    a = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
+    a = _ids(ids)
     newly = ctypes.c_uint64()
     check(fn(h, a.ctypes.data if a.size else None, a.size, ctypes.byref(newly)))
     return newly.value
@@ -350,13 +361,19 @@ class ShardedTable:
         """every row of `src` into this empty table, device to device (mi_knn_sharded_rebalance)"""
         check(lib().mi_knn_sharded_rebalance(self._h, src._h))
 
-    def knn(self, reference: np.ndarray, k: int = K_REFERENCE):
+    def knn(self, reference: np.ndarray, k: int = K_REFERENCE, within=None):
+        """EmbeddingTable.knn over all shards; within: global ids (mi_knn_sharded_search_filtered)"""
         q = _f32(reference)
         single = q.ndim == 1
         q = q.reshape(-1, self.dim)
         idx = np.empty((q.shape[0], k), np.uint64)
         dist = np.empty((q.shape[0], k), np.float32)
-        check(lib().mi_knn_sharded_search(self._h, q.ctypes.data, q.shape[0], k, idx.ctypes.data, dist.ctypes.data))
+        if within is None:
+            check(lib().mi_knn_sharded_search(self._h, q.ctypes.data, q.shape[0], k, idx.ctypes.data, dist.ctypes.data))
+        else:
+            ids = _ids(within)
+            check(lib().mi_knn_sharded_search_filtered(self._h, q.ctypes.data, q.shape[0], k, ids.ctypes.data if ids.size else None,
+                                                       ids.size, idx.ctypes.data, dist.ctypes.data))
         return (idx[0], dist[0]) if single else (idx, dist)
 
     def delete(self, ids) -> int:
@@ -588,17 +605,25 @@ class ImageIndex:
         rows = [int(i) for i in ids]
         return rows, [self.table.rows(r, 1)[0] for r in rows]
 
-    def web_search_text(self, text_embedding: np.ndarray, referenced_images: Sequence[str] = (), k: int = K_REFERENCE):
+    def web_search_text(self, text_embedding: np.ndarray, referenced_images: Sequence[str] = (), k: int = K_REFERENCE,
+                        folders: Optional[Sequence[str]] = None):
         """search.rs:20-110 after the text tower: refine with the marked images that are in the
         table, K nearest by cosine distance, paths mapped back under `media/`.
-        Returns [(id, image_path, similarity)] with similarity = vector::distance::knn()."""
+        Returns [(id, image_path, similarity)] with similarity = vector::distance::knn().
+        folders: client names ("media/2024/trip"; "media/" = everything): the K nearest among the
+        images under them, whole path components (mi_index_search_within)."""
         q = _f32(text_embedding).reshape(-1)
         refs = list(referenced_images)
         idx = np.empty(k, np.uint64)
         dist = np.empty(k, np.float32)
         n = ctypes.c_uint32()
-        check(lib().mi_index_search(self._h, q.ctypes.data, _cstrs(refs), len(refs), k, idx.ctypes.data, dist.ctypes.data,
-                                    ctypes.byref(n)))
+        if folders is None:
+            check(lib().mi_index_search(self._h, q.ctypes.data, _cstrs(refs), len(refs), k, idx.ctypes.data, dist.ctypes.data,
+                                        ctypes.byref(n)))
+        else:
+            fs = list(folders)
+            check(lib().mi_index_search_within(self._h, q.ctypes.data, _cstrs(refs), len(refs), _cstrs(fs), len(fs), k,
+                                               idx.ctypes.data, dist.ctypes.data, ctypes.byref(n)))
         return [(int(idx[i]), self.path(int(idx[i]), web=True), float(dist[i])) for i in range(n.value)]
 
     def save(self, directory: str):

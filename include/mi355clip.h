@@ -321,6 +321,15 @@ int mi_knn_search_device(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, u
  * 32 MB of candidate rows + keys, and the select / sort buffers; a failed allocation fails that search with MI_ERR_OOM. */
 int mi_knn_search_batched_device(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_idx,
                                  float* d_dist, void* stream);
+/* Filtered search: the k nearest among the rows the ids name (`WHERE embedding <|K|> $reference AND id IN $ids` as a
+ * pre-filter — exactly k hits whenever k rows qualify).  The result is bit-identical to mi_knn_search over a table that
+ * holds only the filter's live rows under their own ids: ids, order (distance ascending, then id, NaN last) and distance
+ * bits, MI_KNN_NO_ID / +inf behind the last hit.  ids: any order, duplicates allowed, n_ids may be 0 (then every result is
+ * MI_KNN_NO_ID); every id must be a row of the table (MI_ERR_INVALID otherwise, and nothing runs); ids of deleted rows
+ * are allowed and left out.  k <= 4096 (MI_ERR_UNSUPPORTED above).  Runs on the handle's stream behind every write and
+ * search enqueued before it; reads only the filter's fp32 rows (n x dim x 4 bytes; the "prefilter" mirrors are not used). */
+int mi_knn_search_filtered(mi_knn* t, const float* q, uint32_t nq, uint32_t k, const uint64_t* ids, uint64_t n_ids,
+                           uint64_t* idx, float* dist);
 
 /* ---------------------------------------------- Seam B over several GPUs, ONE process */
 
@@ -373,6 +382,10 @@ int mi_knn_sharded_load(mi_knn_sharded* t, const char* prefix);
  * (any shard count and block size) and rebalance carry the deletions */
 int mi_knn_sharded_delete(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint64_t* newly);
 int mi_knn_sharded_deleted(mi_knn_sharded* t, uint64_t* ids, uint64_t cap, uint64_t* count);
+/* mi_knn_search_filtered on global ids: every shard searches the ids it holds, the merge does the rest; the result equals
+ * the filtered search of one table that holds every row.  Waits for its results. */
+int mi_knn_sharded_search_filtered(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, const uint64_t* ids,
+                                   uint64_t n_ids, uint64_t* idx, float* dist);
 /* Change the layout of a LIVE table: every row of `src` into the empty `dst` (another shard count, device set or block
  * size), block by block, device to device — a plain copy where source and destination shard share a GPU,
  * hipMemcpyPeerAsync over xGMI where they do not; nothing passes through the host.  src is unchanged. */
@@ -483,6 +496,14 @@ int mi_index_path(mi_index* ix, uint64_t id, int web, char* buf, size_t cap, siz
  * refine the query; idx/dist [k] as mi_knn_search; *n_found (may be NULL) = results before the MI_KNN_NO_ID padding */
 int mi_index_search(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref, uint32_t k,
                     uint64_t* idx, float* dist, uint32_t* n_found);
+/* mi_index_search among the rows under the given folders (`... AND string::starts_with(image_path, $folder)`, as a
+ * pre-filter: exactly k hits whenever k rows qualify).  Folders are client names: "media/2024/trip" matches whole path
+ * components (media/2024/trip/a.jpg and media/2024/trip/x/b.jpg, not media/2024/tripb/c.jpg); "media/" is the whole media
+ * directory; names outside "media/" match nothing.  Refinement by referenced_images as in mi_index_search, marked images
+ * outside the folders included.  Removed paths match nothing.  k <= 4096. */
+int mi_index_search_within(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
+                           const char* const* folders, size_t n_folders, uint32_t k, uint64_t* idx, float* dist,
+                           uint32_t* n_found);
 /* `<dir>/embedding.miknn` + `<dir>/image_path.bin`, each through a temporary file, fsync and rename, the path file
  * last: after a crash the directory holds a consistent index (at worst the one before the save). */
 int mi_index_save(mi_index* ix, const char* dir);
