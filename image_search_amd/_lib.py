@@ -58,6 +58,12 @@ SYMBOLS = {
     "mi_knn_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, c_vp]),
     "mi_knn_search_batched_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, c_vp]),
     "mi_knn_search_filtered": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, ctypes.c_uint64, c_vp, c_vp]),
+    "mi_knn_near_pairs": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint64, c_vp, c_vp, c_vp, ctypes.c_uint64, c_u64p]),
+    "mi_knn_near_pairs_stats": (ctypes.c_int, [c_vp, c_u64p]),
+    "mi_pairs_to_groups": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_u64p,
+                                          c_u64p]),
+    "mi_index_duplicates": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,
+                                           ctypes.c_uint64, c_u64p, c_u64p]),
     "mi_knn_sharded_create": (ctypes.c_int, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_uint32,
                                              ctypes.POINTER(c_vp)]),
     "mi_knn_sharded_free": (None, [c_vp]),

@@ -199,6 +199,10 @@ struct mi_knn {
     size_t n_flist = 0, h_flist_cap = 0;
     uint32_t* d_flist = nullptr;
     size_t flist_cap = 0;
+    // Threshold self-join (mi_knn_near_pairs, join.hip): candidate pairs one strip of stage 1 may hand to stage 2 (option
+    // "join_cap"; its buffers live for the call only), and {candidates, pairs, strips, tiles} of the last call.
+    uint32_t join_cap = 1u << 22;
+    uint64_t join_stats[4] = {0, 0, 0, 0};
     std::mutex mu;
 };
 

@@ -1,0 +1,354 @@
+// join.hip — host side of the threshold self-join (mi_knn_near_pairs, mi_pairs_to_groups, mi_index_duplicates).
+// The kernels and the bound that makes the bf16 first stage exact: join_kernels.h.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include <mutex>
+#include <vector>
+
+#include "common.h"
+#include "handles.h"
+#include "join_kernels.h"
+
+using namespace mi;
+using namespace mi_join::mi;
+
+namespace {
+
+struct JoinPair { uint32_t a, b; float d; };
+
+// device memory of one call, freed on every way out
+struct Scratch {
+    std::vector<void*> p;
+    void* get(size_t bytes) {
+        void* q = nullptr;
+        HIP_CHECK(hipMalloc(&q, std::max<size_t>(bytes, 16)));
+        p.push_back(q);
+        return q;
+    }
+    ~Scratch() {
+        for (void* q : p) (void)hipFree(q);
+    }
+};
+
+// the table's own mirror grows with its capacity, keeping the rows mirrored so far (what the two-stage search does)
+void grow_keep(mi_knn* t, void** p, size_t* have, size_t want, size_t elem, size_t keep) {
+    if (*have >= want) return;
+    t->reads.sync();
+    void* np_ = nullptr;
+    HIP_CHECK(hipMalloc(&np_, want * elem));
+    if (*p && keep) HIP_CHECK(hipMemcpy(np_, *p, std::min(keep, *have) * elem, hipMemcpyDeviceToDevice));
+    if (*p) HIP_CHECK(hipFree(*p));
+    *p = np_;
+    *have = want;
+}
+
+struct Join {
+    mi_knn* t;
+    hipStream_t s;
+    const uint16_t* mirror;
+    const float* xx;
+    const uint64_t* tomb;
+    uint32_t n_rows, first_new, n_blocks;
+    float max_dist, c;
+    uint32_t cand_cap;
+    uint64_t user_cap;
+    uint2 *d_cand, *d_pairs;
+    float* d_dist;
+    unsigned long long* d_count;   // [0]: candidates of the strip, [1] (low word): pairs stage 2 kept
+    std::vector<uint2> h_pairs;
+    std::vector<float> h_dist;
+    std::vector<JoinPair> out;
+    uint64_t stats[4] = {0, 0, 0, 0};
+    bool over = false;
+
+    template <int NCH>
+    void rect(uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) {
+        if (over) return;
+        bc0 = std::max(bc0, br0);
+        if (bc0 >= bc1 || br0 >= br1) return;
+        static DevOnce once;
+        allow_lds_once(once, join_tiles_kernel<NCH>, JOIN_LDS);
+        HIP_CHECK(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), s));
+        hipLaunchKernelGGL((join_tiles_kernel<NCH>), dim3(bc1 - bc0, br1 - br0), dim3(256), JOIN_LDS, s, mirror, xx, tomb, n_rows,
+                           first_new, br0, bc0, c, cand_cap, d_cand, d_count);
+        HIP_CHECK(hipGetLastError());
+        unsigned long long n_cand = 0;
+        HIP_CHECK(hipMemcpyAsync(&n_cand, d_count, sizeof n_cand, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        ++stats[2];
+        for (uint32_t bi = br0; bi < br1; ++bi) stats[3] += bc1 - std::max(bc0, bi);
+        if (n_cand > cand_cap) {   // nothing is dropped: the same ground again in two halves, rows first, then columns
+            if (overflowed) *overflowed = true;
+            if (br1 - br0 > 1) {
+                const uint32_t mid = br0 + (br1 - br0) / 2;
+                rect<NCH>(br0, mid, bc0, bc1, nullptr);
+                rect<NCH>(mid, br1, bc0, bc1, nullptr);
+            } else if (bc1 - bc0 > 1) {
+                const uint32_t mid = bc0 + (bc1 - bc0) / 2;
+                rect<NCH>(br0, br1, bc0, mid, nullptr);
+                rect<NCH>(br0, br1, mid, bc1, nullptr);
+            } else {
+                fail(MI_ERR_INVALID, "one tile reported %llu candidates (the buffer holds %u)", n_cand, cand_cap);
+            }
+            return;
+        }
+        stats[0] += n_cand;
+        if (n_cand == 0) return;
+        const uint32_t C = (uint32_t)n_cand;
+        const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)t->n_cu * 8, (C + 15) / 16));
+        hipLaunchKernelGGL((join_rescore_kernel<NCH>), dim3(blocks), dim3(256), 0, s, t->table, d_cand, C, max_dist, d_pairs, d_dist,
+                           reinterpret_cast<uint32_t*>(d_count + 1));
+        HIP_CHECK(hipGetLastError());
+        uint32_t kept = 0;
+        HIP_CHECK(hipMemcpyAsync(&kept, d_count + 1, sizeof kept, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (kept) {
+            h_pairs.resize(kept);
+            h_dist.resize(kept);
+            HIP_CHECK(hipMemcpyAsync(h_pairs.data(), d_pairs, (size_t)kept * sizeof(uint2), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(h_dist.data(), d_dist, (size_t)kept * sizeof(float), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            const size_t at = out.size();
+            out.resize(at + kept);
+            for (uint32_t j = 0; j < kept; ++j) out[at + j] = JoinPair{h_pairs[j].x, h_pairs[j].y, h_dist[j]};
+        }
+        stats[1] += kept;
+        if (stats[1] > user_cap) over = true;   // checked between strips: the call stops here
+    }
+
+    template <int NCH>
+    void run() {
+        const uint32_t fnb = first_new / JOIN_TILE;   // column blocks below hold no b >= first_new
+        const uint32_t n_cols = n_blocks - fnb;
+        // strips of tile rows: enough tiles per launch to fill the device a few times over, few enough that an ordinary
+        // corpus never meets the candidate buffer's end
+        uint32_t strip = std::max<uint32_t>(1u, std::min<uint32_t>(256u, (1u << 18) / std::max(n_cols, 1u)));
+        for (uint32_t br = 0; br < n_blocks && !over;) {
+            const uint32_t end = std::min(n_blocks, br + strip);
+            bool overflowed = false;
+            rect<NCH>(br, end, fnb, n_blocks, &overflowed);
+            if (overflowed) strip = std::max(1u, strip / 2);
+            br = end;
+        }
+    }
+};
+
+// first_new (an id of the table, one past its last id, or 0 = everything) -> local row
+uint32_t local_first_new(const mi_knn* t, uint64_t first_new) {
+    if (first_new == 0) return 0;
+    const IdMap map{t->base, t->cyc_block, t->cyc_n, t->cyc_rank};
+    if (first_new == id_of_local(map, t->rows)) return (uint32_t)t->rows;
+    // (ids are monotone in the local ordinal: a binary search serves the plain and the block-cyclic map alike)
+    uint64_t lo = 0, hi = t->rows;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (id_of_local(map, mid) < first_new) lo = mid + 1; else hi = mid;
+    }
+    if (lo >= t->rows || id_of_local(map, lo) != first_new)
+        fail(MI_ERR_INVALID, "first_new %llu is neither a row of this table (base %llu, %llu rows) nor one past its last",
+             (unsigned long long)first_new, (unsigned long long)t->base, (unsigned long long)t->rows);
+    return (uint32_t)lo;
+}
+
+// the join itself: pairs as local rows, ascending by (a, b); *over = more than user_cap pairs qualify (out is then partial)
+void near_pairs(mi_knn* t, float max_dist, uint64_t first_new_id, uint64_t user_cap, std::vector<JoinPair>* out, bool* over) {
+    out->clear();
+    *over = false;
+    std::lock_guard<std::mutex> l(t->mu);
+    for (uint64_t& v : t->join_stats) v = 0;
+    const uint32_t fn = local_first_new(t, first_new_id);
+    if (t->dim % 128 != 0 || (t->dim / 64 != 2 && t->dim / 64 != 4 && t->dim / 64 != 8 && t->dim / 64 != 12 && t->dim / 64 != 16))
+        fail(MI_ERR_UNSUPPORTED, "dim %u: the join's bf16 mirror is built for dim in {128, 256, 512, 768, 1024}", t->dim);
+    if (t->rows < 2 || fn >= t->rows) return;
+    DeviceGuard g(t->device);
+    hipStream_t s = knn_own_stream(t);
+    // behind every write and search enqueued before this call, on whichever stream
+    t->writes.begin(s);
+    t->reads.begin(s);
+
+    Scratch scratch;
+    struct Settle {   // whatever happens, the handle's stream is idle and its order words say so when the call leaves
+        mi_knn* t; hipStream_t s;
+        ~Settle() { (void)hipStreamSynchronize(s); t->reads.pending = false; }
+    } settle{t, s};
+    Join j;
+    j.t = t; j.s = s;
+    j.n_rows = (uint32_t)t->rows; j.first_new = fn;
+    j.n_blocks = (uint32_t)((t->rows + JOIN_TILE - 1) / JOIN_TILE);
+    j.max_dist = max_dist;
+    const float eps2 = 0x1p-7f + 0x1p-16f + 4.1f * (float)(t->dim + 8) * 0x1p-24f + 2e-6f;
+    j.c = 1.0f - (max_dist + eps2);
+    j.cand_cap = std::max<uint32_t>(JOIN_CAP_MIN, t->join_cap);
+    j.user_cap = user_cap;
+    j.tomb = t->dead.empty() ? nullptr : t->d_tomb;
+
+    // the mirror: the table's own when "prefilter" = 1 keeps one (caught up here as a search would), else one for this call
+    uint16_t* mirror = nullptr;
+    float* xx = nullptr;
+    uint64_t from = 0;
+    if (t->prefilter == 1) {
+        t->mirror_rows = std::min(t->mirror_rows, t->rows);
+        grow_keep(t, (void**)&t->d_mirror, &t->mirror_cap, (size_t)t->cap * t->dim, sizeof(uint16_t), (size_t)t->mirror_rows * t->dim);
+        grow_keep(t, (void**)&t->d_xx, &t->xx_cap, (size_t)t->cap, sizeof(float), (size_t)t->mirror_rows);
+        mirror = t->d_mirror; xx = t->d_xx; from = t->mirror_rows;
+    } else {
+        mirror = (uint16_t*)scratch.get((size_t)t->rows * t->dim * sizeof(uint16_t));
+        xx = (float*)scratch.get((size_t)t->rows * sizeof(float));
+    }
+    if (from < t->rows) {
+        const uint64_t todo = t->rows - from;
+        const uint32_t mb = std::max<uint32_t>(1u, (uint32_t)std::min<uint64_t>((uint64_t)t->n_cu * 8, (todo + 15) / 16));
+        switch (t->dim / 64) {
+#define MI_CASE(NCH) case NCH: hipLaunchKernelGGL((knn_mirror_kernel<NCH>), dim3(mb), dim3(256), 0, s, t->table, from, t->rows, mirror, xx); break;
+            MI_CASE(2) MI_CASE(4) MI_CASE(8) MI_CASE(12) MI_CASE(16)
+#undef MI_CASE
+        }
+        HIP_CHECK(hipGetLastError());
+        if (t->prefilter == 1) t->mirror_rows = t->rows;
+    }
+    j.mirror = mirror; j.xx = xx;
+    j.d_cand = (uint2*)scratch.get((size_t)j.cand_cap * sizeof(uint2));
+    j.d_pairs = (uint2*)scratch.get((size_t)j.cand_cap * sizeof(uint2));
+    j.d_dist = (float*)scratch.get((size_t)j.cand_cap * sizeof(float));
+    j.d_count = (unsigned long long*)scratch.get(2 * sizeof(unsigned long long));
+
+    switch (t->dim / 64) {
+        case 2: j.run<2>(); break;
+        case 4: j.run<4>(); break;
+        case 8: j.run<8>(); break;
+        case 12: j.run<12>(); break;
+        case 16: j.run<16>(); break;
+    }
+    for (int i = 0; i < 4; ++i) t->join_stats[i] = j.stats[i];
+    *over = j.over;
+    if (j.over) return;
+    std::sort(j.out.begin(), j.out.end(), [](const JoinPair& x, const JoinPair& y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
+    out->swap(j.out);
+}
+
+void check_join_args(const mi_knn* t, float max_dist) {
+    if (!(max_dist >= 0.0f)) fail(MI_ERR_INVALID, "max_dist must be a number >= 0 (got %g)", (double)max_dist);
+    if (!t) fail(MI_ERR_INVALID, "null table handle");
+}
+
+// pairs -> connected components.  ids_out: every id of a pair, grouped; starts: n_groups + 1 offsets into it
+void groups_of(const uint64_t* a, const uint64_t* b, uint64_t n_pairs, std::vector<uint64_t>* ids_out, std::vector<uint64_t>* starts) {
+    std::vector<uint64_t> ids;
+    ids.reserve((size_t)n_pairs * 2);
+    for (uint64_t i = 0; i < n_pairs; ++i) { ids.push_back(a[i]); ids.push_back(b[i]); }
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    const size_t n = ids.size();
+    std::vector<uint32_t> parent(n);
+    for (size_t i = 0; i < n; ++i) parent[i] = (uint32_t)i;
+    auto find = [&](uint32_t x) {
+        while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; }
+        return x;
+    };
+    auto slot = [&](uint64_t id) { return (uint32_t)(std::lower_bound(ids.begin(), ids.end(), id) - ids.begin()); };
+    for (uint64_t i = 0; i < n_pairs; ++i) {
+        const uint32_t x = find(slot(a[i])), y = find(slot(b[i]));
+        if (x != y) parent[std::max(x, y)] = std::min(x, y);   // the root is the component's smallest id
+    }
+    // groups ordered by their smallest id (= their root), ids ascending inside: a stable counting pass over the sorted ids
+    std::vector<uint32_t> root(n), order;
+    std::vector<uint64_t> size(n, 0);
+    for (size_t i = 0; i < n; ++i) { root[i] = find((uint32_t)i); ++size[root[i]]; }
+    std::vector<uint64_t> at(n, 0);
+    starts->clear();
+    uint64_t run = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (root[i] == i) { at[i] = run; starts->push_back(run); run += size[i]; }
+    starts->push_back(run);
+    ids_out->assign(n, 0);
+    for (size_t i = 0; i < n; ++i) (*ids_out)[at[root[i]]++] = ids[i];
+}
+
+void write_groups(const std::vector<uint64_t>& gids, const std::vector<uint64_t>& starts, uint64_t* ids, uint64_t cap_ids,
+                  uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups) {
+    *n_ids = gids.size();
+    *n_groups = starts.size() - 1;
+    if (ids) std::copy(gids.begin(), gids.begin() + (size_t)std::min<uint64_t>(cap_ids, gids.size()), ids);
+    if (group_start) std::copy(starts.begin(), starts.begin() + (size_t)std::min<uint64_t>(cap_groups, starts.size()), group_start);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_knn_near_pairs(mi_knn* t, float max_dist, uint64_t first_new, uint64_t* a, uint64_t* b, float* dist, uint64_t cap,
+                      uint64_t* count) {
+    return guarded([&] {
+        if (count) *count = 0;
+        check_join_args(t, max_dist);
+        if (!count) fail(MI_ERR_INVALID, "count is null");
+        if (cap && (!a || !b || !dist)) fail(MI_ERR_INVALID, "a, b or dist is null with cap %llu", (unsigned long long)cap);
+        std::vector<JoinPair> pairs;
+        bool over = false;
+        near_pairs(t, max_dist, first_new, cap, &pairs, &over);
+        if (over) {
+            *count = cap + 1;
+            fail(MI_ERR_UNSUPPORTED, "more than %llu pairs lie within %g: lower max_dist or raise cap", (unsigned long long)cap,
+                 (double)max_dist);
+        }
+        const IdMap map{t->base, t->cyc_block, t->cyc_n, t->cyc_rank};
+        for (size_t i = 0; i < pairs.size(); ++i) {
+            a[i] = id_of_local(map, pairs[i].a);
+            b[i] = id_of_local(map, pairs[i].b);
+            dist[i] = pairs[i].d;
+        }
+        *count = pairs.size();
+    });
+}
+
+int mi_knn_near_pairs_stats(mi_knn* t, uint64_t out[4]) {
+    return guarded([&] {
+        if (!t || !out) fail(MI_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> l(t->mu);
+        for (int i = 0; i < 4; ++i) out[i] = t->join_stats[i];
+    });
+}
+
+int mi_pairs_to_groups(const uint64_t* a, const uint64_t* b, uint64_t n_pairs, uint64_t* ids, uint64_t cap_ids, uint64_t* group_start,
+                       uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups) {
+    return guarded([&] {
+        if (!n_ids || !n_groups) fail(MI_ERR_INVALID, "n_ids or n_groups is null");
+        *n_ids = 0; *n_groups = 0;
+        if (n_pairs && (!a || !b)) fail(MI_ERR_INVALID, "a or b is null with %llu pairs", (unsigned long long)n_pairs);
+        if ((cap_ids && !ids) || (cap_groups && !group_start)) fail(MI_ERR_INVALID, "an output array is null with a cap > 0");
+        if (n_pairs >= (1ull << 31)) fail(MI_ERR_UNSUPPORTED, "at most 2^31 - 1 pairs (got %llu)", (unsigned long long)n_pairs);
+        std::vector<uint64_t> gids, starts;
+        groups_of(a, b, n_pairs, &gids, &starts);
+        write_groups(gids, starts, ids, cap_ids, group_start, cap_groups, n_ids, n_groups);
+    });
+}
+
+int mi_index_duplicates(mi_index* ix, float max_dist, uint64_t first_new, uint64_t max_pairs, uint64_t* ids, uint64_t cap_ids,
+                        uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups) {
+    return guarded([&] {
+        if (n_ids) *n_ids = 0;
+        if (n_groups) *n_groups = 0;
+        if (!ix) fail(MI_ERR_INVALID, "null index handle");
+        mi_knn* t = mi_index_table(ix);
+        check_join_args(t, max_dist);
+        if (!n_ids || !n_groups) fail(MI_ERR_INVALID, "n_ids or n_groups is null");
+        if ((cap_ids && !ids) || (cap_groups && !group_start)) fail(MI_ERR_INVALID, "an output array is null with a cap > 0");
+        std::vector<JoinPair> pairs;
+        bool over = false;
+        // (a removed path's rows are deleted rows of the table: the join never reports them)
+        near_pairs(t, max_dist, first_new, max_pairs, &pairs, &over);
+        if (over)
+            fail(MI_ERR_UNSUPPORTED, "more than %llu pairs lie within %g: lower max_dist or raise max_pairs",
+                 (unsigned long long)max_pairs, (double)max_dist);
+        const IdMap map{t->base, t->cyc_block, t->cyc_n, t->cyc_rank};
+        std::vector<uint64_t> pa(pairs.size()), pb(pairs.size());
+        for (size_t i = 0; i < pairs.size(); ++i) { pa[i] = id_of_local(map, pairs[i].a); pb[i] = id_of_local(map, pairs[i].b); }
+        std::vector<uint64_t> gids, starts;
+        groups_of(pa.data(), pb.data(), pairs.size(), &gids, &starts);
+        write_groups(gids, starts, ids, cap_ids, group_start, cap_groups, n_ids, n_groups);
+    });
+}
+
+}  // extern "C"

@@ -1037,8 +1037,13 @@ int mi_knn_set_option(mi_knn* t, const char* key, int value) {
             // count does not, pref_fold); 0: every query tries stage 1
             pref_reset(t);
             t->pref_adaptive = value != 0;
+        } else if (k == "join_cap") {
+            // candidate pairs one strip of mi_knn_near_pairs' first stage may hand to its second (default 2^22; at least one
+            // full tile, 2^14): a strip that finds more is redone in smaller pieces.  Same answers whatever the value.
+            if (value < (1 << 14)) fail(MI_ERR_INVALID, "join_cap must be >= 16384 (got %d)", value);
+            t->join_cap = (uint32_t)value;
         } else {
-            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1)", key);
+            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap)", key);
         }
     });
 }

@@ -137,9 +137,37 @@ class EmbeddingTable {
         return {idx, dist};
     }
     mi_knn* handle() const { return h_; }
+    // near-duplicates (mi_knn_near_pairs): every pair of live rows a < b with cosine distance <= max_dist, ascending by
+    // (a, b), with the distance knn(row a) reports for row b; first_new: only pairs with b >= first_new
+    struct NearPairs { std::vector<uint64_t> a, b; std::vector<float> dist; };
+    NearPairs near_pairs(float max_dist, uint64_t first_new = 0, uint64_t cap = 1ull << 20) const {
+        NearPairs r;
+        r.a.resize(cap); r.b.resize(cap); r.dist.resize(cap);
+        uint64_t n = 0;
+        check(mi_knn_near_pairs(h_, max_dist, first_new, r.a.data(), r.b.data(), r.dist.data(), cap, &n));
+        r.a.resize(n); r.b.resize(n); r.dist.resize(n);
+        return r;
+    }
+    // {candidate pairs, pairs accepted, strips run, tiles visited} of the last near_pairs
+    std::vector<uint64_t> near_pairs_stats() const { std::vector<uint64_t> v(4); check(mi_knn_near_pairs_stats(h_, v.data())); return v; }
     // "prefilter" = 2 (bytes) or 1 (bf16): the two-stage exact search, same results from a quarter / a half of the bytes
     void set_option(const std::string& key, int value) { check(mi_knn_set_option(h_, key.c_str(), value)); }
 };
+
+// pairs -> groups (mi_pairs_to_groups: connected components), ordered by their smallest id, ids ascending inside
+inline std::vector<std::vector<uint64_t>> groups_from(const std::vector<uint64_t>& ids, const std::vector<uint64_t>& start) {
+    std::vector<std::vector<uint64_t>> out;
+    for (size_t g = 0; g + 1 < start.size(); ++g) out.emplace_back(ids.begin() + (ptrdiff_t)start[g], ids.begin() + (ptrdiff_t)start[g + 1]);
+    return out;
+}
+inline std::vector<std::vector<uint64_t>> pairs_to_groups(const std::vector<uint64_t>& a, const std::vector<uint64_t>& b) {
+    if (a.size() != b.size()) throw std::runtime_error("pairs_to_groups: a and b differ in length");
+    uint64_t n_ids = 0, n_groups = 0;
+    check(mi_pairs_to_groups(a.data(), b.data(), a.size(), nullptr, 0, nullptr, 0, &n_ids, &n_groups));
+    std::vector<uint64_t> ids(n_ids), start(n_groups + 1);
+    check(mi_pairs_to_groups(a.data(), b.data(), a.size(), ids.data(), ids.size(), start.data(), start.size(), &n_ids, &n_groups));
+    return groups_from(ids, start);
+}
 
 // the whole table `image` {id, image_path, embedding} (server/src/search.rs:13-18) and the four statements the
 // server issues against it
@@ -198,6 +226,21 @@ class ImageIndex {
         check(mi_index_search(h_, text_embedding.data(), p.data(), p.size(), k, idx.data(), dist.data(), &n));
         std::vector<std::pair<uint64_t, float>> out;
         for (uint32_t i = 0; i < n; ++i) out.emplace_back(idx[i], dist[i]);
+        return out;
+    }
+    // groups of near-duplicate images as paths (mi_index_duplicates), what a /duplicates handler returns; removed paths
+    // never appear; first_new: only what the rows from that id on duplicate
+    std::vector<std::vector<std::string>> duplicates(float max_dist, uint64_t first_new = 0, bool web = false,
+                                                      uint64_t max_pairs = 1ull << 20) const {
+        uint64_t n_ids = 0, n_groups = 0;
+        check(mi_index_duplicates(h_, max_dist, first_new, max_pairs, nullptr, 0, nullptr, 0, &n_ids, &n_groups));
+        std::vector<uint64_t> ids(n_ids), start(n_groups + 1);
+        check(mi_index_duplicates(h_, max_dist, first_new, max_pairs, ids.data(), ids.size(), start.data(), start.size(), &n_ids, &n_groups));
+        std::vector<std::vector<std::string>> out;
+        for (const auto& g : groups_from(ids, start)) {
+            out.emplace_back();
+            for (uint64_t id : g) out.back().push_back(path(id, web));
+        }
         return out;
     }
     void save(const std::string& dir) const { check(mi_index_save(h_, dir.c_str())); }

@@ -150,6 +150,42 @@ class EmbeddingTable:
         fn = lib().mi_knn_search_batched_device if batched else lib().mi_knn_search_device
         check(fn(self._h, d_q, nq, k, d_idx, d_dist, stream))
 
+    def near_pairs(self, max_dist: float, first_new: int = 0, cap: int = 1 << 20):
+        """Near-duplicates (mi_knn_near_pairs): every pair of live rows a < b with cosine distance <= max_dist as
+        (a, b, dist), ascending by (a, b); dist is what knn(row a) reports for row b, bit for bit.  first_new: only pairs
+        with b >= first_new.  More than `cap` pairs: MiError (MI_ERR_UNSUPPORTED) — lower max_dist or raise cap."""
+        a, b = np.empty(cap, np.uint64), np.empty(cap, np.uint64)
+        dist = np.empty(cap, np.float32)
+        n = ctypes.c_uint64()
+        check(lib().mi_knn_near_pairs(self._h, float(max_dist), int(first_new), a.ctypes.data if cap else None,
+                                      b.ctypes.data if cap else None, dist.ctypes.data if cap else None, cap, ctypes.byref(n)))
+        return a[:n.value].copy(), b[:n.value].copy(), dist[:n.value].copy()
+
+    def near_pairs_stats(self):
+        """mi_knn_near_pairs_stats, of the last near_pairs on this table"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_near_pairs_stats(self._h, out))
+        return {"candidates": out[0], "pairs": out[1], "strips": out[2], "tiles": out[3]}
+
+
+def _groups(ids: np.ndarray, starts: np.ndarray) -> list:
+    return [ids[int(starts[g]):int(starts[g + 1])] for g in range(len(starts) - 1)]
+
+
+def pairs_to_groups(a, b) -> list:
+    """Pairs -> groups (mi_pairs_to_groups: connected components): arrays of ids, ascending inside a group, the groups
+    ordered by their smallest id."""
+    a, b = _ids(a), _ids(b)
+    if a.size != b.size:
+        raise ValueError(f"{a.size} first ids for {b.size} second ids")
+    n_ids, n_groups = ctypes.c_uint64(), ctypes.c_uint64()
+    pa, pb = (a.ctypes.data, b.ctypes.data) if a.size else (None, None)
+    check(lib().mi_pairs_to_groups(pa, pb, a.size, None, 0, None, 0, ctypes.byref(n_ids), ctypes.byref(n_groups)))
+    ids, starts = np.empty(n_ids.value, np.uint64), np.empty(n_groups.value + 1, np.uint64)
+    check(lib().mi_pairs_to_groups(pa, pb, a.size, ids.ctypes.data if ids.size else None, ids.size, starts.ctypes.data, starts.size,
+                                   ctypes.byref(n_ids), ctypes.byref(n_groups)))
+    return _groups(ids, starts)
+
 
 def _ids(ids) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
@@ -625,6 +661,18 @@ class ImageIndex:
             check(lib().mi_index_search_within(self._h, q.ctypes.data, _cstrs(refs), len(refs), _cstrs(fs), len(fs), k,
                                                idx.ctypes.data, dist.ctypes.data, ctypes.byref(n)))
         return [(int(idx[i]), self.path(int(idx[i]), web=True), float(dist[i])) for i in range(n.value)]
+
+    def duplicates(self, max_dist: float, first_new: int = 0, web: bool = False, max_pairs: int = 1 << 20) -> list:
+        """Groups of near-duplicate images (mi_index_duplicates): lists of paths whose embeddings are chained by cosine
+        distances <= max_dist, ordered by row id inside a group and by their first row between groups; removed paths
+        never appear.  first_new: only what the rows from that id on duplicate.  web: names as sent to the client."""
+        n_ids, n_groups = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().mi_index_duplicates(self._h, float(max_dist), int(first_new), max_pairs, None, 0, None, 0,
+                                        ctypes.byref(n_ids), ctypes.byref(n_groups)))
+        ids, starts = np.empty(n_ids.value, np.uint64), np.empty(n_groups.value + 1, np.uint64)
+        check(lib().mi_index_duplicates(self._h, float(max_dist), int(first_new), max_pairs, ids.ctypes.data if ids.size else None,
+                                        ids.size, starts.ctypes.data, starts.size, ctypes.byref(n_ids), ctypes.byref(n_groups)))
+        return [[self.path(int(i), web=web) for i in g] for g in _groups(ids, starts)]
 
     def save(self, directory: str):
         check(lib().mi_index_save(self._h, directory.encode()))

@@ -330,6 +330,29 @@ int mi_knn_search_batched_device(mi_knn* t, const float* d_q, uint32_t nq, uint3
  * search enqueued before it; reads only the filter's fp32 rows (n x dim x 4 bytes; the "prefilter" mirrors are not used). */
 int mi_knn_search_filtered(mi_knn* t, const float* q, uint32_t nq, uint32_t k, const uint64_t* ids, uint64_t n_ids,
                            uint64_t* idx, float* dist);
+/* Near-duplicates ("which of my images are there twice?"): a threshold self-join on the matrix pipe.  Stage 1 multiplies a
+ * bf16 mirror of the rows with itself in tiles (the table's own mirror when "prefilter" = 1 keeps one, else one built for
+ * the call and freed before it returns: + 50 % of the rows' bytes meanwhile, MI_ERR_OOM when that does not fit; dim % 128
+ * == 0, MI_ERR_UNSUPPORTED otherwise); every pair a rigorous data-independent bound cannot exclude is re-evaluated from the
+ * fp32 rows.  Memory is bounded (option "join_cap": candidate pairs per strip of stage 1, default 2^22, >= 2^14; a strip
+ * that finds more is redone in smaller pieces, nothing is dropped).  Runs on the handle's stream behind every write and
+ * search enqueued before it, and waits for its results.
+ * every pair of live rows (a < b) with cosine distance <= max_dist, ascending by (a, b); dist = what mi_knn_search(q = row a)
+ * reports for row b, bit for bit.  first_new: only pairs with b >= first_new (0 = all pairs): "what did the rows I have just
+ * appended duplicate?" without redoing the old-against-old part.  a, b, dist: [cap] (may be NULL when cap = 0);
+ * *count = number of pairs.  More than cap pairs qualify: MI_ERR_UNSUPPORTED ("lower max_dist or raise cap"), *count =
+ * cap + 1, the arrays' contents unspecified; the call stops early.  max_dist NaN or < 0: MI_ERR_INVALID.
+ * first_new is not an id of the table and is not one past its last id (the end: no pairs): MI_ERR_INVALID. */
+int mi_knn_near_pairs(mi_knn* t, float max_dist, uint64_t first_new, uint64_t* a, uint64_t* b, float* dist,
+                      uint64_t cap, uint64_t* count);
+/* of the last mi_knn_near_pairs on this handle: out = {candidate pairs stage 1 passed to stage 2, pairs accepted,
+ * strips run (re-runs after an overflow included), tiles visited} */
+int mi_knn_near_pairs_stats(mi_knn* t, uint64_t out[4]);
+/* host-only: pairs -> groups (connected components, union-find).  ids: every id that occurs in a pair, grouped; groups
+ * ordered by their smallest id, ids ascending inside a group; group_start[g] .. group_start[g + 1] index ids
+ * (group_start holds n_groups + 1 entries).  Two-call protocol: counts are always written, arrays up to their caps. */
+int mi_pairs_to_groups(const uint64_t* a, const uint64_t* b, uint64_t n_pairs, uint64_t* ids, uint64_t cap_ids,
+                       uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups);
 
 /* ---------------------------------------------- Seam B over several GPUs, ONE process */
 
@@ -518,6 +541,10 @@ int mi_index_remove(mi_index* ix, const char* const* paths, size_t n, uint64_t* 
  * of the whole list, whole paths up to `cap` bytes are written (buf may be NULL) — what a scan's prune compares with the
  * files it found (search.py prune_missing_images) */
 int mi_index_live_paths(mi_index* ix, char* buf, size_t cap, size_t* needed);
+/* duplicate groups of table `image`: mi_knn_near_pairs on mi_index_table + mi_pairs_to_groups; removed paths never appear.
+ * max_pairs bounds the join (MI_ERR_UNSUPPORTED beyond it). */
+int mi_index_duplicates(mi_index* ix, float max_dist, uint64_t first_new, uint64_t max_pairs, uint64_t* ids,
+                        uint64_t cap_ids, uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups);
 
 /* ------------------------------------------------------------ query refinement */
 
