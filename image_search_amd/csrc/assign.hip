@@ -1,0 +1,401 @@
+// assign.hip — host side of mi_knn_assign (every row labelled by the nearest of C vectors), mi_knn_kmeans (Lloyd's
+// iterations on top of it) and mi_knn_sharded_assign.  The kernels and the superset argument: assign_kernels.h.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include <mutex>
+#include <thread>
+#include <vector>
+
+#include "common.h"
+#include "handles.h"
+#include "assign_kernels.h"
+
+using namespace mi;
+using namespace mi_assign::mi;
+
+namespace {
+
+constexpr uint32_t ASSIGN_MAX_C = 65536;
+
+// device memory of one call, freed on every way out
+struct Scratch {
+    std::vector<void*> p;
+    void* get(size_t bytes) {
+        void* q = nullptr;
+        HIP_CHECK(hipMalloc(&q, std::max<size_t>(bytes, 16)));
+        p.push_back(q);
+        return q;
+    }
+    ~Scratch() {
+        for (void* q : p) (void)hipFree(q);
+    }
+};
+
+// the table's own mirror grows with its capacity, keeping the rows mirrored so far (as join.hip)
+void grow_keep(mi_knn* t, void** p, size_t* have, size_t want, size_t elem, size_t keep) {
+    if (*have >= want) return;
+    t->reads.sync();
+    void* np_ = nullptr;
+    HIP_CHECK(hipMalloc(&np_, want * elem));
+    if (*p && keep) HIP_CHECK(hipMemcpy(np_, *p, std::min(keep, *have) * elem, hipMemcpyDeviceToDevice));
+    if (*p) HIP_CHECK(hipFree(*p));
+    *p = np_;
+    *have = want;
+}
+
+template <int NCH>
+void launch_mirror(hipStream_t s, int n_cu, const float* rows, uint64_t from, uint64_t end, uint16_t* mirror, float* xx) {
+    const uint32_t mb = std::max<uint32_t>(1u, (uint32_t)std::min<uint64_t>((uint64_t)n_cu * 8, (end - from + 15) / 16));
+    hipLaunchKernelGGL((knn_mirror_kernel<NCH>), dim3(mb), dim3(256), 0, s, rows, from, end, mirror, xx);
+    HIP_CHECK(hipGetLastError());
+}
+
+// One call's state: the rows' mirror (built once), the vectors (replaced per assign), the results on the device.
+struct Assign {
+    mi_knn* t = nullptr;
+    hipStream_t s = nullptr;
+    Scratch scratch;
+    uint32_t n_rows = 0, C = 0, n_cb = 0, cand_cap = 0;
+    float thr = 0.0f;
+    const uint16_t* mirror = nullptr;
+    const float* xx = nullptr;
+    const uint64_t* tomb = nullptr;
+    float* d_vec = nullptr;          // [C][dim] fp32
+    uint16_t* d_vmirror = nullptr;
+    float* d_vxx = nullptr;
+    uint2* d_cand = nullptr;
+    unsigned long long *d_count = nullptr, *d_best = nullptr, *d_changed = nullptr;
+    uint32_t* d_labels = nullptr;
+    float* d_dist = nullptr;
+    uint32_t strip = 0;
+    uint64_t stats[4] = {0, 0, 0, 0};
+
+    template <int NCH>
+    void rect(uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) {
+        if (bc0 >= bc1 || br0 >= br1) return;
+        static DevOnce once;
+        allow_lds_once(once, assign_tiles_kernel<NCH>, ASG_LDS);
+        HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+        hipLaunchKernelGGL((assign_tiles_kernel<NCH>), dim3(br1 - br0), dim3(256), ASG_LDS, s, mirror, xx, tomb, n_rows, d_vmirror,
+                           d_vxx, C, br0, bc0, bc1, thr, cand_cap, d_cand, d_count);
+        HIP_CHECK(hipGetLastError());
+        unsigned long long n_cand = 0;
+        HIP_CHECK(hipMemcpyAsync(&n_cand, d_count, sizeof n_cand, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        ++stats[2];
+        stats[3] += (uint64_t)(br1 - br0) * (bc1 - bc0);
+        if (n_cand > cand_cap) {   // nothing is dropped: the same ground again in two halves, rows first, then columns
+            if (overflowed) *overflowed = true;
+            if (br1 - br0 > 1) {
+                const uint32_t mid = br0 + (br1 - br0) / 2;
+                rect<NCH>(br0, mid, bc0, bc1, nullptr);
+                rect<NCH>(mid, br1, bc0, bc1, nullptr);
+            } else if (bc1 - bc0 > 1) {
+                const uint32_t mid = bc0 + (bc1 - bc0) / 2;
+                rect<NCH>(br0, br1, bc0, mid, nullptr);
+                rect<NCH>(br0, br1, mid, bc1, nullptr);
+            } else {
+                fail(MI_ERR_INVALID, "one tile reported %llu candidates (the buffer holds %u)", n_cand, cand_cap);
+            }
+            return;
+        }
+        stats[0] += n_cand;
+        if (n_cand == 0) return;
+        const uint32_t n = (uint32_t)n_cand;
+        const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)t->n_cu * 8, (n + 15) / 16));
+        hipLaunchKernelGGL((assign_rescore_kernel<NCH>), dim3(blocks), dim3(256), 0, s, t->table, d_vec, d_cand, n, d_best);
+        HIP_CHECK(hipGetLastError());
+    }
+
+    // d_vec holds the vectors: -> d_labels / d_dist.  prev_in_labels: count the rows whose label changes into *changed
+    template <int NCH>
+    void run(bool count_changed, uint64_t* changed) {
+        for (uint64_t& v : stats) v = 0;
+        launch_mirror<NCH>(s, t->n_cu, d_vec, 0, C, d_vmirror, d_vxx);
+        HIP_CHECK(hipMemsetAsync(d_best, 0xFF, (size_t)n_rows * sizeof(unsigned long long), s));
+        const uint32_t n_rb = (n_rows + ASG_TILE - 1) / ASG_TILE;
+        // strips of row tiles: as many as keep an ordinary corpus (a few candidates per row and column tile) inside the buffer
+        if (strip == 0) strip = std::max<uint32_t>(1u, std::min<uint32_t>(2048u, cand_cap / (ASG_TILE * 4u * n_cb)));
+        for (uint32_t br = 0; br < n_rb;) {
+            const uint32_t end = std::min(n_rb, br + strip);
+            bool overflowed = false;
+            rect<NCH>(br, end, 0, n_cb, &overflowed);
+            if (overflowed) strip = std::max(1u, strip / 2);
+            br = end;
+        }
+        if (count_changed) HIP_CHECK(hipMemsetAsync(d_changed, 0, sizeof(unsigned long long), s));
+        hipLaunchKernelGGL(assign_finalize_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, s, d_best, tomb, n_rows,
+                           count_changed ? d_labels : (const uint32_t*)nullptr, d_labels, d_dist, d_changed);
+        HIP_CHECK(hipGetLastError());
+        if (count_changed) {
+            unsigned long long c = 0;
+            HIP_CHECK(hipMemcpyAsync(&c, d_changed, sizeof c, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            *changed = c;
+        }
+        stats[1] = (uint64_t)n_rows - t->dead.size();
+        for (int i = 0; i < 4; ++i) t->assign_stats[i] = stats[i];
+    }
+
+    void run(bool count_changed = false, uint64_t* changed = nullptr) {
+        switch (t->dim / 64) {
+            case 2: run<2>(count_changed, changed); break;
+            case 4: run<4>(count_changed, changed); break;
+            case 8: run<8>(count_changed, changed); break;
+            case 12: run<12>(count_changed, changed); break;
+            case 16: run<16>(count_changed, changed); break;
+        }
+    }
+
+    // t->mu held, device selected, arguments checked, the table not empty
+    void setup(mi_knn* table, uint32_t n_vec) {
+        t = table;
+        C = n_vec;
+        s = knn_own_stream(t);
+        // behind every write and search enqueued before this call, on whichever stream
+        t->writes.begin(s);
+        t->reads.begin(s);
+        n_rows = (uint32_t)t->rows;
+        n_cb = (C + ASG_TILE - 1) / ASG_TILE;
+        // the join's bound, unchanged (join_kernels.h): both operands are rounded to bf16
+        const float eps2 = 0x1p-7f + 0x1p-16f + 4.1f * (float)(t->dim + 8) * 0x1p-24f + 2e-6f;
+        thr = 2.0f * eps2;
+        cand_cap = std::max<uint32_t>(ASG_CAP_MIN, t->join_cap);
+        tomb = t->dead.empty() ? nullptr : t->d_tomb;
+        // the mirror: the table's own when "prefilter" = 1 keeps one (caught up here as a search would), else one for this call
+        uint16_t* m = nullptr;
+        float* x = nullptr;
+        uint64_t from = 0;
+        if (t->prefilter == 1) {
+            t->mirror_rows = std::min(t->mirror_rows, t->rows);
+            grow_keep(t, (void**)&t->d_mirror, &t->mirror_cap, (size_t)t->cap * t->dim, sizeof(uint16_t), (size_t)t->mirror_rows * t->dim);
+            grow_keep(t, (void**)&t->d_xx, &t->xx_cap, (size_t)t->cap, sizeof(float), (size_t)t->mirror_rows);
+            m = t->d_mirror; x = t->d_xx; from = t->mirror_rows;
+        } else {
+            m = (uint16_t*)scratch.get((size_t)t->rows * t->dim * sizeof(uint16_t));
+            x = (float*)scratch.get((size_t)t->rows * sizeof(float));
+        }
+        if (from < t->rows) {
+            switch (t->dim / 64) {
+#define MI_CASE(NCH) case NCH: launch_mirror<NCH>(s, t->n_cu, t->table, from, t->rows, m, x); break;
+                MI_CASE(2) MI_CASE(4) MI_CASE(8) MI_CASE(12) MI_CASE(16)
+#undef MI_CASE
+            }
+            if (t->prefilter == 1) t->mirror_rows = t->rows;
+        }
+        mirror = m; xx = x;
+        d_vec = (float*)scratch.get((size_t)C * t->dim * sizeof(float));
+        d_vmirror = (uint16_t*)scratch.get((size_t)C * t->dim * sizeof(uint16_t));
+        d_vxx = (float*)scratch.get((size_t)C * sizeof(float));
+        d_cand = (uint2*)scratch.get((size_t)cand_cap * sizeof(uint2));
+        d_count = (unsigned long long*)scratch.get(2 * sizeof(unsigned long long));
+        d_changed = d_count + 1;
+        d_best = (unsigned long long*)scratch.get((size_t)n_rows * sizeof(unsigned long long));
+        d_labels = (uint32_t*)scratch.get((size_t)n_rows * sizeof(uint32_t));
+        d_dist = (float*)scratch.get((size_t)n_rows * sizeof(float));
+    }
+};
+
+// whatever happens, the handle's stream is idle and its order words say so when the call leaves
+struct Settle {
+    mi_knn* t; hipStream_t s;
+    ~Settle() { (void)hipStreamSynchronize(s); t->reads.pending = false; }
+};
+
+void check_args(const mi_knn* t, const float* vectors, uint32_t C, const uint32_t* labels, bool labels_needed) {
+    if (!t) fail(MI_ERR_INVALID, "null table handle");
+    if (!vectors) fail(MI_ERR_INVALID, "vectors is null");
+    if (labels_needed && !labels) fail(MI_ERR_INVALID, "labels is null");
+    if (C == 0) fail(MI_ERR_INVALID, "C must be >= 1");
+    if (C > ASSIGN_MAX_C) fail(MI_ERR_UNSUPPORTED, "at most %u vectors (got %u)", ASSIGN_MAX_C, C);
+    if (t->dim % 128 != 0 || (t->dim / 64 != 2 && t->dim / 64 != 4 && t->dim / 64 != 8 && t->dim / 64 != 12 && t->dim / 64 != 16))
+        fail(MI_ERR_UNSUPPORTED, "dim %u: the assign's bf16 mirror is built for dim in {128, 256, 512, 768, 1024}", t->dim);
+}
+
+// labels / dist of the shard's local rows
+void assign_local(mi_knn* t, const float* vectors, uint32_t C, uint32_t* labels, float* dist) {
+    std::lock_guard<std::mutex> l(t->mu);
+    for (uint64_t& v : t->assign_stats) v = 0;
+    if (t->rows == 0) return;
+    DeviceGuard g(t->device);
+    Assign a;
+    a.setup(t, C);
+    Settle settle{t, a.s};
+    HIP_CHECK(hipMemcpyAsync(a.d_vec, vectors, (size_t)C * t->dim * sizeof(float), hipMemcpyHostToDevice, a.s));
+    a.run();
+    HIP_CHECK(hipMemcpyAsync(labels, a.d_labels, (size_t)a.n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, a.s));
+    if (dist) HIP_CHECK(hipMemcpyAsync(dist, a.d_dist, (size_t)a.n_rows * sizeof(float), hipMemcpyDeviceToHost, a.s));
+    HIP_CHECK(hipStreamSynchronize(a.s));
+}
+
+// one update: d_labels / d_dist -> d_vec, in an order the row ids fix (assign_kernels.h)
+struct Update {
+    uint32_t n_waves = 0, chunk = 0, max_segs = 0;
+    uint32_t *d_hist = nullptr, *d_total = nullptr, *d_start = nullptr, *d_seg = nullptr, *d_sorted = nullptr;
+    float *d_inv = nullptr, *d_part = nullptr;
+
+    template <int NCH>
+    void setup(Assign& a) {
+        const uint32_t n = a.n_rows, C = a.C;
+        n_waves = std::max<uint32_t>(1u, std::min<uint32_t>({4096u, (1u << 24) / (C + 1), (n + 1023) / 1024}));
+        n_waves = (n_waves + 3) / 4 * 4;
+        chunk = ((n + n_waves - 1) / n_waves + 63) / 64 * 64;
+        max_segs = n / KM_SEG + C;
+        d_hist = (uint32_t*)a.scratch.get((size_t)n_waves * (C + 1) * sizeof(uint32_t));
+        d_total = (uint32_t*)a.scratch.get((size_t)(C + 2) * sizeof(uint32_t));
+        d_start = (uint32_t*)a.scratch.get((size_t)(C + 2) * sizeof(uint32_t));
+        d_seg = (uint32_t*)a.scratch.get((size_t)(C + 2) * sizeof(uint32_t));
+        d_sorted = (uint32_t*)a.scratch.get((size_t)n * sizeof(uint32_t));
+        d_inv = (float*)a.scratch.get((size_t)n * sizeof(float));
+        d_part = (float*)a.scratch.get((size_t)max_segs * a.t->dim * sizeof(float));
+        const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)a.t->n_cu * 8, (n + 15) / 16));
+        hipLaunchKernelGGL((km_inv_norm_kernel<NCH>), dim3(blocks), dim3(256), 0, a.s, a.t->table, n, d_inv);
+        HIP_CHECK(hipGetLastError());
+    }
+
+    template <int NCH>
+    void run(Assign& a) {
+        const uint32_t n = a.n_rows, C = a.C;
+        hipStream_t s = a.s;
+        HIP_CHECK(hipMemsetAsync(d_hist, 0, (size_t)n_waves * (C + 1) * sizeof(uint32_t), s));
+        hipLaunchKernelGGL(km_hist_kernel, dim3(n_waves / 4), dim3(256), 0, s, a.d_labels, a.d_dist, n, C, chunk, d_hist);
+        hipLaunchKernelGGL(km_scan_kernel, dim3((C + 1 + 255) / 256), dim3(256), 0, s, d_hist, n_waves, C, d_total);
+        hipLaunchKernelGGL(km_offsets_kernel, dim3(1), dim3(1024), 0, s, d_total, C, d_start, d_seg);
+        hipLaunchKernelGGL(km_place_kernel, dim3(n_waves / 4), dim3(256), 0, s, a.d_labels, a.d_dist, n, C, chunk, d_hist, d_start,
+                           d_sorted);
+        hipLaunchKernelGGL((km_sum_kernel<NCH>), dim3(std::max(max_segs, 1u)), dim3(256), 0, s, a.t->table, d_inv, d_sorted, d_start,
+                           d_seg, C, d_part);
+        const uint64_t el = (uint64_t)C * a.t->dim;
+        hipLaunchKernelGGL(km_centroid_kernel, dim3((uint32_t)((el + 255) / 256)), dim3(256), 0, s, d_part, d_total, d_seg, C,
+                           a.t->dim, a.d_vec);
+        HIP_CHECK(hipGetLastError());
+    }
+};
+
+template <int NCH>
+void kmeans_loop(Assign& a, uint32_t max_iters, uint32_t* iters_run, uint64_t* changed_last) {
+    Update u;
+    if (max_iters > 0) u.setup<NCH>(a);
+    uint32_t it = 0;
+    uint64_t changed = 0;
+    for (;;) {
+        if (it == 0) {
+            a.run();
+            changed = (uint64_t)a.n_rows - a.t->dead.size();
+        } else {
+            a.run(true, &changed);
+        }
+        if ((it > 0 && changed == 0) || it == max_iters) break;
+        u.run<NCH>(a);
+        ++it;
+    }
+    *iters_run = it;
+    *changed_last = changed;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_knn_assign(mi_knn* t, const float* vectors, uint32_t C, uint32_t* labels, float* dist) {
+    return guarded([&] {
+        check_args(t, vectors, C, labels, true);
+        assign_local(t, vectors, C, labels, dist);
+    });
+}
+
+int mi_knn_assign_stats(mi_knn* t, uint64_t out[4]) {
+    return guarded([&] {
+        if (!t || !out) fail(MI_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> l(t->mu);
+        for (int i = 0; i < 4; ++i) out[i] = t->assign_stats[i];
+    });
+}
+
+int mi_knn_kmeans(mi_knn* t, float* centroids, uint32_t C, uint32_t max_iters, uint32_t* labels, float* dist, uint32_t* iters_run,
+                  uint64_t* changed_last, double* objective) {
+    return guarded([&] {
+        if (iters_run) *iters_run = 0;
+        if (changed_last) *changed_last = 0;
+        if (objective) *objective = 0.0;
+        check_args(t, centroids, C, labels, false);
+        std::lock_guard<std::mutex> l(t->mu);
+        for (uint64_t& v : t->assign_stats) v = 0;
+        if (t->rows == 0) return;
+        DeviceGuard g(t->device);
+        Assign a;
+        a.setup(t, C);
+        Settle settle{t, a.s};
+        const size_t cbytes = (size_t)C * t->dim * sizeof(float);
+        HIP_CHECK(hipMemcpyAsync(a.d_vec, centroids, cbytes, hipMemcpyHostToDevice, a.s));
+        uint32_t it = 0;
+        uint64_t changed = 0;
+        switch (t->dim / 64) {
+            case 2: kmeans_loop<2>(a, max_iters, &it, &changed); break;
+            case 4: kmeans_loop<4>(a, max_iters, &it, &changed); break;
+            case 8: kmeans_loop<8>(a, max_iters, &it, &changed); break;
+            case 12: kmeans_loop<12>(a, max_iters, &it, &changed); break;
+            case 16: kmeans_loop<16>(a, max_iters, &it, &changed); break;
+        }
+        std::vector<uint32_t> h_labels;
+        std::vector<float> h_dist;
+        uint32_t* pl = labels;
+        float* pd = dist;
+        if (!pl) { h_labels.resize(a.n_rows); pl = h_labels.data(); }
+        if (!pd) { h_dist.resize(a.n_rows); pd = h_dist.data(); }
+        HIP_CHECK(hipMemcpyAsync(pl, a.d_labels, (size_t)a.n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, a.s));
+        HIP_CHECK(hipMemcpyAsync(pd, a.d_dist, (size_t)a.n_rows * sizeof(float), hipMemcpyDeviceToHost, a.s));
+        if (it > 0) HIP_CHECK(hipMemcpyAsync(centroids, a.d_vec, cbytes, hipMemcpyDeviceToHost, a.s));
+        HIP_CHECK(hipStreamSynchronize(a.s));
+        double obj = 0.0;   // in row order
+        for (uint32_t r = 0; r < a.n_rows; ++r)
+            if (pl[r] != MI_KNN_NO_LABEL && pd[r] == pd[r]) obj += (double)pd[r];
+        if (iters_run) *iters_run = it;
+        if (changed_last) *changed_last = changed;
+        if (objective) *objective = obj;
+    });
+}
+
+int mi_knn_sharded_assign(mi_knn_sharded* t, const float* vectors, uint32_t C, uint32_t* labels, float* dist) {
+    return guarded([&] {
+        if (!t) fail(MI_ERR_INVALID, "null table handle");
+        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
+        check_args(t->shard[0], vectors, C, labels, true);
+        std::lock_guard<std::mutex> l(t->mu);
+        sharded_deliver_all(t);
+        // every shard on its own stream, driven by a host thread of its own (a shard's assign reads its candidate counts
+        // back between launches); results land at the rows' global ids
+        const uint32_t n = t->n();
+        std::vector<int> codes(n, MI_OK);
+        std::vector<std::string> msgs(n);
+        std::vector<std::thread> threads;
+        for (uint32_t si = 0; si < n; ++si) {
+            threads.emplace_back([&, si] {
+                try {
+                    mi_knn* sh = t->shard[si];
+                    const uint64_t rows = sh->rows;
+                    std::vector<uint32_t> lab(rows);
+                    std::vector<float> dd(dist ? rows : 0);
+                    assign_local(sh, vectors, C, lab.data(), dist ? dd.data() : nullptr);
+                    const IdMap map{sh->base, sh->cyc_block, sh->cyc_n, sh->cyc_rank};
+                    for (uint64_t r = 0; r < rows; ++r) {
+                        const uint64_t id = id_of_local(map, r);
+                        labels[id] = lab[r];
+                        if (dist) dist[id] = dd[r];
+                    }
+                } catch (const Error& e) {
+                    codes[si] = e.code; msgs[si] = e.what();
+                } catch (const std::exception& e) {
+                    codes[si] = MI_ERR_INVALID; msgs[si] = e.what();
+                }
+            });
+        }
+        for (std::thread& th : threads) th.join();
+        for (uint32_t si = 0; si < n; ++si)
+            if (codes[si] != MI_OK) fail(codes[si], "shard %u: %s", si, msgs[si].c_str());
+    });
+}
+
+}  // extern "C"

@@ -203,6 +203,8 @@ struct mi_knn {
     // "join_cap"; its buffers live for the call only), and {candidates, pairs, strips, tiles} of the last call.
     uint32_t join_cap = 1u << 22;
     uint64_t join_stats[4] = {0, 0, 0, 0};
+    // mi_knn_assign (assign.hip): {candidates, live rows labelled, stage-1 launches, tiles} of the last assign
+    uint64_t assign_stats[4] = {0, 0, 0, 0};
     std::mutex mu;
 };
 

@@ -150,6 +150,30 @@ class EmbeddingTable {
     }
     // {candidate pairs, pairs accepted, strips run, tiles visited} of the last near_pairs
     std::vector<uint64_t> near_pairs_stats() const { std::vector<uint64_t> v(4); check(mi_knn_near_pairs_stats(h_, v.data())); return v; }
+    // label every row by the nearest of C vectors (mi_knn_assign): for a live row what a table of the vectors answers to
+    // knn(row, 1), id and distance bits; MI_KNN_NO_LABEL / +inf for a deleted row.  vectors: [C * dim]
+    struct Assignment { std::vector<uint32_t> labels; std::vector<float> dist; };
+    Assignment assign(const std::vector<float>& vectors, uint32_t C) const {
+        uint64_t n = 0;
+        check(mi_knn_size(h_, &n));
+        Assignment r;
+        r.labels.resize(n); r.dist.resize(n);
+        check(mi_knn_assign(h_, vectors.data(), C, r.labels.data(), r.dist.data()));
+        return r;
+    }
+    // {candidates, live rows labelled, stage-1 launches, tiles visited} of the last assign
+    std::vector<uint64_t> assign_stats() const { std::vector<uint64_t> v(4); check(mi_knn_assign_stats(h_, v.data())); return v; }
+    // spherical k-means (mi_knn_kmeans): centroids [C * dim] in = initial, out = final; labels / dist = assign(centroids)
+    struct KMeans { Assignment assignment; uint32_t iters = 0; uint64_t changed = 0; double objective = 0.0; };
+    KMeans kmeans(std::vector<float>& centroids, uint32_t C, uint32_t max_iters = 20) const {
+        uint64_t n = 0;
+        check(mi_knn_size(h_, &n));
+        KMeans r;
+        r.assignment.labels.resize(n); r.assignment.dist.resize(n);
+        check(mi_knn_kmeans(h_, centroids.data(), C, max_iters, r.assignment.labels.data(), r.assignment.dist.data(), &r.iters,
+                            &r.changed, &r.objective));
+        return r;
+    }
     // "prefilter" = 2 (bytes) or 1 (bf16): the two-stage exact search, same results from a quarter / a half of the bytes
     void set_option(const std::string& key, int value) { check(mi_knn_set_option(h_, key.c_str(), value)); }
 };

@@ -20,6 +20,7 @@ from ._lib import c_f, c_vp, check, lib
 
 K_REFERENCE = 1000  # `<|1000|>` in server/src/search.rs:76
 NO_ID = np.uint64(0xFFFFFFFFFFFFFFFF)
+NO_LABEL = np.uint32(0xFFFFFFFF)  # MI_KNN_NO_LABEL: the label of a deleted row
 
 
 def _f32(a) -> np.ndarray:
@@ -166,6 +167,56 @@ class EmbeddingTable:
         out = (ctypes.c_uint64 * 4)()
         check(lib().mi_knn_near_pairs_stats(self._h, out))
         return {"candidates": out[0], "pairs": out[1], "strips": out[2], "tiles": out[3]}
+
+    def assign(self, vectors: np.ndarray):
+        """Label every row by the nearest of C vectors (mi_knn_assign): (labels [rows] uint32, dist [rows] f32) — for a live
+        row what a table of the vectors answers to knn(row, 1), id and distance bits; NO_LABEL / +inf for a deleted row."""
+        v = _f32(vectors).reshape(-1, self.dim)
+        n = len(self)
+        labels, dist = np.empty(n, np.uint32), np.empty(n, np.float32)
+        check(lib().mi_knn_assign(self._h, v.ctypes.data, v.shape[0], labels.ctypes.data, dist.ctypes.data))
+        return labels, dist
+
+    def assign_stats(self):
+        """mi_knn_assign_stats, of the last assign (or the last assign inside kmeans) on this table"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_assign_stats(self._h, out))
+        return {"candidates": out[0], "rows": out[1], "launches": out[2], "tiles": out[3]}
+
+    def kmeans(self, k_or_centroids, max_iters: int = 20, seed: int = 0) -> dict:
+        """Spherical k-means over the live rows (mi_knn_kmeans).  k_or_centroids: the initial centroids [C, dim], or an int
+        k: k distinct live rows picked with np.random.default_rng(seed).  Returns dict(centroids, labels, dist, iters,
+        changed, objective); labels / dist are exactly assign(centroids)."""
+        if isinstance(k_or_centroids, (int, np.integer)):
+            rows = initial_centroid_rows(len(self), self.deleted(), int(k_or_centroids), seed)
+            cent = np.concatenate([self.rows(int(r), 1) for r in rows]) if rows.size else np.empty((0, self.dim), np.float32)
+        else:
+            cent = np.array(k_or_centroids, dtype=np.float32, order="C").reshape(-1, self.dim)
+        n = len(self)
+        labels, dist = np.empty(n, np.uint32), np.empty(n, np.float32)
+        iters, changed, obj = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_double()
+        check(lib().mi_knn_kmeans(self._h, cent.ctypes.data, cent.shape[0], int(max_iters), labels.ctypes.data, dist.ctypes.data,
+                                  ctypes.byref(iters), ctypes.byref(changed), ctypes.byref(obj)))
+        return {"centroids": cent, "labels": labels, "dist": dist, "iters": iters.value, "changed": changed.value,
+                "objective": obj.value}
+
+
+def initial_centroid_rows(n_rows: int, deleted, k: int, seed: int = 0) -> np.ndarray:
+    """k distinct live rows of a table of n_rows rows, ascending: the seeded choice kmeans(k) starts from"""
+    live = np.setdiff1d(np.arange(n_rows, dtype=np.uint64), _ids(deleted), assume_unique=False)
+    if not 1 <= k <= live.size:
+        raise ValueError(f"k = {k} initial centroids from {live.size} live rows")
+    return np.sort(np.random.default_rng(seed).choice(live, size=k, replace=False))
+
+
+def clusters_of(labels, keys) -> list:
+    """labels[i] of keys[i] (NO_LABEL = leave out) -> lists of keys, one per non-empty cluster: the largest first, equal
+    sizes by label; inside a list the keys keep their order"""
+    by = {}
+    for lab, key in zip(labels, keys):
+        if int(lab) != int(NO_LABEL):
+            by.setdefault(int(lab), []).append(key)
+    return [by[lab] for lab in sorted(by, key=lambda c: (-len(by[c]), c))]
 
 
 def _groups(ids: np.ndarray, starts: np.ndarray) -> list:
@@ -411,6 +462,14 @@ class ShardedTable:
             check(lib().mi_knn_sharded_search_filtered(self._h, q.ctypes.data, q.shape[0], k, ids.ctypes.data if ids.size else None,
                                                        ids.size, idx.ctypes.data, dist.ctypes.data))
         return (idx[0], dist[0]) if single else (idx, dist)
+
+    def assign(self, vectors: np.ndarray):
+        """EmbeddingTable.assign over all shards (mi_knn_sharded_assign): labels / dist by global row id"""
+        v = _f32(vectors).reshape(-1, self.dim)
+        n = len(self)
+        labels, dist = np.empty(n, np.uint32), np.empty(n, np.float32)
+        check(lib().mi_knn_sharded_assign(self._h, v.ctypes.data, v.shape[0], labels.ctypes.data, dist.ctypes.data))
+        return labels, dist
 
     def delete(self, ids) -> int:
         """EmbeddingTable.delete on global ids (mi_knn_sharded_delete)"""
@@ -673,6 +732,25 @@ class ImageIndex:
         check(lib().mi_index_duplicates(self._h, float(max_dist), int(first_new), max_pairs, ids.ctypes.data if ids.size else None,
                                         ids.size, starts.ctypes.data, starts.size, ctypes.byref(n_ids), ctypes.byref(n_groups)))
         return [[self.path(int(i), web=web) for i in g] for g in _groups(ids, starts)]
+
+    def label(self, vectors: np.ndarray, names: Optional[Sequence[str]] = None, web: bool = False) -> dict:
+        """"Tag my library" (EmbeddingTable.assign): {path: (label, distance)} for every path that has not been removed;
+        label = the index of the nearest of `vectors` (text embeddings of the tags), or names[index].  A path with several
+        rows reports its last row."""
+        labels, dist = self.table.assign(vectors)
+        out = {}
+        for r in range(labels.size):
+            if labels[r] != NO_LABEL:
+                lab = int(labels[r])
+                out[self.path(r, web=web)] = (names[lab] if names is not None else lab, float(dist[r]))
+        return out
+
+    def clusters(self, k: int, max_iters: int = 20, seed: int = 0, web: bool = False) -> list:
+        """"Group my library into k themes" (EmbeddingTable.kmeans): lists of paths, the largest cluster first; removed
+        paths never appear, empty clusters are left out."""
+        res = self.table.kmeans(int(k), max_iters=max_iters, seed=seed)
+        rows = [r for r in range(res["labels"].size) if res["labels"][r] != NO_LABEL]
+        return clusters_of(res["labels"][rows], [self.path(r, web=web) for r in rows])
 
     def save(self, directory: str):
         check(lib().mi_index_save(self._h, directory.encode()))

@@ -348,6 +348,39 @@ int mi_knn_near_pairs(mi_knn* t, float max_dist, uint64_t first_new, uint64_t* a
 /* of the last mi_knn_near_pairs on this handle: out = {candidate pairs stage 1 passed to stage 2, pairs accepted,
  * strips run (re-runs after an overflow included), tiles visited} */
 int mi_knn_near_pairs_stats(mi_knn* t, uint64_t out[4]);
+/* Label every row by its nearest of C vectors ("tag my library" with C text embeddings; the inner step of k-means): the
+ * search turned round.  For every row r of the table (rows = mi_knn_size, deleted rows counted):
+ *   r live     labels[r], dist[r] = the first entry of mi_knn_search(T_v, q = row r, k = 1) where T_v holds exactly the C
+ *              vectors under ids 0 .. C - 1: the same id and the same distance bits under the search's order (distance
+ *              ascending, then id, NaN last).  A tie goes to the lower label; a row whose every distance is NaN (zero norm,
+ *              a non-finite element) gets label 0 and NaN.
+ *   r deleted  MI_KNN_NO_LABEL, +inf.
+ * vectors: [C, dim] host f32, 1 <= C <= 65536 (MI_ERR_UNSUPPORTED above, MI_ERR_INVALID for 0 or a null pointer); labels:
+ * [rows]; dist: [rows] or NULL.  dim as mi_knn_near_pairs requires (MI_ERR_UNSUPPORTED otherwise); an empty table succeeds
+ * and writes nothing.  Stage 1 multiplies the rows' bf16 mirror (the table's own when "prefilter" = 1 keeps one, else one
+ * built for the call and freed) with the vectors' on the matrix pipe and keeps, per row, every vector the join's bound
+ * cannot separate from the best one; stage 2 re-evaluates those from the fp32 rows.  Memory is bounded by "join_cap" as for
+ * the join (a strip of rows that finds more candidates is redone in smaller pieces, nothing is dropped).  Runs on the
+ * handle's stream behind every write and search enqueued before it, and waits for its results. */
+#define MI_KNN_NO_LABEL UINT32_MAX
+int mi_knn_assign(mi_knn* t, const float* vectors, uint32_t C, uint32_t* labels, float* dist);
+/* of the last mi_knn_assign (or the last assign inside mi_knn_kmeans) on this handle: out = {candidates stage 1 handed to
+ * stage 2, live rows labelled, stage-1 launches (re-runs after an overflow included), tiles visited} */
+int mi_knn_assign_stats(mi_knn* t, uint64_t out[4]);
+/* Spherical k-means (Lloyd's iterations) over the live rows, mi_knn_assign as its inner step:
+ *   it = 0
+ *   loop: labels = assign(centroids); changed = rows whose label differs from the previous assign (first: the live rows)
+ *         stop when (it > 0 and changed == 0) or it == max_iters
+ *         every c: S = sum of x / |x| over the live rows labelled c whose dist is not NaN, n_c their number;
+ *                  n_c > 0: centroid[c] = S / n_c, else unchanged;  it += 1
+ * centroids: [C, dim] host, in = initial, out = final.  labels / dist ([rows], either may be NULL): exactly what
+ * mi_knn_assign(t, returned centroids) reports.  *iters_run = updates done, *changed_last = as counted by the last assign,
+ * *objective = sum of dist over the live rows with a non-NaN distance, in double, in row order (any of the three may be
+ * NULL).  Deterministic: the sums run in an order fixed by the row ids (rows bucketed by label, fixed segments, segments in
+ * order), so the same table, centroids and max_iters give the same bits.  max_iters = 0: one assign, centroids untouched.
+ * Rows, labels and sums stay on the device between iterations.  Arguments and errors as mi_knn_assign. */
+int mi_knn_kmeans(mi_knn* t, float* centroids, uint32_t C, uint32_t max_iters, uint32_t* labels, float* dist,
+                  uint32_t* iters_run, uint64_t* changed_last, double* objective);
 /* host-only: pairs -> groups (connected components, union-find).  ids: every id that occurs in a pair, grouped; groups
  * ordered by their smallest id, ids ascending inside a group; group_start[g] .. group_start[g + 1] index ids
  * (group_start holds n_groups + 1 entries).  Two-call protocol: counts are always written, arrays up to their caps. */
@@ -409,6 +442,10 @@ int mi_knn_sharded_deleted(mi_knn_sharded* t, uint64_t* ids, uint64_t cap, uint6
  * the filtered search of one table that holds every row.  Waits for its results. */
 int mi_knn_sharded_search_filtered(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, const uint64_t* ids,
                                    uint64_t n_ids, uint64_t* idx, float* dist);
+/* mi_knn_assign over the whole table: every shard labels its own rows on its own stream (concurrently: no exchange is
+ * needed), the results land at the rows' global ids.  labels / dist: [rows of the table]; equals the one-table result
+ * bit for bit.  (k-means over a sharded table is not offered: its update needs a cross-shard reduction.) */
+int mi_knn_sharded_assign(mi_knn_sharded* t, const float* vectors, uint32_t C, uint32_t* labels, float* dist);
 /* Change the layout of a LIVE table: every row of `src` into the empty `dst` (another shard count, device set or block
  * size), block by block, device to device — a plain copy where source and destination shard share a GPU,
  * hipMemcpyPeerAsync over xGMI where they do not; nothing passes through the host.  src is unchanged. */
