@@ -13,7 +13,8 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libmi355clip.so")
-SOURCES = ["core.hip", "knn.hip", "vit.hip", "preprocess.hip", "pipeline.hip", "sharded.hip", "index.hip", "join.hip", "assign.hip"]
+SOURCES = ["core.hip", "knn.hip", "vit.hip", "preprocess.hip", "pipeline.hip", "sharded.hip", "index.hip", "join.hip", "assign.hip",
+           "assign_multi.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-ffp-contract=off",
          "-Wall", "-Wno-unused-function", "-Wno-unused-const-variable"]
 
@@ -33,6 +34,8 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers.append(os.path.join(os.path.dirname(PKG), "include", "mi355clip.h"))
+    if not force and not _stale(LIB, srcs + headers):
+        return LIB   # a library newer than every source needs no object files (they do not travel with a copied tree)
     objs = []
     for s in srcs:
         o = s[:-4] + ".o"

@@ -205,6 +205,8 @@ struct mi_knn {
     uint64_t join_stats[4] = {0, 0, 0, 0};
     // mi_knn_assign (assign.hip): {candidates, live rows labelled, stage-1 launches, tiles} of the last assign
     uint64_t assign_stats[4] = {0, 0, 0, 0};
+    // mi_knn_assign_multi (assign_multi.hip): {candidates, (row, label) hits written, stage-1 launches, tiles} of the last call
+    uint64_t assign_multi_stats[4] = {0, 0, 0, 0};
     std::mutex mu;
 };
 

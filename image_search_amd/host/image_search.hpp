@@ -7,6 +7,7 @@
 //   the `embedding <|K|> $reference` statement                  server/src/search.rs:70-86
 // Where the reference panics (assert!/unwrap) this throws std::runtime_error with the same message.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -163,6 +164,18 @@ class EmbeddingTable {
     }
     // {candidates, live rows labelled, stage-1 launches, tiles visited} of the last assign
     std::vector<uint64_t> assign_stats() const { std::vector<uint64_t> v(4); check(mi_knn_assign_stats(h_, v.data())); return v; }
+    // up to m labels per row, only those within max_dist (mi_knn_assign_multi): labels / dist are [rows * m], a row's hits
+    // nearest first, MI_KNN_NO_LABEL / +inf behind the last one and for a deleted row.  vectors: [C * dim]
+    Assignment assign_multi(const std::vector<float>& vectors, uint32_t C, uint32_t m, float max_dist = INFINITY) const {
+        uint64_t n = 0;
+        check(mi_knn_size(h_, &n));
+        Assignment r;
+        r.labels.resize(n * m); r.dist.resize(n * m);
+        check(mi_knn_assign_multi(h_, vectors.data(), C, m, max_dist, r.labels.data(), r.dist.data()));
+        return r;
+    }
+    // {candidates, (row, label) hits written, stage-1 launches, tiles visited} of the last assign_multi
+    std::vector<uint64_t> assign_multi_stats() const { std::vector<uint64_t> v(4); check(mi_knn_assign_multi_stats(h_, v.data())); return v; }
     // spherical k-means (mi_knn_kmeans): centroids [C * dim] in = initial, out = final; labels / dist = assign(centroids)
     struct KMeans { Assignment assignment; uint32_t iters = 0; uint64_t changed = 0; double objective = 0.0; };
     KMeans kmeans(std::vector<float>& centroids, uint32_t C, uint32_t max_iters = 20) const {
@@ -300,6 +313,15 @@ class ShardedTable {
     void set_option(const std::string& key, int value) { check(mi_knn_sharded_set_option(h_, key.c_str(), value)); }
     // {searches, ncclAllGather calls, transport copies, device merges} issued so far
     std::vector<uint64_t> stats() const { std::vector<uint64_t> v(4); check(mi_knn_sharded_stats(h_, v.data())); return v; }
+    // EmbeddingTable::assign_multi over all shards (mi_knn_sharded_assign_multi): labels / dist [rows * m] by global row id
+    std::pair<std::vector<uint32_t>, std::vector<float>> assign_multi(const std::vector<float>& vectors, uint32_t C, uint32_t m,
+                                                                      float max_dist = INFINITY) const {
+        const uint64_t n = size();
+        std::vector<uint32_t> labels(n * m);
+        std::vector<float> dist(n * m);
+        check(mi_knn_sharded_assign_multi(h_, vectors.data(), C, m, max_dist, labels.data(), dist.data()));
+        return {std::move(labels), std::move(dist)};
+    }
     std::pair<std::vector<uint64_t>, std::vector<float>> knn(const std::vector<float>& reference, uint32_t k = 1000) const {
         std::vector<uint64_t> idx(k);
         std::vector<float> dist(k);

@@ -183,6 +183,23 @@ class EmbeddingTable:
         check(lib().mi_knn_assign_stats(self._h, out))
         return {"candidates": out[0], "rows": out[1], "launches": out[2], "tiles": out[3]}
 
+    def assign_multi(self, vectors: np.ndarray, m: int, max_dist: float = float("inf")):
+        """Up to m labels per row (mi_knn_assign_multi): (labels [rows, m] uint32, dist [rows, m] f32) — for a live row what a
+        table of the vectors answers to knn(row, m) without the entries whose distance is NaN or > max_dist, ids and distance
+        bits; NO_LABEL / +inf behind a row's last hit and for a deleted row."""
+        v = _f32(vectors).reshape(-1, self.dim)
+        n = len(self)
+        labels, dist = np.empty((n, int(m)), np.uint32), np.empty((n, int(m)), np.float32)
+        check(lib().mi_knn_assign_multi(self._h, v.ctypes.data, v.shape[0], int(m), float(max_dist), labels.ctypes.data,
+                                        dist.ctypes.data))
+        return labels, dist
+
+    def assign_multi_stats(self):
+        """mi_knn_assign_multi_stats, of the last assign_multi on this table"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_assign_multi_stats(self._h, out))
+        return {"candidates": out[0], "hits": out[1], "launches": out[2], "tiles": out[3]}
+
     def kmeans(self, k_or_centroids, max_iters: int = 20, seed: int = 0) -> dict:
         """Spherical k-means over the live rows (mi_knn_kmeans).  k_or_centroids: the initial centroids [C, dim], or an int
         k: k distinct live rows picked with np.random.default_rng(seed).  Returns dict(centroids, labels, dist, iters,
@@ -199,6 +216,23 @@ class EmbeddingTable:
                                   ctypes.byref(iters), ctypes.byref(changed), ctypes.byref(obj)))
         return {"centroids": cent, "labels": labels, "dist": dist, "iters": iters.value, "changed": changed.value,
                 "objective": obj.value}
+
+
+def rows_of_labels(labels: np.ndarray, C: int) -> list:
+    """"Show me everything tagged X": labels [rows, m] (or [rows]) as assign_multi / assign report them -> per label
+    0 .. C - 1 the ascending ids (uint64) of the rows that carry it; NO_LABEL entries carry nothing."""
+    lab = np.asarray(labels, np.uint32)
+    lab = lab.reshape(lab.shape[0], -1) if lab.size else lab.reshape(0, 1)
+    if np.any((lab >= C) & (lab != NO_LABEL)):
+        raise ValueError(f"a label beyond C = {C}")
+    rows = np.repeat(np.arange(lab.shape[0], dtype=np.uint64), lab.shape[1])
+    flat = lab.reshape(-1)
+    keep = flat != NO_LABEL
+    rows, flat = rows[keep], flat[keep]
+    order = np.lexsort((rows, flat))
+    rows, flat = rows[order], flat[order]
+    cuts = np.searchsorted(flat, np.arange(C + 1))
+    return [rows[cuts[c]:cuts[c + 1]] for c in range(C)]
 
 
 def initial_centroid_rows(n_rows: int, deleted, k: int, seed: int = 0) -> np.ndarray:
@@ -469,6 +503,15 @@ class ShardedTable:
         n = len(self)
         labels, dist = np.empty(n, np.uint32), np.empty(n, np.float32)
         check(lib().mi_knn_sharded_assign(self._h, v.ctypes.data, v.shape[0], labels.ctypes.data, dist.ctypes.data))
+        return labels, dist
+
+    def assign_multi(self, vectors: np.ndarray, m: int, max_dist: float = float("inf")):
+        """EmbeddingTable.assign_multi over all shards (mi_knn_sharded_assign_multi): labels / dist by global row id"""
+        v = _f32(vectors).reshape(-1, self.dim)
+        n = len(self)
+        labels, dist = np.empty((n, int(m)), np.uint32), np.empty((n, int(m)), np.float32)
+        check(lib().mi_knn_sharded_assign_multi(self._h, v.ctypes.data, v.shape[0], int(m), float(max_dist), labels.ctypes.data,
+                                                dist.ctypes.data))
         return labels, dist
 
     def delete(self, ids) -> int:
@@ -743,6 +786,22 @@ class ImageIndex:
             if labels[r] != NO_LABEL:
                 lab = int(labels[r])
                 out[self.path(r, web=web)] = (names[lab] if names is not None else lab, float(dist[r]))
+        return out
+
+    def tags(self, vectors: np.ndarray, names: Optional[Sequence[str]] = None, m: int = 5, max_dist: float = float("inf"),
+             web: bool = False) -> dict:
+        """Several tags per image, none where nothing matches (EmbeddingTable.assign_multi): {path: [(label, distance), ...]}
+        for every path that has not been removed, nearest first, at most m of them and only those within max_dist — an
+        untagged image has an empty list.  label = the index into `vectors` (text embeddings of the tags), or names[index].
+        A path with several rows reports its last row."""
+        labels, dist = self.table.assign_multi(vectors, m, max_dist)
+        deleted = set(int(r) for r in self.table.deleted())
+        out = {}
+        for r in range(labels.shape[0]):
+            if r in deleted:
+                continue
+            hits = [(int(l), float(d)) for l, d in zip(labels[r], dist[r]) if l != NO_LABEL]
+            out[self.path(r, web=web)] = [(names[l] if names is not None else l, d) for l, d in hits]
         return out
 
     def clusters(self, k: int, max_iters: int = 20, seed: int = 0, web: bool = False) -> list:

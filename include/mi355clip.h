@@ -367,6 +367,24 @@ int mi_knn_assign(mi_knn* t, const float* vectors, uint32_t C, uint32_t* labels,
 /* of the last mi_knn_assign (or the last assign inside mi_knn_kmeans) on this handle: out = {candidates stage 1 handed to
  * stage 2, live rows labelled, stage-1 launches (re-runs after an overflow included), tiles visited} */
 int mi_knn_assign_stats(mi_knn* t, uint64_t out[4]);
+/* Up to m labels per row, and only those within a distance ("beach", "sunset" and "dog" at once; no tag for a photo that
+ * matches nothing; with a large m, the range search "every (row, vector) pair within max_dist").  For every row r of the
+ * table (rows = mi_knn_size):
+ *   r live     entries j = 0 .. m-1 of  mi_knn_search(T_v, q = row r, k = m)  over a table T_v that holds exactly the C
+ *              vectors under ids 0 .. C-1, AFTER removing every entry whose distance is NaN or > max_dist: same ids, same
+ *              distance bits, the search's order (distance ascending, then label).  Behind the last hit: MI_KNN_NO_LABEL / +inf.
+ *   r deleted  m x (MI_KNN_NO_LABEL, +inf).
+ * A row whose every distance is NaN gets only padding (unlike mi_knn_assign's "label 0, NaN": a NaN is never a tag).
+ * labels: [rows][m] uint32, dist: [rows][m] f32 or NULL.  1 <= m <= 16, 1 <= C <= 65536 (MI_ERR_UNSUPPORTED above, MI_ERR_INVALID
+ * for 0 / NULL); m > C is allowed (padding).  max_dist: +INFINITY = no threshold; NaN or < 0: MI_ERR_INVALID.  dim, mirror,
+ * "join_cap", stream ordering and the empty table: as mi_knn_assign.  Stage 1 keeps, per row, every vector the join's bound
+ * cannot separate from the m-th best one or from max_dist; stage 2 re-evaluates those from the fp32 rows and keeps the m
+ * smallest per row in an order that does not depend on their arrival.  The rows are walked in strips whose results are
+ * copied out one by one: the device workspace does not grow with rows x m. */
+int mi_knn_assign_multi(mi_knn* t, const float* vectors, uint32_t C, uint32_t m, float max_dist, uint32_t* labels, float* dist);
+/* of the last mi_knn_assign_multi on this handle: out = {candidates stage 1 handed to stage 2, (row, label) hits written,
+ * stage-1 launches (re-runs after an overflow included), tiles visited} */
+int mi_knn_assign_multi_stats(mi_knn* t, uint64_t out[4]);
 /* Spherical k-means (Lloyd's iterations) over the live rows, mi_knn_assign as its inner step:
  *   it = 0
  *   loop: labels = assign(centroids); changed = rows whose label differs from the previous assign (first: the live rows)
@@ -446,6 +464,10 @@ int mi_knn_sharded_search_filtered(mi_knn_sharded* t, const float* q, uint32_t n
  * needed), the results land at the rows' global ids.  labels / dist: [rows of the table]; equals the one-table result
  * bit for bit.  (k-means over a sharded table is not offered: its update needs a cross-shard reduction.) */
 int mi_knn_sharded_assign(mi_knn_sharded* t, const float* vectors, uint32_t C, uint32_t* labels, float* dist);
+/* mi_knn_assign_multi over the whole table, as mi_knn_sharded_assign: per shard, results ([rows of the table][m]) at the
+ * rows' global ids; equals the one-table result bit for bit */
+int mi_knn_sharded_assign_multi(mi_knn_sharded* t, const float* vectors, uint32_t C, uint32_t m, float max_dist,
+                                uint32_t* labels, float* dist);
 /* Change the layout of a LIVE table: every row of `src` into the empty `dst` (another shard count, device set or block
  * size), block by block, device to device — a plain copy where source and destination shard share a GPU,
  * hipMemcpyPeerAsync over xGMI where they do not; nothing passes through the host.  src is unchanged. */
