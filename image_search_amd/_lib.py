@@ -64,6 +64,9 @@ SYMBOLS = {
     "mi_knn_assign_stats": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_knn_assign_multi": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp]),
     "mi_knn_assign_multi_stats": (ctypes.c_int, [c_vp, c_u64p]),
+    "mi_knn_search_many": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
+    "mi_knn_search_many_stats": (ctypes.c_int, [c_vp, c_u64p]),
+    "mi_knn_neighbors": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_kmeans": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32),
                                      c_u64p, ctypes.POINTER(ctypes.c_double)]),
     "mi_pairs_to_groups": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_u64p,
@@ -95,6 +98,7 @@ SYMBOLS = {
                                                       c_vp]),
     "mi_knn_sharded_assign": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_sharded_assign_multi": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp]),
+    "mi_knn_sharded_search_many": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_sharded_place": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32),
                                             c_u64p]),
     "mi_knn_sharded_id": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, c_u64p]),

@@ -207,6 +207,11 @@ struct mi_knn {
     uint64_t assign_stats[4] = {0, 0, 0, 0};
     // mi_knn_assign_multi (assign_multi.hip): {candidates, (row, label) hits written, stage-1 launches, tiles} of the last call
     uint64_t assign_multi_stats[4] = {0, 0, 0, 0};
+    // mi_knn_search_many / mi_knn_neighbors (search_many.hip): {candidates, (query, row) hits written, stage-1 launches, tiles} of
+    // the last call; column segments of a stage-1 launch (option "many_segments": 0 = from the tile counts) and the stride of
+    // the threshold pass over the column tiles (option "many_sample": 0 = chosen by the table's size)
+    uint64_t search_many_stats[4] = {0, 0, 0, 0};
+    int many_segments = 0, many_sample = 0;
     std::mutex mu;
 };
 

@@ -1042,8 +1042,18 @@ int mi_knn_set_option(mi_knn* t, const char* key, int value) {
             // full tile, 2^14): a strip that finds more is redone in smaller pieces.  Same answers whatever the value.
             if (value < (1 << 14)) fail(MI_ERR_INVALID, "join_cap must be >= 16384 (got %d)", value);
             t->join_cap = (uint32_t)value;
+        } else if (k == "many_segments") {
+            // mi_knn_search_many / mi_knn_neighbors: column segments of a stage-1 launch.  0 (default): from the query and column
+            // tile counts; v >= 1: exactly min(v, column tiles).  Same answers whatever the value.
+            if (value < 0) fail(MI_ERR_INVALID, "many_segments must be >= 0 (got %d)", value);
+            t->many_segments = value;
+        } else if (k == "many_sample") {
+            // ... the threshold pass visits every v-th column tile.  0 (default): chosen by the table's size; 1: every tile.
+            // Same answers whatever the value (a sparser sample hands stage 2 more candidates).
+            if (value < 0) fail(MI_ERR_INVALID, "many_sample must be >= 0 (got %d)", value);
+            t->many_sample = value;
         } else {
-            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap)", key);
+            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, many_segments, many_sample)", key);
         }
     });
 }

@@ -176,6 +176,25 @@ class EmbeddingTable {
     }
     // {candidates, (row, label) hits written, stage-1 launches, tiles visited} of the last assign_multi
     std::vector<uint64_t> assign_multi_stats() const { std::vector<uint64_t> v(4); check(mi_knn_assign_multi_stats(h_, v.data())); return v; }
+    // the k <= 16 nearest live rows for each of nq queries (mi_knn_search_many): idx / dist are [nq * k], per query what
+    // knn(query, k) answers without the NaN distances, MI_KNN_NO_ID / +inf behind the last hit.  queries: [nq * dim]
+    struct Neighbors { std::vector<uint64_t> idx; std::vector<float> dist; };
+    Neighbors knn_many(const std::vector<float>& queries, uint32_t nq, uint32_t k) const {
+        Neighbors r;
+        r.idx.resize((size_t)nq * k); r.dist.resize((size_t)nq * k);
+        check(mi_knn_search_many(h_, queries.data(), nq, k, r.idx.data(), r.dist.data()));
+        return r;
+    }
+    // a slice of the kNN graph (mi_knn_neighbors): for the rows with ids first .. first + n - 1 the k <= 15 nearest OTHER
+    // live rows, [n * k]; a deleted row gets MI_KNN_NO_ID / +inf
+    Neighbors neighbors(uint32_t k, uint64_t first, uint64_t n) const {
+        Neighbors r;
+        r.idx.resize(n * k); r.dist.resize(n * k);
+        check(mi_knn_neighbors(h_, first, n, k, r.idx.data(), r.dist.data()));
+        return r;
+    }
+    // {candidates, (query, row) hits written, stage-1 launches, tiles visited} of the last knn_many / neighbors
+    std::vector<uint64_t> search_many_stats() const { std::vector<uint64_t> v(4); check(mi_knn_search_many_stats(h_, v.data())); return v; }
     // spherical k-means (mi_knn_kmeans): centroids [C * dim] in = initial, out = final; labels / dist = assign(centroids)
     struct KMeans { Assignment assignment; uint32_t iters = 0; uint64_t changed = 0; double objective = 0.0; };
     KMeans kmeans(std::vector<float>& centroids, uint32_t C, uint32_t max_iters = 20) const {
@@ -321,6 +340,13 @@ class ShardedTable {
         std::vector<float> dist(n * m);
         check(mi_knn_sharded_assign_multi(h_, vectors.data(), C, m, max_dist, labels.data(), dist.data()));
         return {std::move(labels), std::move(dist)};
+    }
+    // EmbeddingTable::knn_many over all shards (mi_knn_sharded_search_many): idx / dist [nq * k], global ids
+    std::pair<std::vector<uint64_t>, std::vector<float>> knn_many(const std::vector<float>& queries, uint32_t nq, uint32_t k) const {
+        std::vector<uint64_t> idx((size_t)nq * k);
+        std::vector<float> dist((size_t)nq * k);
+        check(mi_knn_sharded_search_many(h_, queries.data(), nq, k, idx.data(), dist.data()));
+        return {std::move(idx), std::move(dist)};
     }
     std::pair<std::vector<uint64_t>, std::vector<float>> knn(const std::vector<float>& reference, uint32_t k = 1000) const {
         std::vector<uint64_t> idx(k);

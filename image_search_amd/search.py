@@ -84,6 +84,7 @@ class EmbeddingTable:
 
     def set_base(self, base: int):
         check(lib().mi_knn_set_base(self._h, base))
+        self._base_id = int(base)
 
     def reserve(self, rows: int):
         check(lib().mi_knn_reserve(self._h, rows))
@@ -200,6 +201,31 @@ class EmbeddingTable:
         check(lib().mi_knn_assign_multi_stats(self._h, out))
         return {"candidates": out[0], "hits": out[1], "launches": out[2], "tiles": out[3]}
 
+    def knn_many(self, queries: np.ndarray, k: int):
+        """The k <= 16 nearest live rows for each of many queries (mi_knn_search_many): (idx [nq, k] uint64, dist [nq, k] f32)
+        — per query what knn(query, k) answers without the entries whose distance is NaN, ids and distance bits; NO_ID /
+        +inf behind a query's last hit."""
+        q = _f32(queries).reshape(-1, self.dim)
+        idx, dist = np.empty((q.shape[0], int(k)), np.uint64), np.empty((q.shape[0], int(k)), np.float32)
+        check(lib().mi_knn_search_many(self._h, q.ctypes.data, q.shape[0], int(k), idx.ctypes.data, dist.ctypes.data))
+        return idx, dist
+
+    def neighbors(self, k: int, first: int = 0, n: Optional[int] = None):
+        """A slice of the kNN graph (mi_knn_neighbors): for the rows with ids first .. first + n - 1 (n = None: to the
+        table's end) the k <= 15 nearest OTHER live rows, (idx [n, k] uint64, dist [n, k] f32); a deleted row gets NO_ID /
+        +inf.  On a table with a base (set_base) the first id is the base."""
+        if n is None:
+            n = max(int(getattr(self, "_base_id", 0)) + len(self) - int(first), 0)
+        idx, dist = np.empty((int(n), int(k)), np.uint64), np.empty((int(n), int(k)), np.float32)
+        check(lib().mi_knn_neighbors(self._h, int(first), int(n), int(k), idx.ctypes.data, dist.ctypes.data))
+        return idx, dist
+
+    def search_many_stats(self):
+        """mi_knn_search_many_stats, of the last knn_many / neighbors on this table"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_search_many_stats(self._h, out))
+        return {"candidates": out[0], "hits": out[1], "launches": out[2], "tiles": out[3]}
+
     def kmeans(self, k_or_centroids, max_iters: int = 20, seed: int = 0) -> dict:
         """Spherical k-means over the live rows (mi_knn_kmeans).  k_or_centroids: the initial centroids [C, dim], or an int
         k: k distinct live rows picked with np.random.default_rng(seed).  Returns dict(centroids, labels, dist, iters,
@@ -216,6 +242,19 @@ class EmbeddingTable:
                                   ctypes.byref(iters), ctypes.byref(changed), ctypes.byref(obj)))
         return {"centroids": cent, "labels": labels, "dist": dist, "iters": iters.value, "changed": changed.value,
                 "objective": obj.value}
+
+
+def drop_self(idx: np.ndarray, dist: np.ndarray, self_ids) -> tuple:
+    """knn_many(rows, k + 1) -> the k nearest OTHER rows: from row i of idx / dist [n, k + 1] the entry whose id is
+    self_ids[i] is removed, or, where that is absent (only padding; k + 1 or more exact copies of the row at lower ids),
+    the last entry.  Returns (idx [n, k], dist [n, k])."""
+    idx = np.asarray(idx, np.uint64)
+    dist = np.asarray(dist, np.float32)
+    n, m = idx.shape
+    own = idx == np.asarray(self_ids, np.uint64).reshape(n, 1)
+    drop = np.where(own.any(axis=1), own.argmax(axis=1), m - 1)
+    keep = np.arange(m)[None, :] != drop[:, None]
+    return idx[keep].reshape(n, m - 1), dist[keep].reshape(n, m - 1)
 
 
 def rows_of_labels(labels: np.ndarray, C: int) -> list:
@@ -514,6 +553,30 @@ class ShardedTable:
                                                 dist.ctypes.data))
         return labels, dist
 
+    def knn_many(self, queries: np.ndarray, k: int):
+        """EmbeddingTable.knn_many over all shards (mi_knn_sharded_search_many): global ids"""
+        q = _f32(queries).reshape(-1, self.dim)
+        idx, dist = np.empty((q.shape[0], int(k)), np.uint64), np.empty((q.shape[0], int(k)), np.float32)
+        check(lib().mi_knn_sharded_search_many(self._h, q.ctypes.data, q.shape[0], int(k), idx.ctypes.data, dist.ctypes.data))
+        return idx, dist
+
+    def neighbors(self, k: int, first: int = 0, n: Optional[int] = None):
+        """EmbeddingTable.neighbors over all shards, composed on the host: the rows are read back (rows()), searched with
+        k + 1 (knn_many) and lose their own entry (drop_self); deleted rows are padded"""
+        if n is None:
+            n = max(len(self) - int(first), 0)
+        if not (0 <= int(first) and int(first) + int(n) <= len(self)):
+            raise ValueError(f"rows [{first}, {int(first) + int(n)}) are not rows of this table ({len(self)} rows)")
+        if not 1 <= int(k) <= 15:
+            raise ValueError("1 <= k <= 15")
+        if n == 0:
+            return np.empty((0, int(k)), np.uint64), np.empty((0, int(k)), np.float32)
+        ids = np.arange(int(first), int(first) + int(n), dtype=np.uint64)
+        idx, dist = drop_self(*self.knn_many(self.rows(int(first), int(n)), int(k) + 1), ids)
+        gone = np.isin(ids, self.deleted())
+        idx[gone], dist[gone] = NO_ID, np.inf
+        return idx, dist
+
     def delete(self, ids) -> int:
         """EmbeddingTable.delete on global ids (mi_knn_sharded_delete)"""
         return _delete(lib().mi_knn_sharded_delete, self._h, ids)
@@ -803,6 +866,32 @@ class ImageIndex:
             hits = [(int(l), float(d)) for l, d in zip(labels[r], dist[r]) if l != NO_LABEL]
             out[self.path(r, web=web)] = [(names[l] if names is not None else l, d) for l, d in hits]
         return out
+
+    def related(self, k: int = 10, web: bool = False) -> dict:
+        """"More like this" for every image (EmbeddingTable.neighbors): {path: [(path, distance), ...]} over the paths that
+        have not been removed, nearest first, at most k other images each.  A path with several rows reports its last row."""
+        idx, dist = self.table.neighbors(k)
+        deleted = set(int(r) for r in self.table.deleted())
+        names = {}
+
+        def name(r):
+            if r not in names:
+                names[r] = self.path(r, web=web)
+            return names[r]
+
+        out = {}
+        for r in range(idx.shape[0]):
+            if r not in deleted:
+                out[name(r)] = [(name(int(i)), float(d)) for i, d in zip(idx[r], dist[r]) if i != NO_ID]
+        return out
+
+    def best_per_label(self, vectors: np.ndarray, names: Optional[Sequence[str]] = None, k: int = 10, web: bool = False) -> dict:
+        """"The best k images for each of my tags" (EmbeddingTable.knn_many): {label: [(path, distance), ...]}, nearest
+        first; label = the index into `vectors` (text embeddings of the tags), or names[index].  Removed paths never
+        appear."""
+        idx, dist = self.table.knn_many(vectors, k)
+        return {(names[c] if names is not None else c): [(self.path(int(i), web=web), float(d)) for i, d in zip(idx[c], dist[c]) if i != NO_ID]
+                for c in range(idx.shape[0])}
 
     def clusters(self, k: int, max_iters: int = 20, seed: int = 0, web: bool = False) -> list:
         """"Group my library into k themes" (EmbeddingTable.kmeans): lists of paths, the largest cluster first; removed

@@ -385,6 +385,28 @@ int mi_knn_assign_multi(mi_knn* t, const float* vectors, uint32_t C, uint32_t m,
 /* of the last mi_knn_assign_multi on this handle: out = {candidates stage 1 handed to stage 2, (row, label) hits written,
  * stage-1 launches (re-runs after an overflow included), tiles visited} */
 int mi_knn_assign_multi_stats(mi_knn* t, uint64_t out[4]);
+/* Many queries at once ("the best k images for each of my C tags").  For each of nq queries (q: [nq][dim] host f32) the
+ * entries of mi_knn_search(t, query, k) AFTER removing every entry whose distance is NaN: same ids, same distance bits, same
+ * order (distance ascending, then id); MI_KNN_NO_ID / +inf behind the last hit.  idx: [nq][k] uint64, dist: [nq][k] f32.
+ * 1 <= k <= 16 (MI_ERR_UNSUPPORTED above), nq >= 1 of any size (walked in strips: the device workspace does not grow with
+ * nq); 0 / NULL: MI_ERR_INVALID.  dim, mirror, "join_cap" and stream ordering: as mi_knn_assign_multi.  Deleted rows are
+ * never returned.  Empty table: all padding, MI_OK.  Stage 1 is a bf16 MFMA tile product of the queries with the table's
+ * mirror, the table's columns spread over the machine (option "many_segments": 0 = chosen, v >= 1 = exactly min(v, column
+ * tiles) segments; "many_sample": the threshold pass visits every v-th column tile, 0 = chosen); stage 2 re-evaluates what
+ * the join's bound cannot exclude from the fp32 rows.  Same answers whatever the options. */
+int mi_knn_search_many(mi_knn* t, const float* q, uint32_t nq, uint32_t k, uint64_t* idx, float* dist);
+/* out = {candidates stage 1 handed to stage 2, (query, row) hits written, stage-1 launches (threshold and emit passes and
+ * re-runs after an overflow all counted), tiles visited} of the last search_many / neighbors on this handle */
+int mi_knn_search_many_stats(mi_knn* t, uint64_t out[4]);
+/* The kNN graph ("more like this" for every image), a slice at a time: for the n rows with ids first .. first + n - 1 (must
+ * be rows of the table, else MI_ERR_INVALID and nothing runs; n may be 0) the k nearest OTHER live rows:
+ * mi_knn_search_many(q = the row, k + 1) with the entry whose id is the row's own removed, or, where that entry is absent
+ * (a row whose every distance is NaN; k + 1 or more exact copies of the row at lower ids), the last entry removed.
+ * Distances are what mi_knn_search(q = row a) reports for row b, bit for bit (the contract of mi_knn_near_pairs).  A deleted
+ * row gets k x (MI_KNN_NO_ID, +inf).  1 <= k <= 15.  idx: [n][k], dist: [n][k].  The queries are read where they lie: no
+ * copy of the rows, their mirror rows are the table's.  Not offered on a shard borrowed from a sharded table (its ids are
+ * not contiguous: MI_ERR_UNSUPPORTED). */
+int mi_knn_neighbors(mi_knn* t, uint64_t first, uint64_t n, uint32_t k, uint64_t* idx, float* dist);
 /* Spherical k-means (Lloyd's iterations) over the live rows, mi_knn_assign as its inner step:
  *   it = 0
  *   loop: labels = assign(centroids); changed = rows whose label differs from the previous assign (first: the live rows)
@@ -468,6 +490,10 @@ int mi_knn_sharded_assign(mi_knn_sharded* t, const float* vectors, uint32_t C, u
  * rows' global ids; equals the one-table result bit for bit */
 int mi_knn_sharded_assign_multi(mi_knn_sharded* t, const float* vectors, uint32_t C, uint32_t m, float max_dist,
                                 uint32_t* labels, float* dist);
+/* mi_knn_search_many over the whole table: every shard answers on its own stream and host thread (as
+ * mi_knn_sharded_assign_multi), the per-shard lists are merged with mi_knn_merge's ordering; equals the one-table result
+ * bit for bit */
+int mi_knn_sharded_search_many(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, uint64_t* idx, float* dist);
 /* Change the layout of a LIVE table: every row of `src` into the empty `dst` (another shard count, device set or block
  * size), block by block, device to device — a plain copy where source and destination shard share a GPU,
  * hipMemcpyPeerAsync over xGMI where they do not; nothing passes through the host.  src is unchanged. */
