@@ -11,46 +11,13 @@
 #include "common.h"
 #include "handles.h"
 #include "assign_kernels.h"
+#include "two_stage.h"
 
 using namespace mi;
-using namespace mi_assign::mi;
 
 namespace {
 
 constexpr uint32_t ASSIGN_MAX_C = 65536;
-
-// device memory of one call, freed on every way out
-struct Scratch {
-    std::vector<void*> p;
-    void* get(size_t bytes) {
-        void* q = nullptr;
-        HIP_CHECK(hipMalloc(&q, std::max<size_t>(bytes, 16)));
-        p.push_back(q);
-        return q;
-    }
-    ~Scratch() {
-        for (void* q : p) (void)hipFree(q);
-    }
-};
-
-// the table's own mirror grows with its capacity, keeping the rows mirrored so far (as join.hip)
-void grow_keep(mi_knn* t, void** p, size_t* have, size_t want, size_t elem, size_t keep) {
-    if (*have >= want) return;
-    t->reads.sync();
-    void* np_ = nullptr;
-    HIP_CHECK(hipMalloc(&np_, want * elem));
-    if (*p && keep) HIP_CHECK(hipMemcpy(np_, *p, std::min(keep, *have) * elem, hipMemcpyDeviceToDevice));
-    if (*p) HIP_CHECK(hipFree(*p));
-    *p = np_;
-    *have = want;
-}
-
-template <int NCH>
-void launch_mirror(hipStream_t s, int n_cu, const float* rows, uint64_t from, uint64_t end, uint16_t* mirror, float* xx) {
-    const uint32_t mb = std::max<uint32_t>(1u, (uint32_t)std::min<uint64_t>((uint64_t)n_cu * 8, (end - from + 15) / 16));
-    hipLaunchKernelGGL((knn_mirror_kernel<NCH>), dim3(mb), dim3(256), 0, s, rows, from, end, mirror, xx);
-    HIP_CHECK(hipGetLastError());
-}
 
 // One call's state: the rows' mirror (built once), the vectors (replaced per assign), the results on the device.
 struct Assign {
@@ -74,50 +41,35 @@ struct Assign {
 
     template <int NCH>
     void rect(uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) {
-        if (bc0 >= bc1 || br0 >= br1) return;
-        static DevOnce once;
-        allow_lds_once(once, assign_tiles_kernel<NCH>, ASG_LDS);
-        HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
-        hipLaunchKernelGGL((assign_tiles_kernel<NCH>), dim3(br1 - br0), dim3(256), ASG_LDS, s, mirror, xx, tomb, n_rows, d_vmirror,
-                           d_vxx, C, br0, bc0, bc1, thr, cand_cap, d_cand, d_count);
-        HIP_CHECK(hipGetLastError());
-        unsigned long long n_cand = 0;
-        HIP_CHECK(hipMemcpyAsync(&n_cand, d_count, sizeof n_cand, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        ++stats[2];
-        stats[3] += (uint64_t)(br1 - br0) * (bc1 - bc0);
-        if (n_cand > cand_cap) {   // nothing is dropped: the same ground again in two halves, rows first, then columns
-            if (overflowed) *overflowed = true;
-            if (br1 - br0 > 1) {
-                const uint32_t mid = br0 + (br1 - br0) / 2;
-                rect<NCH>(br0, mid, bc0, bc1, nullptr);
-                rect<NCH>(mid, br1, bc0, bc1, nullptr);
-            } else if (bc1 - bc0 > 1) {
-                const uint32_t mid = bc0 + (bc1 - bc0) / 2;
-                rect<NCH>(br0, br1, bc0, mid, nullptr);
-                rect<NCH>(br0, br1, mid, bc1, nullptr);
-            } else {
-                fail(MI_ERR_INVALID, "one tile reported %llu candidates (the buffer holds %u)", n_cand, cand_cap);
-            }
-            return;
-        }
-        stats[0] += n_cand;
-        if (n_cand == 0) return;
-        const uint32_t n = (uint32_t)n_cand;
-        const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)t->n_cu * 8, (n + 15) / 16));
-        hipLaunchKernelGGL((assign_rescore_kernel<NCH>), dim3(blocks), dim3(256), 0, s, t->table, d_vec, d_cand, n, d_best);
-        HIP_CHECK(hipGetLastError());
+        auto stage1 = [&](uint32_t r0, uint32_t r1, uint32_t& c0, uint32_t c1) {
+            static DevOnce once;
+            allow_lds_once(once, assign_tiles_kernel<NCH>, ASG_LDS);
+            HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+            hipLaunchKernelGGL((assign_tiles_kernel<NCH>), dim3(r1 - r0), dim3(256), ASG_LDS, s, mirror, xx, tomb, n_rows, d_vmirror,
+                               d_vxx, C, r0, c0, c1, thr, cand_cap, d_cand, d_count);
+            HIP_CHECK(hipGetLastError());
+            ++stats[2];
+            stats[3] += (uint64_t)(r1 - r0) * (c1 - c0);
+            return read_count(d_count, s);
+        };
+        auto stage2 = [&](uint32_t n) {   // (the rows' minima live in d_best: they join the pieces of a row)
+            stats[0] += n;
+            hipLaunchKernelGGL((assign_rescore_kernel<NCH>), dim3(group16_blocks(t, n)), dim3(256), 0, s, t->table, d_vec, d_cand, n,
+                               d_best);
+            HIP_CHECK(hipGetLastError());
+        };
+        rect_stages(br0, br1, bc0, bc1, cand_cap, overflowed, stage1, stage2);
     }
 
     // d_vec holds the vectors: -> d_labels / d_dist.  prev_in_labels: count the rows whose label changes into *changed
     template <int NCH>
     void run(bool count_changed, uint64_t* changed) {
         for (uint64_t& v : stats) v = 0;
-        launch_mirror<NCH>(s, t->n_cu, d_vec, 0, C, d_vmirror, d_vxx);
+        mirror_rows(t, s, d_vec, 0, C, d_vmirror, d_vxx);
         HIP_CHECK(hipMemsetAsync(d_best, 0xFF, (size_t)n_rows * sizeof(unsigned long long), s));
-        const uint32_t n_rb = (n_rows + ASG_TILE - 1) / ASG_TILE;
+        const uint32_t n_rb = (n_rows + TILE - 1) / TILE;
         // strips of row tiles: as many as keep an ordinary corpus (a few candidates per row and column tile) inside the buffer
-        if (strip == 0) strip = std::max<uint32_t>(1u, std::min<uint32_t>(2048u, cand_cap / (ASG_TILE * 4u * n_cb)));
+        if (strip == 0) strip = std::max<uint32_t>(1u, std::min<uint32_t>(2048u, cand_cap / (TILE * 4u * n_cb)));
         for (uint32_t br = 0; br < n_rb;) {
             const uint32_t end = std::min(n_rb, br + strip);
             bool overflowed = false;
@@ -140,13 +92,7 @@ struct Assign {
     }
 
     void run(bool count_changed = false, uint64_t* changed = nullptr) {
-        switch (t->dim / 64) {
-            case 2: run<2>(count_changed, changed); break;
-            case 4: run<4>(count_changed, changed); break;
-            case 8: run<8>(count_changed, changed); break;
-            case 12: run<12>(count_changed, changed); break;
-            case 16: run<16>(count_changed, changed); break;
-        }
+        dispatch_nch(t->dim, [&](auto nch) { run<decltype(nch)::value>(count_changed, changed); });
     }
 
     // t->mu held, device selected, arguments checked, the table not empty
@@ -158,34 +104,11 @@ struct Assign {
         t->writes.begin(s);
         t->reads.begin(s);
         n_rows = (uint32_t)t->rows;
-        n_cb = (C + ASG_TILE - 1) / ASG_TILE;
-        // the join's bound, unchanged (join_kernels.h): both operands are rounded to bf16
-        const float eps2 = 0x1p-7f + 0x1p-16f + 4.1f * (float)(t->dim + 8) * 0x1p-24f + 2e-6f;
-        thr = 2.0f * eps2;
-        cand_cap = std::max<uint32_t>(ASG_CAP_MIN, t->join_cap);
-        tomb = t->dead.empty() ? nullptr : t->d_tomb;
-        // the mirror: the table's own when "prefilter" = 1 keeps one (caught up here as a search would), else one for this call
-        uint16_t* m = nullptr;
-        float* x = nullptr;
-        uint64_t from = 0;
-        if (t->prefilter == 1) {
-            t->mirror_rows = std::min(t->mirror_rows, t->rows);
-            grow_keep(t, (void**)&t->d_mirror, &t->mirror_cap, (size_t)t->cap * t->dim, sizeof(uint16_t), (size_t)t->mirror_rows * t->dim);
-            grow_keep(t, (void**)&t->d_xx, &t->xx_cap, (size_t)t->cap, sizeof(float), (size_t)t->mirror_rows);
-            m = t->d_mirror; x = t->d_xx; from = t->mirror_rows;
-        } else {
-            m = (uint16_t*)scratch.get((size_t)t->rows * t->dim * sizeof(uint16_t));
-            x = (float*)scratch.get((size_t)t->rows * sizeof(float));
-        }
-        if (from < t->rows) {
-            switch (t->dim / 64) {
-#define MI_CASE(NCH) case NCH: launch_mirror<NCH>(s, t->n_cu, t->table, from, t->rows, m, x); break;
-                MI_CASE(2) MI_CASE(4) MI_CASE(8) MI_CASE(12) MI_CASE(16)
-#undef MI_CASE
-            }
-            if (t->prefilter == 1) t->mirror_rows = t->rows;
-        }
-        mirror = m; xx = x;
+        n_cb = (C + TILE - 1) / TILE;
+        thr = 2.0f * eps2(t->dim);   // the join's bound, unchanged (join_kernels.h): both operands are rounded to bf16
+        cand_cap = std::max<uint32_t>(TILE_CAP_MIN, t->join_cap);
+        const TableMirror tm = table_mirror(t, s, scratch);
+        mirror = tm.mirror; xx = tm.xx; tomb = tm.tomb;
         d_vec = (float*)scratch.get((size_t)C * t->dim * sizeof(float));
         d_vmirror = (uint16_t*)scratch.get((size_t)C * t->dim * sizeof(uint16_t));
         d_vxx = (float*)scratch.get((size_t)C * sizeof(float));
@@ -198,20 +121,13 @@ struct Assign {
     }
 };
 
-// whatever happens, the handle's stream is idle and its order words say so when the call leaves
-struct Settle {
-    mi_knn* t; hipStream_t s;
-    ~Settle() { (void)hipStreamSynchronize(s); t->reads.pending = false; }
-};
-
 void check_args(const mi_knn* t, const float* vectors, uint32_t C, const uint32_t* labels, bool labels_needed) {
     if (!t) fail(MI_ERR_INVALID, "null table handle");
     if (!vectors) fail(MI_ERR_INVALID, "vectors is null");
     if (labels_needed && !labels) fail(MI_ERR_INVALID, "labels is null");
     if (C == 0) fail(MI_ERR_INVALID, "C must be >= 1");
     if (C > ASSIGN_MAX_C) fail(MI_ERR_UNSUPPORTED, "at most %u vectors (got %u)", ASSIGN_MAX_C, C);
-    if (t->dim % 128 != 0 || (t->dim / 64 != 2 && t->dim / 64 != 4 && t->dim / 64 != 8 && t->dim / 64 != 12 && t->dim / 64 != 16))
-        fail(MI_ERR_UNSUPPORTED, "dim %u: the assign's bf16 mirror is built for dim in {128, 256, 512, 768, 1024}", t->dim);
+    check_mirror_dim(t->dim, "the assign's");
 }
 
 // labels / dist of the shard's local rows
@@ -250,8 +166,7 @@ struct Update {
         d_sorted = (uint32_t*)a.scratch.get((size_t)n * sizeof(uint32_t));
         d_inv = (float*)a.scratch.get((size_t)n * sizeof(float));
         d_part = (float*)a.scratch.get((size_t)max_segs * a.t->dim * sizeof(float));
-        const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)a.t->n_cu * 8, (n + 15) / 16));
-        hipLaunchKernelGGL((km_inv_norm_kernel<NCH>), dim3(blocks), dim3(256), 0, a.s, a.t->table, n, d_inv);
+        hipLaunchKernelGGL((km_inv_norm_kernel<NCH>), dim3(group16_blocks(a.t, n)), dim3(256), 0, a.s, a.t->table, n, d_inv);
         HIP_CHECK(hipGetLastError());
     }
 
@@ -332,13 +247,7 @@ int mi_knn_kmeans(mi_knn* t, float* centroids, uint32_t C, uint32_t max_iters, u
         HIP_CHECK(hipMemcpyAsync(a.d_vec, centroids, cbytes, hipMemcpyHostToDevice, a.s));
         uint32_t it = 0;
         uint64_t changed = 0;
-        switch (t->dim / 64) {
-            case 2: kmeans_loop<2>(a, max_iters, &it, &changed); break;
-            case 4: kmeans_loop<4>(a, max_iters, &it, &changed); break;
-            case 8: kmeans_loop<8>(a, max_iters, &it, &changed); break;
-            case 12: kmeans_loop<12>(a, max_iters, &it, &changed); break;
-            case 16: kmeans_loop<16>(a, max_iters, &it, &changed); break;
-        }
+        dispatch_nch(t->dim, [&](auto nch) { kmeans_loop<decltype(nch)::value>(a, max_iters, &it, &changed); });
         std::vector<uint32_t> h_labels;
         std::vector<float> h_dist;
         uint32_t* pl = labels;
@@ -365,36 +274,19 @@ int mi_knn_sharded_assign(mi_knn_sharded* t, const float* vectors, uint32_t C, u
         check_args(t->shard[0], vectors, C, labels, true);
         std::lock_guard<std::mutex> l(t->mu);
         sharded_deliver_all(t);
-        // every shard on its own stream, driven by a host thread of its own (a shard's assign reads its candidate counts
-        // back between launches); results land at the rows' global ids
-        const uint32_t n = t->n();
-        std::vector<int> codes(n, MI_OK);
-        std::vector<std::string> msgs(n);
-        std::vector<std::thread> threads;
-        for (uint32_t si = 0; si < n; ++si) {
-            threads.emplace_back([&, si] {
-                try {
-                    mi_knn* sh = t->shard[si];
-                    const uint64_t rows = sh->rows;
-                    std::vector<uint32_t> lab(rows);
-                    std::vector<float> dd(dist ? rows : 0);
-                    assign_local(sh, vectors, C, lab.data(), dist ? dd.data() : nullptr);
-                    const IdMap map{sh->base, sh->cyc_block, sh->cyc_n, sh->cyc_rank};
-                    for (uint64_t r = 0; r < rows; ++r) {
-                        const uint64_t id = id_of_local(map, r);
-                        labels[id] = lab[r];
-                        if (dist) dist[id] = dd[r];
-                    }
-                } catch (const Error& e) {
-                    codes[si] = e.code; msgs[si] = e.what();
-                } catch (const std::exception& e) {
-                    codes[si] = MI_ERR_INVALID; msgs[si] = e.what();
-                }
-            });
-        }
-        for (std::thread& th : threads) th.join();
-        for (uint32_t si = 0; si < n; ++si)
-            if (codes[si] != MI_OK) fail(codes[si], "shard %u: %s", si, msgs[si].c_str());
+        // every shard on its own stream; results land at the rows' global ids
+        for_each_shard(t, [&](uint32_t, mi_knn* sh) {
+            const uint64_t rows = sh->rows;
+            std::vector<uint32_t> lab(rows);
+            std::vector<float> dd(dist ? rows : 0);
+            assign_local(sh, vectors, C, lab.data(), dist ? dd.data() : nullptr);
+            const IdMap map{sh->base, sh->cyc_block, sh->cyc_n, sh->cyc_rank};
+            for (uint64_t r = 0; r < rows; ++r) {
+                const uint64_t id = id_of_local(map, r);
+                labels[id] = lab[r];
+                if (dist) dist[id] = dd[r];
+            }
+        });
     });
 }
 

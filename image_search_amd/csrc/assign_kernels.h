@@ -37,30 +37,11 @@
 #include <cstdint>
 
 #include "common.h"
+#include "tile128.h"
 
-// the shared device code (RowAcc, row16_sum, knn_mirror_kernel, the keys) through a namespace of its own: see join_kernels.h
-namespace mi_assign {
-#include "knn_kernels.h"
-}
-
-namespace mi_assign {
 namespace mi {
 
-typedef __bf16 asg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float asg_f32x16 __attribute__((ext_vector_type(16)));
-typedef int asg_i32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int ASG_TILE = 128;                                   // rows / vectors of a tile
-constexpr int ASG_KC = 64;                                      // elements of K per LDS image (128 bytes per row)
-constexpr int ASG_IMG = ASG_TILE * ASG_KC * 2;                  // bytes of one operand's image
-constexpr int ASG_LDS = 4 * ASG_IMG + 3 * ASG_TILE * 4;         // two buffers of two operands + row weights, column weights, row maxima
-constexpr uint32_t ASG_CAP_MIN = ASG_TILE * ASG_TILE;           // a candidate buffer holds at least one full tile
-
-// the join's LDS layout (join_lds_off): 16-byte chunk `ch` of row `row`, xor-spread over the banks
-__device__ __forceinline__ uint32_t asg_lds_off(int row, int ch) { return (uint32_t)(row * 128 + ((ch ^ ((row >> 1) & 7)) << 4)); }
-// floats as integers of the same order (an involution), for ds_max_i32
-__device__ __forceinline__ int asg_ord(float f) { const int b = __float_as_int(f); return b ^ ((b >> 31) & 0x7FFFFFFF); }
-__device__ __forceinline__ float asg_unord(int o) { return __int_as_float(o ^ ((o >> 31) & 0x7FFFFFFF)); }
+constexpr int ASG_LDS = TILE_IMGS + 3 * TILE * 4;               // the tile's images + row weights, column weights, row maxima
 
 // grid.x = row tiles: workgroup x takes rows of tile br0 + x against the column tiles [bc0, bc1).  thr = 2 eps2.
 // count: all candidates found, also those beyond cap (the caller then redoes the piece in smaller ones); cand: the first
@@ -72,114 +53,36 @@ __global__ __launch_bounds__(256) void assign_tiles_kernel(const uint16_t* __res
                                                             uint32_t n_vec, uint32_t br0, uint32_t bc0, uint32_t bc1, float thr,
                                                             uint32_t cap, uint2* __restrict__ cand,
                                                             unsigned long long* __restrict__ count) {
-    static_assert(NCH % 2 == 0, "rows of whole 256-byte bf16 chunks (the mirror's own condition)");
-    constexpr int DIM = NCH * 64, NK = DIM / ASG_KC;
+    constexpr int DIM = NCH * 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wib = tid >> 6;
-    const int wr = wib >> 1, wc = wib & 1, l31 = lane & 31, lh = lane >> 5;
+    const int tid = threadIdx.x;
+    const TileFrag f = tile_frag();
+    const int wr = f.wr, wc = f.wc, l31 = f.l31, lh = f.lh;
     // weights: rows  > 0 = sqrt of the stored norm, -1 = marked, 0 = not there;  columns  > 0 = 1 / sqrt(norm), -1, 0
-    float* roww = reinterpret_cast<float*>(smem + 4 * ASG_IMG);
-    float* colw = roww + ASG_TILE;
-    int* rowmax = reinterpret_cast<int*>(colw + ASG_TILE);
-    const uint32_t row0 = (br0 + blockIdx.x) * ASG_TILE;
+    float* roww = reinterpret_cast<float*>(smem + TILE_IMGS);
+    float* colw = roww + TILE;
+    int* rowmax = reinterpret_cast<int*>(colw + TILE);
+    const uint32_t row0 = (br0 + blockIdx.x) * TILE;
 
-    if (tid < ASG_TILE) {
+    if (tid < TILE) {
         const uint32_t r = row0 + (uint32_t)tid;
-        float w = 0.0f;
-        if (r < n_rows) {
-            const bool dead = tomb && ((tomb[r >> 6] >> (r & 63)) & 1ull);
-            if (!dead) {
-                const float s = xx[r];
-                w = s < 0.0f ? -1.0f : sqrtf(s);
-            }
-        }
-        roww[tid] = w;
-        rowmax[tid] = asg_ord(-__uint_as_float(0x7F800000u));
+        roww[tid] = tile_weight<false>(xx, r, r < n_rows, tomb, r, -1.0f, 0.0f);
+        rowmax[tid] = TILE_ORD_NINF;
     }
-
-    // global -> registers -> LDS: thread t moves chunk t & 7 of rows t >> 3, + 32, + 64, + 96 of both operands
     const uint16_t *ga[4], *gb[4];
-    uint32_t lo[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = (tid >> 3) + 32 * j, ch = tid & 7;
-        const uint32_t ra = min(row0 + (uint32_t)row, n_rows - 1);   // a ragged last tile rereads the last row
-        ga[j] = mirror + (size_t)ra * DIM + ch * 8;
-        lo[j] = asg_lds_off(row, ch);
-    }
-    u32x4 sa[4], sb[4];
-#define MI_ASG_FETCH(kc)                                                           \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                \
-        sa[j] = *reinterpret_cast<const u32x4*>(ga[j] + (kc) * ASG_KC);            \
-        sb[j] = *reinterpret_cast<const u32x4*>(gb[j] + (kc) * ASG_KC);            \
-    }
-#define MI_ASG_STASH(buf)                                                          \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                \
-        *reinterpret_cast<u32x4*>(smem + (buf) * (2 * ASG_IMG) + lo[j]) = sa[j];   \
-        *reinterpret_cast<u32x4*>(smem + (buf) * (2 * ASG_IMG) + ASG_IMG + lo[j]) = sb[j]; \
-    }
-
-    // operand lane map of the 32x32x16 form: lane (r = l & 31, h = l >> 5) holds elements k = 8 h .. 8 h + 7 of row r
-    uint32_t fa[2], fb[2];
-    const int swz_a0 = ((wr * 64 + l31) >> 1) & 7, swz_b0 = ((wc * 64 + l31) >> 1) & 7;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        fa[t] = (uint32_t)((wr * 64 + t * 32 + l31) * 128);
-        fb[t] = (uint32_t)(ASG_IMG + (wc * 64 + t * 32 + l31) * 128);
-    }
+    tile_src<DIM>(ga, mirror, row0, n_rows);
 
 #pragma unroll 1
     for (uint32_t bj = bc0; bj < bc1; ++bj) {
-        const uint32_t col0 = bj * ASG_TILE;
+        const uint32_t col0 = bj * TILE;
         // (the previous tile's readers of colw and of the images passed the barrier that ends this iteration)
-        if (tid < ASG_TILE) {
+        if (tid < TILE) {
             const uint32_t cidx = col0 + (uint32_t)tid;
-            float w = 0.0f;
-            if (cidx < n_vec) {
-                const float s = vxx[cidx];
-                w = s < 0.0f ? -1.0f : 1.0f / sqrtf(s);
-            }
-            colw[tid] = w;
+            colw[tid] = tile_weight<true>(vxx, cidx, cidx < n_vec, nullptr, 0u, -1.0f, 0.0f);
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int row = (tid >> 3) + 32 * j, ch = tid & 7;
-            const uint32_t rb = min(col0 + (uint32_t)row, n_vec - 1);
-            gb[j] = vmirror + (size_t)rb * DIM + ch * 8;
-        }
-        asg_f32x16 acc[2][2];
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[ti][tj][e] = 0.0f;
-
-        MI_ASG_FETCH(0)
-        MI_ASG_STASH(0)
-        __syncthreads();
-#pragma unroll 1
-        for (int kc = 0; kc < NK; ++kc) {
-            if (kc + 1 < NK) { MI_ASG_FETCH(kc + 1) }
-            const unsigned char* img = smem + (kc & 1) * (2 * ASG_IMG);
-#pragma unroll
-            for (int s = 0; s < ASG_KC / 16; ++s) {
-                const int ch = 2 * s + lh;
-                asg_bf16x8 af[2], bf[2];
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    af[t] = *reinterpret_cast<const asg_bf16x8*>(img + fa[t] + ((ch ^ swz_a0) << 4));
-                    bf[t] = *reinterpret_cast<const asg_bf16x8*>(img + fb[t] + ((ch ^ swz_b0) << 4));
-                }
-#pragma unroll
-                for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                    for (int tj = 0; tj < 2; ++tj)
-                        acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ti], bf[tj], acc[ti][tj], 0, 0, 0);
-            }
-            if (kc + 1 < NK) { MI_ASG_STASH((kc + 1) & 1) }
-            __syncthreads();
-        }
+        tile_src<DIM>(gb, vmirror, col0, n_vec);
+        f32x16 acc[2][2];
+        tile_accumulate<NCH>(smem, f, ga, gb, acc);
 
         // C/D map: register e of lane l is row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31 of its 32 x 32 block
         const float cw0 = colw[wc * 64 + l31], cw1 = colw[wc * 64 + 32 + l31];
@@ -190,13 +93,13 @@ __global__ __launch_bounds__(256) void assign_tiles_kernel(const uint16_t* __res
             for (int q = 0; q < 4; ++q) {
                 const int ra0 = wr * 64 + ti * 32 + 8 * q + 4 * lh;
                 const f32x4 wa = *reinterpret_cast<const f32x4*>(roww + ra0);
-                const asg_i32x4 mo = *reinterpret_cast<const asg_i32x4*>(rowmax + ra0);
+                const i32x4 mo = *reinterpret_cast<const i32x4*>(rowmax + ra0);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     float best = -__uint_as_float(0x7F800000u);
                     if (cw0 > 0.0f) best = fmaxf(best, acc[ti][0][4 * q + j] * cw0);
                     if (cw1 > 0.0f) best = fmaxf(best, acc[ti][1][4 * q + j] * cw1);
-                    const int ob = asg_ord(best);
+                    const int ob = tile_ord(best);
                     if (wa[j] > 0.0f && ob > mo[j]) atomicMax(rowmax + ra0 + j, ob);
                 }
             }
@@ -210,10 +113,10 @@ __global__ __launch_bounds__(256) void assign_tiles_kernel(const uint16_t* __res
             for (int q = 0; q < 4; ++q) {
                 const int ra0 = wr * 64 + ti * 32 + 8 * q + 4 * lh;
                 const f32x4 wa = *reinterpret_cast<const f32x4*>(roww + ra0);
-                const asg_i32x4 mo = *reinterpret_cast<const asg_i32x4*>(rowmax + ra0);
+                const i32x4 mo = *reinterpret_cast<const i32x4*>(rowmax + ra0);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float bound = asg_unord(mo[j]) - thr * wa[j];
+                    const float bound = tile_unord(mo[j]) - thr * wa[j];
 #pragma unroll
                     for (int tj = 0; tj < 2; ++tj) {
                         const float cw = tj ? cw1 : cw0;
@@ -224,32 +127,9 @@ __global__ __launch_bounds__(256) void assign_tiles_kernel(const uint16_t* __res
                 }
             }
         }
-        const uint32_t mine = (uint32_t)__popcll(hit);
-        if (__ballot(mine != 0u) != 0ull) {
-            uint32_t incl = mine;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t v = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += v;
-            }
-            unsigned long long base = 0ull;
-            if (lane == 63) base = atomicAdd(count, (unsigned long long)incl);
-            base = ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(base >> 32), 63, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)base, 63, 64);
-            unsigned long long at = base + incl - mine;
-            while (hit) {
-                const int bit = __ffsll((long long)hit) - 1;
-                hit &= hit - 1ull;
-                const int e = bit & 15, ti = bit >> 5, tj = (bit >> 4) & 1;
-                const uint32_t a = row0 + (uint32_t)(wr * 64 + ti * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh);
-                const uint32_t b = col0 + (uint32_t)(wc * 64 + tj * 32 + l31);
-                if (at < cap) cand[at] = make_uint2(a, b);
-                ++at;
-            }
-        }
+        tile_append(hit, f, row0, col0, cap, cand, count);
         __syncthreads();   // colw and the images may be overwritten
     }
-#undef MI_ASG_FETCH
-#undef MI_ASG_STASH
 }
 
 // stage 2: n candidates (row, label) -> best[row] = min over them of (distance key << 32 | label)
@@ -477,4 +357,3 @@ __global__ __launch_bounds__(256) void km_centroid_kernel(const float* __restric
 }
 
 }  // namespace mi
-}  // namespace mi_assign

@@ -16,47 +16,44 @@
 #include "common.h"
 #include "handles.h"
 #include "assign_multi_kernels.h"
+#include "two_stage.h"
 
 using namespace mi;
-using namespace mi_assign_multi::mi;
+
+namespace mi {
+
+// a strip's slots -> labels / dist of its n_local rows, [n_local][m]; MI_KNN_NO_LABEL / +inf behind a row's last hit and for
+// every entry of a deleted row.  dist may be null.  *hits += the (row, label) entries written (an integer count).
+__global__ __launch_bounds__(256) void assign_multi_finalize_kernel(const unsigned long long* __restrict__ slot,
+                                                                    const uint64_t* __restrict__ tomb, uint32_t row_base,
+                                                                    uint32_t n_local, uint32_t m, uint32_t* __restrict__ labels,
+                                                                    float* __restrict__ dist, unsigned long long* __restrict__ hits) {
+    const uint64_t at = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    bool is_hit = false;
+    if (at < (uint64_t)n_local * m) {
+        const uint32_t r = row_base + (uint32_t)(at / m);
+        const bool dead = tomb && ((tomb[r >> 6] >> (r & 63)) & 1ull);
+        const unsigned long long key = slot[at];
+        uint32_t lab = MI_KNN_NO_LABEL;
+        float d = __uint_as_float(0x7F800000u);
+        if (!dead && key != KEY_MAX) {
+            lab = (uint32_t)key;
+            d = u32_to_dist((uint32_t)(key >> 32));
+            is_hit = true;
+        }
+        labels[at] = lab;
+        if (dist) dist[at] = d;
+    }
+    const unsigned long long b = __ballot(is_hit);
+    if ((threadIdx.x & 63) == 0 && b != 0ull) atomicAdd(hits, (unsigned long long)__popcll(b));
+}
+
+}  // namespace mi
 
 namespace {
 
 constexpr uint32_t ASSIGN_MAX_C = 65536;
 constexpr uint32_t STRIP_MAX = 2048;   // row tiles of a strip
-
-// device memory of one call, freed on every way out
-struct Scratch {
-    std::vector<void*> p;
-    void* get(size_t bytes) {
-        void* q = nullptr;
-        HIP_CHECK(hipMalloc(&q, std::max<size_t>(bytes, 16)));
-        p.push_back(q);
-        return q;
-    }
-    ~Scratch() {
-        for (void* q : p) (void)hipFree(q);
-    }
-};
-
-// the table's own mirror grows with its capacity, keeping the rows mirrored so far (as join.hip)
-void grow_keep(mi_knn* t, void** p, size_t* have, size_t want, size_t elem, size_t keep) {
-    if (*have >= want) return;
-    t->reads.sync();
-    void* np_ = nullptr;
-    HIP_CHECK(hipMalloc(&np_, want * elem));
-    if (*p && keep) HIP_CHECK(hipMemcpy(np_, *p, std::min(keep, *have) * elem, hipMemcpyDeviceToDevice));
-    if (*p) HIP_CHECK(hipFree(*p));
-    *p = np_;
-    *have = want;
-}
-
-template <int NCH>
-void launch_mirror(hipStream_t s, int n_cu, const float* rows, uint64_t from, uint64_t end, uint16_t* mirror, float* xx) {
-    const uint32_t mb = std::max<uint32_t>(1u, (uint32_t)std::min<uint64_t>((uint64_t)n_cu * 8, (end - from + 15) / 16));
-    hipLaunchKernelGGL((knn_mirror_kernel<NCH>), dim3(mb), dim3(256), 0, s, rows, from, end, mirror, xx);
-    HIP_CHECK(hipGetLastError());
-}
 
 // One call's state: the rows' mirror, the vectors, one strip's slots and results on the device.
 struct AssignMulti {
@@ -80,52 +77,36 @@ struct AssignMulti {
 
     template <int NCH>
     void rect(uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) {
-        if (bc0 >= bc1 || br0 >= br1) return;
-        static DevOnce once;
-        allow_lds_once(once, assign_multi_tiles_kernel<NCH>, AMU_LDS);
-        HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
-        hipLaunchKernelGGL((assign_multi_tiles_kernel<NCH>), dim3(br1 - br0), dim3(256), AMU_LDS, s, mirror, xx, tomb, n_rows,
-                           d_vmirror, d_vxx, C, m, br0, bc0, bc1, thr, cdist, cand_cap, d_cand, d_count);
-        HIP_CHECK(hipGetLastError());
-        unsigned long long n_cand = 0;
-        HIP_CHECK(hipMemcpyAsync(&n_cand, d_count, sizeof n_cand, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        ++stats[2];
-        stats[3] += (uint64_t)(br1 - br0) * (bc1 - bc0);
-        if (n_cand > cand_cap) {   // nothing is dropped: the same ground again in two halves, rows first, then columns
-            if (overflowed) *overflowed = true;
-            if (br1 - br0 > 1) {
-                const uint32_t mid = br0 + (br1 - br0) / 2;
-                rect<NCH>(br0, mid, bc0, bc1, nullptr);
-                rect<NCH>(mid, br1, bc0, bc1, nullptr);
-            } else if (bc1 - bc0 > 1) {   // (the row tile's slots of stage 2 live in d_slot: they join the column pieces)
-                const uint32_t mid = bc0 + (bc1 - bc0) / 2;
-                rect<NCH>(br0, br1, bc0, mid, nullptr);
-                rect<NCH>(br0, br1, mid, bc1, nullptr);
-            } else {
-                fail(MI_ERR_INVALID, "one tile reported %llu candidates (the buffer holds %u)", n_cand, cand_cap);
-            }
-            return;
-        }
-        stats[0] += n_cand;
-        if (n_cand == 0) return;
-        const uint32_t n = (uint32_t)n_cand;
-        const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)t->n_cu * 8, (n + 15) / 16));
-        hipLaunchKernelGGL((assign_multi_rescore_kernel<NCH>), dim3(blocks), dim3(256), 0, s, t->table, d_vec, d_cand, n, m, max_dist,
-                           row_base, d_slot);
-        HIP_CHECK(hipGetLastError());
+        auto stage1 = [&](uint32_t r0, uint32_t r1, uint32_t& c0, uint32_t c1) {
+            static DevOnce once;
+            allow_lds_once(once, assign_multi_tiles_kernel<NCH>, AMU_LDS);
+            HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+            hipLaunchKernelGGL((assign_multi_tiles_kernel<NCH>), dim3(r1 - r0), dim3(256), AMU_LDS, s, mirror, xx, tomb, n_rows,
+                               d_vmirror, d_vxx, C, m, r0, c0, c1, thr, cdist, cand_cap, d_cand, d_count);
+            HIP_CHECK(hipGetLastError());
+            ++stats[2];
+            stats[3] += (uint64_t)(r1 - r0) * (c1 - c0);
+            return read_count(d_count, s);
+        };
+        auto stage2 = [&](uint32_t n) {   // (the row tile's slots of stage 2 live in d_slot: they join the column pieces)
+            stats[0] += n;
+            hipLaunchKernelGGL((assign_multi_rescore_kernel<NCH>), dim3(group16_blocks(t, n)), dim3(256), 0, s, t->table, d_vec, d_cand,
+                               n, m, max_dist, row_base, d_slot);
+            HIP_CHECK(hipGetLastError());
+        };
+        rect_stages(br0, br1, bc0, bc1, cand_cap, overflowed, stage1, stage2);
     }
 
     // d_vec holds the vectors: -> labels / dist on the host, strip by strip
     template <int NCH>
     void run(uint32_t* labels, float* dist) {
-        launch_mirror<NCH>(s, t->n_cu, d_vec, 0, C, d_vmirror, d_vxx);
+        mirror_rows(t, s, d_vec, 0, C, d_vmirror, d_vxx);
         HIP_CHECK(hipMemsetAsync(d_hits, 0, sizeof(unsigned long long), s));
-        const uint32_t n_rb = (n_rows + AMU_TILE - 1) / AMU_TILE;
+        const uint32_t n_rb = (n_rows + TILE - 1) / TILE;
         for (uint32_t br = 0; br < n_rb;) {
             const uint32_t end = std::min(n_rb, br + strip);
-            row_base = br * AMU_TILE;
-            const uint32_t n_local = std::min<uint32_t>(n_rows, end * AMU_TILE) - row_base;
+            row_base = br * TILE;
+            const uint32_t n_local = std::min<uint32_t>(n_rows, end * TILE) - row_base;
             const size_t el = (size_t)n_local * m;
             HIP_CHECK(hipMemsetAsync(d_slot, 0xFF, el * sizeof(unsigned long long), s));
             bool overflowed = false;
@@ -147,13 +128,7 @@ struct AssignMulti {
     }
 
     void run(uint32_t* labels, float* dist) {
-        switch (t->dim / 64) {
-            case 2: run<2>(labels, dist); break;
-            case 4: run<4>(labels, dist); break;
-            case 8: run<8>(labels, dist); break;
-            case 12: run<12>(labels, dist); break;
-            case 16: run<16>(labels, dist); break;
-        }
+        dispatch_nch(t->dim, [&](auto nch) { run<decltype(nch)::value>(labels, dist); });
     }
 
     // t->mu held, device selected, arguments checked, the table not empty
@@ -167,40 +142,18 @@ struct AssignMulti {
         t->writes.begin(s);
         t->reads.begin(s);
         n_rows = (uint32_t)t->rows;
-        n_cb = (C + AMU_TILE - 1) / AMU_TILE;
-        // the join's bound, unchanged (join_kernels.h): both operands are rounded to bf16
-        const float eps2 = 0x1p-7f + 0x1p-16f + 4.1f * (float)(t->dim + 8) * 0x1p-24f + 2e-6f;
-        thr = 2.0f * eps2;
-        cdist = 1.0f - (max_dist + eps2);   // the join's c; -inf without a threshold
-        cand_cap = std::max<uint32_t>(AMU_CAP_MIN, t->join_cap);
-        tomb = t->dead.empty() ? nullptr : t->d_tomb;
-        // the mirror: the table's own when "prefilter" = 1 keeps one (caught up here as a search would), else one for this call
-        uint16_t* mr = nullptr;
-        float* x = nullptr;
-        uint64_t from = 0;
-        if (t->prefilter == 1) {
-            t->mirror_rows = std::min(t->mirror_rows, t->rows);
-            grow_keep(t, (void**)&t->d_mirror, &t->mirror_cap, (size_t)t->cap * t->dim, sizeof(uint16_t), (size_t)t->mirror_rows * t->dim);
-            grow_keep(t, (void**)&t->d_xx, &t->xx_cap, (size_t)t->cap, sizeof(float), (size_t)t->mirror_rows);
-            mr = t->d_mirror; x = t->d_xx; from = t->mirror_rows;
-        } else {
-            mr = (uint16_t*)scratch.get((size_t)t->rows * t->dim * sizeof(uint16_t));
-            x = (float*)scratch.get((size_t)t->rows * sizeof(float));
-        }
-        if (from < t->rows) {
-            switch (t->dim / 64) {
-#define MI_CASE(NCH) case NCH: launch_mirror<NCH>(s, t->n_cu, t->table, from, t->rows, mr, x); break;
-                MI_CASE(2) MI_CASE(4) MI_CASE(8) MI_CASE(12) MI_CASE(16)
-#undef MI_CASE
-            }
-            if (t->prefilter == 1) t->mirror_rows = t->rows;
-        }
-        mirror = mr; xx = x;
+        n_cb = (C + TILE - 1) / TILE;
+        const float e2 = eps2(t->dim);   // the join's bound, unchanged (join_kernels.h): both operands are rounded to bf16
+        thr = 2.0f * e2;
+        cdist = 1.0f - (max_dist + e2);   // the join's c; -inf without a threshold
+        cand_cap = std::max<uint32_t>(TILE_CAP_MIN, t->join_cap);
+        const TableMirror tm = table_mirror(t, s, scratch);
+        mirror = tm.mirror; xx = tm.xx; tomb = tm.tomb;
         // strips of row tiles: as many as keep an ordinary corpus (the running threshold of m slots lets a few candidates per
         // label, row and column tile through) inside the buffer
-        const uint32_t n_rb = (n_rows + AMU_TILE - 1) / AMU_TILE;
-        strip = std::max<uint32_t>(1u, std::min<uint32_t>({STRIP_MAX, n_rb, cand_cap / (AMU_TILE * 4u * m * n_cb)}));
-        const size_t strip_el = (size_t)std::min<uint64_t>((uint64_t)strip * AMU_TILE, n_rows) * m;
+        const uint32_t n_rb = (n_rows + TILE - 1) / TILE;
+        strip = std::max<uint32_t>(1u, std::min<uint32_t>({STRIP_MAX, n_rb, cand_cap / (TILE * 4u * m * n_cb)}));
+        const size_t strip_el = (size_t)std::min<uint64_t>((uint64_t)strip * TILE, n_rows) * m;
         d_vec = (float*)scratch.get((size_t)C * t->dim * sizeof(float));
         d_vmirror = (uint16_t*)scratch.get((size_t)C * t->dim * sizeof(uint16_t));
         d_vxx = (float*)scratch.get((size_t)C * sizeof(float));
@@ -213,12 +166,6 @@ struct AssignMulti {
     }
 };
 
-// whatever happens, the handle's stream is idle and its order words say so when the call leaves
-struct Settle {
-    mi_knn* t; hipStream_t s;
-    ~Settle() { (void)hipStreamSynchronize(s); t->reads.pending = false; }
-};
-
 void check_args(const mi_knn* t, const float* vectors, uint32_t C, uint32_t m, float max_dist, const uint32_t* labels) {
     if (!t) fail(MI_ERR_INVALID, "null table handle");
     if (!vectors) fail(MI_ERR_INVALID, "vectors is null");
@@ -228,8 +175,7 @@ void check_args(const mi_knn* t, const float* vectors, uint32_t C, uint32_t m, f
     if (!(max_dist >= 0.0f)) fail(MI_ERR_INVALID, "max_dist must be >= 0 (+inf: no threshold), not NaN");
     if (C > ASSIGN_MAX_C) fail(MI_ERR_UNSUPPORTED, "at most %u vectors (got %u)", ASSIGN_MAX_C, C);
     if (m > (uint32_t)AMU_MAX_M) fail(MI_ERR_UNSUPPORTED, "at most %d labels per row (got %u)", AMU_MAX_M, m);
-    if (t->dim % 128 != 0 || (t->dim / 64 != 2 && t->dim / 64 != 4 && t->dim / 64 != 8 && t->dim / 64 != 12 && t->dim / 64 != 16))
-        fail(MI_ERR_UNSUPPORTED, "dim %u: the assign's bf16 mirror is built for dim in {128, 256, 512, 768, 1024}", t->dim);
+    check_mirror_dim(t->dim, "the assign's");
 }
 
 // labels / dist of the shard's local rows, [rows][m]
@@ -272,36 +218,19 @@ int mi_knn_sharded_assign_multi(mi_knn_sharded* t, const float* vectors, uint32_
         check_args(t->shard[0], vectors, C, m, max_dist, labels);
         std::lock_guard<std::mutex> l(t->mu);
         sharded_deliver_all(t);
-        // every shard on its own stream, driven by a host thread of its own (a shard's assign reads its candidate counts
-        // back between launches); results land at the rows' global ids
-        const uint32_t n = t->n();
-        std::vector<int> codes(n, MI_OK);
-        std::vector<std::string> msgs(n);
-        std::vector<std::thread> threads;
-        for (uint32_t si = 0; si < n; ++si) {
-            threads.emplace_back([&, si] {
-                try {
-                    mi_knn* sh = t->shard[si];
-                    const uint64_t rows = sh->rows;
-                    std::vector<uint32_t> lab(rows * m);
-                    std::vector<float> dd(dist ? rows * m : 0);
-                    assign_multi_local(sh, vectors, C, m, max_dist, lab.data(), dist ? dd.data() : nullptr);
-                    const IdMap map{sh->base, sh->cyc_block, sh->cyc_n, sh->cyc_rank};
-                    for (uint64_t r = 0; r < rows; ++r) {
-                        const uint64_t id = id_of_local(map, r);
-                        std::memcpy(labels + id * m, lab.data() + r * m, m * sizeof(uint32_t));
-                        if (dist) std::memcpy(dist + id * m, dd.data() + r * m, m * sizeof(float));
-                    }
-                } catch (const Error& e) {
-                    codes[si] = e.code; msgs[si] = e.what();
-                } catch (const std::exception& e) {
-                    codes[si] = MI_ERR_INVALID; msgs[si] = e.what();
-                }
-            });
-        }
-        for (std::thread& th : threads) th.join();
-        for (uint32_t si = 0; si < n; ++si)
-            if (codes[si] != MI_OK) fail(codes[si], "shard %u: %s", si, msgs[si].c_str());
+        // every shard on its own stream; results land at the rows' global ids
+        for_each_shard(t, [&](uint32_t, mi_knn* sh) {
+            const uint64_t rows = sh->rows;
+            std::vector<uint32_t> lab(rows * m);
+            std::vector<float> dd(dist ? rows * m : 0);
+            assign_multi_local(sh, vectors, C, m, max_dist, lab.data(), dist ? dd.data() : nullptr);
+            const IdMap map{sh->base, sh->cyc_block, sh->cyc_n, sh->cyc_rank};
+            for (uint64_t r = 0; r < rows; ++r) {
+                const uint64_t id = id_of_local(map, r);
+                std::memcpy(labels + id * m, lab.data() + r * m, m * sizeof(uint32_t));
+                if (dist) std::memcpy(dist + id * m, dd.data() + r * m, m * sizeof(float));
+            }
+        });
     });
 }
 

@@ -30,40 +30,21 @@
 //     old = atomicMin(&slot[r][j], key);  key = max(old, key);  on to slot j + 1.
 // Slot 0 ends as the minimum of everything offered; what is carried on is everything else, so by induction slot j ends as
 // the (j + 1)-th smallest whatever the interleaving (a candidate is offered once: an overflowing launch is not rescored).
-// assign_multi_finalize_kernel unpacks a strip's slots, pads behind the last hit and pads the deleted rows.
+// assign_multi_finalize_kernel (assign_multi.hip, its one user: search_many.hip includes this header for the rescore kernel)
+// unpacks a strip's slots, pads behind the last hit and pads the deleted rows.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "common.h"
+#include "tile128.h"
 
-// the shared device code (RowAcc, row16_sum, knn_mirror_kernel, the keys) through a namespace of its own: see join_kernels.h
-namespace mi_assign_multi {
-#include "knn_kernels.h"
-}
-
-namespace mi_assign_multi {
 namespace mi {
 
-typedef __bf16 amu_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float amu_f32x16 __attribute__((ext_vector_type(16)));
-typedef int amu_i32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int AMU_TILE = 128;                                   // rows / vectors of a tile
-constexpr int AMU_KC = 64;                                      // elements of K per LDS image (128 bytes per row)
-constexpr int AMU_IMG = AMU_TILE * AMU_KC * 2;                  // bytes of one operand's image
-constexpr int AMU_MAX_M = 16;                                   // labels per row
-// two buffers of two operands + row weights, column 1 / w, column w, row thresholds + the rows' slots
-constexpr int AMU_SLOT_STRIDE = AMU_TILE + 4;                   // ints between a row's slots: the 16 slots start 4 banks apart
-constexpr int AMU_LDS = 4 * AMU_IMG + 4 * AMU_TILE * 4 + AMU_SLOT_STRIDE * AMU_MAX_M * 4;
-constexpr uint32_t AMU_CAP_MIN = AMU_TILE * AMU_TILE;           // a candidate buffer holds at least one full tile
-
-// the join's LDS layout (join_lds_off): 16-byte chunk `ch` of row `row`, xor-spread over the banks
-__device__ __forceinline__ uint32_t amu_lds_off(int row, int ch) { return (uint32_t)(row * 128 + ((ch ^ ((row >> 1) & 7)) << 4)); }
-// floats as integers of the same order (an involution), for ds_max_i32
-__device__ __forceinline__ int amu_ord(float f) { const int b = __float_as_int(f); return b ^ ((b >> 31) & 0x7FFFFFFF); }
-__device__ __forceinline__ float amu_unord(int o) { return __int_as_float(o ^ ((o >> 31) & 0x7FFFFFFF)); }
+constexpr int AMU_MAX_M = SLOT_MAX_M;                           // labels per row
+// the tile's images + row weights, column 1 / w, column w, row thresholds + the rows' slots
+constexpr int AMU_LDS = TILE_IMGS + 4 * TILE * 4 + SLOT_STRIDE * SLOT_MAX_M * 4;
 
 // grid.x = row tiles: workgroup x takes rows of tile br0 + x against the column tiles [bc0, bc1).  1 <= m <= AMU_MAX_M.
 // thr = 2 eps2, cdist = 1 - max_dist - eps2 (-inf = no threshold).  count: all candidates found, also those beyond cap
@@ -75,151 +56,52 @@ __global__ __launch_bounds__(256, 2) void assign_multi_tiles_kernel(const uint16
                                                                   uint32_t n_vec, uint32_t m, uint32_t br0, uint32_t bc0, uint32_t bc1,
                                                                   float thr, float cdist, uint32_t cap, uint2* __restrict__ cand,
                                                                   unsigned long long* __restrict__ count) {
-    static_assert(NCH % 2 == 0, "rows of whole 256-byte bf16 chunks (the mirror's own condition)");
-    constexpr int DIM = NCH * 64, NK = DIM / AMU_KC;
+    constexpr int DIM = NCH * 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wib = tid >> 6;
-    const int wr = wib >> 1, wc = wib & 1, l31 = lane & 31, lh = lane >> 5;
+    const int tid = threadIdx.x;
+    const TileFrag f = tile_frag();
+    const int wr = f.wr, wc = f.wc, l31 = f.l31, lh = f.lh;
     // weights: rows  > 0 = sqrt of the stored norm, -1 = marked, 0 = not there;  columns  colw > 0 = 1 / sqrt(norm), -1, 0
     // and colsq = sqrt(norm) where colw > 0
-    float* roww = reinterpret_cast<float*>(smem + 4 * AMU_IMG);
-    float* colw = roww + AMU_TILE;
-    float* colsq = colw + AMU_TILE;
-    float* rowthr = colsq + AMU_TILE;
-    int* slots = reinterpret_cast<int*>(rowthr + AMU_TILE);   // [slot][AMU_SLOT_STRIDE]: slot j of row r at j * stride + r
-    const uint32_t row0 = (br0 + blockIdx.x) * AMU_TILE;
-    const float ninf = -__uint_as_float(0x7F800000u);
+    float* roww = reinterpret_cast<float*>(smem + TILE_IMGS);
+    float* colw = roww + TILE;
+    float* colsq = colw + TILE;
+    float* rowthr = colsq + TILE;
+    int* slots = reinterpret_cast<int*>(rowthr + TILE);   // [slot][SLOT_STRIDE]: slot j of row r at j * stride + r
+    const uint32_t row0 = (br0 + blockIdx.x) * TILE;
 
-    if (tid < AMU_TILE) {
+    if (tid < TILE) {
         const uint32_t r = row0 + (uint32_t)tid;
-        float w = 0.0f;
-        if (r < n_rows) {
-            const bool dead = tomb && ((tomb[r >> 6] >> (r & 63)) & 1ull);
-            if (!dead) {
-                const float s = xx[r];
-                w = s < 0.0f ? -1.0f : sqrtf(s);
-            }
-        }
-        roww[tid] = w;
+        roww[tid] = tile_weight<false>(xx, r, r < n_rows, tomb, r, -1.0f, 0.0f);
     }
-    for (int j = tid; j < AMU_SLOT_STRIDE * (int)m; j += 256) slots[j] = amu_ord(ninf);
-
-    // global -> registers -> LDS: thread t moves chunk t & 7 of rows t >> 3, + 32, + 64, + 96 of both operands
+    for (int j = tid; j < SLOT_STRIDE * (int)m; j += 256) slots[j] = TILE_ORD_NINF;
     const uint16_t *ga[4], *gb[4];
-    uint32_t lo[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = (tid >> 3) + 32 * j, ch = tid & 7;
-        const uint32_t ra = min(row0 + (uint32_t)row, n_rows - 1);   // a ragged last tile rereads the last row
-        ga[j] = mirror + (size_t)ra * DIM + ch * 8;
-        lo[j] = amu_lds_off(row, ch);
-    }
-    u32x4 sa[4], sb[4];
-#define MI_AMU_FETCH(kc)                                                           \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                \
-        sa[j] = *reinterpret_cast<const u32x4*>(ga[j] + (kc) * AMU_KC);            \
-        sb[j] = *reinterpret_cast<const u32x4*>(gb[j] + (kc) * AMU_KC);            \
-    }
-#define MI_AMU_STASH(buf)                                                          \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                \
-        *reinterpret_cast<u32x4*>(smem + (buf) * (2 * AMU_IMG) + lo[j]) = sa[j];   \
-        *reinterpret_cast<u32x4*>(smem + (buf) * (2 * AMU_IMG) + AMU_IMG + lo[j]) = sb[j]; \
-    }
-
-    // operand lane map of the 32x32x16 form: lane (r = l & 31, h = l >> 5) holds elements k = 8 h .. 8 h + 7 of row r
-    uint32_t fa[2], fb[2];
-    const int swz_a0 = ((wr * 64 + l31) >> 1) & 7, swz_b0 = ((wc * 64 + l31) >> 1) & 7;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        fa[t] = (uint32_t)((wr * 64 + t * 32 + l31) * 128);
-        fb[t] = (uint32_t)(AMU_IMG + (wc * 64 + t * 32 + l31) * 128);
-    }
+    tile_src<DIM>(ga, mirror, row0, n_rows);
 
 #pragma unroll 1
     for (uint32_t bj = bc0; bj < bc1; ++bj) {
-        const uint32_t col0 = bj * AMU_TILE;
+        const uint32_t col0 = bj * TILE;
         // (the previous tile's readers of the column weights and of the images passed the barrier that ends this iteration)
-        if (tid < AMU_TILE) {
+        if (tid < TILE) {
             const uint32_t cidx = col0 + (uint32_t)tid;
-            float w = 0.0f, sq = 0.0f;
-            if (cidx < n_vec) {
-                const float s = vxx[cidx];
-                sq = s < 0.0f ? 0.0f : sqrtf(s);
-                w = s < 0.0f ? -1.0f : 1.0f / sq;
-            }
-            colw[tid] = w;
-            colsq[tid] = sq;
+            colw[tid] = tile_weight<true>(vxx, cidx, cidx < n_vec, nullptr, 0u, -1.0f, 0.0f);
+            colsq[tid] = tile_weight<false>(vxx, cidx, cidx < n_vec, nullptr, 0u, 0.0f, 0.0f);
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int row = (tid >> 3) + 32 * j, ch = tid & 7;
-            const uint32_t rb = min(col0 + (uint32_t)row, n_vec - 1);
-            gb[j] = vmirror + (size_t)rb * DIM + ch * 8;
-        }
-        amu_f32x16 acc[2][2];
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[ti][tj][e] = 0.0f;
-
-        MI_AMU_FETCH(0)
-        MI_AMU_STASH(0)
-        __syncthreads();
-#pragma unroll 1
-        for (int kc = 0; kc < NK; ++kc) {
-            if (kc + 1 < NK) { MI_AMU_FETCH(kc + 1) }
-            const unsigned char* img = smem + (kc & 1) * (2 * AMU_IMG);
-#pragma unroll
-            for (int s = 0; s < AMU_KC / 16; ++s) {
-                const int ch = 2 * s + lh;
-                amu_bf16x8 af[2], bf[2];
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    af[t] = *reinterpret_cast<const amu_bf16x8*>(img + fa[t] + ((ch ^ swz_a0) << 4));
-                    bf[t] = *reinterpret_cast<const amu_bf16x8*>(img + fb[t] + ((ch ^ swz_b0) << 4));
-                }
-#pragma unroll
-                for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                    for (int tj = 0; tj < 2; ++tj)
-                        acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ti], bf[tj], acc[ti][tj], 0, 0, 0);
-            }
-            if (kc + 1 < NK) { MI_AMU_STASH((kc + 1) & 1) }
-            __syncthreads();
-        }
+        tile_src<DIM>(gb, vmirror, col0, n_vec);
+        f32x16 acc[2][2];
+        tile_accumulate<NCH>(smem, f, ga, gb, acc);
 
         // C/D map: register e of lane l is row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31 of its 32 x 32 block
         const int cl0 = wc * 64 + l31, cl1 = cl0 + 32;
         const float cw0 = colw[cl0], cw1 = colw[cl1];
         // (a) the tile's columns into the slots of their residues
-        int* p0 = slots + ((col0 + (uint32_t)cl0) % m) * AMU_SLOT_STRIDE + wr * 64 + 4 * lh;
-        int* p1 = slots + ((col0 + (uint32_t)cl1) % m) * AMU_SLOT_STRIDE + wr * 64 + 4 * lh;
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int ro = ti * 32 + 8 * q;
-                const f32x4 wa = *reinterpret_cast<const f32x4*>(roww + wr * 64 + 4 * lh + ro);
-                const amu_i32x4 mo0 = *reinterpret_cast<const amu_i32x4*>(p0 + ro);
-                const amu_i32x4 mo1 = *reinterpret_cast<const amu_i32x4*>(p1 + ro);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    // (a NaN never enters a slot)
-                    const int ob0 = amu_ord(fmaxf(ninf, acc[ti][0][4 * q + j] * cw0));
-                    const int ob1 = amu_ord(fmaxf(ninf, acc[ti][1][4 * q + j] * cw1));
-                    if (wa[j] > 0.0f && cw0 > 0.0f && ob0 > mo0[j]) atomicMax(p0 + ro + j, ob0);
-                    if (wa[j] > 0.0f && cw1 > 0.0f && ob1 > mo1[j]) atomicMax(p1 + ro + j, ob1);
-                }
-            }
-        }
+        tile_slots_max(slots, roww, f, acc, col0, m, cw0, cw1);
         __syncthreads();
         // t_row (times w_a): the minimum over the row's slots
-        if (tid < AMU_TILE) {
+        if (tid < TILE) {
             int lowest = slots[tid];
-            for (uint32_t j = 1; j < m; ++j) lowest = min(lowest, slots[j * AMU_SLOT_STRIDE + tid]);
-            rowthr[tid] = amu_unord(lowest);
+            for (uint32_t j = 1; j < m; ++j) lowest = min(lowest, slots[j * SLOT_STRIDE + tid]);
+            rowthr[tid] = tile_unord(lowest);
         }
         __syncthreads();
         // (b) what the thresholds cannot exclude
@@ -246,32 +128,9 @@ __global__ __launch_bounds__(256, 2) void assign_multi_tiles_kernel(const uint16
                 }
             }
         }
-        const uint32_t mine = (uint32_t)__popcll(hit);
-        if (__ballot(mine != 0u) != 0ull) {
-            uint32_t incl = mine;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t v = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += v;
-            }
-            unsigned long long base = 0ull;
-            if (lane == 63) base = atomicAdd(count, (unsigned long long)incl);
-            base = ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(base >> 32), 63, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)base, 63, 64);
-            unsigned long long at = base + incl - mine;
-            while (hit) {
-                const int bit = __ffsll((long long)hit) - 1;
-                hit &= hit - 1ull;
-                const int e = bit & 15, ti = bit >> 5, tj = (bit >> 4) & 1;
-                const uint32_t a = row0 + (uint32_t)(wr * 64 + ti * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh);
-                const uint32_t b = col0 + (uint32_t)(wc * 64 + tj * 32 + l31);
-                if (at < cap) cand[at] = make_uint2(a, b);
-                ++at;
-            }
-        }
+        tile_append(hit, f, row0, col0, cap, cand, count);
         __syncthreads();   // the column weights and the images may be overwritten
     }
-#undef MI_AMU_FETCH
-#undef MI_AMU_STASH
 }
 
 // stage 2: n candidates (row, label) -> the m smallest keys of every row in slot[(row - row_base) * m + 0 .. m), ascending
@@ -316,31 +175,4 @@ __global__ __launch_bounds__(256) void assign_multi_rescore_kernel(const float* 
     }
 }
 
-// a strip's slots -> labels / dist of its n_local rows, [n_local][m]; MI_KNN_NO_LABEL / +inf behind a row's last hit and for
-// every entry of a deleted row.  dist may be null.  *hits += the (row, label) entries written (an integer count).
-__global__ __launch_bounds__(256) void assign_multi_finalize_kernel(const unsigned long long* __restrict__ slot,
-                                                                    const uint64_t* __restrict__ tomb, uint32_t row_base,
-                                                                    uint32_t n_local, uint32_t m, uint32_t* __restrict__ labels,
-                                                                    float* __restrict__ dist, unsigned long long* __restrict__ hits) {
-    const uint64_t at = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    bool is_hit = false;
-    if (at < (uint64_t)n_local * m) {
-        const uint32_t r = row_base + (uint32_t)(at / m);
-        const bool dead = tomb && ((tomb[r >> 6] >> (r & 63)) & 1ull);
-        const unsigned long long key = slot[at];
-        uint32_t lab = MI_KNN_NO_LABEL;
-        float d = __uint_as_float(0x7F800000u);
-        if (!dead && key != KEY_MAX) {
-            lab = (uint32_t)key;
-            d = u32_to_dist((uint32_t)(key >> 32));
-            is_hit = true;
-        }
-        labels[at] = lab;
-        if (dist) dist[at] = d;
-    }
-    const unsigned long long b = __ballot(is_hit);
-    if ((threadIdx.x & 63) == 0 && b != 0ull) atomicAdd(hits, (unsigned long long)__popcll(b));
-}
-
 }  // namespace mi
-}  // namespace mi_assign_multi

@@ -10,39 +10,13 @@
 #include "common.h"
 #include "handles.h"
 #include "join_kernels.h"
+#include "two_stage.h"
 
 using namespace mi;
-using namespace mi_join::mi;
 
 namespace {
 
 struct JoinPair { uint32_t a, b; float d; };
-
-// device memory of one call, freed on every way out
-struct Scratch {
-    std::vector<void*> p;
-    void* get(size_t bytes) {
-        void* q = nullptr;
-        HIP_CHECK(hipMalloc(&q, std::max<size_t>(bytes, 16)));
-        p.push_back(q);
-        return q;
-    }
-    ~Scratch() {
-        for (void* q : p) (void)hipFree(q);
-    }
-};
-
-// the table's own mirror grows with its capacity, keeping the rows mirrored so far (what the two-stage search does)
-void grow_keep(mi_knn* t, void** p, size_t* have, size_t want, size_t elem, size_t keep) {
-    if (*have >= want) return;
-    t->reads.sync();
-    void* np_ = nullptr;
-    HIP_CHECK(hipMalloc(&np_, want * elem));
-    if (*p && keep) HIP_CHECK(hipMemcpy(np_, *p, std::min(keep, *have) * elem, hipMemcpyDeviceToDevice));
-    if (*p) HIP_CHECK(hipFree(*p));
-    *p = np_;
-    *have = want;
-}
 
 struct Join {
     mi_knn* t;
@@ -63,64 +37,51 @@ struct Join {
     uint64_t stats[4] = {0, 0, 0, 0};
     bool over = false;
 
+    // The join's stages for rect_stages (two_stage.h).  Its tiles lie on or above the diagonal: bc0 is raised to br0, the
+    // grid is two-dimensional and the tiles counted are the triangle's; once more than user_cap pairs qualify nothing more
+    // is launched (checked between launches: the call stops there).
     template <int NCH>
     void rect(uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) {
-        if (over) return;
-        bc0 = std::max(bc0, br0);
-        if (bc0 >= bc1 || br0 >= br1) return;
-        static DevOnce once;
-        allow_lds_once(once, join_tiles_kernel<NCH>, JOIN_LDS);
-        HIP_CHECK(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), s));
-        hipLaunchKernelGGL((join_tiles_kernel<NCH>), dim3(bc1 - bc0, br1 - br0), dim3(256), JOIN_LDS, s, mirror, xx, tomb, n_rows,
-                           first_new, br0, bc0, c, cand_cap, d_cand, d_count);
-        HIP_CHECK(hipGetLastError());
-        unsigned long long n_cand = 0;
-        HIP_CHECK(hipMemcpyAsync(&n_cand, d_count, sizeof n_cand, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        ++stats[2];
-        for (uint32_t bi = br0; bi < br1; ++bi) stats[3] += bc1 - std::max(bc0, bi);
-        if (n_cand > cand_cap) {   // nothing is dropped: the same ground again in two halves, rows first, then columns
-            if (overflowed) *overflowed = true;
-            if (br1 - br0 > 1) {
-                const uint32_t mid = br0 + (br1 - br0) / 2;
-                rect<NCH>(br0, mid, bc0, bc1, nullptr);
-                rect<NCH>(mid, br1, bc0, bc1, nullptr);
-            } else if (bc1 - bc0 > 1) {
-                const uint32_t mid = bc0 + (bc1 - bc0) / 2;
-                rect<NCH>(br0, br1, bc0, mid, nullptr);
-                rect<NCH>(br0, br1, mid, bc1, nullptr);
-            } else {
-                fail(MI_ERR_INVALID, "one tile reported %llu candidates (the buffer holds %u)", n_cand, cand_cap);
-            }
-            return;
-        }
-        stats[0] += n_cand;
-        if (n_cand == 0) return;
-        const uint32_t C = (uint32_t)n_cand;
-        const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)t->n_cu * 8, (C + 15) / 16));
-        hipLaunchKernelGGL((join_rescore_kernel<NCH>), dim3(blocks), dim3(256), 0, s, t->table, d_cand, C, max_dist, d_pairs, d_dist,
-                           reinterpret_cast<uint32_t*>(d_count + 1));
-        HIP_CHECK(hipGetLastError());
-        uint32_t kept = 0;
-        HIP_CHECK(hipMemcpyAsync(&kept, d_count + 1, sizeof kept, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (kept) {
-            h_pairs.resize(kept);
-            h_dist.resize(kept);
-            HIP_CHECK(hipMemcpyAsync(h_pairs.data(), d_pairs, (size_t)kept * sizeof(uint2), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipMemcpyAsync(h_dist.data(), d_dist, (size_t)kept * sizeof(float), hipMemcpyDeviceToHost, s));
+        auto stage1 = [&](uint32_t r0, uint32_t r1, uint32_t& c0, uint32_t c1) -> unsigned long long {
+            c0 = std::max(c0, r0);
+            if (over || c0 >= c1) return 0;
+            static DevOnce once;
+            allow_lds_once(once, join_tiles_kernel<NCH>, JOIN_LDS);
+            HIP_CHECK(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), s));
+            hipLaunchKernelGGL((join_tiles_kernel<NCH>), dim3(c1 - c0, r1 - r0), dim3(256), JOIN_LDS, s, mirror, xx, tomb, n_rows,
+                               first_new, r0, c0, c, cand_cap, d_cand, d_count);
+            HIP_CHECK(hipGetLastError());
+            ++stats[2];
+            for (uint32_t bi = r0; bi < r1; ++bi) stats[3] += c1 - std::max(c0, bi);
+            return read_count(d_count, s);
+        };
+        auto stage2 = [&](uint32_t C) {
+            stats[0] += C;
+            hipLaunchKernelGGL((join_rescore_kernel<NCH>), dim3(group16_blocks(t, C)), dim3(256), 0, s, t->table, d_cand, C, max_dist,
+                               d_pairs, d_dist, reinterpret_cast<uint32_t*>(d_count + 1));
+            HIP_CHECK(hipGetLastError());
+            uint32_t kept = 0;
+            HIP_CHECK(hipMemcpyAsync(&kept, d_count + 1, sizeof kept, hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
-            const size_t at = out.size();
-            out.resize(at + kept);
-            for (uint32_t j = 0; j < kept; ++j) out[at + j] = JoinPair{h_pairs[j].x, h_pairs[j].y, h_dist[j]};
-        }
-        stats[1] += kept;
-        if (stats[1] > user_cap) over = true;   // checked between strips: the call stops here
+            if (kept) {
+                h_pairs.resize(kept);
+                h_dist.resize(kept);
+                HIP_CHECK(hipMemcpyAsync(h_pairs.data(), d_pairs, (size_t)kept * sizeof(uint2), hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipMemcpyAsync(h_dist.data(), d_dist, (size_t)kept * sizeof(float), hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipStreamSynchronize(s));
+                const size_t at = out.size();
+                out.resize(at + kept);
+                for (uint32_t j = 0; j < kept; ++j) out[at + j] = JoinPair{h_pairs[j].x, h_pairs[j].y, h_dist[j]};
+            }
+            stats[1] += kept;
+            if (stats[1] > user_cap) over = true;
+        };
+        rect_stages(br0, br1, bc0, bc1, cand_cap, overflowed, stage1, stage2);
     }
 
     template <int NCH>
     void run() {
-        const uint32_t fnb = first_new / JOIN_TILE;   // column blocks below hold no b >= first_new
+        const uint32_t fnb = first_new / TILE;   // column blocks below hold no b >= first_new
         const uint32_t n_cols = n_blocks - fnb;
         // strips of tile rows: enough tiles per launch to fill the device a few times over, few enough that an ordinary
         // corpus never meets the candidate buffer's end
@@ -159,8 +120,7 @@ void near_pairs(mi_knn* t, float max_dist, uint64_t first_new_id, uint64_t user_
     std::lock_guard<std::mutex> l(t->mu);
     for (uint64_t& v : t->join_stats) v = 0;
     const uint32_t fn = local_first_new(t, first_new_id);
-    if (t->dim % 128 != 0 || (t->dim / 64 != 2 && t->dim / 64 != 4 && t->dim / 64 != 8 && t->dim / 64 != 12 && t->dim / 64 != 16))
-        fail(MI_ERR_UNSUPPORTED, "dim %u: the join's bf16 mirror is built for dim in {128, 256, 512, 768, 1024}", t->dim);
+    check_mirror_dim(t->dim, "the join's");
     if (t->rows < 2 || fn >= t->rows) return;
     DeviceGuard g(t->device);
     hipStream_t s = knn_own_stream(t);
@@ -169,58 +129,23 @@ void near_pairs(mi_knn* t, float max_dist, uint64_t first_new_id, uint64_t user_
     t->reads.begin(s);
 
     Scratch scratch;
-    struct Settle {   // whatever happens, the handle's stream is idle and its order words say so when the call leaves
-        mi_knn* t; hipStream_t s;
-        ~Settle() { (void)hipStreamSynchronize(s); t->reads.pending = false; }
-    } settle{t, s};
+    Settle settle{t, s};
     Join j;
     j.t = t; j.s = s;
     j.n_rows = (uint32_t)t->rows; j.first_new = fn;
-    j.n_blocks = (uint32_t)((t->rows + JOIN_TILE - 1) / JOIN_TILE);
+    j.n_blocks = (uint32_t)((t->rows + TILE - 1) / TILE);
     j.max_dist = max_dist;
-    const float eps2 = 0x1p-7f + 0x1p-16f + 4.1f * (float)(t->dim + 8) * 0x1p-24f + 2e-6f;
-    j.c = 1.0f - (max_dist + eps2);
-    j.cand_cap = std::max<uint32_t>(JOIN_CAP_MIN, t->join_cap);
+    j.c = 1.0f - (max_dist + eps2(t->dim));
+    j.cand_cap = std::max<uint32_t>(TILE_CAP_MIN, t->join_cap);
     j.user_cap = user_cap;
-    j.tomb = t->dead.empty() ? nullptr : t->d_tomb;
-
-    // the mirror: the table's own when "prefilter" = 1 keeps one (caught up here as a search would), else one for this call
-    uint16_t* mirror = nullptr;
-    float* xx = nullptr;
-    uint64_t from = 0;
-    if (t->prefilter == 1) {
-        t->mirror_rows = std::min(t->mirror_rows, t->rows);
-        grow_keep(t, (void**)&t->d_mirror, &t->mirror_cap, (size_t)t->cap * t->dim, sizeof(uint16_t), (size_t)t->mirror_rows * t->dim);
-        grow_keep(t, (void**)&t->d_xx, &t->xx_cap, (size_t)t->cap, sizeof(float), (size_t)t->mirror_rows);
-        mirror = t->d_mirror; xx = t->d_xx; from = t->mirror_rows;
-    } else {
-        mirror = (uint16_t*)scratch.get((size_t)t->rows * t->dim * sizeof(uint16_t));
-        xx = (float*)scratch.get((size_t)t->rows * sizeof(float));
-    }
-    if (from < t->rows) {
-        const uint64_t todo = t->rows - from;
-        const uint32_t mb = std::max<uint32_t>(1u, (uint32_t)std::min<uint64_t>((uint64_t)t->n_cu * 8, (todo + 15) / 16));
-        switch (t->dim / 64) {
-#define MI_CASE(NCH) case NCH: hipLaunchKernelGGL((knn_mirror_kernel<NCH>), dim3(mb), dim3(256), 0, s, t->table, from, t->rows, mirror, xx); break;
-            MI_CASE(2) MI_CASE(4) MI_CASE(8) MI_CASE(12) MI_CASE(16)
-#undef MI_CASE
-        }
-        HIP_CHECK(hipGetLastError());
-        if (t->prefilter == 1) t->mirror_rows = t->rows;
-    }
-    j.mirror = mirror; j.xx = xx;
+    const TableMirror tm = table_mirror(t, s, scratch);
+    j.mirror = tm.mirror; j.xx = tm.xx; j.tomb = tm.tomb;
     j.d_cand = (uint2*)scratch.get((size_t)j.cand_cap * sizeof(uint2));
     j.d_pairs = (uint2*)scratch.get((size_t)j.cand_cap * sizeof(uint2));
     j.d_dist = (float*)scratch.get((size_t)j.cand_cap * sizeof(float));
     j.d_count = (unsigned long long*)scratch.get(2 * sizeof(unsigned long long));
 
-    switch (t->dim / 64) {
-        case 2: j.run<2>(); break;
-        case 4: j.run<4>(); break;
-        case 8: j.run<8>(); break;
-        case 12: j.run<12>(); break;
-        case 16: j.run<16>(); break;
-    }
+    dispatch_nch(t->dim, [&](auto nch) { j.template run<decltype(nch)::value>(); });
     for (int i = 0; i < 4; ++i) t->join_stats[i] = j.stats[i];
     *over = j.over;
     if (j.over) return;

@@ -34,10 +34,10 @@
 
 #include <cstdint>
 
+#include "knn_shared.h"
+
 namespace mi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __amdgpu_buffer_rsrc_t rsrc_c8;
 // (device functions, not the builtins themselves, inside a kernel's lambdas: a builtin the HOST target does not know, met while
 // the host pass instantiates the lambda, makes clang drop the kernel's host stub without a diagnostic)
@@ -49,39 +49,6 @@ __device__ __forceinline__ void c8_dma16_nt(rsrc_c8 r, uint32_t voff, void* lds_
 }
 __device__ __forceinline__ void c8_dma4(rsrc_c8 r, uint32_t voff, void* lds_wave_base) {       // 4 bytes per lane
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 4, voff, 0, 0, 0);
-}
-
-constexpr uint64_t KEY_MAX = 0xFFFFFFFFFFFFFFFFull;
-
-// ---- DPP helpers (16-lane rows) -------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __builtin_bit_cast(
-        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// After the xor-1 and xor-2 steps the four lanes of a quad agree, so the half-mirror
-// (lane -> 7-lane) delivers the other quad's sum = the xor-4 partner's; likewise the
-// row mirror (lane -> 15-lane) is the xor-8 partner once the 8-lane halves agree.
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]  : xor 1
-    v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]  : xor 2
-    v += dpp_mov<0x141>(v);  // row_half_mirror      : xor 4
-    v += dpp_mov<0x140>(v);  // row_mirror           : xor 8
-    return v;
-}
-
-// ---- keys -----------------------------------------------------------------------
-__device__ __forceinline__ uint32_t dist_to_u32(float d) {
-    uint32_t b = __float_as_uint(d);
-    if (d != d) return 0xFFFFFFFFu;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float u32_to_dist(uint32_t k) {
-    if (k == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-__device__ __forceinline__ uint64_t make_key(float d, uint32_t row) {
-    return ((uint64_t)dist_to_u32(d) << 32) | row;
 }
 
 __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
@@ -204,22 +171,7 @@ struct WaveTopLds {
     __device__ uint64_t lane_key(int j) const { return buf[j]; }
 };
 
-// ---- the scan ---------------------------------------------------------------------
-// One fp32 fmaf per (row element, accumulator); NCH = dim / 64 chunks of 256 bytes.
-template <int NCH>
-struct RowAcc {
-    float d0, d1, d2, d3, s0, s1, s2, s3;
-    __device__ __forceinline__ void zero() { d0 = d1 = d2 = d3 = s0 = s1 = s2 = s3 = 0.0f; }
-    __device__ __forceinline__ void step(const f32x4& q, const f32x4& x) {
-        d0 = __builtin_fmaf(q.x, x.x, d0); d1 = __builtin_fmaf(q.y, x.y, d1);
-        d2 = __builtin_fmaf(q.z, x.z, d2); d3 = __builtin_fmaf(q.w, x.w, d3);
-        s0 = __builtin_fmaf(x.x, x.x, s0); s1 = __builtin_fmaf(x.y, x.y, s1);
-        s2 = __builtin_fmaf(x.z, x.z, s2); s3 = __builtin_fmaf(x.w, x.w, s3);
-    }
-    __device__ __forceinline__ float dot() const { return row16_sum((d0 + d1) + (d2 + d3)); }
-    __device__ __forceinline__ float sumsq() const { return row16_sum((s0 + s1) + (s2 + s3)); }
-};
-
+// ---- the scan (RowAcc, one fp32 fmaf per (row element, accumulator): knn_shared.h) -------------------------------
 // A group of queries that share their launches (the batched two-stage search): query y = blockIdx.y of a kernel works on
 // its OWN copy of every per-query buffer, found at base + y * stride.  Strides in elements of the buffer's type; all
 // zero (and gridDim.y == 1) for a single query, which is then exactly the code that ran before the groups existed.
@@ -549,42 +501,6 @@ __global__ __launch_bounds__(1024) void knn_select_sort_kernel(const uint64_t* _
 #define PREF_DEPTH 3
 #endif
 constexpr uint32_t PREF_MARK = 0xFFFFFFFEu;  // coarse key of a marked row: no distance maps to it (NaN is 0xFFFFFFFF), it ranks behind every real one
-constexpr uint32_t PREF_CAP = 1u << 22;  // candidates stage 2 accepts (4 M rows = 12.9 GB of fp32 rows at dim 768: two fifths of a 10 M-row pass)
-
-// rows [first, end) of the table -> bf16 mirror rows + stored squared norms (-1 = "always a candidate")
-template <int NCH>
-__global__ __launch_bounds__(256) void knn_mirror_kernel(const float* __restrict__ table, uint64_t first, uint64_t end,
-                                                         uint16_t* __restrict__ mirror, float* __restrict__ xx) {
-    constexpr int DIM = NCH * 64;
-    const int lane = threadIdx.x & 63, i = lane & 15;
-    const uint64_t group = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 4, n_groups = ((uint64_t)gridDim.x * 256) >> 4;
-    for (uint64_t r0 = first + group; r0 < ((end - first + n_groups - 1) / n_groups) * n_groups + first; r0 += n_groups) {
-        const bool live = r0 < end;  // (whole 16-lane groups stay in the loop: row16_sum is a cross-lane operation)
-        const uint64_t r = live ? r0 : end - 1;
-        const f32x4* p = reinterpret_cast<const f32x4*>(table + r * DIM) + i;
-        float s = 0.0f;
-        bool bad = false;
-#pragma unroll
-        for (int t = 0; t < NCH; ++t) {
-            const f32x4 v = p[16 * t];
-            const float e[4] = {v.x, v.y, v.z, v.w};
-            uint32_t b[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                bad |= !(fabsf(e[j]) <= 3.0e38f);  // NaN, inf, and what bf16 would round to inf
-                s = __builtin_fmaf(e[j], e[j], s);
-                const uint32_t u = __float_as_uint(e[j]);
-                b[j] = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;  // round to nearest even
-            }
-            if (live) *reinterpret_cast<uint2*>(mirror + r * DIM + 64 * t + 4 * i) = make_uint2(b[0] | (b[1] << 16), b[2] | (b[3] << 16));
-        }
-        s = row16_sum(s);
-        const unsigned long long bm = __ballot(bad);
-        const bool any_bad = ((bm >> (lane & 48)) & 0xFFFFull) != 0ull;
-        if (live && i == 0) xx[r] = (any_bad || !(s >= 1.0e-30f && s <= 1.0e30f)) ? -1.0f : s;
-    }
-}
-
 // stage 1: every row's coarse distance key (PREF_MARK for the marked rows: they must not count towards the k-th) from the mirror; geometry of knn_scan_kernel with
 // rows of dim * 2 bytes: lane i of a 16-lane group loads the 16 bytes (8 bf16) at element 128 u + 8 i of its row
 template <int NCH>
@@ -1652,15 +1568,6 @@ __global__ __launch_bounds__(256) void knn_merge_block_kernel(const uint64_t* __
     }
     if (s_cnt) block_sort();
     for (uint32_t j = tid; j < k; j += 256) out[(size_t)blockIdx.x * k + j] = buf[j];
-}
-
-// Row ids of a shard.  Plain: id = base + local ordinal.  Block-cyclic (a shard of mi_knn_sharded: global row r lives in
-// block r / B, blocks are dealt round-robin to the n shards): id = base + ((local / B) * n + rank) * B + local % B —
-// monotone in the local ordinal, so "(distance asc, local asc)" inside a shard IS "(distance asc, id asc)".
-struct IdMap { uint64_t base; uint32_t block, n, rank; };
-__host__ __device__ inline uint64_t id_of_local(const IdMap& m, uint64_t local) {
-    if (m.n <= 1 || m.block == 0) return m.base + local;
-    return m.base + ((local / m.block) * m.n + m.rank) * m.block + local % m.block;
 }
 
 // keys (ascending, KEY_MAX = none) -> (id, distance); one thread per result slot.

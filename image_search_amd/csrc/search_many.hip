@@ -20,60 +20,19 @@
 #include "common.h"
 #include "handles.h"
 #include "search_many_kernels.h"
+#include "two_stage.h"
 
 namespace mi {
 void merge_lists(const uint64_t* idx_in, const float* dist_in, uint32_t lists, uint32_t k, uint64_t* idx, float* dist);   // core.hip
 }
 
 using namespace mi;
-using namespace mi_search_many::mi_assign_multi::mi;
 
 namespace {
 
 constexpr uint32_t STRIP_TILES = 512;   // query tiles of a strip (65 536 queries)
 constexpr uint32_t MAX_K = 16;
 constexpr uint32_t MAX_SEGMENTS = 65535;   // grid.y
-
-// device memory of one call, freed on every way out
-struct Scratch {
-    std::vector<void*> p;
-    void* get(size_t bytes) {
-        void* q = nullptr;
-        HIP_CHECK(hipMalloc(&q, std::max<size_t>(bytes, 16)));
-        p.push_back(q);
-        return q;
-    }
-    ~Scratch() {
-        for (void* q : p) (void)hipFree(q);
-    }
-};
-
-// the table's own mirror grows with its capacity, keeping the rows mirrored so far (as assign_multi.hip)
-void grow_keep(mi_knn* t, void** p, size_t* have, size_t want, size_t elem, size_t keep) {
-    if (*have >= want) return;
-    t->reads.sync();
-    void* np_ = nullptr;
-    HIP_CHECK(hipMalloc(&np_, want * elem));
-    if (*p && keep) HIP_CHECK(hipMemcpy(np_, *p, std::min(keep, *have) * elem, hipMemcpyDeviceToDevice));
-    if (*p) HIP_CHECK(hipFree(*p));
-    *p = np_;
-    *have = want;
-}
-
-template <int NCH>
-void launch_mirror(hipStream_t s, int n_cu, const float* rows, uint64_t from, uint64_t end, uint16_t* mirror, float* xx) {
-    const uint32_t mb = std::max<uint32_t>(1u, (uint32_t)std::min<uint64_t>((uint64_t)n_cu * 8, (end - from + 15) / 16));
-    hipLaunchKernelGGL((knn_mirror_kernel<NCH>), dim3(mb), dim3(256), 0, s, rows, from, end, mirror, xx);
-    HIP_CHECK(hipGetLastError());
-}
-
-void mirror_rows(mi_knn* t, hipStream_t s, const float* rows, uint64_t from, uint64_t end, uint16_t* mirror, float* xx) {
-    switch (t->dim / 64) {
-#define MI_CASE(NCH) case NCH: launch_mirror<NCH>(s, t->n_cu, rows, from, end, mirror, xx); break;
-        MI_CASE(2) MI_CASE(4) MI_CASE(8) MI_CASE(12) MI_CASE(16)
-#undef MI_CASE
-    }
-}
 
 // One call's state: the table's mirror (the columns), one strip's queries, slots and results on the device.
 struct SearchMany {
@@ -126,34 +85,18 @@ struct SearchMany {
     // the emit pass of query tiles [br0, br1) x column tiles [bc0, bc1), and stage 2 of what it found
     template <int NCH>
     void rect(uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) {
-        if (bc0 >= bc1 || br0 >= br1) return;
-        HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
-        tiles<NCH, true>(br0, br1, bc0, 1, bc1 - bc0);
-        unsigned long long n_cand = 0;
-        HIP_CHECK(hipMemcpyAsync(&n_cand, d_count, sizeof n_cand, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (n_cand > cand_cap) {   // nothing is dropped and nothing rescored: the same ground again in two halves
-            if (overflowed) *overflowed = true;
-            if (br1 - br0 > 1) {
-                const uint32_t mid = br0 + (br1 - br0) / 2;
-                rect<NCH>(br0, mid, bc0, bc1, nullptr);
-                rect<NCH>(mid, br1, bc0, bc1, nullptr);
-            } else if (bc1 - bc0 > 1) {   // (the queries' slots of stage 2 live in d_slot: they join the column pieces)
-                const uint32_t mid = bc0 + (bc1 - bc0) / 2;
-                rect<NCH>(br0, br1, bc0, mid, nullptr);
-                rect<NCH>(br0, br1, mid, bc1, nullptr);
-            } else {
-                fail(MI_ERR_INVALID, "one tile reported %llu candidates (the buffer holds %u)", n_cand, cand_cap);
-            }
-            return;
-        }
-        stats[0] += n_cand;
-        if (n_cand == 0) return;
-        const uint32_t n = (uint32_t)n_cand;
-        const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)t->n_cu * 8, (n + 15) / 16));
-        hipLaunchKernelGGL((assign_multi_rescore_kernel<NCH>), dim3(blocks), dim3(256), 0, s, qf, t->table, d_cand, n, m,
-                           __builtin_inff(), 0u, d_slot);
-        HIP_CHECK(hipGetLastError());
+        auto stage1 = [&](uint32_t r0, uint32_t r1, uint32_t& c0, uint32_t c1) {
+            HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+            tiles<NCH, true>(r0, r1, c0, 1, c1 - c0);
+            return read_count(d_count, s);
+        };
+        auto stage2 = [&](uint32_t n) {   // (the queries' slots of stage 2 live in d_slot: they join the column pieces)
+            stats[0] += n;
+            hipLaunchKernelGGL((assign_multi_rescore_kernel<NCH>), dim3(group16_blocks(t, n)), dim3(256), 0, s, qf, t->table, d_cand, n,
+                               m, __builtin_inff(), 0u, d_slot);
+            HIP_CHECK(hipGetLastError());
+        };
+        rect_stages(br0, br1, bc0, bc1, cand_cap, overflowed, stage1, stage2);
     }
 
     // qf / qm / qx / q_tomb / q_local0 / n_s describe the strip -> idx / dist of its n_s queries on the host
@@ -161,10 +104,10 @@ struct SearchMany {
     void strip(uint64_t* idx, float* dist) {
         const size_t el = (size_t)n_s * m;
         HIP_CHECK(hipMemsetAsync(d_slot, 0xFF, el * sizeof(unsigned long long), s));
-        HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_gslot, SMY_ORD_NINF, el, s));
-        const uint32_t n_rt = (n_s + AMU_TILE - 1) / AMU_TILE;
+        HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_gslot, TILE_ORD_NINF, el, s));
+        const uint32_t n_rt = (n_s + TILE - 1) / TILE;
         tiles<NCH, false>(0, n_rt, 0, sample, (n_cb + sample - 1) / sample);
-        uint32_t piece = std::max(1u, std::min(n_rt, cand_cap / (AMU_TILE * 16u * m)));
+        uint32_t piece = std::max(1u, std::min(n_rt, cand_cap / (TILE * 16u * m)));
         for (uint32_t br = 0; br < n_rt;) {
             const uint32_t end = std::min(n_rt, br + piece);
             const uint64_t before = stats[0];
@@ -185,13 +128,7 @@ struct SearchMany {
     }
 
     void strip(uint64_t* idx, float* dist) {
-        switch (t->dim / 64) {
-            case 2: strip<2>(idx, dist); break;
-            case 4: strip<4>(idx, dist); break;
-            case 8: strip<8>(idx, dist); break;
-            case 12: strip<12>(idx, dist); break;
-            case 16: strip<16>(idx, dist); break;
-        }
+        dispatch_nch(t->dim, [&](auto nch) { strip<decltype(nch)::value>(idx, dist); });
     }
 
     // nq queries on the host -> idx / dist [nq][k]
@@ -242,34 +179,15 @@ struct SearchMany {
         t->writes.begin(s);
         t->reads.begin(s);
         n_cols = (uint32_t)t->rows;
-        n_cb = (n_cols + AMU_TILE - 1) / AMU_TILE;
-        // the join's bound, unchanged (join_kernels.h): both operands are rounded to bf16
-        const float eps2 = 0x1p-7f + 0x1p-16f + 4.1f * (float)(t->dim + 8) * 0x1p-24f + 2e-6f;
-        thr = 2.0f * eps2;
-        cand_cap = std::max<uint32_t>(AMU_CAP_MIN, t->join_cap);
-        tomb = t->dead.empty() ? nullptr : t->d_tomb;
+        n_cb = (n_cols + TILE - 1) / TILE;
+        thr = 2.0f * eps2(t->dim);   // the join's bound, unchanged (join_kernels.h): both operands are rounded to bf16
+        cand_cap = std::max<uint32_t>(TILE_CAP_MIN, t->join_cap);
         // the threshold pass visits every sample-th column tile ("many_sample"; by default all of them: DESIGN.md 5.18)
         sample = t->many_sample > 0 ? (uint32_t)t->many_sample : 1u;
         sample = std::max(1u, std::min(sample, n_cb));
-        // the mirror: the table's own when "prefilter" = 1 keeps one (caught up here as a search would), else one for this call
-        uint16_t* mr = nullptr;
-        float* x = nullptr;
-        uint64_t from = 0;
-        if (t->prefilter == 1) {
-            t->mirror_rows = std::min(t->mirror_rows, t->rows);
-            grow_keep(t, (void**)&t->d_mirror, &t->mirror_cap, (size_t)t->cap * t->dim, sizeof(uint16_t), (size_t)t->mirror_rows * t->dim);
-            grow_keep(t, (void**)&t->d_xx, &t->xx_cap, (size_t)t->cap, sizeof(float), (size_t)t->mirror_rows);
-            mr = t->d_mirror; x = t->d_xx; from = t->mirror_rows;
-        } else {
-            mr = (uint16_t*)scratch.get((size_t)t->rows * t->dim * sizeof(uint16_t));
-            x = (float*)scratch.get((size_t)t->rows * sizeof(float));
-        }
-        if (from < t->rows) {
-            mirror_rows(t, s, t->table, from, t->rows, mr, x);
-            if (t->prefilter == 1) t->mirror_rows = t->rows;
-        }
-        mirror = mr; xx = x;
-        strip_rows = (uint32_t)std::min<uint64_t>((uint64_t)STRIP_TILES * AMU_TILE, nq);
+        const TableMirror tm = table_mirror(t, s, scratch);
+        mirror = tm.mirror; xx = tm.xx; tomb = tm.tomb;
+        strip_rows = (uint32_t)std::min<uint64_t>((uint64_t)STRIP_TILES * TILE, nq);
         const size_t strip_el = (size_t)strip_rows * m;
         d_cand = (uint2*)scratch.get((size_t)cand_cap * sizeof(uint2));
         d_count = (unsigned long long*)scratch.get(2 * sizeof(unsigned long long));
@@ -282,15 +200,8 @@ struct SearchMany {
     }
 };
 
-// whatever happens, the handle's stream is idle and its order words say so when the call leaves
-struct Settle {
-    mi_knn* t; hipStream_t s;
-    ~Settle() { (void)hipStreamSynchronize(s); t->reads.pending = false; }
-};
-
 void check_table(const mi_knn* t) {
-    if (t->dim % 128 != 0 || (t->dim / 64 != 2 && t->dim / 64 != 4 && t->dim / 64 != 8 && t->dim / 64 != 12 && t->dim / 64 != 16))
-        fail(MI_ERR_UNSUPPORTED, "dim %u: the bf16 mirror is built for dim in {128, 256, 512, 768, 1024}", t->dim);
+    check_mirror_dim(t->dim, "the");
     // (a shard never grows beyond this: the candidate record is a pair of uint32)
     if (t->rows > 0xFFFFFFFFull) fail(MI_ERR_UNSUPPORTED, "a shard holds at most 2^32-1 rows");
 }
@@ -373,29 +284,14 @@ int mi_knn_sharded_search_many(mi_knn_sharded* t, const float* q, uint32_t nq, u
         check_args(t->shard[0], q, nq, k, idx, dist);
         std::lock_guard<std::mutex> l(t->mu);
         sharded_deliver_all(t);
-        // every shard on its own stream, driven by a host thread of its own (a shard's search reads its candidate counts
-        // back between launches); the lists carry global ids
+        // every shard on its own stream; the lists carry global ids
         const uint32_t n = t->n();
         const size_t el = (size_t)nq * k;
         std::vector<uint64_t> all_idx(el * n);
         std::vector<float> all_dist(el * n);
-        std::vector<int> codes(n, MI_OK);
-        std::vector<std::string> msgs(n);
-        std::vector<std::thread> threads;
-        for (uint32_t si = 0; si < n; ++si) {
-            threads.emplace_back([&, si] {
-                try {
-                    search_many_local(t->shard[si], q, nq, k, all_idx.data() + el * si, all_dist.data() + el * si);
-                } catch (const Error& e) {
-                    codes[si] = e.code; msgs[si] = e.what();
-                } catch (const std::exception& e) {
-                    codes[si] = MI_ERR_INVALID; msgs[si] = e.what();
-                }
-            });
-        }
-        for (std::thread& th : threads) th.join();
-        for (uint32_t si = 0; si < n; ++si)
-            if (codes[si] != MI_OK) fail(codes[si], "shard %u: %s", si, msgs[si].c_str());
+        for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
+            search_many_local(sh, q, nq, k, all_idx.data() + el * si, all_dist.data() + el * si);
+        });
         // mi_knn_merge's ordering, query by query
         std::vector<uint64_t> li((size_t)n * k);
         std::vector<float> ld((size_t)n * k);

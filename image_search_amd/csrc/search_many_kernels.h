@@ -37,20 +37,12 @@
 #include <cstdint>
 
 #include "common.h"
+#include "assign_multi_kernels.h"   // stage 2: assign_multi_rescore_kernel
 
-// the shared device code (the tile constants, the rescore, knn_mirror_kernel, the keys, IdMap) through a namespace of its
-// own: see join_kernels.h
-namespace mi_search_many {
-#include "assign_multi_kernels.h"
-}
-
-namespace mi_search_many {
-namespace mi_assign_multi {
 namespace mi {
 
-constexpr int SMY_LDS_EMIT = 4 * AMU_IMG + 4 * AMU_TILE * 4;                             // images + weights + thresholds
-constexpr int SMY_LDS_THR = SMY_LDS_EMIT + AMU_SLOT_STRIDE * AMU_MAX_M * 4;              // + the rows' slots
-constexpr int SMY_ORD_NINF = (int)0x807FFFFFu;                                           // amu_ord(-inf): an empty slot
+constexpr int SMY_LDS_EMIT = TILE_IMGS + 4 * TILE * 4;                                   // images + weights + thresholds
+constexpr int SMY_LDS_THR = SMY_LDS_EMIT + SLOT_STRIDE * SLOT_MAX_M * 4;                 // + the rows' slots
 
 // grid = (row tiles, segments).  Workgroup (x, y): query rows of tile br0 + x (strip-local rows, n_q of them; row r is the
 // table's row q_local0 + r where q_tomb is given) against the column tiles bc0 + i * step, i in [y n_i / segments,
@@ -63,154 +55,54 @@ __global__ __launch_bounds__(256, 2) void search_many_tiles_kernel(const uint16_
                                                                  const uint64_t* __restrict__ tomb, uint32_t n_cols, uint32_t m,
                                                                  uint32_t br0, uint32_t bc0, uint32_t step, uint32_t n_i, float thr, int* __restrict__ gslot, uint32_t cap,
                                                                  uint2* __restrict__ cand, unsigned long long* __restrict__ count) {
-    static_assert(NCH % 2 == 0, "rows of whole 256-byte bf16 chunks (the mirror's own condition)");
-    constexpr int DIM = NCH * 64, NK = DIM / AMU_KC;
+    constexpr int DIM = NCH * 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wib = tid >> 6;
-    const int wr = wib >> 1, wc = wib & 1, l31 = lane & 31, lh = lane >> 5;
+    const int tid = threadIdx.x;
+    const TileFrag f = tile_frag();
+    const int wr = f.wr, wc = f.wc, l31 = f.l31, lh = f.lh;
     // weights: rows  > 0 = sqrt of the stored norm, -1 = marked, 0 = not there;  columns  colw > 0 = 1 / sqrt(norm), -1, 0
-    float* roww = reinterpret_cast<float*>(smem + 4 * AMU_IMG);
-    float* colw = roww + AMU_TILE;
-    float* rowthr = colw + AMU_TILE;                              // (EMIT) t_row times w_a
-    int* slots = reinterpret_cast<int*>(rowthr + 2 * AMU_TILE);   // (!EMIT) [slot][AMU_SLOT_STRIDE]
-    const uint32_t row0 = (br0 + blockIdx.x) * AMU_TILE;
-    const float ninf = -__uint_as_float(0x7F800000u);
+    float* roww = reinterpret_cast<float*>(smem + TILE_IMGS);
+    float* colw = roww + TILE;
+    float* rowthr = colw + TILE;                              // (EMIT) t_row times w_a
+    int* slots = reinterpret_cast<int*>(rowthr + 2 * TILE);   // (!EMIT) [slot][SLOT_STRIDE]
+    const uint32_t row0 = (br0 + blockIdx.x) * TILE;
     const uint32_t i0 = (uint32_t)((uint64_t)blockIdx.y * n_i / gridDim.y), i1 = (uint32_t)((uint64_t)(blockIdx.y + 1) * n_i / gridDim.y);
 
-    if (tid < AMU_TILE) {
+    if (tid < TILE) {
         const uint32_t r = row0 + (uint32_t)tid;
-        float w = 0.0f;
-        int lowest = SMY_ORD_NINF;
-        if (r < n_q) {
-            const uint32_t g = q_local0 + r;
-            const bool dead = q_tomb && ((q_tomb[g >> 6] >> (g & 63)) & 1ull);
-            if (!dead) {
-                const float s = qxx[r];
-                w = s < 0.0f ? -1.0f : sqrtf(s);
-            }
-            if (EMIT) {
+        roww[tid] = tile_weight<false>(qxx, r, r < n_q, q_tomb, q_local0 + r, -1.0f, 0.0f);
+        if (EMIT) {
+            int lowest = TILE_ORD_NINF;
+            if (r < n_q) {
                 lowest = gslot[(size_t)r * m];
                 for (uint32_t j = 1; j < m; ++j) lowest = min(lowest, gslot[(size_t)r * m + j]);
             }
+            rowthr[tid] = tile_unord(lowest);
         }
-        roww[tid] = w;
-        if (EMIT) rowthr[tid] = amu_unord(lowest);
     }
     if (!EMIT)
-        for (int j = tid; j < AMU_SLOT_STRIDE * (int)m; j += 256) slots[j] = SMY_ORD_NINF;
-
-    // global -> registers -> LDS: thread t moves chunk t & 7 of rows t >> 3, + 32, + 64, + 96 of both operands
+        for (int j = tid; j < SLOT_STRIDE * (int)m; j += 256) slots[j] = TILE_ORD_NINF;
     const uint16_t *ga[4], *gb[4];
-    uint32_t lo[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = (tid >> 3) + 32 * j, ch = tid & 7;
-        const uint32_t ra = min(row0 + (uint32_t)row, n_q - 1);   // a ragged last tile rereads the last row
-        ga[j] = qmirror + (size_t)ra * DIM + ch * 8;
-        lo[j] = amu_lds_off(row, ch);
-    }
-    u32x4 sa[4], sb[4];
-#define MI_SMY_FETCH(kc)                                                           \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                \
-        sa[j] = *reinterpret_cast<const u32x4*>(ga[j] + (kc) * AMU_KC);            \
-        sb[j] = *reinterpret_cast<const u32x4*>(gb[j] + (kc) * AMU_KC);            \
-    }
-#define MI_SMY_STASH(buf)                                                          \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                \
-        *reinterpret_cast<u32x4*>(smem + (buf) * (2 * AMU_IMG) + lo[j]) = sa[j];   \
-        *reinterpret_cast<u32x4*>(smem + (buf) * (2 * AMU_IMG) + AMU_IMG + lo[j]) = sb[j]; \
-    }
-
-    // operand lane map of the 32x32x16 form: lane (r = l & 31, h = l >> 5) holds elements k = 8 h .. 8 h + 7 of row r
-    uint32_t fa[2], fb[2];
-    const int swz_a0 = ((wr * 64 + l31) >> 1) & 7, swz_b0 = ((wc * 64 + l31) >> 1) & 7;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        fa[t] = (uint32_t)((wr * 64 + t * 32 + l31) * 128);
-        fb[t] = (uint32_t)(AMU_IMG + (wc * 64 + t * 32 + l31) * 128);
-    }
+    tile_src<DIM>(ga, qmirror, row0, n_q);
 
 #pragma unroll 1
     for (uint32_t it = i0; it < i1; ++it) {
-        const uint32_t col0 = (bc0 + it * step) * AMU_TILE;
+        const uint32_t col0 = (bc0 + it * step) * TILE;
         // (the previous tile's readers of the column weights and of the images passed the barrier that ends this iteration)
-        if (tid < AMU_TILE) {
+        if (tid < TILE) {
             const uint32_t cidx = col0 + (uint32_t)tid;
-            float w = 0.0f;
-            if (cidx < n_cols) {
-                const bool dead = tomb && ((tomb[cidx >> 6] >> (cidx & 63)) & 1ull);
-                if (!dead) {
-                    const float s = xx[cidx];
-                    w = s < 0.0f ? -1.0f : 1.0f / sqrtf(s);
-                }
-            }
-            colw[tid] = w;
+            colw[tid] = tile_weight<true>(xx, cidx, cidx < n_cols, tomb, cidx, -1.0f, 0.0f);
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int row = (tid >> 3) + 32 * j, ch = tid & 7;
-            const uint32_t rb = min(col0 + (uint32_t)row, n_cols - 1);
-            gb[j] = mirror + (size_t)rb * DIM + ch * 8;
-        }
-        amu_f32x16 acc[2][2];
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[ti][tj][e] = 0.0f;
-
-        MI_SMY_FETCH(0)
-        MI_SMY_STASH(0)
-        __syncthreads();
-#pragma unroll 1
-        for (int kc = 0; kc < NK; ++kc) {
-            if (kc + 1 < NK) { MI_SMY_FETCH(kc + 1) }
-            const unsigned char* img = smem + (kc & 1) * (2 * AMU_IMG);
-#pragma unroll
-            for (int s = 0; s < AMU_KC / 16; ++s) {
-                const int ch = 2 * s + lh;
-                amu_bf16x8 af[2], bf[2];
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    af[t] = *reinterpret_cast<const amu_bf16x8*>(img + fa[t] + ((ch ^ swz_a0) << 4));
-                    bf[t] = *reinterpret_cast<const amu_bf16x8*>(img + fb[t] + ((ch ^ swz_b0) << 4));
-                }
-#pragma unroll
-                for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                    for (int tj = 0; tj < 2; ++tj)
-                        acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ti], bf[tj], acc[ti][tj], 0, 0, 0);
-            }
-            if (kc + 1 < NK) { MI_SMY_STASH((kc + 1) & 1) }
-            __syncthreads();
-        }
+        tile_src<DIM>(gb, mirror, col0, n_cols);
+        f32x16 acc[2][2];
+        tile_accumulate<NCH>(smem, f, ga, gb, acc);
 
         // C/D map: register e of lane l is row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31 of its 32 x 32 block
         const int cl0 = wc * 64 + l31, cl1 = cl0 + 32;
         const float cw0 = colw[cl0], cw1 = colw[cl1];
         if (!EMIT) {
             // the tile's columns into the slots of their residues
-            int* p0 = slots + ((col0 + (uint32_t)cl0) % m) * AMU_SLOT_STRIDE + wr * 64 + 4 * lh;
-            int* p1 = slots + ((col0 + (uint32_t)cl1) % m) * AMU_SLOT_STRIDE + wr * 64 + 4 * lh;
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int ro = ti * 32 + 8 * q;
-                    const f32x4 wa = *reinterpret_cast<const f32x4*>(roww + wr * 64 + 4 * lh + ro);
-                    const amu_i32x4 mo0 = *reinterpret_cast<const amu_i32x4*>(p0 + ro);
-                    const amu_i32x4 mo1 = *reinterpret_cast<const amu_i32x4*>(p1 + ro);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        // (a NaN never enters a slot)
-                        const int ob0 = amu_ord(fmaxf(ninf, acc[ti][0][4 * q + j] * cw0));
-                        const int ob1 = amu_ord(fmaxf(ninf, acc[ti][1][4 * q + j] * cw1));
-                        if (wa[j] > 0.0f && cw0 > 0.0f && ob0 > mo0[j]) atomicMax(p0 + ro + j, ob0);
-                        if (wa[j] > 0.0f && cw1 > 0.0f && ob1 > mo1[j]) atomicMax(p1 + ro + j, ob1);
-                    }
-                }
-            }
+            tile_slots_max(slots, roww, f, acc, col0, m, cw0, cw1);
         } else {
             // what the thresholds cannot exclude
             unsigned long long hit = 0ull;   // bit (2 ti + tj) * 16 + e
@@ -235,40 +127,17 @@ __global__ __launch_bounds__(256, 2) void search_many_tiles_kernel(const uint16_
                     }
                 }
             }
-            const uint32_t mine = (uint32_t)__popcll(hit);
-            if (__ballot(mine != 0u) != 0ull) {
-                uint32_t incl = mine;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t v = __shfl_up(incl, d, 64);
-                    if (lane >= d) incl += v;
-                }
-                unsigned long long base = 0ull;
-                if (lane == 63) base = atomicAdd(count, (unsigned long long)incl);
-                base = ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(base >> 32), 63, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)base, 63, 64);
-                unsigned long long at = base + incl - mine;
-                while (hit) {
-                    const int bit = __ffsll((long long)hit) - 1;
-                    hit &= hit - 1ull;
-                    const int e = bit & 15, ti = bit >> 5, tj = (bit >> 4) & 1;
-                    const uint32_t a = row0 + (uint32_t)(wr * 64 + ti * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh);
-                    const uint32_t b = col0 + (uint32_t)(wc * 64 + tj * 32 + l31);
-                    if (at < cap) cand[at] = make_uint2(a, b);
-                    ++at;
-                }
-            }
+            tile_append(hit, f, row0, col0, cap, cand, count);
         }
         __syncthreads();   // the column weights and the images may be overwritten
     }
-#undef MI_SMY_FETCH
-#undef MI_SMY_STASH
     if (!EMIT) {
         // the segment's slots into the strip's (vector atomics on global memory; an empty slot changes nothing)
-        for (int j = tid; j < AMU_TILE * (int)m; j += 256) {
-            const int row = j & (AMU_TILE - 1), sl = j / AMU_TILE;
-            const int v = slots[sl * AMU_SLOT_STRIDE + row];
+        for (int j = tid; j < TILE * (int)m; j += 256) {
+            const int row = j & (TILE - 1), sl = j / TILE;
+            const int v = slots[sl * SLOT_STRIDE + row];
             const uint32_t r = row0 + (uint32_t)row;
-            if (r < n_q && v > SMY_ORD_NINF) atomicMax(gslot + (size_t)r * m + sl, v);
+            if (r < n_q && v > TILE_ORD_NINF) atomicMax(gslot + (size_t)r * m + sl, v);
         }
     }
 }
@@ -311,5 +180,3 @@ __global__ __launch_bounds__(256) void search_many_finalize_kernel(const unsigne
 }
 
 }  // namespace mi
-}  // namespace mi_assign_multi
-}  // namespace mi_search_many

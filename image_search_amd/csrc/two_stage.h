@@ -1,0 +1,173 @@
+// two_stage.h — host side shared by the calls whose first stage is the 128 x 128 bf16 tile (tile128.h) and whose second
+// stage rescoring decides in the search's arithmetic: the join, the assign, the multi-label assign and the many-query
+// search.  One call's device memory, the table's mirror for the call, the dispatch over the dims the mirror is built for,
+// the scheme that redoes a launch whose candidates overflowed the buffer, and the per-shard fan-out of the sharded calls.
+#pragma once
+#include <algorithm>
+#include <string>
+#include <thread>
+#include <type_traits>
+#include <vector>
+
+#include "common.h"
+#include "handles.h"
+#include "knn_shared.h"
+
+namespace mi {
+
+// device memory of one call, freed on every way out
+struct Scratch {
+    std::vector<void*> p;
+    void* get(size_t bytes) {
+        void* q = nullptr;
+        HIP_CHECK(hipMalloc(&q, std::max<size_t>(bytes, 16)));
+        p.push_back(q);
+        return q;
+    }
+    ~Scratch() {
+        for (void* q : p) (void)hipFree(q);
+    }
+};
+
+// whatever happens, the handle's stream is idle and its order words say so when the call leaves
+struct Settle {
+    mi_knn* t; hipStream_t s;
+    ~Settle() { (void)hipStreamSynchronize(s); t->reads.pending = false; }
+};
+
+// The bound of a first stage with BOTH operands rounded to bf16 (derived in join_kernels.h):
+// |coarse - exact| <= eps2 on the cosine of every pair the mirror does not mark.
+inline float eps2(uint32_t dim) { return 0x1p-7f + 0x1p-16f + 4.1f * (float)(dim + 8) * 0x1p-24f + 2e-6f; }
+
+// `whose`: "the join's", "the assign's", ... for the message
+inline void check_mirror_dim(uint32_t dim, const char* whose) {
+    if (dim % 128 != 0 || (dim / 64 != 2 && dim / 64 != 4 && dim / 64 != 8 && dim / 64 != 12 && dim / 64 != 16))
+        fail(MI_ERR_UNSUPPORTED, "dim %u: %s bf16 mirror is built for dim in {128, 256, 512, 768, 1024}", dim, whose);
+}
+
+// f(std::integral_constant<int, NCH>) with NCH = dim / 64; dim has passed check_mirror_dim
+template <class F>
+void dispatch_nch(uint32_t dim, F&& f) {
+    switch (dim / 64) {
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        case 12: f(std::integral_constant<int, 12>{}); break;
+        case 16: f(std::integral_constant<int, 16>{}); break;
+    }
+}
+
+// workgroups of a kernel that gives each of n items a 16-lane group and strides over them
+inline uint32_t group16_blocks(const mi_knn* t, uint64_t n) {
+    return std::max<uint32_t>(1u, (uint32_t)std::min<uint64_t>((uint64_t)t->n_cu * 8, (n + 15) / 16));
+}
+
+// rows [from, end) of `rows` -> bf16 mirror rows + stored squared norms
+inline void mirror_rows(mi_knn* t, hipStream_t s, const float* rows, uint64_t from, uint64_t end, uint16_t* mirror, float* xx) {
+    dispatch_nch(t->dim, [&](auto nch) {
+        hipLaunchKernelGGL((knn_mirror_kernel<decltype(nch)::value>), dim3(group16_blocks(t, end - from)), dim3(256), 0, s, rows, from, end,
+                           mirror, xx);
+    });
+    HIP_CHECK(hipGetLastError());
+}
+
+// the table's own mirror grows with its capacity, keeping the rows mirrored so far (what the two-stage search does)
+inline void grow_keep(mi_knn* t, void** p, size_t* have, size_t want, size_t elem, size_t keep) {
+    if (*have >= want) return;
+    t->reads.sync();
+    void* np_ = nullptr;
+    HIP_CHECK(hipMalloc(&np_, want * elem));
+    if (*p && keep) HIP_CHECK(hipMemcpy(np_, *p, std::min(keep, *have) * elem, hipMemcpyDeviceToDevice));
+    if (*p) HIP_CHECK(hipFree(*p));
+    *p = np_;
+    *have = want;
+}
+
+// The table's mirror for this call: the table's own when "prefilter" = 1 keeps one (caught up here as a search would), else
+// one built for the call in `scratch`.  tomb: the deleted rows' bits, null when there are none.  t->mu held, t not empty.
+struct TableMirror {
+    const uint16_t* mirror;
+    const float* xx;
+    const uint64_t* tomb;
+};
+inline TableMirror table_mirror(mi_knn* t, hipStream_t s, Scratch& scratch) {
+    uint16_t* m = nullptr;
+    float* x = nullptr;
+    uint64_t from = 0;
+    if (t->prefilter == 1) {
+        t->mirror_rows = std::min(t->mirror_rows, t->rows);
+        grow_keep(t, (void**)&t->d_mirror, &t->mirror_cap, (size_t)t->cap * t->dim, sizeof(uint16_t), (size_t)t->mirror_rows * t->dim);
+        grow_keep(t, (void**)&t->d_xx, &t->xx_cap, (size_t)t->cap, sizeof(float), (size_t)t->mirror_rows);
+        m = t->d_mirror; x = t->d_xx; from = t->mirror_rows;
+    } else {
+        m = (uint16_t*)scratch.get((size_t)t->rows * t->dim * sizeof(uint16_t));
+        x = (float*)scratch.get((size_t)t->rows * sizeof(float));
+    }
+    if (from < t->rows) {
+        mirror_rows(t, s, t->table, from, t->rows, m, x);
+        if (t->prefilter == 1) t->mirror_rows = t->rows;
+    }
+    return TableMirror{m, x, t->dead.empty() ? nullptr : t->d_tomb};
+}
+
+// Stage 1 and stage 2 over the tiles [br0, br1) x [bc0, bc1) with a candidate buffer of `cap`.
+//   stage1(br0, br1, bc0, bc1) launches stage 1 on the rectangle and returns the candidates it COUNTED (the buffer holds
+//       the first cap of them).  bc0 is passed by reference: the join raises it to the diagonal.
+//   stage2(n) consumes the buffer's n <= cap candidates.
+// More than cap: nothing is dropped and nothing consumed — the same ground again in two halves, rows first, then columns
+// (whatever stage 2 keeps per row must therefore join the pieces of a row).  *overflowed (nullable) is set then.
+template <class Stage1, class Stage2>
+void rect_stages(uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, uint32_t cap, bool* overflowed, Stage1& stage1, Stage2& stage2) {
+    if (bc0 >= bc1 || br0 >= br1) return;
+    const unsigned long long n_cand = stage1(br0, br1, bc0, bc1);
+    if (n_cand > cap) {
+        if (overflowed) *overflowed = true;
+        if (br1 - br0 > 1) {
+            const uint32_t mid = br0 + (br1 - br0) / 2;
+            rect_stages(br0, mid, bc0, bc1, cap, nullptr, stage1, stage2);
+            rect_stages(mid, br1, bc0, bc1, cap, nullptr, stage1, stage2);
+        } else if (bc1 - bc0 > 1) {
+            const uint32_t mid = bc0 + (bc1 - bc0) / 2;
+            rect_stages(br0, br1, bc0, mid, cap, nullptr, stage1, stage2);
+            rect_stages(br0, br1, mid, bc1, cap, nullptr, stage1, stage2);
+        } else {
+            fail(MI_ERR_INVALID, "one tile reported %llu candidates (the buffer holds %u)", n_cand, cap);
+        }
+        return;
+    }
+    if (n_cand) stage2((uint32_t)n_cand);
+}
+
+// the candidates a stage-1 launch counted into *d_count, read back (the stream is idle afterwards)
+inline unsigned long long read_count(const unsigned long long* d_count, hipStream_t s) {
+    unsigned long long n = 0;
+    HIP_CHECK(hipMemcpyAsync(&n, d_count, sizeof n, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return n;
+}
+
+// f(si, shard) for every shard, each on a host thread of its own (a shard's call reads its candidate counts back between
+// launches); the first shard that failed is reported.  t->mu held.
+template <class F>
+void for_each_shard(mi_knn_sharded* t, F&& f) {
+    const uint32_t n = t->n();
+    std::vector<int> codes(n, MI_OK);
+    std::vector<std::string> msgs(n);
+    std::vector<std::thread> threads;
+    for (uint32_t si = 0; si < n; ++si) {
+        threads.emplace_back([&, si] {
+            try {
+                f(si, t->shard[si]);
+            } catch (const Error& e) {
+                codes[si] = e.code; msgs[si] = e.what();
+            } catch (const std::exception& e) {
+                codes[si] = MI_ERR_INVALID; msgs[si] = e.what();
+            }
+        });
+    }
+    for (std::thread& th : threads) th.join();
+    for (uint32_t si = 0; si < n; ++si)
+        if (codes[si] != MI_OK) fail(codes[si], "shard %u: %s", si, msgs[si].c_str());
+}
+
+}  // namespace mi
