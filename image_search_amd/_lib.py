@@ -69,6 +69,9 @@ SYMBOLS = {
     "mi_knn_neighbors": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_kmeans": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32),
                                      c_u64p, ctypes.POINTER(ctypes.c_double)]),
+    "mi_knn_kmeans_seed": (ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, c_vp,
+                                          ctypes.POINTER(ctypes.c_double)]),
+    "mi_knn_kmeans_seed_stats": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_pairs_to_groups": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_u64p,
                                           c_u64p]),
     "mi_index_duplicates": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,

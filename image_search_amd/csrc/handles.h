@@ -212,6 +212,8 @@ struct mi_knn {
     // the threshold pass over the column tiles (option "many_sample": 0 = chosen by the table's size)
     uint64_t search_many_stats[4] = {0, 0, 0, 0};
     int many_segments = 0, many_sample = 0;
+    // mi_knn_kmeans_seed (kmeans_seed.hip): {candidates, passes run, fallback picks, 0} of the last call
+    uint64_t kmeans_seed_stats[4] = {0, 0, 0, 0};
     std::mutex mu;
 };
 

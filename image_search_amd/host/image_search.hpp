@@ -206,6 +206,19 @@ class EmbeddingTable {
                             &r.changed, &r.objective));
         return r;
     }
+    // k-means++ seeding (mi_knn_kmeans_seed): C rows drawn in proportion to their cosine distance from the nearest row drawn
+    // so far, among the live rows or the ids in `among`; centroids [C * dim] are what kmeans() takes as its start
+    struct Seeds { std::vector<uint64_t> rows; std::vector<float> centroids; double potential = 0.0; };
+    Seeds kmeans_seed(uint32_t C, uint64_t seed = 0, const std::vector<uint64_t>* among = nullptr) const {
+        Seeds r;
+        r.rows.resize(C); r.centroids.resize((size_t)C * dim_);
+        static const uint64_t none = 0;   // an empty `among` is an empty set of candidates, not "every row"
+        const uint64_t* ids = among ? (among->empty() ? &none : among->data()) : nullptr;
+        check(mi_knn_kmeans_seed(h_, C, seed, ids, among ? among->size() : 0, r.rows.data(), r.centroids.data(), &r.potential));
+        return r;
+    }
+    // {candidates, passes run, fallback picks, 0} of the last kmeans_seed
+    std::vector<uint64_t> kmeans_seed_stats() const { std::vector<uint64_t> v(4); check(mi_knn_kmeans_seed_stats(h_, v.data())); return v; }
     // "prefilter" = 2 (bytes) or 1 (bf16): the two-stage exact search, same results from a quarter / a half of the bytes
     void set_option(const std::string& key, int value) { check(mi_knn_set_option(h_, key.c_str(), value)); }
 };

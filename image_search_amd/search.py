@@ -226,11 +226,47 @@ class EmbeddingTable:
         check(lib().mi_knn_search_many_stats(self._h, out))
         return {"candidates": out[0], "hits": out[1], "launches": out[2], "tiles": out[3]}
 
-    def kmeans(self, k_or_centroids, max_iters: int = 20, seed: int = 0) -> dict:
+    def kmeans_seed(self, k: int, seed: int = 0, among=None) -> dict:
+        """k-means++ seeding on the device (mi_knn_kmeans_seed): k rows, each drawn with probability proportional to its
+        cosine distance from the nearest row drawn so far; exact and deterministic in `seed`.  among: ids (any order,
+        duplicates allowed) to draw from, None = every live row.  Returns dict(rows [k] uint64 in pick order, centroids
+        [k, dim] = those rows' values, potential = the k-means++ potential of the seeds)."""
+        k = int(k)
+        rows, cent = np.empty(max(k, 0), np.uint64), np.empty((max(k, 0), self.dim), np.float32)
+        pot = ctypes.c_double()
+        ids, n_ids = None, 0
+        if among is not None:
+            a = _ids(among)
+            n_ids = a.size
+            if a.size == 0:   # an empty set of candidates, not "every row"
+                a = np.zeros(1, np.uint64)
+            ids = a.ctypes.data
+        check(lib().mi_knn_kmeans_seed(self._h, k, int(seed), ids, n_ids, rows.ctypes.data if k else None,
+                                       cent.ctypes.data if k else None, ctypes.byref(pot)))
+        return {"rows": rows, "centroids": cent, "potential": pot.value}
+
+    def kmeans_seed_stats(self):
+        """mi_knn_kmeans_seed_stats, of the last kmeans_seed on this table"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_kmeans_seed_stats(self._h, out))
+        return {"candidates": out[0], "passes": out[1], "fallbacks": out[2]}
+
+    def kmeans(self, k_or_centroids, max_iters: int = 20, seed: int = 0, init: str = "uniform", sample: Optional[int] = None) -> dict:
         """Spherical k-means over the live rows (mi_knn_kmeans).  k_or_centroids: the initial centroids [C, dim], or an int
-        k: k distinct live rows picked with np.random.default_rng(seed).  Returns dict(centroids, labels, dist, iters,
+        k.  init = "uniform": k distinct live rows picked with np.random.default_rng(seed); init = "kmeans++": the rows
+        kmeans_seed(k, seed) picks — among all live rows, or, where there are more than `sample` of them (None =
+        max(64 k, 16 384)), among a seeded uniform subset of that size.  Returns dict(centroids, labels, dist, iters,
         changed, objective); labels / dist are exactly assign(centroids)."""
-        if isinstance(k_or_centroids, (int, np.integer)):
+        if init not in ("uniform", "kmeans++"):
+            raise ValueError(f'init = {init!r}: "uniform" or "kmeans++"')
+        if isinstance(k_or_centroids, (int, np.integer)) and init == "kmeans++":
+            k = int(k_or_centroids)
+            sample = max(64 * k, 16384) if sample is None else int(sample)
+            base = np.uint64(getattr(self, "_base_id", 0))
+            live = np.setdiff1d(np.arange(len(self), dtype=np.uint64) + base, self.deleted())
+            among = np.sort(np.random.default_rng(seed).choice(live, size=sample, replace=False)) if live.size > sample else None
+            cent = self.kmeans_seed(k, seed, among)["centroids"]
+        elif isinstance(k_or_centroids, (int, np.integer)):
             rows = initial_centroid_rows(len(self), self.deleted(), int(k_or_centroids), seed)
             cent = np.concatenate([self.rows(int(r), 1) for r in rows]) if rows.size else np.empty((0, self.dim), np.float32)
         else:
@@ -893,10 +929,11 @@ class ImageIndex:
         return {(names[c] if names is not None else c): [(self.path(int(i), web=web), float(d)) for i, d in zip(idx[c], dist[c]) if i != NO_ID]
                 for c in range(idx.shape[0])}
 
-    def clusters(self, k: int, max_iters: int = 20, seed: int = 0, web: bool = False) -> list:
+    def clusters(self, k: int, max_iters: int = 20, seed: int = 0, web: bool = False, init: str = "uniform",
+                 sample: Optional[int] = None) -> list:
         """"Group my library into k themes" (EmbeddingTable.kmeans): lists of paths, the largest cluster first; removed
-        paths never appear, empty clusters are left out."""
-        res = self.table.kmeans(int(k), max_iters=max_iters, seed=seed)
+        paths never appear, empty clusters are left out.  init / sample: the seeding, as EmbeddingTable.kmeans."""
+        res = self.table.kmeans(int(k), max_iters=max_iters, seed=seed, init=init, sample=sample)
         rows = [r for r in range(res["labels"].size) if res["labels"][r] != NO_LABEL]
         return clusters_of(res["labels"][rows], [self.path(r, web=web) for r in rows])
 

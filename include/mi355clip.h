@@ -421,6 +421,37 @@ int mi_knn_neighbors(mi_knn* t, uint64_t first, uint64_t n, uint32_t k, uint64_t
  * Rows, labels and sums stay on the device between iterations.  Arguments and errors as mi_knn_assign. */
 int mi_knn_kmeans(mi_knn* t, float* centroids, uint32_t C, uint32_t max_iters, uint32_t* labels, float* dist,
                   uint32_t* iters_run, uint64_t* changed_last, double* objective);
+/* k-means++ seeding on the device ("what mi_knn_kmeans should start from"): C rows, each drawn with probability proportional
+ * to its cosine distance from the nearest row drawn so far.  For unit vectors the squared chord distance is 2 (1 - cos), so
+ * the k-means++ weight of spherical k-means is the cosine distance itself, not its square.  Exact and deterministic: every
+ * quantity the choice depends on is an integer or a distance with the search's bits.
+ *   candidates  among == NULL: every live row, ascending by id.  Otherwise the n_among ids given, sorted and made unique,
+ *               deleted rows left out (any order and duplicates allowed, as for mi_knn_search_filtered); an id that is not a
+ *               row of the table: MI_ERR_INVALID, nothing runs.  S = their number, position p = 0 .. S-1 in that order.
+ *   usable      a candidate for which mi_knn_search(q = the row) reports a non-NaN distance for the row itself (finite,
+ *               non-zero norm).
+ *   z_0, z_1 .. the outputs of splitmix64 started at `seed`: state += 0x9E3779B97F4A7C15; z = state;
+ *               z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; output z ^ z >> 31.
+ *   pick j      over weights w_p (uint32), total = sum of w_p, exact in uint64.  total > 0: T = floor(z_j * total / 2^64) (a
+ *               64 x 64 -> high 64 multiply), the pick is the smallest p whose inclusive prefix sum exceeds T.  total == 0:
+ *               the smallest p not picked before (a "fallback pick").  z_j is consumed either way.
+ *   weights     for pick 0: w_p = 1 if p is usable, else 0.  After pick j with centre row c: d_p = the distance bits
+ *               mi_knn_search(q = row c) reports for row p; D_p = d_p if d_p is not NaN and (D_p is unset or d_p < D_p), else
+ *               unchanged; w_p = 0 if p was picked, is unusable or D_p is unset, else
+ *               w_p = (uint32) floor(min(max(D_p, 0), 2) * 2^30) (an exact power-of-two scaling in fp32, then truncation).
+ * rows: [C] = the id of pick j, in pick order.  centroids: [C, dim] or NULL = those rows' fp32 values, bit for bit (what
+ * mi_knn_kmeans takes as its initial centroids).  potential (or NULL) = sum of w_p * 2^-30 in double after one more weight
+ * update with the last pick: the k-means++ potential of the seeds.
+ * C == 0, a null `rows` or C > S: MI_ERR_INVALID.  C > 65536: MI_ERR_UNSUPPORTED.  A shard borrowed from a sharded table:
+ * MI_ERR_UNSUPPORTED, as for mi_knn_neighbors.  dim as mi_knn_near_pairs requires; the call reads the fp32 rows only: the
+ * "prefilter" mirrors are not used and the result does not depend on that option.  One fp32 pass over the candidate rows
+ * per seed, all launches enqueued without a host round trip.  Runs on the handle's stream behind every write and search
+ * enqueued before it, and waits for its results. */
+int mi_knn_kmeans_seed(mi_knn* t, uint32_t C, uint64_t seed, const uint64_t* among, uint64_t n_among, uint64_t* rows,
+                       float* centroids, double* potential);
+/* of the last mi_knn_kmeans_seed on this handle: out = {candidates S, passes over the candidates (the usable pass and one per
+ * seed: C + 1), fallback picks, 0} */
+int mi_knn_kmeans_seed_stats(mi_knn* t, uint64_t out[4]);
 /* host-only: pairs -> groups (connected components, union-find).  ids: every id that occurs in a pair, grouped; groups
  * ordered by their smallest id, ids ascending inside a group; group_start[g] .. group_start[g + 1] index ids
  * (group_start holds n_groups + 1 entries).  Two-call protocol: counts are always written, arrays up to their caps. */
