@@ -72,6 +72,9 @@ SYMBOLS = {
     "mi_knn_kmeans_seed": (ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, c_vp,
                                           ctypes.POINTER(ctypes.c_double)]),
     "mi_knn_kmeans_seed_stats": (ctypes.c_int, [c_vp, c_u64p]),
+    "mi_knn_search_diverse": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, ctypes.c_uint64,
+                                             c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32)]),
+    "mi_knn_search_diverse_stats": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_pairs_to_groups": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_u64p,
                                           c_u64p]),
     "mi_index_duplicates": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,
@@ -124,6 +127,9 @@ SYMBOLS = {
     "mi_index_search_within": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t,
                                               ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_uint32, c_vp, c_vp,
                                               ctypes.POINTER(ctypes.c_uint32)]),
+    "mi_index_search_diverse": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t,
+                                               ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
+                                               ctypes.c_float, c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32)]),
     "mi_index_save": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_index_load": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_knn_merge": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),

@@ -214,6 +214,8 @@ struct mi_knn {
     int many_segments = 0, many_sample = 0;
     // mi_knn_kmeans_seed (kmeans_seed.hip): {candidates, passes run, fallback picks, 0} of the last call
     uint64_t kmeans_seed_stats[4] = {0, 0, 0, 0};
+    // mi_knn_search_diverse (diverse.hip): {pool entries P, candidate pairs, conflicting pairs, pool entries hidden} of the last call
+    uint64_t diverse_stats[4] = {0, 0, 0, 0};
     std::mutex mu;
 };
 

@@ -96,6 +96,25 @@ uint32_t hits(const uint64_t* idx, uint32_t k) {
     return n;
 }
 
+// the ids of the live rows under `folders` (client names, whole path components): each folder is one range of the ordered
+// live paths, found by lower_bound
+std::vector<uint64_t> folder_rows(mi_index* ix, const char* const* folders, size_t n_folders) {
+    std::vector<uint64_t> ids;
+    std::lock_guard<std::mutex> l(ix->mu);
+    for (size_t i = 0; i < n_folders; ++i) {
+        if (!folders[i]) fail(MI_ERR_INVALID, "folder %zu is null", i);
+        std::string prefix;
+        if (!to_disk(ix, folders[i], &prefix)) continue;  // not under "media/": matches nothing
+        // "media/" is the media directory itself; any deeper folder matches whole components: "<dir>/"
+        if (prefix.size() > ix->media_dir.size() && prefix.back() != '/') prefix += '/';
+        for (auto it = ix->live.lower_bound(prefix); it != ix->live.end() && it->compare(0, prefix.size(), prefix) == 0; ++it) {
+            const std::vector<uint64_t>& r = ix->rows_of.at(*it);
+            ids.insert(ids.end(), r.begin(), r.end());
+        }
+    }
+    return ids;
+}
+
 void write_all(int fd, const void* p, size_t n, const char* what) {
     const char* c = static_cast<const char*>(p);
     while (n) {
@@ -247,33 +266,37 @@ int mi_index_search(mi_index* ix, const float* text_embedding, const char* const
     });
 }
 
-// ... among the rows under `folders` (client names, whole path components): each folder is one range of the ordered live
-// paths, found by lower_bound; the search is mi_knn_search_filtered over those rows
+// ... among the rows under `folders` (folder_rows); the search is mi_knn_search_filtered over those rows
 int mi_index_search_within(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
                            const char* const* folders, size_t n_folders, uint32_t k, uint64_t* idx, float* dist,
                            uint32_t* n_found) {
     return guarded([&] {
         if (!ix || !text_embedding || !idx || !dist || (n_ref && !referenced_images) || (n_folders && !folders))
             fail(MI_ERR_INVALID, "null argument");
-        std::vector<uint64_t> ids;
-        {
-            std::lock_guard<std::mutex> l(ix->mu);
-            for (size_t i = 0; i < n_folders; ++i) {
-                if (!folders[i]) fail(MI_ERR_INVALID, "folder %zu is null", i);
-                std::string prefix;
-                if (!to_disk(ix, folders[i], &prefix)) continue;  // not under "media/": matches nothing
-                // "media/" is the media directory itself; any deeper folder matches whole components: "<dir>/"
-                if (prefix.size() > ix->media_dir.size() && prefix.back() != '/') prefix += '/';
-                for (auto it = ix->live.lower_bound(prefix); it != ix->live.end() && it->compare(0, prefix.size(), prefix) == 0; ++it) {
-                    const std::vector<uint64_t>& r = ix->rows_of.at(*it);
-                    ids.insert(ids.end(), r.begin(), r.end());
-                }
-            }
-        }
+        const std::vector<uint64_t> ids = folder_rows(ix, folders, n_folders);
         const std::vector<float> query = refined_query(ix, text_embedding, referenced_images, n_ref);
         const int e = mi_knn_search_filtered(ix->table, query.data(), 1, k, ids.data(), ids.size(), idx, dist);
         if (e != MI_OK) fail(e, "%s", mi_last_error());
         if (n_found) *n_found = hits(idx, k);
+    });
+}
+
+// web_search_text with near-duplicates collapsed: the refined query of mi_index_search, the row set of mi_index_search_within
+// when folders are given (n_folders = 0: the whole table), then mi_knn_search_diverse
+int mi_index_search_diverse(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
+                            const char* const* folders, size_t n_folders, uint32_t k, uint32_t pool, float min_gap, uint64_t* idx,
+                            float* dist, uint32_t* hidden, uint32_t* n_found) {
+    return guarded([&] {
+        if (!ix || !text_embedding || !idx || !dist || (n_ref && !referenced_images) || (n_folders && !folders))
+            fail(MI_ERR_INVALID, "null argument");
+        std::vector<uint64_t> ids;
+        if (n_folders) ids = folder_rows(ix, folders, n_folders);
+        const std::vector<float> query = refined_query(ix, text_embedding, referenced_images, n_ref);
+        const uint64_t none = 0;   // folders that match nothing are an empty row set, not "the whole table"
+        const uint64_t* among = n_folders ? (ids.empty() ? &none : ids.data()) : nullptr;
+        const int e = mi_knn_search_diverse(ix->table, query.data(), k, pool, min_gap, among, ids.size(), idx, dist, hidden, nullptr,
+                                            n_found);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
     });
 }
 

@@ -7,6 +7,7 @@
 //   the `embedding <|K|> $reference` statement                  server/src/search.rs:70-86
 // Where the reference panics (assert!/unwrap) this throws std::runtime_error with the same message.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
@@ -219,6 +220,23 @@ class EmbeddingTable {
     }
     // {candidates, passes run, fallback picks, 0} of the last kmeans_seed
     std::vector<uint64_t> kmeans_seed_stats() const { std::vector<uint64_t> v(4); check(mi_knn_kmeans_seed_stats(h_, v.data())); return v; }
+    // the k best DISTINCT results (mi_knn_search_diverse): the first `pool` results of knn(query) walked in order, an entry
+    // within cosine distance min_gap of an earlier kept one hidden behind it.  idx / dist / hidden [k] (padding MI_KNN_NO_ID /
+    // +inf / 0 behind n_kept), rep [pool]: per pool rank its slot, MI_KNN_NO_LABEL when left over.  pool = 0: min(4096, max(4 k, 64))
+    struct Diverse { std::vector<uint64_t> idx; std::vector<float> dist; std::vector<uint32_t> hidden, rep; uint32_t n_kept = 0; };
+    Diverse knn_diverse(const std::vector<float>& query, uint32_t k, float min_gap, uint32_t pool = 0,
+                        const std::vector<uint64_t>* among = nullptr) const {
+        if (pool == 0) pool = std::min<uint32_t>(4096u, std::max<uint32_t>(4u * k, 64u));
+        Diverse r;
+        r.idx.resize(k); r.dist.resize(k); r.hidden.resize(k); r.rep.resize(pool);
+        static const uint64_t none = 0;   // an empty `among` is an empty pool, not "the whole table"
+        const uint64_t* ids = among ? (among->empty() ? &none : among->data()) : nullptr;
+        check(mi_knn_search_diverse(h_, query.data(), k, pool, min_gap, ids, among ? among->size() : 0, r.idx.data(), r.dist.data(),
+                                    r.hidden.data(), r.rep.data(), &r.n_kept));
+        return r;
+    }
+    // {pool entries P, candidate pairs, conflicting pairs, pool entries hidden} of the last knn_diverse
+    std::vector<uint64_t> knn_diverse_stats() const { std::vector<uint64_t> v(4); check(mi_knn_search_diverse_stats(h_, v.data())); return v; }
     // "prefilter" = 2 (bytes) or 1 (bf16): the two-stage exact search, same results from a quarter / a half of the bytes
     void set_option(const std::string& key, int value) { check(mi_knn_set_option(h_, key.c_str(), value)); }
 };
@@ -295,6 +313,25 @@ class ImageIndex {
         check(mi_index_search(h_, text_embedding.data(), p.data(), p.size(), k, idx.data(), dist.data(), &n));
         std::vector<std::pair<uint64_t, float>> out;
         for (uint32_t i = 0; i < n; ++i) out.emplace_back(idx[i], dist[i]);
+        return out;
+    }
+    // search() with near-duplicates collapsed (mi_index_search_diverse): the k best distinct images as (id, distance,
+    // look-alikes hidden behind it); folders as the client names them, none = everything; pool = 0: min(4096, max(4 k, 64))
+    struct DiverseHit { uint64_t id; float dist; uint32_t hidden; };
+    std::vector<DiverseHit> search_diverse(const std::vector<float>& text_embedding, const std::vector<std::string>& referenced_images,
+                                           uint32_t k, float min_gap, uint32_t pool = 0,
+                                           const std::vector<std::string>& folders = {}) const {
+        if (pool == 0) pool = std::min<uint32_t>(4096u, std::max<uint32_t>(4u * k, 64u));
+        std::vector<uint64_t> idx(k);
+        std::vector<float> dist(k);
+        std::vector<uint32_t> hidden(k);
+        uint32_t n = 0;
+        const auto p = ptrs(referenced_images);
+        const auto f = ptrs(folders);
+        check(mi_index_search_diverse(h_, text_embedding.data(), p.data(), p.size(), f.data(), f.size(), k, pool, min_gap, idx.data(),
+                                      dist.data(), hidden.data(), &n));
+        std::vector<DiverseHit> out;
+        for (uint32_t i = 0; i < n; ++i) out.push_back(DiverseHit{idx[i], dist[i], hidden[i]});
         return out;
     }
     // groups of near-duplicate images as paths (mi_index_duplicates), what a /duplicates handler returns; removed paths

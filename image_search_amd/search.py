@@ -226,6 +226,35 @@ class EmbeddingTable:
         check(lib().mi_knn_search_many_stats(self._h, out))
         return {"candidates": out[0], "hits": out[1], "launches": out[2], "tiles": out[3]}
 
+    def knn_diverse(self, reference: np.ndarray, k: int, min_gap: float, pool: Optional[int] = None, within=None):
+        """The k best DISTINCT results (mi_knn_search_diverse): the list knn(reference, pool, within) walked in order, an
+        entry within cosine distance min_gap (the bits near_pairs reports) of an earlier KEPT entry hidden behind it.
+        Returns (idx [k] uint64, dist [k] f32, hidden [k] uint32 = look-alikes behind each kept entry, rep [pool] uint32 =
+        per pool rank the slot it was kept in or hidden behind, NO_LABEL when left over or beyond the pool's end); NO_ID /
+        +inf / 0 behind the last kept entry.  pool = None: min(4096, max(4 * k, 64))."""
+        q = _f32(reference).reshape(-1)
+        k = int(k)
+        pool = min(4096, max(4 * k, 64)) if pool is None else int(pool)
+        idx, dist = np.empty(max(k, 0), np.uint64), np.empty(max(k, 0), np.float32)
+        hidden, rep = np.empty(max(k, 0), np.uint32), np.empty(max(pool, 0), np.uint32)
+        ids, n_ids = None, 0
+        if within is not None:
+            a = _ids(within)
+            n_ids = a.size
+            if a.size == 0:   # an empty row set, not "the whole table"
+                a = np.zeros(1, np.uint64)
+            ids = a.ctypes.data
+        check(lib().mi_knn_search_diverse(self._h, q.ctypes.data, k, pool, float(min_gap), ids, n_ids, idx.ctypes.data if k else None,
+                                          dist.ctypes.data if k else None, hidden.ctypes.data if k else None,
+                                          rep.ctypes.data if pool > 0 else None, None))
+        return idx, dist, hidden, rep
+
+    def knn_diverse_stats(self):
+        """mi_knn_search_diverse_stats, of the last knn_diverse on this table"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_search_diverse_stats(self._h, out))
+        return {"pool": out[0], "candidates": out[1], "conflicts": out[2], "hidden": out[3]}
+
     def kmeans_seed(self, k: int, seed: int = 0, among=None) -> dict:
         """k-means++ seeding on the device (mi_knn_kmeans_seed): k rows, each drawn with probability proportional to its
         cosine distance from the nearest row drawn so far; exact and deterministic in `seed`.  among: ids (any order,
@@ -862,6 +891,22 @@ class ImageIndex:
             check(lib().mi_index_search_within(self._h, q.ctypes.data, _cstrs(refs), len(refs), _cstrs(fs), len(fs), k,
                                                idx.ctypes.data, dist.ctypes.data, ctypes.byref(n)))
         return [(int(idx[i]), self.path(int(idx[i]), web=True), float(dist[i])) for i in range(n.value)]
+
+    def web_search_diverse(self, text_embedding: np.ndarray, referenced_images: Sequence[str] = (), k: int = 100,
+                           min_gap: float = 0.05, pool: Optional[int] = None, folders: Sequence[str] = (), web: bool = False):
+        """web_search_text with near-duplicates collapsed (mi_index_search_diverse): the k best distinct images, each with
+        the number of look-alikes (cosine distance <= min_gap to it) hidden behind it.  Returns [(id, image_path,
+        similarity, hidden)].  pool: how many results of the plain search are looked at, None = min(4096, max(4 * k, 64));
+        folders: as web_search_text, () = everything; web: paths as sent to the client."""
+        q = _f32(text_embedding).reshape(-1)
+        refs, fs = list(referenced_images), list(folders)
+        k = int(k)
+        pool = min(4096, max(4 * k, 64)) if pool is None else int(pool)
+        idx, dist, hidden = np.empty(max(k, 1), np.uint64), np.empty(max(k, 1), np.float32), np.empty(max(k, 1), np.uint32)
+        n = ctypes.c_uint32()
+        check(lib().mi_index_search_diverse(self._h, q.ctypes.data, _cstrs(refs), len(refs), _cstrs(fs), len(fs), k, pool,
+                                            float(min_gap), idx.ctypes.data, dist.ctypes.data, hidden.ctypes.data, ctypes.byref(n)))
+        return [(int(idx[i]), self.path(int(idx[i]), web=web), float(dist[i]), int(hidden[i])) for i in range(n.value)]
 
     def duplicates(self, max_dist: float, first_new: int = 0, web: bool = False, max_pairs: int = 1 << 20) -> list:
         """Groups of near-duplicate images (mi_index_duplicates): lists of paths whose embeddings are chained by cosine

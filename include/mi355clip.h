@@ -452,6 +452,40 @@ int mi_knn_kmeans_seed(mi_knn* t, uint32_t C, uint64_t seed, const uint64_t* amo
 /* of the last mi_knn_kmeans_seed on this handle: out = {candidates S, passes over the candidates (the usable pass and one per
  * seed: C + 1), fallback picks, 0} */
 int mi_knn_kmeans_seed_stats(mi_knn* t, uint64_t out[4]);
+/* The k best DISTINCT results of a search ("the grid without the same shot ten times"): the search's own list with
+ * near-duplicates collapsed behind the best of them, greedily, and how many look-alikes stand behind each kept result.
+ *   pool        L = the result of mi_knn_search(t, q, 1, pool) when among == NULL, else of mi_knn_search_filtered(t, q, 1,
+ *               pool, among, n_among), with the entries that are MI_KNN_NO_ID or carry a NaN distance removed.  P = |L|; ranks
+ *               r = 0 .. P-1 in the search's order (distance ascending, then id).
+ *   g(x, y)     for two distinct ids, lo = min(x, y), hi = max(x, y): the distance mi_knn_search(q = row lo) reports for row
+ *               hi, bit for bit (the contract of mi_knn_near_pairs).
+ *   conflict    x and y conflict iff g(x, y) <= min_gap.  A NaN never conflicts.
+ *   walk        ranks 0 .. P-1 in order.  For L[r] let F be the KEPT entry of smallest rank that conflicts with it.  F
+ *               exists: L[r] is hidden behind F, hidden[slot(F)] += 1, rep[r] = slot(F).  Otherwise, fewer than k entries
+ *               kept so far: L[r] is kept in the next slot, rep[r] = its slot.  Otherwise L[r] is left over, rep[r] =
+ *               MI_KNN_NO_LABEL.  Greedy, not connected components: with A ~ B, B ~ C, A not ~ C in rank order, A is kept,
+ *               B is hidden behind A and C is kept.
+ * idx [k], dist [k]: the kept entries in slot order with the ids and distance bits the search reported; MI_KNN_NO_ID / +inf
+ * behind the last kept entry.  hidden [k] (may be NULL): 0 in the padding.  rep [pool] (may be NULL): MI_KNN_NO_LABEL at
+ * positions >= P.  *n_kept (may be NULL).
+ * 1 <= k <= pool <= 4096: zero or a null t / q / idx / dist is MI_ERR_INVALID, pool > 4096 or k > pool MI_ERR_UNSUPPORTED; a
+ * pool larger than the table is fine.  min_gap NaN or < 0: MI_ERR_INVALID; min_gap = +INFINITY keeps exactly one entry.
+ * among as for mi_knn_search_filtered (any order, duplicates and deleted rows allowed, n_among may be 0: an empty pool); an id
+ * that is not a row of the table: MI_ERR_INVALID and nothing runs.  No output is written on MI_ERR_INVALID.  dim as
+ * mi_knn_near_pairs requires.  A shard borrowed from a sharded table: MI_ERR_UNSUPPORTED, as for mi_knn_neighbors.  An empty
+ * table, or P = 0: all padding, *n_kept = 0, MI_OK.
+ * The search's list stays on the device.  Its P rows are gathered into a contiguous copy (at most 12 MB at dim 768) whose
+ * bf16 mirror is built for the call (the table's own mirror is not used); the join's stage 1 finds every pair of the pool
+ * its bound cannot exclude, each is re-evaluated from the fp32 rows and the conflicts are set in a P x P bit matrix (at most
+ * 2 MB, atomic ORs: order-free); one workgroup then performs the walk.  Candidates are bounded by "join_cap" as for the
+ * join (an overflowing strip is redone in smaller pieces, nothing is dropped).  The result does not depend on the
+ * "prefilter" option, on "join_cap" or on the order candidates arrive in.  Runs on the handle's stream behind every write
+ * and search enqueued before it, and waits for its results. */
+int mi_knn_search_diverse(mi_knn* t, const float* q, uint32_t k, uint32_t pool, float min_gap, const uint64_t* among,
+                          uint64_t n_among, uint64_t* idx, float* dist, uint32_t* hidden, uint32_t* rep, uint32_t* n_kept);
+/* of the last mi_knn_search_diverse on this handle: out = {P, candidate pairs stage 1 handed to stage 2, conflicting pairs
+ * found, pool entries hidden} */
+int mi_knn_search_diverse_stats(mi_knn* t, uint64_t out[4]);
 /* host-only: pairs -> groups (connected components, union-find).  ids: every id that occurs in a pair, grouped; groups
  * ordered by their smallest id, ids ascending inside a group; group_start[g] .. group_start[g + 1] index ids
  * (group_start holds n_groups + 1 entries).  Two-call protocol: counts are always written, arrays up to their caps. */
@@ -643,6 +677,13 @@ int mi_index_search(mi_index* ix, const float* text_embedding, const char* const
 int mi_index_search_within(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
                            const char* const* folders, size_t n_folders, uint32_t k, uint64_t* idx, float* dist,
                            uint32_t* n_found);
+/* mi_index_search with near-duplicates collapsed (mi_knn_search_diverse): the query is refined as in mi_index_search;
+ * n_folders = 0: the pool comes from the whole table, otherwise from the rows mi_index_search_within would search (folders
+ * that match nothing: an empty pool).  idx / dist / hidden [k] as mi_knn_search_diverse (hidden may be NULL); *n_found (may
+ * be NULL) = kept results before the padding. */
+int mi_index_search_diverse(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
+                            const char* const* folders, size_t n_folders, uint32_t k, uint32_t pool, float min_gap,
+                            uint64_t* idx, float* dist, uint32_t* hidden, uint32_t* n_found);
 /* `<dir>/embedding.miknn` + `<dir>/image_path.bin`, each through a temporary file, fsync and rename, the path file
  * last: after a crash the directory holds a consistent index (at worst the one before the save). */
 int mi_index_save(mi_index* ix, const char* dir);
