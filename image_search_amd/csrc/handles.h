@@ -216,6 +216,10 @@ struct mi_knn {
     uint64_t kmeans_seed_stats[4] = {0, 0, 0, 0};
     // mi_knn_search_diverse (diverse.hip): {pool entries P, candidate pairs, conflicting pairs, pool entries hidden} of the last call
     uint64_t diverse_stats[4] = {0, 0, 0, 0};
+    // mi_knn_search_compound (compound.hip): {rows or list entries scanned, rows excluded by a negative term, rows with a NaN
+    // score, results written} of the last call; workgroups of its scan (option "compound_blocks": 0 = the batched search's grid)
+    uint64_t compound_stats[4] = {0, 0, 0, 0};
+    int compound_blocks = 0;
     std::mutex mu;
 };
 
@@ -295,9 +299,19 @@ void knn_truncate(mi_knn* t, uint64_t rows);        // forget the rows behind `r
 // the filtered search of nq queries (contiguous at d_q) over the ids (every one a row of t: checked by the caller), on s
 void knn_search_filtered_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, const uint64_t* ids, uint64_t n_ids,
                               uint64_t* d_idx, float* d_dist, hipStream_t s);   // t->mu held, device selected
+// for the calls that run a scan of their own through the search's selection (compound.hip); t->mu held, device selected
+void knn_reserve(mi_knn* t, void** p, size_t* have, size_t want, size_t elem);   // a workspace buffer of the handle holds `want` elements (may wait for searches in flight)
+void knn_filter_rows(mi_knn* t, const uint64_t* ids, uint64_t n_ids);            // ids -> t->h_flist / n_flist: live local rows, ascending, once each; MI_ERR_INVALID for an id that is not a row
+void knn_filter_upload(mi_knn* t, hipStream_t s);                                // ... -> t->d_flist
+void knn_reduce_lists64(mi_knn* t, uint32_t lists, uint32_t k, uint64_t* keys_out, hipStream_t s);   // the per-wave register lists in t->d_cand (lists x k keys, k <= 64) -> the k smallest, ascending
+// the k <= 4096 smallest (key, position) of the n 32-bit keys in t->d_keys32, ascending; list (nullable): positions -> list[position]
+void knn_select_keys32(mi_knn* t, uint64_t n, uint32_t k, uint64_t* keys_out, const uint32_t* list, hipStream_t s);
 // list l of query u: ids at d_idx_in + l * idx_stride + u * k, distances at d_dist_in + l * dist_stride + u * k (elements)
 void knn_merge_lists_device(const uint64_t* d_idx_in, const float* d_dist_in, uint32_t lists, uint32_t nq, uint32_t k,
                             size_t idx_stride, size_t dist_stride, uint64_t* d_idx, float* d_dist, hipStream_t s);   // caller has the device selected
+// compound.hip: mi_knn_search_compound behind its argument check (compound_host.h); takes t->mu
+void knn_search_compound(mi_knn* t, const float* pos, uint32_t n_pos, int mode, const float* neg, const float* neg_within, uint32_t n_neg,
+                         uint32_t k, const uint64_t* among, uint64_t n_among, uint64_t* idx, float* dist, float* term_dist);
 // sharded.hip
 void sharded_place(const mi_knn_sharded* t, uint64_t r, uint32_t* s, uint64_t* local);
 uint64_t sharded_rows_of(const mi_knn_sharded* t, uint64_t total, uint32_t s);  // rows shard s holds when the table holds `total`

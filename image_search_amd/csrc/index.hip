@@ -300,6 +300,23 @@ int mi_index_search_diverse(mi_index* ix, const float* text_embedding, const cha
     });
 }
 
+// mi_knn_search_compound with the row set of mi_index_search_within when folders are given (n_folders = 0: the whole table).
+// No refinement in here: a term that should be refined goes through mi_refine first.
+int mi_index_search_compound(mi_index* ix, const float* pos, uint32_t n_pos, int mode, const float* neg, const float* neg_within,
+                             uint32_t n_neg, const char* const* folders, size_t n_folders, uint32_t k, uint64_t* idx, float* dist,
+                             float* term_dist, uint32_t* n_found) {
+    return guarded([&] {
+        if (!ix || !pos || !idx || !dist || (n_folders && !folders)) fail(MI_ERR_INVALID, "null argument");
+        std::vector<uint64_t> ids;
+        if (n_folders) ids = folder_rows(ix, folders, n_folders);
+        const uint64_t none = 0;   // folders that match nothing are an empty row set, not "the whole table"
+        const uint64_t* among = n_folders ? (ids.empty() ? &none : ids.data()) : nullptr;
+        const int e = mi_knn_search_compound(ix->table, pos, n_pos, mode, neg, neg_within, n_neg, k, among, ids.size(), idx, dist, term_dist);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        if (n_found) *n_found = hits(idx, k);
+    });
+}
+
 int mi_index_save(mi_index* ix, const char* dir) {
     return guarded([&] {
         if (!ix || !dir) fail(MI_ERR_INVALID, "null argument");

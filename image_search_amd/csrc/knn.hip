@@ -811,6 +811,20 @@ void gather_lists(mi_knn* t, const float* d_q, uint32_t n, uint32_t kp, uint64_t
     reduce_wave_lists<Top>(t, lists, kp, keys_out, s, nullptr, 1, qg);
 }
 
+// the radix select over the n compact keys in t->d_keys32 with the entry's position as the low word (t->d_sel zeroed, t->d_cand
+// holds 4096 keys); list (nullable): positions back to rows afterwards
+void select_keys32(mi_knn* t, uint64_t n, uint32_t k, uint64_t* keys_out, const uint32_t* list, hipStream_t s) {
+    const uint32_t hb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)t->n_cu * 8, (n + 255) / 256));
+    uint32_t* count = t->d_sel + 6 * SEL_BINS;
+    SelState* states = reinterpret_cast<SelState*>(t->d_sel + 6 * SEL_BINS + 4);
+    for (int p = 0; p < 6; ++p)
+        hipLaunchKernelGGL(knn_select_hist_kernel, dim3(hb), dim3(256), 0, s, t->d_keys32, n, k, p, t->d_sel, states);
+    hipLaunchKernelGGL(knn_select_collect_kernel, dim3(hb), dim3(256), 0, s, t->d_keys32, n, k, t->d_sel, states, t->d_cand, count);
+    hipLaunchKernelGGL(knn_select_sort_kernel, dim3(1), dim3(1024), 0, s, t->d_cand, count, k, keys_out);
+    if (list) hipLaunchKernelGGL(knn_gather_rows_kernel, dim3((k + 255) / 256), dim3(256), 0, s, keys_out, k, list);
+    HIP_CHECK(hipGetLastError());
+}
+
 // the k <= 4096 smallest keys of the n entries, ascending, into keys_out: one distance key per entry, the radix select over
 // (key, position), then positions back to rows
 void gather_select(mi_knn* t, const float* d_q, uint32_t n, uint32_t k, uint64_t* keys_out, hipStream_t s) {
@@ -830,15 +844,7 @@ void gather_select(mi_knn* t, const float* d_q, uint32_t n, uint32_t k, uint64_t
         default: fail(MI_ERR_UNSUPPORTED, "dim %u: built for dim/64 in {1,2,4,8,12,16}", t->dim);
     }
     HIP_CHECK(hipGetLastError());
-    const uint32_t hb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)t->n_cu * 8, ((uint64_t)n + 255) / 256));
-    uint32_t* count = t->d_sel + 6 * SEL_BINS;
-    SelState* states = reinterpret_cast<SelState*>(t->d_sel + 6 * SEL_BINS + 4);
-    for (int p = 0; p < 6; ++p)
-        hipLaunchKernelGGL(knn_select_hist_kernel, dim3(hb), dim3(256), 0, s, t->d_keys32, (uint64_t)n, k, p, t->d_sel, states);
-    hipLaunchKernelGGL(knn_select_collect_kernel, dim3(hb), dim3(256), 0, s, t->d_keys32, (uint64_t)n, k, t->d_sel, states, t->d_cand, count);
-    hipLaunchKernelGGL(knn_select_sort_kernel, dim3(1), dim3(1024), 0, s, t->d_cand, count, k, keys_out);
-    hipLaunchKernelGGL(knn_gather_rows_kernel, dim3((k + 255) / 256), dim3(256), 0, s, keys_out, k, t->d_flist);
-    HIP_CHECK(hipGetLastError());
+    select_keys32(t, n, k, keys_out, t->d_flist, s);
 }
 
 // Per-wave lists or the radix select for 64 < k <= 1024: the lists pay while a wave sees many more entries than k (most of
@@ -928,6 +934,20 @@ void knn_search_filtered_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t
     filtered_many(t, d_q, nq, k, d_idx, d_dist, s);
 }
 hipStream_t knn_own_stream(mi_knn* t) { return own_stream(t); }
+void knn_reserve(mi_knn* t, void** p, size_t* have, size_t want, size_t elem) { ensure(t, p, have, want, elem); }
+void knn_filter_rows(mi_knn* t, const uint64_t* ids, uint64_t n_ids) { filter_rows(t, ids, n_ids); }
+void knn_filter_upload(mi_knn* t, hipStream_t s) { upload_filter(t, s); }
+void knn_reduce_lists64(mi_knn* t, uint32_t lists, uint32_t k, uint64_t* keys_out, hipStream_t s) {
+    QGroup qg;
+    qg.lists = (uint64_t)lists * k;
+    reduce_wave_lists<WaveTopReg>(t, lists, k, keys_out, s, nullptr, 1, qg);
+}
+void knn_select_keys32(mi_knn* t, uint64_t n, uint32_t k, uint64_t* keys_out, const uint32_t* list, hipStream_t s) {
+    ensure(t, (void**)&t->d_sel, &t->sel_cap, (size_t)SEL_WORDS, sizeof(uint32_t));
+    ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)4096, sizeof(uint64_t));
+    HIP_CHECK(hipMemsetAsync(t->d_sel, 0, (size_t)SEL_WORDS * sizeof(uint32_t), s));
+    select_keys32(t, n, k, keys_out, list, s);
+}
 void knn_search_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
     search_many(t, d_q, nq, k, d_idx, d_dist, s);
 }
@@ -1052,8 +1072,13 @@ int mi_knn_set_option(mi_knn* t, const char* key, int value) {
             // Same answers whatever the value (a sparser sample hands stage 2 more candidates).
             if (value < 0) fail(MI_ERR_INVALID, "many_sample must be >= 0 (got %d)", value);
             t->many_sample = value;
+        } else if (k == "compound_blocks") {
+            // mi_knn_search_compound: workgroups of its scan.  0 (default): the grid the batched search takes; v >= 1: exactly
+            // min(v, tiles / 4) — a small table can then make a wave walk several tiles.  Same answers whatever the value.
+            if (value < 0) fail(MI_ERR_INVALID, "compound_blocks must be >= 0 (got %d)", value);
+            t->compound_blocks = value;
         } else {
-            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, many_segments, many_sample)", key);
+            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, many_segments, many_sample, compound_blocks)", key);
         }
     });
 }

@@ -51,64 +51,7 @@ __device__ __forceinline__ void c8_dma4(rsrc_c8 r, uint32_t voff, void* lds_wave
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 4, voff, 0, 0, 0);
 }
 
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
-    uint32_t lo = __shfl((uint32_t)v, src, 64), hi = __shfl((uint32_t)(v >> 32), src, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
-    uint32_t lo = __shfl_xor((uint32_t)v, m, 64), hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint64_t umax64(uint64_t a, uint64_t b) { return a < b ? b : a; }
-
-// ---- per-wave top-k, register form (one key per lane) -----------------------------
-struct WaveTopReg {
-    static constexpr int KP = 64;
-    static constexpr int LDS_KEYS = 0;
-    uint64_t best, thr;
-    uint32_t k;
-    int lane;
-
-    __device__ void init(uint64_t*, uint32_t k_, int lane_) {
-        best = KEY_MAX; thr = KEY_MAX; k = k_; lane = lane_;
-    }
-    __device__ static uint64_t sort_asc(uint64_t v, int lane) {
-#pragma unroll
-        for (int kk = 2; kk <= 64; kk <<= 1) {
-#pragma unroll
-            for (int j = kk >> 1; j > 0; j >>= 1) {
-                const uint64_t o = shfl_xor64(v, j);
-                const bool up = (lane & kk) == 0, lower = (lane & j) == 0;
-                v = (lower == up) ? umin64(v, o) : umax64(v, o);
-            }
-        }
-        return v;
-    }
-    __device__ static uint64_t merge_bitonic(uint64_t v, int lane) {
-#pragma unroll
-        for (int j = 32; j > 0; j >>= 1) {
-            const uint64_t o = shfl_xor64(v, j);
-            v = ((lane & j) == 0) ? umin64(v, o) : umax64(v, o);
-        }
-        return v;
-    }
-    // wave-collective: every lane offers one key (KEY_MAX = nothing)
-    __device__ void offer(uint64_t key) {
-        const bool pass = key < thr;
-        if (__ballot(pass) == 0ull) return;
-        uint64_t c = sort_asc(pass ? key : KEY_MAX, lane);
-        c = shfl64(c, 63 - lane);
-        best = merge_bitonic(umin64(best, c), lane);
-        thr = shfl64(best, (int)k - 1);
-    }
-    __device__ void finish() {}
-    // store the k best keys, ascending
-    __device__ void store(uint64_t* out) const {
-        if ((uint32_t)lane < k) out[lane] = best;
-    }
-    __device__ uint64_t lane_key(int) const { return best; }
-};
+// (shfl64 / umin64 / umax64 and WaveTopReg, the register form of the per-wave top-k: knn_shared.h)
 
 // ---- per-wave top-k, LDS form (KP keys + KP pending) ------------------------------
 template <int KP_>

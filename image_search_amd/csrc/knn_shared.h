@@ -1,5 +1,6 @@
 // knn_shared.h — the search's arithmetic that other translation units build on: the vector types, the 16-lane sum and
-// RowAcc (the summation order that defines "the search's bits"), the 64-bit keys, the bf16 mirror (knn_mirror_kernel) and
+// RowAcc (the summation order that defines "the search's bits"), the 64-bit keys and the register form of the per-wave top-k
+// (WaveTopReg), the bf16 mirror (knn_mirror_kernel) and
 // the row ids of a shard.  Everything here is a template or inline, so any number of translation units may include it;
 // knn_kernels.h includes it and keeps the search's own kernels.
 #pragma once
@@ -44,6 +45,66 @@ __device__ __forceinline__ float u32_to_dist(uint32_t k) {
 __device__ __forceinline__ uint64_t make_key(float d, uint32_t row) {
     return ((uint64_t)dist_to_u32(d) << 32) | row;
 }
+// ---- 64-bit keys across lanes --------------------------------------------------------
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
+    uint32_t lo = __shfl((uint32_t)v, src, 64), hi = __shfl((uint32_t)(v >> 32), src, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
+    uint32_t lo = __shfl_xor((uint32_t)v, m, 64), hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+__device__ __forceinline__ uint64_t umax64(uint64_t a, uint64_t b) { return a < b ? b : a; }
+
+// ---- per-wave top-k, register form (one key per lane) -----------------------------
+struct WaveTopReg {
+    static constexpr int KP = 64;
+    static constexpr int LDS_KEYS = 0;
+    uint64_t best, thr;
+    uint32_t k;
+    int lane;
+
+    __device__ void init(uint64_t*, uint32_t k_, int lane_) {
+        best = KEY_MAX; thr = KEY_MAX; k = k_; lane = lane_;
+    }
+    __device__ static uint64_t sort_asc(uint64_t v, int lane) {
+#pragma unroll
+        for (int kk = 2; kk <= 64; kk <<= 1) {
+#pragma unroll
+            for (int j = kk >> 1; j > 0; j >>= 1) {
+                const uint64_t o = shfl_xor64(v, j);
+                const bool up = (lane & kk) == 0, lower = (lane & j) == 0;
+                v = (lower == up) ? umin64(v, o) : umax64(v, o);
+            }
+        }
+        return v;
+    }
+    __device__ static uint64_t merge_bitonic(uint64_t v, int lane) {
+#pragma unroll
+        for (int j = 32; j > 0; j >>= 1) {
+            const uint64_t o = shfl_xor64(v, j);
+            v = ((lane & j) == 0) ? umin64(v, o) : umax64(v, o);
+        }
+        return v;
+    }
+    // wave-collective: every lane offers one key (KEY_MAX = nothing)
+    __device__ void offer(uint64_t key) {
+        const bool pass = key < thr;
+        if (__ballot(pass) == 0ull) return;
+        uint64_t c = sort_asc(pass ? key : KEY_MAX, lane);
+        c = shfl64(c, 63 - lane);
+        best = merge_bitonic(umin64(best, c), lane);
+        thr = shfl64(best, (int)k - 1);
+    }
+    __device__ void finish() {}
+    // store the k best keys, ascending
+    __device__ void store(uint64_t* out) const {
+        if ((uint32_t)lane < k) out[lane] = best;
+    }
+    __device__ uint64_t lane_key(int) const { return best; }
+};
+
 // ---- the scan ---------------------------------------------------------------------
 // One fp32 fmaf per (row element, accumulator); NCH = dim / 64 chunks of 256 bytes.
 template <int NCH>

@@ -37,9 +37,15 @@
 #include <vector>
 
 #include "common.h"
+#include "compound_host.h"
 #include "handles.h"
+#include "two_stage.h"
 
 using namespace mi;
+
+namespace mi {
+void merge_lists(const uint64_t* idx_in, const float* dist_in, uint32_t lists, uint32_t k, uint64_t* idx, float* dist);   // core.hip
+}
 
 namespace {
 
@@ -572,6 +578,39 @@ int mi_knn_sharded_search_filtered(mi_knn_sharded* t, const float* q, uint32_t n
         if (nq == 0) return;
         sharded_search_enqueue(t, q, nq, k, idx, dist, &per);
         sharded_deliver_all(t);
+    });
+}
+
+// mi_knn_search_compound on global ids: every shard answers for the rows (the ids of `among`) it holds, on its own stream and
+// host thread; the lists carry global ids and are merged with mi_knn_merge's ordering
+int mi_knn_sharded_search_compound(mi_knn_sharded* t, const float* pos, uint32_t n_pos, int mode, const float* neg,
+                                   const float* neg_within, uint32_t n_neg, uint32_t k, const uint64_t* among, uint64_t n_among,
+                                   uint64_t* idx, float* dist) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = compound_check_args(t, pos, n_pos, mode, neg, neg_within, n_neg, k, among, n_among, idx, dist, &why);
+        if (bad != MI_OK) fail(bad, "%s (n_pos %u, n_neg %u, mode %d, k %u)", why, n_pos, n_neg, mode, k);
+        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
+        std::lock_guard<std::mutex> l(t->mu);
+        const uint32_t n = t->n();
+        std::vector<std::vector<uint64_t>> per(n);
+        for (uint64_t i = 0; i < n_among; ++i) {  // every id checked before anything runs
+            if (among[i] >= t->rows)
+                fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)among[i], (unsigned long long)t->rows);
+            uint32_t s; uint64_t local;
+            sharded_place(t, among[i], &s, &local);
+            per[s].push_back(among[i]);
+        }
+        sharded_deliver_all(t);
+        std::vector<uint64_t> all_idx((size_t)n * k);
+        std::vector<float> all_dist((size_t)n * k);
+        const uint64_t none = 0;   // a shard that holds none of the ids: an empty candidate set, not "every row"
+        for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
+            const uint64_t* ids = among ? (per[si].empty() ? &none : per[si].data()) : nullptr;
+            knn_search_compound(sh, pos, n_pos, mode, neg, neg_within, n_neg, k, ids, per[si].size(), all_idx.data() + (size_t)si * k,
+                                all_dist.data() + (size_t)si * k, nullptr);
+        });
+        merge_lists(all_idx.data(), all_dist.data(), n, k, idx, dist);
     });
 }
 

@@ -237,6 +237,28 @@ class EmbeddingTable {
     }
     // {pool entries P, candidate pairs, conflicting pairs, pool entries hidden} of the last knn_diverse
     std::vector<uint64_t> knn_diverse_stats() const { std::vector<uint64_t> v(4); check(mi_knn_search_diverse_stats(h_, v.data())); return v; }
+    // all-of / any-of / none-of terms in one exact pass (mi_knn_search_compound): terms [n_pos * dim]; mode MI_COMPOUND_ALL scores a
+    // row by its largest distance to them, MI_COMPOUND_ANY by its smallest; without [n_neg * dim] + without_within [n_neg]: a row
+    // within that cosine distance of a negative term is excluded.  idx / dist [k] by (score, id), padding MI_KNN_NO_ID / +inf;
+    // term_dist [k * (n_pos + n_neg)] when asked for: the result rows' distance to every term, positives first
+    struct Compound { std::vector<uint64_t> idx; std::vector<float> dist, term_dist; };
+    Compound knn_compound(const std::vector<float>& terms, int mode, uint32_t k, const std::vector<float>& without = {},
+                          const std::vector<float>& without_within = {}, const std::vector<uint64_t>* among = nullptr,
+                          bool want_term_dist = false) const {
+        const uint32_t n_pos = (uint32_t)(terms.size() / dim_), n_neg = (uint32_t)without_within.size();
+        if (terms.size() != (size_t)n_pos * dim_ || without.size() != (size_t)n_neg * dim_) throw std::runtime_error("terms are not whole vectors");
+        Compound r;
+        r.idx.resize(k); r.dist.resize(k);
+        if (want_term_dist) r.term_dist.resize((size_t)k * (n_pos + n_neg));
+        static const uint64_t none = 0;   // an empty `among` is an empty set of candidates, not "every row"
+        const uint64_t* ids = among ? (among->empty() ? &none : among->data()) : nullptr;
+        check(mi_knn_search_compound(h_, terms.data(), n_pos, mode, n_neg ? without.data() : nullptr, n_neg ? without_within.data() : nullptr,
+                                     n_neg, k, ids, among ? among->size() : 0, r.idx.data(), r.dist.data(),
+                                     want_term_dist ? r.term_dist.data() : nullptr));
+        return r;
+    }
+    // {rows or list entries scanned, rows excluded by a negative term, rows with a NaN score, results written} of the last knn_compound
+    std::vector<uint64_t> knn_compound_stats() const { std::vector<uint64_t> v(4); check(mi_knn_search_compound_stats(h_, v.data())); return v; }
     // "prefilter" = 2 (bytes) or 1 (bf16): the two-stage exact search, same results from a quarter / a half of the bytes
     void set_option(const std::string& key, int value) { check(mi_knn_set_option(h_, key.c_str(), value)); }
 };
@@ -332,6 +354,26 @@ class ImageIndex {
                                       dist.data(), hidden.data(), &n));
         std::vector<DiverseHit> out;
         for (uint32_t i = 0; i < n; ++i) out.push_back(DiverseHit{idx[i], dist[i], hidden[i]});
+        return out;
+    }
+    // and / or / not over embeddings (mi_index_search_compound): EmbeddingTable::knn_compound over the images under `folders`
+    // (none = everything) as (id, score); removed paths never appear.  No refinement in here: refine a term first if wanted.
+    // terms holds n_pos vectors, without one vector per entry of without_within
+    std::vector<std::pair<uint64_t, float>> search_compound(const std::vector<float>& terms, uint32_t n_pos, int mode, uint32_t k,
+                                                            const std::vector<float>& without = {}, const std::vector<float>& without_within = {},
+                                                            const std::vector<std::string>& folders = {}, std::vector<float>* term_dist = nullptr) const {
+        const uint32_t n_neg = (uint32_t)without_within.size();
+        if (n_pos == 0 || terms.size() % n_pos != 0 || without.size() != (size_t)n_neg * (terms.size() / n_pos))
+            throw std::runtime_error("terms are not whole vectors");
+        std::vector<uint64_t> idx(k);
+        std::vector<float> dist(k);
+        if (term_dist) term_dist->assign((size_t)k * (n_pos + n_neg), 0.0f);
+        uint32_t n = 0;
+        const auto f = ptrs(folders);
+        check(mi_index_search_compound(h_, terms.data(), n_pos, mode, n_neg ? without.data() : nullptr, n_neg ? without_within.data() : nullptr,
+                                       n_neg, f.data(), f.size(), k, idx.data(), dist.data(), term_dist ? term_dist->data() : nullptr, &n));
+        std::vector<std::pair<uint64_t, float>> out;
+        for (uint32_t i = 0; i < n; ++i) out.emplace_back(idx[i], dist[i]);
         return out;
     }
     // groups of near-duplicate images as paths (mi_index_duplicates), what a /duplicates handler returns; removed paths

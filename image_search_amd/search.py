@@ -27,6 +27,38 @@ def _f32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+COMPOUND_MODES = {"all": 0, "any": 1}   # MI_COMPOUND_ALL / MI_COMPOUND_ANY
+
+
+def _compound_args(dim: int, terms, mode, without, without_within):
+    """(pos [n_pos, dim], mode code, neg or None, thresholds or None, n_neg) as mi_knn_search_compound takes them"""
+    if mode not in COMPOUND_MODES:
+        raise ValueError(f"mode must be 'all' or 'any' (got {mode!r})")
+    pos = _f32(terms).reshape(-1, dim)
+    if without is None:
+        if without_within is not None:
+            raise ValueError("without_within given without `without`")
+        return pos, COMPOUND_MODES[mode], None, None, 0
+    neg = _f32(without).reshape(-1, dim)
+    if without_within is None:
+        raise ValueError("`without` needs without_within: one cosine distance per negative term (or one for all)")
+    w = _f32(without_within).reshape(-1)
+    if w.size == 1 and neg.shape[0] != 1:
+        w = np.repeat(w, neg.shape[0])
+    if w.size != neg.shape[0]:
+        raise ValueError(f"{w.size} thresholds for {neg.shape[0]} negative terms")
+    return pos, COMPOUND_MODES[mode], neg, _f32(w), neg.shape[0]
+
+
+def _among(within):
+    """(pointer or None, count, the array to keep alive) of an id list; an empty list is an empty row set, not every row"""
+    if within is None:
+        return None, 0, None
+    a = _ids(within)
+    keep = a if a.size else np.zeros(1, np.uint64)
+    return keep.ctypes.data, a.size, keep
+
+
 def _ptrs(vecs):
     arr = (c_f * len(vecs))()
     for i, v in enumerate(vecs):
@@ -254,6 +286,31 @@ class EmbeddingTable:
         out = (ctypes.c_uint64 * 4)()
         check(lib().mi_knn_search_diverse_stats(self._h, out))
         return {"pool": out[0], "candidates": out[1], "conflicts": out[2], "hidden": out[3]}
+
+    def knn_compound(self, terms: np.ndarray, mode: str = "all", without=None, without_within=None, k: int = 10, within=None,
+                     term_dist: bool = False):
+        """All-of / any-of / none-of terms in one exact pass (mi_knn_search_compound).  terms [n_pos, dim]: mode "all" scores a
+        row by its LARGEST distance to them (near every term), "any" by its smallest (near at least one); without [n_neg, dim]
+        with without_within (one cosine distance per negative term, or one for all): a row within that distance of a negative
+        term is excluded.  Every per-term distance has the bits knn(term) reports.  within: ids, as for knn().  Returns
+        (idx [k] uint64, score [k] f32) ascending by (score, id), NO_ID / +inf behind the last hit; term_dist=True adds
+        [k, n_pos + n_neg] f32: the result rows' distances to every term, positives first.  n_pos + n_neg <= 8, k <= 4096."""
+        pos, code, neg, w, n_neg = _compound_args(self.dim, terms, mode, without, without_within)
+        k = int(k)
+        T = pos.shape[0] + n_neg
+        idx, dist = np.empty(max(k, 1), np.uint64), np.empty(max(k, 1), np.float32)
+        td = np.empty((max(k, 1), max(T, 1)), np.float32) if term_dist else None
+        ids, n_ids, _keep = _among(within)
+        check(lib().mi_knn_search_compound(self._h, pos.ctypes.data if pos.size else None, pos.shape[0], code,
+                                           neg.ctypes.data if n_neg else None, w.ctypes.data if n_neg else None, n_neg, k, ids, n_ids,
+                                           idx.ctypes.data, dist.ctypes.data, td.ctypes.data if term_dist else None))
+        return (idx[:k], dist[:k], td[:k, :T]) if term_dist else (idx[:k], dist[:k])
+
+    def knn_compound_stats(self):
+        """mi_knn_search_compound_stats, of the last knn_compound on this table"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_search_compound_stats(self._h, out))
+        return {"scanned": out[0], "excluded": out[1], "nan": out[2], "results": out[3]}
 
     def kmeans_seed(self, k: int, seed: int = 0, among=None) -> dict:
         """k-means++ seeding on the device (mi_knn_kmeans_seed): k rows, each drawn with probability proportional to its
@@ -601,6 +658,17 @@ class ShardedTable:
                                                        ids.size, idx.ctypes.data, dist.ctypes.data))
         return (idx[0], dist[0]) if single else (idx, dist)
 
+    def knn_compound(self, terms: np.ndarray, mode: str = "all", without=None, without_within=None, k: int = 10, within=None):
+        """EmbeddingTable.knn_compound over all shards (mi_knn_sharded_search_compound): global ids, no per-term distances"""
+        pos, code, neg, w, n_neg = _compound_args(self.dim, terms, mode, without, without_within)
+        k = int(k)
+        idx, dist = np.empty(max(k, 1), np.uint64), np.empty(max(k, 1), np.float32)
+        ids, n_ids, _keep = _among(within)
+        check(lib().mi_knn_sharded_search_compound(self._h, pos.ctypes.data if pos.size else None, pos.shape[0], code,
+                                                   neg.ctypes.data if n_neg else None, w.ctypes.data if n_neg else None, n_neg, k, ids,
+                                                   n_ids, idx.ctypes.data, dist.ctypes.data))
+        return idx[:k], dist[:k]
+
     def assign(self, vectors: np.ndarray):
         """EmbeddingTable.assign over all shards (mi_knn_sharded_assign): labels / dist by global row id"""
         v = _f32(vectors).reshape(-1, self.dim)
@@ -907,6 +975,26 @@ class ImageIndex:
         check(lib().mi_index_search_diverse(self._h, q.ctypes.data, _cstrs(refs), len(refs), _cstrs(fs), len(fs), k, pool,
                                             float(min_gap), idx.ctypes.data, dist.ctypes.data, hidden.ctypes.data, ctypes.byref(n)))
         return [(int(idx[i]), self.path(int(idx[i]), web=web), float(dist[i]), int(hidden[i])) for i in range(n.value)]
+
+    def web_search_compound(self, terms: np.ndarray, mode: str = "all", without=None, without_within=None, k: int = 100,
+                            folders: Sequence[str] = (), term_dist: bool = False, web: bool = False):
+        """and / or / not over text (or image) embeddings (mi_index_search_compound): EmbeddingTable.knn_compound over the
+        images under `folders` (() = everything); removed paths never appear.  No refinement happens here: pass a term through
+        refine_query first if it should be refined.  Returns [(id, image_path, score)], with term_dist=True [(id, image_path,
+        score, [distance to every term, positives first])] — which term held a picture back."""
+        pos, code, neg, w, n_neg = _compound_args(self.dim, terms, mode, without, without_within)
+        fs = list(folders)
+        k = int(k)
+        T = pos.shape[0] + n_neg
+        idx, dist = np.empty(max(k, 1), np.uint64), np.empty(max(k, 1), np.float32)
+        td = np.empty((max(k, 1), max(T, 1)), np.float32) if term_dist else None
+        n = ctypes.c_uint32()
+        check(lib().mi_index_search_compound(self._h, pos.ctypes.data if pos.size else None, pos.shape[0], code,
+                                             neg.ctypes.data if n_neg else None, w.ctypes.data if n_neg else None, n_neg, _cstrs(fs),
+                                             len(fs), k, idx.ctypes.data, dist.ctypes.data, td.ctypes.data if term_dist else None,
+                                             ctypes.byref(n)))
+        hits = [(int(idx[i]), self.path(int(idx[i]), web=web), float(dist[i])) for i in range(n.value)]
+        return [h + ([float(v) for v in td[i, :T]],) for i, h in enumerate(hits)] if term_dist else hits
 
     def duplicates(self, max_dist: float, first_new: int = 0, web: bool = False, max_pairs: int = 1 << 20) -> list:
         """Groups of near-duplicate images (mi_index_duplicates): lists of paths whose embeddings are chained by cosine

@@ -486,6 +486,43 @@ int mi_knn_search_diverse(mi_knn* t, const float* q, uint32_t k, uint32_t pool, 
 /* of the last mi_knn_search_diverse on this handle: out = {P, candidate pairs stage 1 handed to stage 2, conflicting pairs
  * found, pool entries hidden} */
 int mi_knn_search_diverse_stats(mi_knn* t, uint64_t out[4]);
+/* All-of / any-of / none-of terms in ONE exact pass over the fp32 rows ("beach AND dog", "sunset OR sunrise", "beach
+ * WITHOUT people"): every candidate row gets the distance to EVERY term before anything is selected; the per-term distances
+ * are combined into one score per row and the k rows with the smallest (score, id) come back.
+ *   per-term distance  d_j(r) is the distance mi_knn_search(q = term j) reports for row r, bit for bit: the same summation
+ *               order and the same expression 1 - dot / (sqrt(qq) * sqrt(xx)).
+ *   order       distances are compared under the search's key order: numeric order, -0 before +0, every NaN last and equal
+ *               to every other NaN.
+ *               MI_COMPOUND_ALL: score(r) = the largest d_j(r) over the positive terms under that order; one NaN term makes
+ *               the score NaN.  MI_COMPOUND_ANY: the smallest; a NaN term is ignored unless every term is NaN.  The score
+ *               carries the bits of the term that decides it (a NaN is 0x7FC00000).
+ *   negatives   row r is excluded iff for some negative term j  d_j(r) <= neg_within[j]  (an ordinary float comparison: a NaN
+ *               distance never excludes).  neg_within[j] NaN or < 0: MI_ERR_INVALID; +INFINITY excludes every row with a
+ *               non-NaN distance to that term.
+ *   candidates  among == NULL: every live row.  Otherwise the ids given, as for mi_knn_search_filtered: any order, duplicates
+ *               allowed, deleted rows left out, n_among may be 0; an id that is not a row: MI_ERR_INVALID and nothing runs.
+ *   result      the k candidates with the smallest (score, id), in that order; excluded rows and rows with a NaN score are
+ *               left out; MI_KNN_NO_ID / +inf behind the last hit, so exactly k hits come back whenever k rows qualify.
+ *               idx [k], dist [k] = the score.  term_dist (may be NULL) [k][n_pos + n_neg] = d_j of the result's row,
+ *               positives first in the order given, then negatives; +inf in the padding.  It lets a UI say which term held a
+ *               picture back.
+ * pos: [n_pos][dim], neg: [n_neg][dim], neg_within: [n_neg].  1 <= n_pos, n_pos + n_neg <= 8, 1 <= k <= 4096 (larger:
+ * MI_ERR_UNSUPPORTED).  MI_ERR_INVALID for zero, a null t / pos / idx / dist, an unknown mode, or n_neg > 0 with a null neg /
+ * neg_within; no output is written on MI_ERR_INVALID.  dim in {128, 256, 512, 768, 1024} (the set mi_knn_kmeans_seed accepts),
+ * MI_ERR_UNSUPPORTED otherwise.  An empty table or an empty candidate set: all padding, MI_OK.
+ * n_pos = 1, n_neg = 0 equals mi_knn_search with its NaN entries removed; repeating a positive term changes nothing.
+ * The call reads the fp32 rows only: the result does not depend on the "prefilter" option, nor on "compound_blocks"
+ * (mi_knn_set_option: workgroups of the scan, 0 = the batched search's grid, v >= 1 = exactly min(v, tiles / 4)).  It works on
+ * a shard borrowed from a sharded table and reports that shard's ids.  Runs on the handle's stream behind every write and
+ * search enqueued before it, and waits for its results. */
+#define MI_COMPOUND_ALL 0 /* near EVERY positive term: score = the largest of their distances  */
+#define MI_COMPOUND_ANY 1 /* near AT LEAST ONE:        score = the smallest                    */
+int mi_knn_search_compound(mi_knn* t, const float* pos, uint32_t n_pos, int mode, const float* neg, const float* neg_within,
+                           uint32_t n_neg, uint32_t k, const uint64_t* among, uint64_t n_among, uint64_t* idx, float* dist,
+                           float* term_dist /* may be NULL */);
+/* of the last mi_knn_search_compound on this handle: out = {rows or list entries scanned, rows excluded by a negative term,
+ * rows (not excluded) with a NaN score, results written} */
+int mi_knn_search_compound_stats(mi_knn* t, uint64_t out[4]);
 /* host-only: pairs -> groups (connected components, union-find).  ids: every id that occurs in a pair, grouped; groups
  * ordered by their smallest id, ids ascending inside a group; group_start[g] .. group_start[g + 1] index ids
  * (group_start holds n_groups + 1 entries).  Two-call protocol: counts are always written, arrays up to their caps. */
@@ -547,6 +584,12 @@ int mi_knn_sharded_deleted(mi_knn_sharded* t, uint64_t* ids, uint64_t cap, uint6
  * the filtered search of one table that holds every row.  Waits for its results. */
 int mi_knn_sharded_search_filtered(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, const uint64_t* ids,
                                    uint64_t n_ids, uint64_t* idx, float* dist);
+/* mi_knn_search_compound on global ids, without term_dist: every shard answers for the rows (or the ids of `among`) it holds
+ * on its own stream, the lists are merged with mi_knn_merge's ordering; the result equals the one-table result bit for bit.
+ * Waits for its results. */
+int mi_knn_sharded_search_compound(mi_knn_sharded* t, const float* pos, uint32_t n_pos, int mode, const float* neg,
+                                   const float* neg_within, uint32_t n_neg, uint32_t k, const uint64_t* among, uint64_t n_among,
+                                   uint64_t* idx, float* dist);
 /* mi_knn_assign over the whole table: every shard labels its own rows on its own stream (concurrently: no exchange is
  * needed), the results land at the rows' global ids.  labels / dist: [rows of the table]; equals the one-table result
  * bit for bit.  (k-means over a sharded table is not offered: its update needs a cross-shard reduction.) */
@@ -684,6 +727,13 @@ int mi_index_search_within(mi_index* ix, const float* text_embedding, const char
 int mi_index_search_diverse(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
                             const char* const* folders, size_t n_folders, uint32_t k, uint32_t pool, float min_gap,
                             uint64_t* idx, float* dist, uint32_t* hidden, uint32_t* n_found);
+/* mi_knn_search_compound over the index: terms as for that call; folders as in mi_index_search_within (n_folders = 0: the whole
+ * table; folders that match nothing: an empty candidate set); removed paths never appear.  There is no refinement inside the
+ * call: a caller who wants a term refined with marked images passes it through mi_refine first.  idx / dist [k], term_dist
+ * [k][n_pos + n_neg] (may be NULL), *n_found (may be NULL) = results before the padding. */
+int mi_index_search_compound(mi_index* ix, const float* pos, uint32_t n_pos, int mode, const float* neg, const float* neg_within,
+                             uint32_t n_neg, const char* const* folders, size_t n_folders, uint32_t k, uint64_t* idx, float* dist,
+                             float* term_dist, uint32_t* n_found);
 /* `<dir>/embedding.miknn` + `<dir>/image_path.bin`, each through a temporary file, fsync and rename, the path file
  * last: after a crash the directory holds a consistent index (at worst the one before the save). */
 int mi_index_save(mi_index* ix, const char* dir);
