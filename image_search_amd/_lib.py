@@ -78,6 +78,8 @@ SYMBOLS = {
     "mi_knn_search_compound": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_int, c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32,
                                               c_vp, ctypes.c_uint64, c_vp, c_vp, c_vp]),
     "mi_knn_search_compound_stats": (ctypes.c_int, [c_vp, c_u64p]),
+    "mi_knn_search_page": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint64, ctypes.c_float, c_vp,
+                                          ctypes.c_uint64, c_vp, c_vp, c_vp]),
     "mi_pairs_to_groups": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_u64p,
                                           c_u64p]),
     "mi_index_duplicates": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,
@@ -107,6 +109,8 @@ SYMBOLS = {
                                                       c_vp]),
     "mi_knn_sharded_search_compound": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_int, c_vp, c_vp, ctypes.c_uint32,
                                                       ctypes.c_uint32, c_vp, ctypes.c_uint64, c_vp, c_vp]),
+    "mi_knn_sharded_search_page": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint64, ctypes.c_float, c_vp,
+                                                  ctypes.c_uint64, c_vp, c_vp, c_vp]),
     "mi_knn_sharded_assign": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_sharded_assign_multi": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp]),
     "mi_knn_sharded_search_many": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
@@ -138,6 +142,9 @@ SYMBOLS = {
     "mi_index_search_compound": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_int, c_vp, c_vp, ctypes.c_uint32,
                                                 ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_uint32, c_vp, c_vp, c_vp,
                                                 ctypes.POINTER(ctypes.c_uint32)]),
+    "mi_index_search_page": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t,
+                                            ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_uint32, ctypes.c_float,
+                                            ctypes.c_uint64, ctypes.c_float, c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32), c_vp]),
     "mi_index_save": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_index_load": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_knn_merge": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),

@@ -220,6 +220,8 @@ struct mi_knn {
     // score, results written} of the last call; workgroups of its scan (option "compound_blocks": 0 = the batched search's grid)
     uint64_t compound_stats[4] = {0, 0, 0, 0};
     int compound_blocks = 0;
+    // mi_knn_search_page (page.hip): workgroups of its scan (option "page_blocks": 0 = the single pass's grid)
+    int page_blocks = 0;
     std::mutex mu;
 };
 
@@ -312,6 +314,10 @@ void knn_merge_lists_device(const uint64_t* d_idx_in, const float* d_dist_in, ui
 // compound.hip: mi_knn_search_compound behind its argument check (compound_host.h); takes t->mu
 void knn_search_compound(mi_knn* t, const float* pos, uint32_t n_pos, int mode, const float* neg, const float* neg_within, uint32_t n_neg,
                          uint32_t k, const uint64_t* among, uint64_t n_among, uint64_t* idx, float* dist, float* term_dist);
+// page.hip: mi_knn_search_page behind its argument check (page_host.h); takes t->mu.  cursor_is_id: the lower end of the window is
+// built from (after_dist, after_id), which must name a row of t; otherwise first_key (inclusive) is taken as given
+void knn_search_page(mi_knn* t, const float* q, uint32_t k, bool cursor_is_id, float after_dist, uint64_t after_id, uint64_t first_key,
+                     float max_dist, const uint64_t* among, uint64_t n_among, uint64_t* idx, float* dist, uint64_t* counts);
 // sharded.hip
 void sharded_place(const mi_knn_sharded* t, uint64_t r, uint32_t* s, uint64_t* local);
 uint64_t sharded_rows_of(const mi_knn_sharded* t, uint64_t total, uint32_t s);  // rows shard s holds when the table holds `total`

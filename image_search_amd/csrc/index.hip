@@ -317,6 +317,25 @@ int mi_index_search_compound(mi_index* ix, const float* pos, uint32_t n_pos, int
     });
 }
 
+// a page of web_search_text: the refined query of mi_index_search, the row set of mi_index_search_within when folders are given
+// (n_folders = 0: the whole table), then mi_knn_search_page
+int mi_index_search_page(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
+                         const char* const* folders, size_t n_folders, uint32_t k, float after_dist, uint64_t after_id, float max_dist,
+                         uint64_t* idx, float* dist, uint32_t* n_results, uint64_t counts[4]) {
+    return guarded([&] {
+        if (!ix || !text_embedding || !idx || !dist || (n_ref && !referenced_images) || (n_folders && !folders))
+            fail(MI_ERR_INVALID, "null argument");
+        std::vector<uint64_t> ids;
+        if (n_folders) ids = folder_rows(ix, folders, n_folders);
+        const std::vector<float> query = refined_query(ix, text_embedding, referenced_images, n_ref);
+        const uint64_t none = 0;   // folders that match nothing are an empty row set, not "the whole table"
+        const uint64_t* among = n_folders ? (ids.empty() ? &none : ids.data()) : nullptr;
+        const int e = mi_knn_search_page(ix->table, query.data(), k, after_dist, after_id, max_dist, among, ids.size(), idx, dist, counts);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        if (n_results) *n_results = hits(idx, k);
+    });
+}
+
 int mi_index_save(mi_index* ix, const char* dir) {
     return guarded([&] {
         if (!ix || !dir) fail(MI_ERR_INVALID, "null argument");

@@ -1077,8 +1077,13 @@ int mi_knn_set_option(mi_knn* t, const char* key, int value) {
             // min(v, tiles / 4) — a small table can then make a wave walk several tiles.  Same answers whatever the value.
             if (value < 0) fail(MI_ERR_INVALID, "compound_blocks must be >= 0 (got %d)", value);
             t->compound_blocks = value;
+        } else if (k == "page_blocks") {
+            // mi_knn_search_page: workgroups of its scan, the rule of "compound_blocks".  0 (default): the single pass's grid;
+            // v >= 1: exactly min(v, tiles / 4).  Same answers whatever the value.
+            if (value < 0) fail(MI_ERR_INVALID, "page_blocks must be >= 0 (got %d)", value);
+            t->page_blocks = value;
         } else {
-            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, many_segments, many_sample, compound_blocks)", key);
+            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, many_segments, many_sample, compound_blocks, page_blocks)", key);
         }
     });
 }

@@ -39,6 +39,7 @@
 #include "common.h"
 #include "compound_host.h"
 #include "handles.h"
+#include "page_host.h"
 #include "two_stage.h"
 
 using namespace mi;
@@ -611,6 +612,53 @@ int mi_knn_sharded_search_compound(mi_knn_sharded* t, const float* pos, uint32_t
                                 all_dist.data() + (size_t)si * k, nullptr);
         });
         merge_lists(all_idx.data(), all_dist.data(), n, k, idx, dist);
+    });
+}
+
+// mi_knn_search_page on global ids: every shard answers for the rows (the ids of `among`) it holds, on its own stream and host
+// thread.  A shard's local rows ascend with their global ids, so its window opens at (after_dist, the number of its rows whose
+// global id is <= after_id) — page_host.h; the lists carry global ids and are merged with mi_knn_merge's ordering, the counts
+// are summed
+int mi_knn_sharded_search_page(mi_knn_sharded* t, const float* q, uint32_t k, float after_dist, uint64_t after_id, float max_dist,
+                               const uint64_t* among, uint64_t n_among, uint64_t* idx, float* dist, uint64_t counts[4]) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = page_check_args(t, q, k, after_dist, after_id, max_dist, among, n_among, idx, dist, &why);
+        if (bad != MI_OK) fail(bad, "%s (k %u)", why, k);
+        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
+        std::lock_guard<std::mutex> l(t->mu);
+        const uint32_t n = t->n();
+        std::vector<std::vector<uint64_t>> per(n);
+        for (uint64_t i = 0; i < n_among; ++i) {  // every id checked before anything runs
+            if (among[i] >= t->rows)
+                fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)among[i], (unsigned long long)t->rows);
+            uint32_t s; uint64_t local;
+            sharded_place(t, among[i], &s, &local);
+            per[s].push_back(among[i]);
+        }
+        if (after_id != MI_KNN_NO_ID && after_id >= t->rows)
+            fail(MI_ERR_INVALID, "after_id %llu is not a row of this table (%llu rows)", (unsigned long long)after_id, (unsigned long long)t->rows);
+        sharded_deliver_all(t);
+        std::vector<uint64_t> all_idx((size_t)n * k), all_counts((size_t)n * 4, 0);
+        std::vector<float> all_dist((size_t)n * k);
+        const uint64_t none = 0;   // a shard that holds none of the ids: an empty candidate set, not "every row"
+        for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
+            const uint64_t* ids = among ? (per[si].empty() ? &none : per[si].data()) : nullptr;
+            const uint64_t first_key =
+                after_id == MI_KNN_NO_ID ? 0 : page_first_key_at(after_dist, page_shard_rows_below(t->block, n, si, after_id));
+            knn_search_page(sh, q, k, false, 0.0f, MI_KNN_NO_ID, first_key, max_dist, ids, per[si].size(), all_idx.data() + (size_t)si * k,
+                            all_dist.data() + (size_t)si * k, all_counts.data() + (size_t)si * 4);
+        });
+        std::vector<uint64_t> m_idx(k);
+        std::vector<float> m_dist(k);
+        merge_lists(all_idx.data(), all_dist.data(), n, k, m_idx.data(), m_dist.data());
+        std::copy(m_idx.begin(), m_idx.end(), idx);
+        std::copy(m_dist.begin(), m_dist.end(), dist);
+        if (counts)
+            for (int c = 0; c < 4; ++c) {
+                counts[c] = 0;
+                for (uint32_t si = 0; si < n; ++si) counts[c] += all_counts[(size_t)si * 4 + c];
+            }
     });
 }
 

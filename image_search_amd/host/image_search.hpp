@@ -106,6 +106,24 @@ class Model {
 }  // namespace clip_vit_large_patch14
 
 // table `image` + index `mt_pts` (server/src/clip.rs:135-143) as one HBM-resident shard
+// one page of results (mi_knn_search_page and its kin): the hits without the padding, counts = {before, window, beyond, nan} of
+// the candidates, and the cursor for the following page — has_next is false when this page came back short
+struct Page {
+    std::vector<uint64_t> idx;
+    std::vector<float> dist;
+    uint64_t counts[4] = {0, 0, 0, 0};
+    bool has_next = false;
+    float next_dist = 0.0f;
+    uint64_t next_id = MI_KNN_NO_ID;
+};
+inline void finish_page(Page& p, uint32_t k) {
+    p.has_next = k > 0 && p.idx[k - 1] != MI_KNN_NO_ID;
+    if (p.has_next) { p.next_dist = p.dist[k - 1]; p.next_id = p.idx[k - 1]; }   // the float as it came: -0 and +0 are different cursors
+    size_t n = 0;
+    while (n < p.idx.size() && p.idx[n] != MI_KNN_NO_ID) ++n;
+    p.idx.resize(n); p.dist.resize(n);
+}
+
 class EmbeddingTable {
     mi_knn* h_ = nullptr;
     uint32_t dim_;
@@ -259,6 +277,20 @@ class EmbeddingTable {
     }
     // {rows or list entries scanned, rows excluded by a negative term, rows with a NaN score, results written} of the last knn_compound
     std::vector<uint64_t> knn_compound_stats() const { std::vector<uint64_t> v(4); check(mi_knn_search_compound_stats(h_, v.data())); return v; }
+    // the k nearest rows after a cursor and within a distance (mi_knn_search_page).  Page 1: after = nullptr; page n + 1: the
+    // previous Page (its next_dist / next_id go back exactly as they came).  max_dist: inclusive; among as for knn_compound
+    Page knn_page(const std::vector<float>& reference, uint32_t k, const Page* after = nullptr, float max_dist = INFINITY,
+                  const std::vector<uint64_t>* among = nullptr) const {
+        Page r;
+        r.idx.resize(k); r.dist.resize(k);
+        static const uint64_t none = 0;   // an empty `among` is an empty set of candidates, not "every row"
+        const uint64_t* ids = among ? (among->empty() ? &none : among->data()) : nullptr;
+        const bool cur = after && after->has_next;
+        check(mi_knn_search_page(h_, reference.data(), k, cur ? after->next_dist : 0.0f, cur ? after->next_id : MI_KNN_NO_ID, max_dist, ids,
+                                 among ? among->size() : 0, r.idx.data(), r.dist.data(), r.counts));
+        finish_page(r, k);
+        return r;
+    }
     // "prefilter" = 2 (bytes) or 1 (bf16): the two-stage exact search, same results from a quarter / a half of the bytes
     void set_option(const std::string& key, int value) { check(mi_knn_set_option(h_, key.c_str(), value)); }
 };
@@ -376,6 +408,21 @@ class ImageIndex {
         for (uint32_t i = 0; i < n; ++i) out.emplace_back(idx[i], dist[i]);
         return out;
     }
+    // one page of search() (mi_index_search_page): the refined query, the images under `folders` (none = everything), then the k
+    // nearest after the cursor and within max_dist; removed paths never appear
+    Page search_page(const std::vector<float>& text_embedding, const std::vector<std::string>& referenced_images, uint32_t k,
+                     const Page* after = nullptr, float max_dist = INFINITY, const std::vector<std::string>& folders = {}) const {
+        Page r;
+        r.idx.resize(k); r.dist.resize(k);
+        const auto p = ptrs(referenced_images);
+        const auto f = ptrs(folders);
+        const bool cur = after && after->has_next;
+        uint32_t n = 0;
+        check(mi_index_search_page(h_, text_embedding.data(), p.data(), p.size(), f.data(), f.size(), k, cur ? after->next_dist : 0.0f,
+                                   cur ? after->next_id : MI_KNN_NO_ID, max_dist, r.idx.data(), r.dist.data(), &n, r.counts));
+        finish_page(r, k);
+        return r;
+    }
     // groups of near-duplicate images as paths (mi_index_duplicates), what a /duplicates handler returns; removed paths
     // never appear; first_new: only what the rows from that id on duplicate
     std::vector<std::vector<std::string>> duplicates(float max_dist, uint64_t first_new = 0, bool web = false,
@@ -439,6 +486,19 @@ class ShardedTable {
         std::vector<float> dist((size_t)nq * k);
         check(mi_knn_sharded_search_many(h_, queries.data(), nq, k, idx.data(), dist.data()));
         return {std::move(idx), std::move(dist)};
+    }
+    // EmbeddingTable::knn_page over all shards (mi_knn_sharded_search_page): global ids, summed counts
+    Page knn_page(const std::vector<float>& reference, uint32_t k, const Page* after = nullptr, float max_dist = INFINITY,
+                  const std::vector<uint64_t>* among = nullptr) const {
+        Page r;
+        r.idx.resize(k); r.dist.resize(k);
+        static const uint64_t none = 0;
+        const uint64_t* ids = among ? (among->empty() ? &none : among->data()) : nullptr;
+        const bool cur = after && after->has_next;
+        check(mi_knn_sharded_search_page(h_, reference.data(), k, cur ? after->next_dist : 0.0f, cur ? after->next_id : MI_KNN_NO_ID, max_dist,
+                                         ids, among ? among->size() : 0, r.idx.data(), r.dist.data(), r.counts));
+        finish_page(r, k);
+        return r;
     }
     std::pair<std::vector<uint64_t>, std::vector<float>> knn(const std::vector<float>& reference, uint32_t k = 1000) const {
         std::vector<uint64_t> idx(k);

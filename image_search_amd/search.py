@@ -59,6 +59,30 @@ def _among(within):
     return keep.ctypes.data, a.size, keep
 
 
+def _page_call(fn, handle, dim, lead, reference, k, after, max_dist, tail_ptr=None, within=None):
+    """one mi_*_search_page call -> (idx [k], dist [k], counts dict, next): `lead` = the arguments between the query and k
+    (the index's references and folders), within = the id list of the table calls; next = the (dist, id) cursor of the last hit,
+    None when the page came back short (nothing is left behind it)"""
+    q = _f32(reference).reshape(-1)
+    if q.size != dim:
+        raise ValueError(f"a query of {q.size} floats for dim {dim}")
+    k = int(k)
+    idx, dist = np.empty(max(k, 1), np.uint64), np.empty(max(k, 1), np.float32)
+    counts = (ctypes.c_uint64 * 4)()
+    a_dist, a_id = (0.0, int(NO_ID)) if after is None else (float(after[0]), int(after[1]))
+    args = [handle, q.ctypes.data] + list(lead) + [k, a_dist, a_id, float(max_dist)]
+    if tail_ptr is None:
+        ids, n_ids, _keep = _among(within)
+        args += [ids, n_ids, idx.ctypes.data, dist.ctypes.data, counts]
+    else:
+        args += [idx.ctypes.data, dist.ctypes.data, tail_ptr, counts]
+    check(fn(*args))
+    idx, dist = idx[:k], dist[:k]
+    full = k > 0 and idx[k - 1] != NO_ID
+    nxt = (dist[k - 1], int(idx[k - 1])) if full else None   # the np.float32 itself: -0 and +0 are different cursors
+    return idx, dist, {"before": counts[0], "window": counts[1], "beyond": counts[2], "nan": counts[3]}, nxt
+
+
 def _ptrs(vecs):
     arr = (c_f * len(vecs))()
     for i, v in enumerate(vecs):
@@ -311,6 +335,27 @@ class EmbeddingTable:
         out = (ctypes.c_uint64 * 4)()
         check(lib().mi_knn_search_compound_stats(self._h, out))
         return {"scanned": out[0], "excluded": out[1], "nan": out[2], "results": out[3]}
+
+    def knn_page(self, reference: np.ndarray, k: int = 100, after=None, max_dist: float = float("inf"), within=None):
+        """The k nearest rows AFTER a cursor and WITHIN a distance (mi_knn_search_page).  after: None (from the start) or the
+        (dist, id) of the previous page's last hit — pass back what came out, the bits of dist matter; its row may have been
+        deleted since.  max_dist: inclusive bound on the cosine distance.  within: ids, as for knn().  Returns (idx [k] uint64,
+        dist [k] f32, counts, next): ascending by (distance, id), NO_ID / +inf behind the last hit, NaN distances never
+        returned; counts = {"before", "window", "beyond", "nan"} of the candidates (they add up to their number); next = the
+        cursor for the following page, None when this page came back short.  k <= 4096."""
+        return _page_call(lib().mi_knn_search_page, self._h, self.dim, (), reference, k, after, max_dist, within=within)
+
+    def pages(self, reference: np.ndarray, k: int = 100, max_dist: float = float("inf"), within=None):
+        """knn_page after knn_page until one comes back short: yields (idx, dist, counts) with the padding cut off.  Rows
+        appended or deleted between two pages are honoured as they stand when each page is asked for."""
+        after = None
+        while True:
+            idx, dist, counts, after = self.knn_page(reference, k, after, max_dist, within)
+            n = int((idx != NO_ID).sum())
+            if n:
+                yield idx[:n], dist[:n], counts
+            if after is None:
+                return
 
     def kmeans_seed(self, k: int, seed: int = 0, among=None) -> dict:
         """k-means++ seeding on the device (mi_knn_kmeans_seed): k rows, each drawn with probability proportional to its
@@ -669,6 +714,10 @@ class ShardedTable:
                                                    n_ids, idx.ctypes.data, dist.ctypes.data))
         return idx[:k], dist[:k]
 
+    def knn_page(self, reference: np.ndarray, k: int = 100, after=None, max_dist: float = float("inf"), within=None):
+        """EmbeddingTable.knn_page over all shards (mi_knn_sharded_search_page): global ids, summed counts"""
+        return _page_call(lib().mi_knn_sharded_search_page, self._h, self.dim, (), reference, k, after, max_dist, within=within)
+
     def assign(self, vectors: np.ndarray):
         """EmbeddingTable.assign over all shards (mi_knn_sharded_assign): labels / dist by global row id"""
         v = _f32(vectors).reshape(-1, self.dim)
@@ -995,6 +1044,19 @@ class ImageIndex:
                                              ctypes.byref(n)))
         hits = [(int(idx[i]), self.path(int(idx[i]), web=web), float(dist[i])) for i in range(n.value)]
         return [h + ([float(v) for v in td[i, :T]],) for i, h in enumerate(hits)] if term_dist else hits
+
+    def web_search_page(self, text_embedding: np.ndarray, referenced_images: Sequence[str] = (), k: int = 100, after=None,
+                        max_dist: float = float("inf"), folders: Sequence[str] = (), web: bool = True):
+        """One page of web_search_text (mi_index_search_page): the query refined with the marked images, the images under
+        `folders` (() = everything), then the k nearest after the cursor `after` and within max_dist; removed paths never
+        appear.  Returns ([(id, image_path, similarity)], counts, next): counts = {"before", "window", "beyond", "nan"} ("101-200
+        of before + window"), next = the cursor for the following page (None: this was the last)."""
+        refs, fs = list(referenced_images), list(folders)
+        n = ctypes.c_uint32()
+        lead = (_cstrs(refs), len(refs), _cstrs(fs), len(fs))
+        idx, dist, counts, nxt = _page_call(lib().mi_index_search_page, self._h, self.dim, lead, text_embedding, k, after, max_dist,
+                                            tail_ptr=ctypes.byref(n))
+        return [(int(idx[i]), self.path(int(idx[i]), web=web), float(dist[i])) for i in range(n.value)], counts, nxt
 
     def duplicates(self, max_dist: float, first_new: int = 0, web: bool = False, max_pairs: int = 1 << 20) -> list:
         """Groups of near-duplicate images (mi_index_duplicates): lists of paths whose embeddings are chained by cosine

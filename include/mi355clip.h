@@ -523,6 +523,41 @@ int mi_knn_search_compound(mi_knn* t, const float* pos, uint32_t n_pos, int mode
 /* of the last mi_knn_search_compound on this handle: out = {rows or list entries scanned, rows excluded by a negative term,
  * rows (not excluded) with a NaN score, results written} */
 int mi_knn_search_compound_stats(mi_knn* t, uint64_t out[4]);
+/* The k nearest rows AFTER a cursor and WITHIN a distance, with the counts a results page needs ("101-200 of 3 412"), exact,
+ * in one pass over the fp32 rows.  Page n costs what page 1 costs, a row never appears on two pages, and no surviving row is
+ * skipped when rows are appended or deleted between two pages.
+ *   candidates  among == NULL: every live row.  Otherwise the live rows the ids name, as for mi_knn_search_filtered: any order,
+ *               duplicates allowed, deleted rows left out, n_among == 0 with a non-null pointer is the empty set; an id that is
+ *               not a row: MI_ERR_INVALID.
+ *   distance    d(r) is what mi_knn_search(q) reports for row r, bit for bit.  key(r) = (dist_to_u32(d(r)) << 32) | local row,
+ *               the search's own 64-bit key: distance ascending (-0 before +0), id ascending among equal distances, NaN last.
+ *   cursor      after_id == MI_KNN_NO_ID: from the start, after_dist is ignored.  Otherwise after_id must be an id of the table
+ *               (a DELETED row is allowed: the picture under the cursor may have been removed since) and after_dist must not be
+ *               NaN.  The cursor key is built from the bits of after_dist exactly as given: -0 and +0 are different keys, so the
+ *               caller passes back what it received — the (dist, idx) of the previous page's last hit.
+ *   window      a candidate is in the window when key > cursor key and dist_to_u32(d) <= dist_to_u32(max_dist): the bound is
+ *               inclusive and uses the key order.  max_dist = +INFINITY: no bound; NaN: MI_ERR_INVALID.
+ *   result      the k smallest keys of the window, ascending by (distance, id): idx [k], dist [k]; MI_KNN_NO_ID / +inf behind
+ *               the last hit.  A candidate whose distance is NaN is never returned, as in mi_knn_search_many.
+ *   counts      (may be NULL) of the candidates, each in the first class that applies, so the four add up to the number of
+ *               candidates: [0] before = key <= cursor key (0 without a cursor), [1] window, [2] beyond = not NaN and past both
+ *               the cursor and the bound, [3] nan.
+ * Any violation above returns MI_ERR_INVALID, and nothing runs or is written.  1 <= k <= 4096 (0: MI_ERR_INVALID, larger:
+ * MI_ERR_UNSUPPORTED); dim in {128, 256, 512, 768, 1024} as for mi_knn_search_compound, MI_ERR_UNSUPPORTED otherwise.  An
+ * empty table or an empty candidate set: all padding, every count 0, MI_OK.
+ * Identities: (a) without a cursor and with max_dist = +INFINITY the result is mi_knn_search(q, k) without its NaN entries;
+ * (b) calling again with the last hit of the previous page as the cursor, until a page has fewer than k hits, concatenates to
+ * exactly the list of (a) with k = all rows, for any page size; with rows appended or deleted between two pages this holds for
+ * the rows that exist when each page is asked for.
+ * The call reads the fp32 rows only: the result does not depend on the "prefilter" option (there is no two-stage form), nor
+ * on "page_blocks" (mi_knn_set_option: workgroups of the scan, 0 = the single pass's grid, v >= 1 = exactly min(v, tiles / 4)).
+ * It works on a shard borrowed from a sharded table with that shard's ids.  Runs on the handle's stream behind every write
+ * and search enqueued before it, and waits for its result. */
+int mi_knn_search_page(mi_knn* t, const float* q, uint32_t k,
+                       float after_dist, uint64_t after_id, /* the cursor: the last entry of the previous page */
+                       float max_dist,                      /* +INFINITY: no bound */
+                       const uint64_t* among, uint64_t n_among,
+                       uint64_t* idx, float* dist, uint64_t counts[4] /* may be NULL */);
 /* host-only: pairs -> groups (connected components, union-find).  ids: every id that occurs in a pair, grouped; groups
  * ordered by their smallest id, ids ascending inside a group; group_start[g] .. group_start[g + 1] index ids
  * (group_start holds n_groups + 1 entries).  Two-call protocol: counts are always written, arrays up to their caps. */
@@ -590,6 +625,12 @@ int mi_knn_sharded_search_filtered(mi_knn_sharded* t, const float* q, uint32_t n
 int mi_knn_sharded_search_compound(mi_knn_sharded* t, const float* pos, uint32_t n_pos, int mode, const float* neg,
                                    const float* neg_within, uint32_t n_neg, uint32_t k, const uint64_t* among, uint64_t n_among,
                                    uint64_t* idx, float* dist);
+/* mi_knn_search_page on global ids: after_id must be a global row id of the table (deleted or not).  Every shard answers on
+ * its own stream and host thread for the rows (or the ids of `among`) it holds; a shard's local rows ascend with their global
+ * ids, so its window starts at (after_dist, the number of its rows with a global id <= after_id).  The lists are merged with
+ * mi_knn_merge's ordering and the counts are summed; the result equals the one-table result bit for bit.  Waits for its result. */
+int mi_knn_sharded_search_page(mi_knn_sharded* t, const float* q, uint32_t k, float after_dist, uint64_t after_id, float max_dist,
+                               const uint64_t* among, uint64_t n_among, uint64_t* idx, float* dist, uint64_t counts[4]);
 /* mi_knn_assign over the whole table: every shard labels its own rows on its own stream (concurrently: no exchange is
  * needed), the results land at the rows' global ids.  labels / dist: [rows of the table]; equals the one-table result
  * bit for bit.  (k-means over a sharded table is not offered: its update needs a cross-shard reduction.) */
@@ -734,6 +775,13 @@ int mi_index_search_diverse(mi_index* ix, const float* text_embedding, const cha
 int mi_index_search_compound(mi_index* ix, const float* pos, uint32_t n_pos, int mode, const float* neg, const float* neg_within,
                              uint32_t n_neg, const char* const* folders, size_t n_folders, uint32_t k, uint64_t* idx, float* dist,
                              float* term_dist, uint32_t* n_found);
+/* mi_knn_search_page over the index: the text embedding refined with referenced_images exactly as mi_index_search does,
+ * folders as in mi_index_search_within (n_folders = 0: the whole table; folders that match nothing: an empty candidate set),
+ * then the page after (after_dist, after_id) within max_dist; removed paths never appear.  idx / dist [k], *n_results (may be
+ * NULL) = results before the padding, counts (may be NULL) as for mi_knn_search_page. */
+int mi_index_search_page(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
+                         const char* const* folders, size_t n_folders, uint32_t k, float after_dist, uint64_t after_id,
+                         float max_dist, uint64_t* idx, float* dist, uint32_t* n_results, uint64_t counts[4]);
 /* `<dir>/embedding.miknn` + `<dir>/image_path.bin`, each through a temporary file, fsync and rename, the path file
  * last: after a crash the directory holds a consistent index (at worst the one before the save). */
 int mi_index_save(mi_index* ix, const char* dir);
