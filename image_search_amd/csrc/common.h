@@ -3,31 +3,15 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
-#include <stdexcept>
 #include <string>
 
-#include "../../include/mi355clip.h"
+#include "error.h"
 
 namespace mi {
 
-struct Error : std::runtime_error {
-    int code;
-    Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
 void set_last_error(const std::string& m);
-
-[[noreturn]] inline void fail(int code, const char* fmt, ...) {
-    char buf[4096];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    throw Error(code, buf);
-}
 
 inline void hip_check(hipError_t e, const char* what, const char* file, int line) {
     if (e != hipSuccess) {

@@ -112,6 +112,34 @@ void* upload_x3(mi_clip* m, const std::vector<float>& h, size_t k) {
 }
 
 void load_layers(mi_clip* m, WeightFile& st, const std::string& prefix);
+bool ln_instantiated(int D);
+int rows_of(const WeightFile& st, const std::string& name) {
+    const TensorInfo& t = st.info(name);
+    if (t.shape.size() != 2) fail(MI_ERR_UNSUPPORTED, "'%s' must be a matrix", name.c_str());
+    return (int)t.shape[0];
+}
+
+// What forward() / forward_text() can run, decided when the file is read (nothing has been uploaded yet): every later
+// "no instantiation" / "built for up to" failure of a launch is a geometry that must not get this far.
+void check_geometry(mi_clip* m, WeightFile& st, const std::string& prefix, const char* path) {
+    auto it = st.meta.find("num_attention_heads");
+    m->H = it != st.meta.end() ? std::atoi(it->second.c_str()) : m->D / 64;
+    if (m->H <= 0 || m->D != m->H * 64)
+        fail(MI_ERR_UNSUPPORTED, "hidden %d with %d heads: the attention kernels are built for head_dim 64", m->D, m->H);
+    if (m->D % 128 != 0 || m->FF % 128 != 0 || m->FF <= 0)
+        fail(MI_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of 128", m->D, m->FF);
+    if (!ln_instantiated(m->D))
+        fail(MI_ERR_UNSUPPORTED, "hidden size %d has no LayerNorm instantiation (128, 256, 384, 512, 768, 1024, 1280, 1536, 1664)", m->D);
+    if (m->E <= 0) fail(MI_ERR_UNSUPPORTED, "the projection has no rows");
+    if (m->S < (m->text ? 1 : 2)) fail(MI_ERR_UNSUPPORTED, "%d positions: %s", m->S, m->text ? "a sequence has one at least" : "an image is the class token and one patch at least");
+    if (m->precision == MI_PRECISION_BF16 && m->S > 288)
+        fail(MI_ERR_UNSUPPORTED, "bf16 attention is built for up to 288 tokens (got %d): load with MI_PRECISION_F32", m->S);
+    // layers 0 .. L-1 were counted by their layer_norm1.weight: a layer behind them means one of those is missing
+    const std::string lp = prefix + "encoder.layers.";
+    for (const std::string& name : st.names())
+        if (name.compare(0, lp.size(), lp) == 0 && std::atoi(name.c_str() + lp.size()) >= m->L)
+            fail(MI_ERR_IO, "'%s' holds '%s' but only %d complete layers (layer_norm1.weight of an earlier layer is missing)", path, name.c_str(), m->L);
+}
 
 // Every reader of the residual stream is a LayerNorm (LN1, LN2, post_layernorm: modeling_clip.py:353-383, :641-651), and a
 // LayerNorm does not see a constant added to all channels of a row.  So the common mode of everything WRITTEN to the stream
@@ -180,15 +208,10 @@ void load_text_weights(mi_clip* m, const char* path) {
     while (st.has(t + "encoder.layers." + std::to_string(L) + ".layer_norm1.weight")) ++L;
     if (L == 0) fail(MI_ERR_IO, "no text encoder layers found in '%s'", path);
     m->L = L;
-    m->FF = (int)st.info(t + "encoder.layers.0.mlp.fc1.weight").shape.at(0);
-    m->E = (int)st.info("text_projection.weight").shape.at(0);
-    m->H = m->D / 64;
-    auto it = st.meta.find("num_attention_heads");
-    if (it != st.meta.end()) m->H = std::atoi(it->second.c_str());
-    if (m->H <= 0 || m->D != m->H * 64)
-        fail(MI_ERR_UNSUPPORTED, "hidden %d with %d heads: the attention kernels are built for head_dim 64", m->D, m->H);
-    if (m->D % 128 != 0 || m->FF % 128 != 0)
-        fail(MI_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of 128", m->D, m->FF);
+    m->FF = rows_of(st, t + "encoder.layers.0.mlp.fc1.weight");
+    m->E = rows_of(st, "text_projection.weight");
+    if (m->vocab <= 0) fail(MI_ERR_UNSUPPORTED, "token_embedding.weight has no rows");
+    check_geometry(m, st, t, path);
     m->image = m->patch = m->grid = 0;
     const int D = m->D;
     m->tok = upload_f32(m, st.read(t + "embeddings.token_embedding.weight", (int64_t)m->vocab * D));
@@ -211,6 +234,7 @@ void load_weights(mi_clip* m, const char* path) {
     const TensorInfo& po = st.info(v + "embeddings.position_embedding.weight");
     if (po.shape.size() != 2 || po.shape[1] != m->D) fail(MI_ERR_UNSUPPORTED, "position_embedding.weight must be [S,D]");
     m->S = (int)po.shape[0];
+    if (m->S < 2) fail(MI_ERR_UNSUPPORTED, "%d positions: an image is the class token and one patch at least", m->S);
     m->grid = (int)std::lround(std::sqrt((double)(m->S - 1)));
     if (m->grid * m->grid + 1 != m->S) fail(MI_ERR_UNSUPPORTED, "token count %d is not G*G+1", m->S);
     m->image = m->grid * m->patch;
@@ -218,15 +242,10 @@ void load_weights(mi_clip* m, const char* path) {
     while (st.has(v + "encoder.layers." + std::to_string(L) + ".layer_norm1.weight")) ++L;
     if (L == 0) fail(MI_ERR_IO, "no encoder layers found in '%s'", path);
     m->L = L;
-    m->FF = (int)st.info(v + "encoder.layers.0.mlp.fc1.weight").shape.at(0);
-    m->E = (int)st.info("visual_projection.weight").shape.at(0);
-    m->H = m->D / 64;
-    auto it = st.meta.find("num_attention_heads");
-    if (it != st.meta.end()) m->H = std::atoi(it->second.c_str());
-    if (m->H <= 0 || m->D != m->H * 64)
-        fail(MI_ERR_UNSUPPORTED, "hidden %d with %d heads: the attention kernels are built for head_dim 64", m->D, m->H);
-    if (m->D % 128 != 0 || m->FF % 128 != 0)
-        fail(MI_ERR_UNSUPPORTED, "hidden (%d) and intermediate (%d) sizes must be multiples of 128", m->D, m->FF);
+    m->FF = rows_of(st, v + "encoder.layers.0.mlp.fc1.weight");
+    m->E = rows_of(st, "visual_projection.weight");
+    if (m->patch <= 0) fail(MI_ERR_UNSUPPORTED, "patch_embedding.weight must be [D,3,P,P] with P >= 1");
+    check_geometry(m, st, v, path);
     // the three-pass GEMM is the persistent 256x256 kernel only, and the attention the exact-f32 MFMA kernel: no fallbacks
     if (is_x3(m) && (m->D % 256 != 0 || m->FF % 256 != 0 || m->S > 272))
         fail(MI_ERR_UNSUPPORTED, "MI_PRECISION_BF16X3 needs hidden (%d) and intermediate (%d) sizes that are multiples of 256 and at most 272 tokens (%d)",
@@ -486,6 +505,12 @@ void gemm(mi_clip* m, const void* X, const void* W, const float* bias, void* out
         case 1664: { constexpr int VEC = 2, NT = 13; CALL; } break;                          \
         default: fail(MI_ERR_UNSUPPORTED, "hidden size %d has no LayerNorm instantiation", D); \
     }
+
+// the widths above, for check_geometry: a file of another hidden size is refused when it is loaded
+bool ln_instantiated(int D) {
+    for (int d : {128, 256, 384, 512, 768, 1024, 1280, 1536, 1664}) if (D == d) return true;
+    return false;
+}
 
 // y pitch: D, or 2D with the lo halves behind the hi halves (split_ln)
 // x_lo: byte offset of the lo plane when x is the 24-bit residual stream (0: plain fp32 rows)

@@ -33,6 +33,7 @@
 #include <unistd.h>
 
 #include <cctype>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -41,7 +42,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "error.h"
 
 namespace mi {
 
@@ -49,24 +50,44 @@ struct TensorInfo {
     std::string dtype;
     std::vector<int64_t> shape;
     uint64_t begin = 0, end = 0;
-    int64_t numel() const {
+    int64_t numel() const {  // cannot overflow: every reader files a shape through checked_numel first
         int64_t n = 1;
         for (auto d : shape) n *= d;
         return n;
     }
 };
 
+// Element count of a shape read from a file: a dimension is 0 .. 2^31 - 1 (every size of the towers is an int) and the
+// product, with 4 bytes per element on top, stays below 2^62.
+inline int64_t checked_numel(const std::vector<int64_t>& shape, const char* what) {
+    int64_t n = 1;
+    bool zero = false;
+    for (auto d : shape) {
+        if (d < 0 || d > 0x7fffffffLL) fail(MI_ERR_IO, "tensor '%s': dimension %lld is outside 0 .. 2^31 - 1", what, (long long)d);
+        zero |= d == 0;
+    }
+    if (zero) return 0;
+    for (auto d : shape) {
+        if (n > (int64_t)(1ull << 60) / d) fail(MI_ERR_IO, "tensor '%s': the shape holds more than 2^60 elements", what);
+        n *= d;
+    }
+    return n;
+}
+inline size_t dtype_size(const std::string& dtype) { return dtype == "F32" ? 4 : (dtype == "F16" || dtype == "BF16") ? 2 : 0; }
+
 // raw little-endian elements -> fp32
 inline void to_f32(const void* src, const std::string& dtype, int64_t n, float* out, const char* what) {
-    if (dtype == "F32") { std::memcpy(out, src, (size_t)n * 4); return; }
-    const uint16_t* raw = static_cast<const uint16_t*>(src);
+    if (dtype == "F32") { if (n > 0) std::memcpy(out, src, (size_t)n * 4); return; }
+    // the bytes of a record lie wherever MessagePack put them: no alignment may be assumed
+    const unsigned char* raw = static_cast<const unsigned char*>(src);
+    auto u16 = [raw](int64_t i) { return (uint32_t)raw[2 * i] | ((uint32_t)raw[2 * i + 1] << 8); };
     if (dtype == "BF16") {
-        for (int64_t i = 0; i < n; ++i) { const uint32_t b = (uint32_t)raw[i] << 16; std::memcpy(&out[i], &b, 4); }
+        for (int64_t i = 0; i < n; ++i) { const uint32_t b = u16(i) << 16; std::memcpy(&out[i], &b, 4); }
         return;
     }
     if (dtype == "F16") {
         for (int64_t i = 0; i < n; ++i) {  // IEEE half -> float
-            const uint32_t hbits = raw[i], sign = (hbits & 0x8000u) << 16;
+            const uint32_t hbits = u16(i), sign = (hbits & 0x8000u) << 16;
             uint32_t ex = (hbits >> 10) & 0x1f, man = hbits & 0x3ffu, b;
             if (ex == 0) {
                 if (man == 0) b = sign;
@@ -112,19 +133,22 @@ struct Json {
         expect('"');
         return s;
     }
-    int64_t num() {
+    int64_t num() {  // an integer that fits int64 (the buffer ends in a NUL: strtoll stops there at the latest)
         ws();
         char* end = nullptr;
+        errno = 0;
         const long long v = std::strtoll(p, &end, 10);
-        if (end == p) fail(MI_ERR_IO, "safetensors header: expected a number");
+        if (end == p || end > e) fail(MI_ERR_IO, "safetensors header: expected a number");
+        if (errno == ERANGE) fail(MI_ERR_IO, "safetensors header: a number does not fit 64 bits");
         p = end;
         return v;
     }
-    void skip() {  // any value
+    void skip(int depth = 1) {  // any value; containers nest 64 deep at most, as in the record reader
+        if (depth > 64) fail(MI_ERR_IO, "safetensors header: nesting too deep");
         ws();
         if (peek('"')) { str(); return; }
-        if (peek('{')) { ++p; if (peek('}')) { ++p; return; } do { str(); expect(':'); skip(); } while (peek(',') && ++p); expect('}'); return; }
-        if (peek('[')) { ++p; if (peek(']')) { ++p; return; } do { skip(); } while (peek(',') && ++p); expect(']'); return; }
+        if (peek('{')) { ++p; if (peek('}')) { ++p; return; } do { str(); expect(':'); skip(depth + 1); } while (peek(',') && ++p); expect('}'); return; }
+        if (peek('[')) { ++p; if (peek(']')) { ++p; return; } do { skip(depth + 1); } while (peek(',') && ++p); expect(']'); return; }
         while (p < e && *p != ',' && *p != '}' && *p != ']') ++p;
     }
 };
@@ -138,11 +162,21 @@ struct SafeTensors : WeightFile {
     explicit SafeTensors(const char* path) {
         f = std::fopen(path, "rb");
         if (!f) fail(MI_ERR_IO, "cannot open weights file '%s'", path);
+        try {
+            parse(path);
+        } catch (...) {  // the destructor does not run for a constructor that throws
+            std::fclose(f);
+            f = nullptr;
+            throw;
+        }
+    }
+    void parse(const char* path) {
         std::fseek(f, 0, SEEK_END);
-        file_size = (uint64_t)std::ftell(f);
+        const long fs = std::ftell(f);
         std::fseek(f, 0, SEEK_SET);
+        file_size = fs < 0 ? 0 : (uint64_t)fs;
         uint64_t hl = 0;
-        if (std::fread(&hl, 8, 1, f) != 1 || hl == 0 || hl > file_size - 8 || hl > (256u << 20))
+        if (file_size < 8 || std::fread(&hl, 8, 1, f) != 1 || hl == 0 || hl > file_size - 8 || hl > (256u << 20))
             fail(MI_ERR_IO, "'%s' is not a safetensors file (bad header length)", path);
         std::string h(hl, '\0');
         if (std::fread(&h[0], 1, hl, f) != hl) fail(MI_ERR_IO, "'%s': truncated header", path);
@@ -170,12 +204,23 @@ struct SafeTensors : WeightFile {
                         if (!j.peek(']')) do { t.shape.push_back(j.num()); } while (j.peek(',') && ++j.p);
                         j.expect(']');
                     } else if (key == "data_offsets") {
-                        j.expect('['); t.begin = (uint64_t)j.num(); j.expect(','); t.end = (uint64_t)j.num(); j.expect(']');
+                        j.expect('[');
+                        const int64_t b = j.num();
+                        j.expect(',');
+                        const int64_t en = j.num();
+                        j.expect(']');
+                        if (b < 0 || en < b || (uint64_t)en > file_size - data_start)
+                            fail(MI_ERR_IO, "tensor '%s': data offsets outside the file", name.c_str());
+                        t.begin = (uint64_t)b;
+                        t.end = (uint64_t)en;
                     } else j.skip();
                 } while (j.peek(',') && ++j.p);
                 j.expect('}');
-                if (data_start + t.end > file_size || t.begin > t.end)
-                    fail(MI_ERR_IO, "tensor '%s': data offsets outside the file", name.c_str());
+                const int64_t n = checked_numel(t.shape, name.c_str());
+                // a dtype this library does not read (an integer tensor of a full checkpoint) is listed as it stands
+                if (const size_t esz = dtype_size(t.dtype))
+                    if (t.end - t.begin != (uint64_t)n * esz) fail(MI_ERR_IO, "tensor '%s': byte size mismatch", name.c_str());
+                if (tensors.count(name)) fail(MI_ERR_IO, "tensor '%s' appears twice in the header", name.c_str());
                 tensors[name] = t;
                 order.push_back(name);
             } while (j.peek(',') && ++j.p);
@@ -197,9 +242,9 @@ struct SafeTensors : WeightFile {
         const TensorInfo& t = info(name);
         if (t.numel() != numel)
             fail(MI_ERR_IO, "tensor '%s' has %lld elements, expected %lld", name.c_str(), (long long)t.numel(), (long long)numel);
-        const size_t esz = t.dtype == "F32" ? 4 : (t.dtype == "F16" || t.dtype == "BF16") ? 2 : 0;
+        const size_t esz = dtype_size(t.dtype);
         if (!esz) fail(MI_ERR_UNSUPPORTED, "tensor '%s': dtype %s (F32/F16/BF16 supported)", name.c_str(), t.dtype.c_str());
-        if (t.end - t.begin != (uint64_t)numel * esz) fail(MI_ERR_IO, "tensor '%s': byte size mismatch", name.c_str());
+        if (t.end - t.begin != (uint64_t)numel * esz) fail(MI_ERR_IO, "tensor '%s': byte size mismatch", name.c_str());  // held since the header was read
         std::vector<float> out((size_t)numel);
         if (fseeko(f, (off_t)(data_start + t.begin), SEEK_SET) != 0) fail(MI_ERR_IO, "seek failed");
         if (esz == 4) {
@@ -364,21 +409,23 @@ struct BurnMpk : WeightFile {
             if (key == "shape") {
                 const Val a = head(c, e);
                 if (a.kind != Val::ARR) bad("tensor shape is not an array");
-                for (size_t j = 0; j < a.n; ++j) { const Val d = head(c, e); if (d.kind != Val::INT || d.i < 0) bad("bad dimension"); t.shape.push_back(d.i); }
+                for (size_t j = 0; j < a.n; ++j) { const Val d = head(c, e); if (d.kind != Val::INT || d.i < 0 || d.i > 0x7fffffffLL) bad("bad dimension"); t.shape.push_back(d.i); }
             } else if (key == "bytes") {
                 const uint8_t* s = c;
                 const Val b = head(c, e);
                 if (b.kind == Val::BIN) { t.data = b.p; t.bytes = b.n; }
                 else if (b.kind == Val::ARR) {  // a sequence of u8 (serde without serde_bytes): copy out
                     t.values.clear();
+                    need(c, e, b.n);  // an element takes a byte at least: the count is held against what is left of the file
                     std::vector<uint8_t> tmp(b.n);
-                    for (size_t j = 0; j < b.n; ++j) { const Val x = head(c, e); if (x.kind != Val::INT) bad("bad byte"); tmp[j] = (uint8_t)x.i; }
+                    for (size_t j = 0; j < b.n; ++j) { const Val x = head(c, e); if (x.kind != Val::INT || x.i < 0 || x.i > 255) bad("bad byte"); tmp[j] = (uint8_t)x.i; }
                     owned.emplace_back(std::move(tmp));
                     t.data = owned.back().data(); t.bytes = owned.back().size();
                 } else { c = s; bad("tensor bytes are neither bin nor array"); }
             } else if (key == "value") {
                 const Val a = head(c, e);
                 if (a.kind != Val::ARR) bad("tensor value is not an array");
+                need(c, e, a.n);
                 t.values.resize(a.n);
                 for (size_t j = 0; j < a.n; ++j) { const Val x = head(c, e); t.values[j] = x.kind == Val::FLT ? (float)x.f : x.kind == Val::INT ? (float)x.i : (bad("bad value"), 0.0f); }
             } else if (key == "dtype") {
@@ -389,10 +436,9 @@ struct BurnMpk : WeightFile {
             } else skip(c, e, depth + 1);
         }
         for (auto& ch : t.dtype) ch = (char)std::toupper((unsigned char)ch);
-        int64_t numel = 1;
-        for (auto d : t.shape) numel *= d;
+        const int64_t numel = checked_numel(t.shape, path.c_str());
         if (t.values.empty() && t.data) {
-            const size_t esz = t.dtype == "F32" ? 4 : (t.dtype == "F16" || t.dtype == "BF16") ? 2 : 0;
+            const size_t esz = dtype_size(t.dtype);
             if (esz && t.bytes != (size_t)numel * esz) fail(MI_ERR_IO, "'%s': tensor '%s' holds %zu bytes for %lld %s elements", path_.c_str(), path.c_str(), t.bytes, (long long)numel, t.dtype.c_str());
         } else if ((int64_t)t.values.size() != numel) fail(MI_ERR_IO, "'%s': tensor '%s' holds %zu values for shape of %lld", path_.c_str(), path.c_str(), t.values.size(), (long long)numel);
         raws.push_back(std::move(t));
@@ -453,8 +499,7 @@ struct BurnMpk : WeightFile {
         //   * a dtype that is not F32 / F16 / BF16;   * fewer elements than the smallest tower dimension can have (< 8).
         std::vector<char> skip_leaf(raws.size(), 0);
         for (size_t i = 0; i < raws.size(); ++i) {
-            int64_t numel = 1;
-            for (auto d : raws[i].shape) numel *= d;
+            const int64_t numel = checked_numel(raws[i].shape, raws[i].path.c_str());
             const bool is_float = raws[i].dtype == "F32" || raws[i].dtype == "F16" || raws[i].dtype == "BF16";
             if (i != conv && (!is_float || numel < 8)) { skip_leaf[i] = 1; skipped.push_back(i); }
         }
@@ -468,7 +513,7 @@ struct BurnMpk : WeightFile {
             else if (s.size() == 2 && s[0] == D && s[1] == D) sq.push_back(i);
             else if (s.size() == 2 && (s[0] == D || s[1] == D)) {
                 const int64_t o = s[0] == D ? s[1] : s[0];
-                const int64_t g = (int64_t)std::llround(std::sqrt((double)(o - 1)));
+                const int64_t g = o >= 1 ? (int64_t)std::llround(std::sqrt((double)(o - 1))) : 0;
                 if (s[1] == D && g * g + 1 == o && o != D) pos.push_back(i);         // [S, D], S - 1 a square: positions
                 else other.push_back(i);
             } else fail(MI_ERR_UNSUPPORTED, "'%s': tensor '%s' fits no role in a CLIP vision tower: %s", path_.c_str(), raws[i].path.c_str(), inventory().c_str());
@@ -534,7 +579,11 @@ struct BurnMpk : WeightFile {
         put(v + "embeddings.patch_embedding.weight", conv, false, raws[conv].shape);
         put(v + "embeddings.position_embedding.weight", pos[0], false, squeeze(raws[pos[0]].shape));
         size_t vd = 0, vf = 0, q = 0, o = 0;
-        auto vec = [&](const std::string& name) { put(name, vecD[vd], false, {D}); ++vd; };
+        auto vec = [&](const std::string& name) {  // (a projection with a bias and a linear without one pass the counts above)
+            if (vd >= vecD.size()) fail(MI_ERR_UNSUPPORTED, "'%s': no [D]-vector left for '%s': %s", path_.c_str(), name.c_str(), inventory().c_str());
+            put(name, vecD[vd], false, {D});
+            ++vd;
+        };
         // Burn keeps a Linear weight [d_in, d_out]; PyTorch (and this library) [d_out, d_in]
         auto lin = [&](const std::string& name, size_t raw, int64_t d_out, int64_t d_in) {
             const auto s = squeeze(raws[raw].shape);
@@ -550,7 +599,8 @@ struct BurnMpk : WeightFile {
                 if (squeeze(raws[it->second].shape)[0] != d_out) fail(MI_ERR_UNSUPPORTED, "'%s': '%s' is not a bias of %lld elements", path_.c_str(), raws[it->second].path.c_str(), (long long)d_out);
                 put(base + ".bias", it->second, false, {d_out});
             } else if (d_out == D) vec(base + ".bias");
-            else put(base + ".bias", vecF[vf++], false, {FF});
+            else if (vf < vecF.size()) put(base + ".bias", vecF[vf++], false, {FF});
+            else fail(MI_ERR_UNSUPPORTED, "'%s': no [FF]-vector left for '%s': %s", path_.c_str(), base.c_str(), inventory().c_str());
         };
         vec(v + "embeddings.class_embedding");
         vec(v + "pre_layrnorm.weight");
@@ -589,12 +639,13 @@ struct BurnMpk : WeightFile {
         auto it = mapped.find(name);
         if (it == mapped.end()) fail(MI_ERR_IO, "weights file lacks tensor '%s'", name.c_str());
         const Raw& r = raws[it->second.raw];
-        int64_t n = 1;
-        for (auto d : r.shape) n *= d;
+        const int64_t n = checked_numel(r.shape, name.c_str());
         if (n != numel) fail(MI_ERR_IO, "tensor '%s' ('%s') has %lld elements, expected %lld", name.c_str(), r.path.c_str(), (long long)n, (long long)numel);
+        // only a dtype this library reads had its byte count held against the shape (tensor()): refuse the others before a buffer is sized
+        if (r.values.empty() && !dtype_size(r.dtype)) fail(MI_ERR_UNSUPPORTED, "tensor '%s': dtype %s (F32/F16/BF16 supported)", name.c_str(), r.dtype.c_str());
         std::vector<float> out((size_t)n);
         if (!r.values.empty()) out = r.values;
-        else to_f32(r.data, r.dtype, n, out.data(), name.c_str());
+        else if (n > 0) to_f32(r.data, r.dtype, n, out.data(), name.c_str());
         if (it->second.transpose) {
             const int64_t rows = it->second.info.shape[0], cols = it->second.info.shape[1];  // target [rows = out][cols = in]; stored [in][out]
             std::vector<float> tr((size_t)n);

@@ -274,16 +274,43 @@ def vit_weights(cfg, seed: int = 0) -> dict:
     return out
 
 
-def save_safetensors(weights: dict, path: str, metadata: dict | None = None) -> None:
+def round_to(w: np.ndarray, dtype: str) -> np.ndarray:
+    """fp32 array -> the nearest values a file of `dtype` ("F32", "F16", "BF16") can hold, as fp32: numpy's float16
+    rounding; round-to-nearest-even to the upper 16 bits for bfloat16."""
+    w = np.ascontiguousarray(w, np.float32)
+    if dtype == "F32":
+        return w
+    if dtype == "F16":
+        with np.errstate(over="ignore"):
+            return w.astype(np.float16).astype(np.float32)
+    if dtype == "BF16":
+        u = w.view(np.uint32)
+        return (((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint32) << 16).view(np.float32)
+    raise ValueError(f"dtype {dtype!r}: use F32, F16 or BF16")
+
+
+def encode(w: np.ndarray, dtype: str) -> bytes:
+    """The little-endian bytes of `w` in a file of `dtype`, rounded as round_to does."""
+    r = round_to(w, dtype)
+    if dtype == "F32":
+        return r.astype("<f4").tobytes()
+    if dtype == "F16":
+        return r.astype("<f2").tobytes()
+    return (r.view(np.uint32) >> 16).astype("<u2").tobytes()
+
+
+def save_safetensors(weights: dict, path: str, metadata: dict | None = None, dtype: str = "F32") -> None:
     """Write a Hugging Face `safetensors` file (8-byte LE header length, JSON header,
-    raw little-endian data) without needing the safetensors package."""
+    raw little-endian data) without needing the safetensors package.  dtype "F16" / "BF16":
+    the tensors are rounded to that type and stored in it."""
     import json
+    esz = {"F32": 4, "F16": 2, "BF16": 2}[dtype]
     header, off = {}, 0
     if metadata:
         header["__metadata__"] = {k: str(v) for k, v in metadata.items()}
     for name, w in weights.items():
-        nbytes = int(w.size) * 4
-        header[name] = {"dtype": "F32", "shape": list(w.shape), "data_offsets": [off, off + nbytes]}
+        nbytes = int(w.size) * esz
+        header[name] = {"dtype": dtype, "shape": list(w.shape), "data_offsets": [off, off + nbytes]}
         off += nbytes
     hj = json.dumps(header, separators=(",", ":")).encode()
     hj += b" " * ((8 - len(hj) % 8) % 8)
@@ -291,4 +318,4 @@ def save_safetensors(weights: dict, path: str, metadata: dict | None = None) -> 
         f.write(len(hj).to_bytes(8, "little"))
         f.write(hj)
         for w in weights.values():
-            f.write(np.ascontiguousarray(w, dtype="<f4").tobytes())
+            f.write(encode(w, dtype))

@@ -77,8 +77,12 @@ int mi_device_count(void);
  * (server/src/clip.rs:46-48; weights produced by clip/build.rs:75-83).
  * `weights_path` is a Hugging Face safetensors file holding the
  * CLIPVisionModelWithProjection tensors (vision_model.* + visual_projection.weight,
- * F32/F16/BF16); dimensions are read from the tensor shapes, so any CLIP ViT
- * geometry with head_dim 64 loads (ViT-L/14: 24 x 1024, 16 heads, 257 tokens).
+ * F32/F16/BF16); dimensions are read from the tensor shapes, so the CLIP ViT
+ * geometries the kernels are built for load (ViT-L/14: 24 x 1024, 16 heads, 257 tokens):
+ * head_dim 64, hidden size 128, 256, 384, 512, 768, 1024, 1280, 1536 or 1664, intermediate
+ * size a multiple of 128, G*G + 1 positions (at most 288 in the bf16 precisions).  Any other
+ * geometry is refused here with MI_ERR_UNSUPPORTED, a malformed file with MI_ERR_IO — never
+ * at the first forward.
  * The handle is meant to stay resident across scans (the reference reloads
  * 1.16 GB on every scan). */
 int mi_clip_load(const char* weights_path, int device, int precision, mi_clip** out);

@@ -23,23 +23,23 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from image_search_amd import synth  # noqa: E402
 
 
-def _tensor(a, legacy):
+def _tensor(a, legacy, dtype="F32"):
     a = np.asarray(a)  # rank 0 stays rank 0 (shape [])
     if a.dtype == np.int64:  # integer leaves (position ids, Reshape shapes): never a tower tensor
         if legacy:
             return {"value": [int(x) for x in a.reshape(-1)], "shape": list(a.shape)}
         return {"bytes": a.tobytes(), "shape": list(a.shape), "dtype": "I64"}
     a = a.astype(np.float32)
-    if legacy:
-        return {"value": [float(x) for x in a.reshape(-1)], "shape": list(a.shape)}
-    return {"bytes": np.ascontiguousarray(a).tobytes(), "shape": list(a.shape), "dtype": "F32"}
+    if legacy:  # a list of numbers has no dtype: the values are those a `dtype` file holds
+        return {"value": [float(x) for x in synth.round_to(a, dtype).reshape(-1)], "shape": list(a.shape)}
+    return {"bytes": synth.encode(a, dtype), "shape": list(a.shape), "dtype": dtype}
 
 
-def _param(a, n, legacy):
-    return {"id": f"{n:032x}", "param": _tensor(a, legacy)}
+def _param(a, n, legacy, dtype="F32"):
+    return {"id": f"{n:032x}", "param": _tensor(a, legacy, dtype)}
 
 
-def burn_record(weights: dict, cfg, legacy: bool = False, decomposed_ln: bool = False, coalesced: bool = True) -> dict:
+def burn_record(weights: dict, cfg, legacy: bool = False, decomposed_ln: bool = False, coalesced: bool = True, dtype: str = "F32") -> dict:
     """`decomposed_ln=False`: LayerNorm as `layernormalizationN {gamma, beta, epsilon}` modules (an opset >= 17 graph).
     `decomposed_ln=True`: the inventory of the graph the reference really imports — opset 16
     (/root/reference/clip/scripts/upgrade_opset.py:9-28), LayerNorm as ReduceMean / Sub / Pow / ReduceMean / Add / Sqrt /
@@ -47,7 +47,8 @@ def burn_record(weights: dict, cfg, legacy: bool = False, decomposed_ln: bool = 
     of the decomposition (the Pow exponent and epsilon as rank-0 F32), the attention scale ([1] F32), the QuickGELU factor
     (rank-0), the position ids (I64 [1,S]) and Reshape shapes (I64 [4]); the class embedding keeps its ONNX shape [D].
     `coalesced=False`: MatMul + Add pairs were NOT turned into Linear modules: every weight is a bare `constantN [in,out]`
-    followed by its bias `constantN [out]`."""
+    followed by its bias `constantN [out]`.
+    `dtype` "F16" / "BF16": the float tensors are rounded to that type and stored in it (Burn's half-precision recorder)."""
     item, n = {}, [0]
     counters = {"linear": 0, "layernormalization": 0, "constant": 0, "embedding": 0}
 
@@ -57,7 +58,7 @@ def burn_record(weights: dict, cfg, legacy: bool = False, decomposed_ln: bool = 
 
     def P(a):
         n[0] += 1
-        return _param(a, n[0], legacy)
+        return _param(a, n[0], legacy, dtype)
 
     def const(a):
         item[field("constant")] = P(a)
@@ -116,8 +117,9 @@ def burn_record(weights: dict, cfg, legacy: bool = False, decomposed_ln: bool = 
             "item": item}
 
 
-def write_mpk(weights: dict, cfg, path: str, legacy: bool = False, mutate=None, decomposed_ln: bool = False, coalesced: bool = True):
-    rec = burn_record(weights, cfg, legacy, decomposed_ln, coalesced)
+def write_mpk(weights: dict, cfg, path: str, legacy: bool = False, mutate=None, decomposed_ln: bool = False, coalesced: bool = True,
+              dtype: str = "F32"):
+    rec = burn_record(weights, cfg, legacy, decomposed_ln, coalesced, dtype)
     if mutate:
         mutate(rec)
     with open(path, "wb") as f:
