@@ -80,6 +80,11 @@ SYMBOLS = {
     "mi_knn_search_compound_stats": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_knn_search_page": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint64, ctypes.c_float, c_vp,
                                           ctypes.c_uint64, c_vp, c_vp, c_vp]),
+    "mi_knn_set_groups": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp]),
+    "mi_knn_get_groups": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp]),
+    "mi_knn_groups_info": (ctypes.c_int, [c_vp, c_u64p]),
+    "mi_knn_search_grouped": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, c_vp, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp,
+                                             c_vp, ctypes.c_uint64, c_vp]),
     "mi_pairs_to_groups": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_u64p,
                                           c_u64p]),
     "mi_index_duplicates": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,
@@ -111,6 +116,11 @@ SYMBOLS = {
                                                       ctypes.c_uint32, c_vp, ctypes.c_uint64, c_vp, c_vp]),
     "mi_knn_sharded_search_page": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint64, ctypes.c_float, c_vp,
                                                   ctypes.c_uint64, c_vp, c_vp, c_vp]),
+    "mi_knn_sharded_set_groups": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp]),
+    "mi_knn_sharded_get_groups": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp]),
+    "mi_knn_sharded_groups_info": (ctypes.c_int, [c_vp, c_u64p]),
+    "mi_knn_sharded_search_grouped": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, c_vp, ctypes.c_uint64, c_vp, c_vp,
+                                                     c_vp, c_vp, c_vp, ctypes.c_uint64, c_vp]),
     "mi_knn_sharded_assign": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_sharded_assign_multi": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp]),
     "mi_knn_sharded_search_many": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
@@ -145,6 +155,12 @@ SYMBOLS = {
     "mi_index_search_page": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t,
                                             ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_uint32, ctypes.c_float,
                                             ctypes.c_uint64, ctypes.c_float, c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32), c_vp]),
+    "mi_index_search_grouped": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t,
+                                               ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_uint32, ctypes.c_float,
+                                               c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32), c_vp, ctypes.c_uint64, c_vp]),
+    "mi_index_group_name": (ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,
+                                           ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_index_group_count": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint32)]),
     "mi_index_save": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_index_load": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_knn_merge": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),

@@ -222,6 +222,26 @@ struct mi_knn {
     int compound_blocks = 0;
     // mi_knn_search_page (page.hip): workgroups of its scan (option "page_blocks": 0 = the single pass's grid)
     int page_blocks = 0;
+    // The group column (grouped.hip): one group id per row of capacity, MI_KNN_NO_GROUP = none.  d_groups exists from the first
+    // mi_knn_set_groups on (sized by `cap`, carried over by grow(), the rows it gains hold no group); h_groups = the same on the
+    // host for the rows it has been told about (what get_groups, groups_info and a rebalance read).  n_groups = 1 + the largest
+    // group id ever set, n_grouped = rows that hold one; groups_epoch counts the set calls (the index tells from it whether the
+    // column still holds what it uploaded).
+    uint32_t* d_groups = nullptr;
+    size_t groups_cap = 0;
+    std::vector<uint32_t> h_groups;
+    uint32_t n_groups = 0;
+    uint64_t n_grouped = 0, groups_epoch = 0;
+    // mi_knn_search_grouped: the slot arrays best [n_groups] u64 | cnt [n_groups] u32 (gslots_cap in 32-bit words) — after a
+    // search they hold that search's values (gslots_valid; gslots_groups = its n_groups) for knn_grouped_members; d_gwin = the
+    // groups asked there and their counts; workgroups of the reduce and mark passes (option "group_blocks": 0 = four per CU)
+    // and the largest n_groups that takes the block-private LDS form of the reduce (option "group_lds_max")
+    uint32_t* d_gslots = nullptr;
+    uint32_t* d_gwin = nullptr;
+    size_t gslots_cap = 0, gwin_cap = 0;
+    bool gslots_valid = false;
+    uint32_t gslots_groups = 0;
+    int group_blocks = 0, group_lds_max = 4096;
     std::mutex mu;
 };
 
@@ -318,6 +338,18 @@ void knn_search_compound(mi_knn* t, const float* pos, uint32_t n_pos, int mode, 
 // built from (after_dist, after_id), which must name a row of t; otherwise first_key (inclusive) is taken as given
 void knn_search_page(mi_knn* t, const float* q, uint32_t k, bool cursor_is_id, float after_dist, uint64_t after_id, uint64_t first_key,
                      float max_dist, const uint64_t* among, uint64_t n_among, uint64_t* idx, float* dist, uint64_t* counts);
+// page.hip: knn_page_scan_kernel<NCH, 1> without a cursor — one distance key per row or list entry (0xFFFFFFFF outside [0, hi]) and
+// counts += {0, window, beyond, nan}; t->mu held, device selected, the query in t->d_q
+void knn_page_scan_keys32(mi_knn* t, hipStream_t s, uint64_t n, const uint32_t* list, const uint64_t* tomb, uint64_t hi, uint32_t k,
+                          uint32_t* keys32, unsigned long long* counts);
+void knn_groups_fit(mi_knn* t);   // knn.hip: the group column covers `cap` rows (created on first use; new rows hold no group); t->mu held, device selected
+// grouped.hip: mi_knn_search_grouped behind its argument check (grouped_host.h); takes t->mu.  cnt_out (nullable): the per-group
+// counts of this search, [t->n_groups]
+void knn_search_grouped(mi_knn* t, const float* q, uint32_t k, float max_dist, const uint64_t* among, uint64_t n_among, uint64_t* idx,
+                        float* dist, uint32_t* group, uint64_t* members, uint64_t* facets, uint64_t cap_facets, uint64_t* totals,
+                        std::vector<uint32_t>* cnt_out);
+// out[j] = t's count, from its last grouped search, of group[j] (0: no group, unknown group, or that search had no candidate); takes t->mu
+void knn_grouped_members(mi_knn* t, const uint32_t* group, uint32_t k, uint32_t* out);
 // sharded.hip
 void sharded_place(const mi_knn_sharded* t, uint64_t r, uint32_t* s, uint64_t* local);
 uint64_t sharded_rows_of(const mi_knn_sharded* t, uint64_t total, uint32_t s);  // rows shard s holds when the table holds `total`

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "common.h"
+#include "grouped_host.h"
 #include "handles.h"
 
 using namespace mi;
@@ -39,6 +40,12 @@ struct mi_index {
     std::unordered_map<std::string, std::vector<uint64_t>> rows_of;  // image_path -> row ids, ascending (live rows only)
     std::set<std::string> live;                                // the keys of rows_of, ordered: a folder is one range of it
     std::vector<uint8_t> removed;                              // row id -> deleted by mi_index_remove (the table's tombstones)
+    // mi_index_search_grouped: directory <-> group id, row id -> group id, and what the table's column holds of it: the first
+    // groups_uploaded rows, as long as the table's groups_epoch is the one our last upload left (anybody else's
+    // mi_knn_set_groups moves it on, and the next grouped search uploads everything again)
+    GroupDict dirs;
+    std::vector<uint32_t> row_dir;
+    uint64_t groups_uploaded = 0, groups_epoch = 0;
     std::mutex mu;
 };
 
@@ -51,6 +58,28 @@ void add_path(mi_index* ix, const std::string& p, bool removed = false) {
     }
     ix->paths.push_back(p);
     ix->removed.push_back(removed ? 1 : 0);
+    ix->row_dir.push_back(ix->dirs.of_path(p));
+}
+
+uint64_t table_groups_epoch(mi_knn* t) {
+    std::lock_guard<std::mutex> l(t->mu);
+    return t->groups_epoch;
+}
+
+// the table's group column holds every row's directory id; ix->mu held
+void sync_groups(mi_index* ix) {
+    if (ix->dirs.names.size() > MI_KNN_GROUPS_MAX) fail(MI_ERR_UNSUPPORTED, "%zu directories: a table holds at most 2^24 groups", ix->dirs.names.size());
+    if (table_groups_epoch(ix->table) != ix->groups_epoch) ix->groups_uploaded = 0;   // somebody else wrote the column (or nobody has)
+    const uint64_t rows = ix->row_dir.size();
+    if (ix->groups_uploaded == rows && (rows || ix->groups_epoch)) return;
+    if (rows > ix->groups_uploaded) {
+        std::vector<uint64_t> ids((size_t)(rows - ix->groups_uploaded));
+        for (size_t i = 0; i < ids.size(); ++i) ids[i] = ix->groups_uploaded + i;
+        const int e = mi_knn_set_groups(ix->table, ids.data(), ids.size(), ix->row_dir.data() + ix->groups_uploaded);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+    }
+    ix->groups_uploaded = rows;
+    ix->groups_epoch = table_groups_epoch(ix->table);
 }
 
 // "media/x.jpg" as the client names it -> the path the row was stored under (search.rs:35-40: only such names are looked up)
@@ -333,6 +362,64 @@ int mi_index_search_page(mi_index* ix, const float* text_embedding, const char* 
         const int e = mi_knn_search_page(ix->table, query.data(), k, after_dist, after_id, max_dist, among, ids.size(), idx, dist, counts);
         if (e != MI_OK) fail(e, "%s", mi_last_error());
         if (n_results) *n_results = hits(idx, k);
+    });
+}
+
+// the best hit per directory: the refined query of mi_index_search, the row set of mi_index_search_within when folders are
+// given (n_folders = 0: the whole table), the table's column brought up to date, then mi_knn_search_grouped
+int mi_index_search_grouped(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
+                            const char* const* folders, size_t n_folders, uint32_t k, float max_dist, uint64_t* idx, float* dist,
+                            uint32_t* group, uint64_t* members, uint32_t* n_found, uint64_t* facets, uint64_t cap_facets,
+                            uint64_t totals[4]) {
+    return guarded([&] {
+        if (!ix || !text_embedding || !idx || !dist || (n_ref && !referenced_images) || (n_folders && !folders))
+            fail(MI_ERR_INVALID, "null argument");
+        std::vector<uint64_t> ids;
+        if (n_folders) ids = folder_rows(ix, folders, n_folders);
+        const std::vector<float> query = refined_query(ix, text_embedding, referenced_images, n_ref);
+        size_t n_dirs = 0;
+        {
+            std::lock_guard<std::mutex> l(ix->mu);
+            n_dirs = ix->dirs.names.size();
+            if (facets && cap_facets < n_dirs) fail(MI_ERR_INVALID, "facets holds %llu entries, the index has %zu groups", (unsigned long long)cap_facets, n_dirs);
+            sync_groups(ix);
+        }
+        // the table may know more groups than the index has directories (labels a caller once set on it): its facets go through
+        // a buffer of the table's size, the directories' part reaches the caller
+        uint64_t info[2] = {0, 0};
+        if (mi_knn_groups_info(ix->table, info) != MI_OK) fail(MI_ERR_INVALID, "%s", mi_last_error());
+        std::vector<uint64_t> all(facets ? (size_t)std::max<uint64_t>(info[0], 1) : 0);
+        const uint64_t none = 0;   // folders that match nothing are an empty row set, not "the whole table"
+        const uint64_t* among = n_folders ? (ids.empty() ? &none : ids.data()) : nullptr;
+        const int e = mi_knn_search_grouped(ix->table, query.data(), k, max_dist, among, ids.size(), idx, dist, group, members,
+                                            facets ? all.data() : nullptr, all.size(), totals);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        if (facets) std::copy(all.begin(), all.begin() + std::min(n_dirs, all.size()), facets);
+        if (n_found) *n_found = hits(idx, k);
+    });
+}
+
+int mi_index_group_name(mi_index* ix, uint32_t group, int web, char* buf, size_t cap, size_t* needed) {
+    return guarded([&] {
+        if (!ix) fail(MI_ERR_INVALID, "null index handle");
+        std::lock_guard<std::mutex> l(ix->mu);
+        if (group >= ix->dirs.names.size()) fail(MI_ERR_INVALID, "group %u is not a directory of this index (%zu groups)", group, ix->dirs.names.size());
+        std::string p = ix->dirs.names[group];
+        if (web && !ix->media_dir.empty() && p.compare(0, ix->media_dir.size(), ix->media_dir) == 0) p = "media/" + p.substr(ix->media_dir.size());
+        if (needed) *needed = p.size() + 1;
+        if (buf && cap) {
+            const size_t n = std::min(cap - 1, p.size());
+            std::memcpy(buf, p.data(), n);
+            buf[n] = '\0';
+        }
+    });
+}
+
+int mi_index_group_count(mi_index* ix, uint32_t* n_groups) {
+    return guarded([&] {
+        if (!ix || !n_groups) fail(MI_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> l(ix->mu);
+        *n_groups = (uint32_t)ix->dirs.names.size();
     });
 }
 

@@ -104,6 +104,26 @@ void tomb_rebuild(mi_knn* t) {
     HIP_CHECK(hipStreamSynchronize(t->stream));
 }
 
+// ---- the group column (handles.h: d_groups; grouped.hip) ---------------------------------------------------------
+// one id per row of capacity, the rows it gains hold MI_KNN_NO_GROUP (all ones); nothing in flight may use the old one
+void groups_fit(mi_knn* t) {
+    const size_t want = std::max<size_t>((size_t)t->cap, 64);
+    if (t->groups_cap >= want && t->d_groups) return;
+    t->writes.sync();
+    t->reads.sync();
+    uint32_t* nb = nullptr;
+    HIP_CHECK(hipMalloc((void**)&nb, want * sizeof(uint32_t)));
+    // on the handle's own stream, and waited for: that stream does not order itself behind the null stream, and an upload
+    // enqueued on it next must not be overtaken by this fill
+    hipStream_t s = own_stream(t);
+    HIP_CHECK(hipMemsetAsync(nb, 0xFF, want * sizeof(uint32_t), s));
+    if (t->d_groups) HIP_CHECK(hipMemcpyAsync(nb, t->d_groups, t->groups_cap * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (t->d_groups) HIP_CHECK(hipFree(t->d_groups));
+    t->d_groups = nb;
+    t->groups_cap = want;
+}
+
 // id -> local row of this table (its own id space: base, and the block-cyclic map of a shard); false if it holds no such row
 bool local_of(const mi_knn* t, uint64_t id, uint64_t* local) {
     if (id < t->base) return false;
@@ -138,6 +158,7 @@ void grow(mi_knn* t, uint64_t want_rows) {
     t->table = nt;
     t->cap = ncap;
     if (t->d_tomb) tomb_fit(t);  // the deletion bitmap keeps one bit per row of capacity
+    if (t->d_groups) groups_fit(t);  // the group column one id
 }
 
 template <class K>
@@ -952,6 +973,7 @@ void knn_search_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint6
     search_many(t, d_q, nq, k, d_idx, d_dist, s);
 }
 void knn_grow(mi_knn* t, uint64_t want_rows) { grow(t, want_rows); }
+void knn_groups_fit(mi_knn* t) { groups_fit(t); }
 void knn_search_one(mi_knn* t, const float* d_q, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
     search_one(t, d_q, k, d_idx, d_dist, s);
 }
@@ -960,6 +982,17 @@ void knn_truncate(mi_knn* t, uint64_t rows) {
     if (rows >= t->rows) return;
     t->rows = rows;
     t->mirror_rows = std::min(t->mirror_rows, rows);
+    // ... and their groups (a later append reuses those rows, without a group)
+    if (t->d_groups && rows < t->groups_cap) {
+        DeviceGuard g(t->device);
+        t->writes.sync();
+        t->reads.sync();
+        HIP_CHECK(hipMemsetAsync(t->d_groups + rows, 0xFF, (t->groups_cap - (size_t)rows) * sizeof(uint32_t), own_stream(t)));
+        HIP_CHECK(hipStreamSynchronize(t->stream));
+        for (size_t r = (size_t)rows; r < t->h_groups.size(); ++r) t->n_grouped -= t->h_groups[r] != MI_KNN_NO_GROUP;
+        if (t->h_groups.size() > rows) t->h_groups.resize((size_t)rows);
+        ++t->groups_epoch;
+    }
     // the rows beyond are forgotten, their tombstones with them (a later append reuses those rows, live)
     const auto cut = std::lower_bound(t->dead.begin(), t->dead.end(), (uint32_t)std::min<uint64_t>(rows, 0xFFFFFFFFull));
     if (cut != t->dead.end()) {
@@ -1012,7 +1045,7 @@ void mi_knn_free(mi_knn* t) {
                     (void*)t->d_idx, (void*)t->d_dist, (void*)t->d_keys32, (void*)t->d_sel, (void*)t->d_mirror,
                     (void*)t->d_xx, (void*)t->d_pref_rows, (void*)t->d_pref_keys, (void*)t->d_pref_flag, (void*)t->d_scale8,
                     (void*)t->d_cfac8, (void*)t->d_rho8, (void*)t->d_g8, (void*)t->d_digits, (void*)t->d_qs, (void*)t->d_skeys, (void*)t->d_tomb, (void*)t->d_dead,
-                    (void*)t->d_flist})
+                    (void*)t->d_flist, (void*)t->d_groups, (void*)t->d_gslots, (void*)t->d_gwin})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : t->pref_ev)
         if (e) (void)hipEventDestroy(e);
@@ -1082,8 +1115,19 @@ int mi_knn_set_option(mi_knn* t, const char* key, int value) {
             // v >= 1: exactly min(v, tiles / 4).  Same answers whatever the value.
             if (value < 0) fail(MI_ERR_INVALID, "page_blocks must be >= 0 (got %d)", value);
             t->page_blocks = value;
+        } else if (k == "group_blocks") {
+            // mi_knn_search_grouped: workgroups of its reduce and mark passes.  0 (default): four per CU; v >= 1: exactly
+            // min(v, keys / 256).  Same answers whatever the value.
+            if (value < 0) fail(MI_ERR_INVALID, "group_blocks must be >= 0 (got %d)", value);
+            t->group_blocks = value;
+        } else if (k == "group_lds_max") {
+            // ... the largest n_groups whose reduce pass builds block-private tables in LDS (12 bytes per group; default and
+            // maximum 4096 = 48 KiB, two workgroups per CU); above it, and with 0 always, the pass works on the global slots.
+            // Same answers whatever the value.
+            if (value < 0 || value > 4096) fail(MI_ERR_INVALID, "group_lds_max must be in [0, 4096] (got %d)", value);
+            t->group_lds_max = value;
         } else {
-            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, many_segments, many_sample, compound_blocks, page_blocks)", key);
+            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, many_segments, many_sample, compound_blocks, page_blocks, group_blocks, group_lds_max)", key);
         }
     });
 }

@@ -40,6 +40,15 @@ PageIds page_ids(const mi_knn* t) { return PageIds{t->base, t->rows, t->cyc_bloc
 
 namespace mi {
 
+// the scan without a cursor in its one-key-per-row form, for the grouped search (grouped.hip): keys32 [n] = the distance key of
+// every row or list entry, 0xFFFFFFFF outside the window [0, hi]; counts += {0, window, beyond, nan}.  t->mu held, device
+// selected, the query in t->d_q
+void knn_page_scan_keys32(mi_knn* t, hipStream_t s, uint64_t n, const uint32_t* list, const uint64_t* tomb, uint64_t hi, uint32_t k,
+                          uint32_t* keys32, unsigned long long* counts) {
+    const uint32_t blocks = page_grid(n, t->n_cu, t->page_blocks);
+    dispatch_nch(t->dim, [&](auto nch) { launch_scan<decltype(nch)::value>(t, blocks, s, n, list, tomb, 0, hi, k, nullptr, keys32, counts); });
+}
+
 // the call behind the C entry points (arguments checked by page_check_args); throws Error.  cursor_is_id: first_key is built
 // here from (after_dist, after_id), which must name a row of t; otherwise the caller — the sharded call — hands first_key over.
 void knn_search_page(mi_knn* t, const float* q, uint32_t k, bool cursor_is_id, float after_dist, uint64_t after_id, uint64_t first_key,

@@ -39,6 +39,7 @@
 #include "common.h"
 #include "compound_host.h"
 #include "handles.h"
+#include "grouped_host.h"
 #include "page_host.h"
 #include "two_stage.h"
 
@@ -662,6 +663,79 @@ int mi_knn_sharded_search_page(mi_knn_sharded* t, const float* q, uint32_t k, fl
     });
 }
 
+// mi_knn_search_grouped on global ids: every shard answers with its k best representatives (global ids, its own column); the
+// host merges them by group id (grouped_host.h: grouped_merge).  members of the winners: every shard gathers its counts of the
+// k winning groups on the device, the host sums k words per shard.  facets / totals[0] need the shards' whole count arrays.
+int mi_knn_sharded_search_grouped(mi_knn_sharded* t, const float* q, uint32_t k, float max_dist, const uint64_t* among,
+                                  uint64_t n_among, uint64_t* idx, float* dist, uint32_t* group, uint64_t* members,
+                                  uint64_t* facets, uint64_t cap_facets, uint64_t totals[4]) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = grouped_check_args(t, q, k, max_dist, among, n_among, idx, dist, &why);
+        if (bad != MI_OK) fail(bad, "%s (k %u)", why, k);
+        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
+        std::lock_guard<std::mutex> l(t->mu);
+        const uint32_t n = t->n();
+        uint64_t n_groups = 0;
+        for (mi_knn* sh : t->shard) {
+            std::lock_guard<std::mutex> ls(sh->mu);
+            n_groups = std::max<uint64_t>(n_groups, sh->n_groups);
+        }
+        if (facets && cap_facets < n_groups)
+            fail(MI_ERR_INVALID, "facets holds %llu entries, the table has %llu groups", (unsigned long long)cap_facets, (unsigned long long)n_groups);
+        std::vector<std::vector<uint64_t>> per(n);
+        for (uint64_t i = 0; i < n_among; ++i) {  // every id checked before anything runs
+            if (among[i] >= t->rows)
+                fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)among[i], (unsigned long long)t->rows);
+            uint32_t s; uint64_t local;
+            sharded_place(t, among[i], &s, &local);
+            per[s].push_back(among[i]);
+        }
+        sharded_deliver_all(t);
+        const bool sums = facets || totals;
+        std::vector<uint64_t> all_idx((size_t)n * k), all_totals((size_t)n * 4, 0);
+        std::vector<float> all_dist((size_t)n * k);
+        std::vector<uint32_t> all_group((size_t)n * k);
+        std::vector<std::vector<uint32_t>> cnt(n);
+        const uint64_t none = 0;   // a shard that holds none of the ids: an empty candidate set, not "every row"
+        for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
+            const uint64_t* ids = among ? (per[si].empty() ? &none : per[si].data()) : nullptr;
+            knn_search_grouped(sh, q, k, max_dist, ids, per[si].size(), all_idx.data() + (size_t)si * k, all_dist.data() + (size_t)si * k,
+                               all_group.data() + (size_t)si * k, nullptr, nullptr, 0, all_totals.data() + (size_t)si * 4,
+                               sums ? &cnt[si] : nullptr);
+        });
+        std::vector<uint64_t> m_idx(k);
+        std::vector<float> m_dist(k);
+        std::vector<uint32_t> m_group(k);
+        grouped_merge(all_idx.data(), all_dist.data(), all_group.data(), n, k, m_idx.data(), m_dist.data(), m_group.data());
+        if (members) {
+            std::vector<uint32_t> part((size_t)n * k, 0);
+            for_each_shard(t, [&](uint32_t si, mi_knn* sh) { knn_grouped_members(sh, m_group.data(), k, part.data() + (size_t)si * k); });
+            for (uint32_t j = 0; j < k; ++j) {
+                uint64_t m = m_idx[j] == MI_KNN_NO_ID ? 0 : m_group[j] == MI_KNN_NO_GROUP ? 1 : 0;
+                if (m_group[j] != MI_KNN_NO_GROUP)
+                    for (uint32_t si = 0; si < n; ++si) m += part[(size_t)si * k + j];
+                members[j] = m;
+            }
+        }
+        std::copy(m_idx.begin(), m_idx.end(), idx);
+        std::copy(m_dist.begin(), m_dist.end(), dist);
+        if (group) std::copy(m_group.begin(), m_group.end(), group);
+        if (sums) {
+            std::vector<uint64_t> reps(n);
+            for (uint32_t si = 0; si < n; ++si) reps[si] = all_totals[(size_t)si * 4];
+            const uint64_t total_reps = grouped_sum_counts(cnt, reps.data(), n_groups, facets);
+            if (totals) {
+                totals[0] = total_reps;
+                for (int c = 1; c < 4; ++c) {
+                    totals[c] = 0;
+                    for (uint32_t si = 0; si < n; ++si) totals[c] += all_totals[(size_t)si * 4 + c];
+                }
+            }
+        }
+    });
+}
+
 int mi_knn_sharded_sync(mi_knn_sharded* t) {
     return guarded([&] {
         if (!t) fail(MI_ERR_INVALID, "null table handle");
@@ -733,6 +807,87 @@ int mi_knn_sharded_deleted(mi_knn_sharded* t, uint64_t* ids, uint64_t cap, uint6
     });
 }
 
+}  // extern "C"
+
+// ---- the group column: every shard keeps the column of its own rows (grouped.hip) -------------------------------------
+namespace {
+// t->mu held: every id (nullptr: the first n global rows) checked first, then f(shard, its ids, the positions they came from)
+template <class F>
+void route_ids(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, F&& f) {
+    if (!ids && n > t->rows) fail(MI_ERR_INVALID, "%llu rows asked of a table of %llu", (unsigned long long)n, (unsigned long long)t->rows);
+    std::vector<std::vector<uint64_t>> per(t->n()), at(t->n());
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t id = ids ? ids[i] : i;
+        if (id >= t->rows)
+            fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)id, (unsigned long long)t->rows);
+        uint32_t s; uint64_t local;
+        sharded_place(t, id, &s, &local);
+        per[s].push_back(id);
+        at[s].push_back(i);
+    }
+    for (uint32_t s = 0; s < t->n(); ++s)
+        if (!per[s].empty()) f(s, per[s], at[s]);
+}
+void set_groups_locked(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, const uint32_t* groups) {
+    const uint64_t bad = grouped_first_bad(groups, n);   // before any shard is written
+    if (bad < n) fail(MI_ERR_INVALID, "group id %u (entry %llu) is neither below 2^24 nor MI_KNN_NO_GROUP", groups[bad], (unsigned long long)bad);
+    route_ids(t, ids, n, [&](uint32_t s, const std::vector<uint64_t>& mine, const std::vector<uint64_t>& at) {
+        std::vector<uint32_t> g(mine.size());
+        for (size_t i = 0; i < mine.size(); ++i) g[i] = groups[at[i]];
+        const int e = mi_knn_set_groups(t->shard[s], mine.data(), mine.size(), g.data());
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+    });
+}
+void get_groups_locked(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint32_t* groups) {
+    route_ids(t, ids, n, [&](uint32_t s, const std::vector<uint64_t>& mine, const std::vector<uint64_t>& at) {
+        std::vector<uint32_t> g(mine.size());
+        const int e = mi_knn_get_groups(t->shard[s], mine.data(), mine.size(), g.data());
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        for (size_t i = 0; i < mine.size(); ++i) groups[at[i]] = g[i];
+    });
+}
+void groups_info_locked(mi_knn_sharded* t, uint64_t info[2]) {
+    info[0] = info[1] = 0;
+    for (mi_knn* sh : t->shard) {
+        uint64_t one[2] = {0, 0};
+        const int e = mi_knn_groups_info(sh, one);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        info[0] = std::max(info[0], one[0]);
+        info[1] += one[1];
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int mi_knn_sharded_set_groups(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, const uint32_t* groups) {
+    return guarded([&] {
+        if (!t) fail(MI_ERR_INVALID, "null table handle");
+        if (n == 0) return;
+        if (!groups) fail(MI_ERR_INVALID, "groups is null");
+        std::lock_guard<std::mutex> l(t->mu);
+        set_groups_locked(t, ids, n, groups);
+    });
+}
+
+int mi_knn_sharded_get_groups(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint32_t* groups) {
+    return guarded([&] {
+        if (!t) fail(MI_ERR_INVALID, "null table handle");
+        if (n == 0) return;
+        if (!groups) fail(MI_ERR_INVALID, "groups is null");
+        std::lock_guard<std::mutex> l(t->mu);
+        get_groups_locked(t, ids, n, groups);
+    });
+}
+
+int mi_knn_sharded_groups_info(mi_knn_sharded* t, uint64_t info[2]) {
+    return guarded([&] {
+        if (!t || !info) fail(MI_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> l(t->mu);
+        groups_info_locked(t, info);
+    });
+}
+
 // Every row of `src` into the EMPTY `dst` (another shard count, device set or block size) without leaving the devices:
 // src's blocks are walked in global order and each contiguous run is routed by append_device_locked — a device-to-device
 // copy when source and destination shard share a GPU, hipMemcpyPeerAsync over xGMI otherwise.  src is unchanged.
@@ -765,6 +920,13 @@ int mi_knn_sharded_rebalance(mi_knn_sharded* dst, mi_knn_sharded* src) {
             }
             const std::vector<uint64_t> dead = deleted_locked(src);  // global ids: the same rows in the new layout
             if (!dead.empty()) delete_locked(dst, dead.data(), dead.size());
+            uint64_t ginfo[2];
+            groups_info_locked(src, ginfo);
+            if (ginfo[1]) {  // the group column, by global id as the deletions
+                std::vector<uint32_t> col((size_t)src->rows);
+                get_groups_locked(src, nullptr, src->rows, col.data());
+                set_groups_locked(dst, nullptr, src->rows, col.data());
+            }
         } catch (...) {
             dst->rows = 0;
             roll_back(dst);

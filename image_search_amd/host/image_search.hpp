@@ -124,6 +124,21 @@ inline void finish_page(Page& p, uint32_t k) {
     p.idx.resize(n); p.dist.resize(n);
 }
 
+// the best hit per group (mi_knn_search_grouped and its kin): the hits without the padding — group[j] = MI_KNN_NO_GROUP for a row
+// that stands for itself, members[j] = the group's candidates within the bound — totals = {representatives, window, beyond,
+// nan}, and facets (when asked for) = every group's count
+struct Grouped {
+    std::vector<uint64_t> idx, members, facets;
+    std::vector<float> dist;
+    std::vector<uint32_t> group;
+    uint64_t totals[4] = {0, 0, 0, 0};
+};
+inline void finish_grouped(Grouped& g) {
+    size_t n = 0;
+    while (n < g.idx.size() && g.idx[n] != MI_KNN_NO_ID) ++n;
+    g.idx.resize(n); g.dist.resize(n); g.group.resize(n); g.members.resize(n);
+}
+
 class EmbeddingTable {
     mi_knn* h_ = nullptr;
     uint32_t dim_;
@@ -291,6 +306,24 @@ class EmbeddingTable {
         finish_page(r, k);
         return r;
     }
+    // the group column (mi_knn_set_groups): groups[i] for row ids[i], or for the first groups.size() rows; not saved
+    void set_groups(const std::vector<uint32_t>& groups, const std::vector<uint64_t>* ids = nullptr) {
+        check(mi_knn_set_groups(h_, ids ? ids->data() : nullptr, groups.size(), groups.data()));
+    }
+    uint64_t n_groups() const { uint64_t info[2]; check(mi_knn_groups_info(h_, info)); return info[0]; }
+    // of every group the row nearest to `reference` within max_dist, the k nearest of those (mi_knn_search_grouped)
+    Grouped knn_grouped(const std::vector<float>& reference, uint32_t k, float max_dist = INFINITY,
+                        const std::vector<uint64_t>* among = nullptr, bool facets = false) const {
+        Grouped r;
+        r.idx.resize(k); r.dist.resize(k); r.group.resize(k); r.members.resize(k);
+        if (facets) r.facets.assign(n_groups(), 0);
+        static const uint64_t none = 0;   // an empty `among` is an empty set of candidates, not "every row"
+        const uint64_t* ids = among ? (among->empty() ? &none : among->data()) : nullptr;
+        check(mi_knn_search_grouped(h_, reference.data(), k, max_dist, ids, among ? among->size() : 0, r.idx.data(), r.dist.data(),
+                                    r.group.data(), r.members.data(), facets ? r.facets.data() : nullptr, r.facets.size(), r.totals));
+        finish_grouped(r);
+        return r;
+    }
     // "prefilter" = 2 (bytes) or 1 (bf16): the two-stage exact search, same results from a quarter / a half of the bytes
     void set_option(const std::string& key, int value) { check(mi_knn_set_option(h_, key.c_str(), value)); }
 };
@@ -423,6 +456,31 @@ class ImageIndex {
         finish_page(r, k);
         return r;
     }
+    // the best picture of every directory (mi_index_search_grouped): search_page's query and folders, one hit per group
+    Grouped search_grouped(const std::vector<float>& text_embedding, const std::vector<std::string>& referenced_images, uint32_t k,
+                           float max_dist = INFINITY, const std::vector<std::string>& folders = {}, bool facets = false) const {
+        Grouped r;
+        r.idx.resize(k); r.dist.resize(k); r.group.resize(k); r.members.resize(k);
+        uint32_t n_groups = 0, n = 0;
+        check(mi_index_group_count(h_, &n_groups));
+        if (facets) r.facets.assign(n_groups, 0);
+        const auto p = ptrs(referenced_images);
+        const auto f = ptrs(folders);
+        check(mi_index_search_grouped(h_, text_embedding.data(), p.data(), p.size(), f.data(), f.size(), k, max_dist, r.idx.data(),
+                                      r.dist.data(), r.group.data(), r.members.data(), &n, facets ? r.facets.data() : nullptr,
+                                      r.facets.size(), r.totals));
+        finish_grouped(r);
+        return r;
+    }
+    // the directory behind a group id of search_grouped (mi_index_group_name)
+    std::string group_name(uint32_t group, bool web = true) const {
+        size_t need = 0;
+        check(mi_index_group_name(h_, group, web ? 1 : 0, nullptr, 0, &need));
+        std::string s(need, '\0');
+        check(mi_index_group_name(h_, group, web ? 1 : 0, &s[0], need, nullptr));
+        s.resize(need ? need - 1 : 0);
+        return s;
+    }
     // groups of near-duplicate images as paths (mi_index_duplicates), what a /duplicates handler returns; removed paths
     // never appear; first_new: only what the rows from that id on duplicate
     std::vector<std::vector<std::string>> duplicates(float max_dist, uint64_t first_new = 0, bool web = false,
@@ -486,6 +544,23 @@ class ShardedTable {
         std::vector<float> dist((size_t)nq * k);
         check(mi_knn_sharded_search_many(h_, queries.data(), nq, k, idx.data(), dist.data()));
         return {std::move(idx), std::move(dist)};
+    }
+    void set_groups(const std::vector<uint32_t>& groups, const std::vector<uint64_t>* ids = nullptr) {
+        check(mi_knn_sharded_set_groups(h_, ids ? ids->data() : nullptr, groups.size(), groups.data()));
+    }
+    uint64_t n_groups() const { uint64_t info[2]; check(mi_knn_sharded_groups_info(h_, info)); return info[0]; }
+    // EmbeddingTable::knn_grouped over all shards (mi_knn_sharded_search_grouped): global ids, a group counted once
+    Grouped knn_grouped(const std::vector<float>& reference, uint32_t k, float max_dist = INFINITY,
+                        const std::vector<uint64_t>* among = nullptr, bool facets = false) const {
+        Grouped r;
+        r.idx.resize(k); r.dist.resize(k); r.group.resize(k); r.members.resize(k);
+        if (facets) r.facets.assign(n_groups(), 0);
+        static const uint64_t none = 0;
+        const uint64_t* ids = among ? (among->empty() ? &none : among->data()) : nullptr;
+        check(mi_knn_sharded_search_grouped(h_, reference.data(), k, max_dist, ids, among ? among->size() : 0, r.idx.data(), r.dist.data(),
+                                            r.group.data(), r.members.data(), facets ? r.facets.data() : nullptr, r.facets.size(), r.totals));
+        finish_grouped(r);
+        return r;
     }
     // EmbeddingTable::knn_page over all shards (mi_knn_sharded_search_page): global ids, summed counts
     Page knn_page(const std::vector<float>& reference, uint32_t k, const Page* after = nullptr, float max_dist = INFINITY,

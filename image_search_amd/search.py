@@ -83,6 +83,49 @@ def _page_call(fn, handle, dim, lead, reference, k, after, max_dist, tail_ptr=No
     return idx, dist, {"before": counts[0], "window": counts[1], "beyond": counts[2], "nan": counts[3]}, nxt
 
 
+NO_GROUP = np.uint32(0xFFFFFFFF)  # MI_KNN_NO_GROUP: a row that belongs to no group
+
+
+def _set_groups(fn, h, groups, ids):
+    g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint32).reshape(-1))
+    a = None if ids is None else _ids(ids)
+    if a is not None and a.size != g.size:
+        raise ValueError(f"{g.size} groups for {a.size} ids")
+    check(fn(h, a.ctypes.data if a is not None and a.size else None, g.size, g.ctypes.data if g.size else None))
+
+
+def _get_groups(fn, h, ids, rows):
+    a = None if ids is None else _ids(ids)
+    n = rows if a is None else a.size
+    out = np.empty(max(n, 1), np.uint32)
+    check(fn(h, a.ctypes.data if a is not None and a.size else None, n, out.ctypes.data))
+    return out[:n]
+
+
+def _grouped_call(fn, handle, dim, lead, reference, k, max_dist, n_groups, facets, tail_ptr=None, within=None):
+    """one mi_*_search_grouped call -> (idx [k], dist [k], group [k], members [k], totals dict[, facets [n_groups]]): `lead` =
+    the arguments between the query and k (the index's references and folders), within = the id list of the table calls"""
+    q = _f32(reference).reshape(-1)
+    if q.size != dim:
+        raise ValueError(f"a query of {q.size} floats for dim {dim}")
+    k = int(k)
+    idx, dist = np.empty(max(k, 1), np.uint64), np.empty(max(k, 1), np.float32)
+    group, members = np.empty(max(k, 1), np.uint32), np.empty(max(k, 1), np.uint64)
+    totals = (ctypes.c_uint64 * 4)()
+    fac = np.zeros(max(int(n_groups), 1), np.uint64) if facets else None
+    args = [handle, q.ctypes.data] + list(lead) + [k, float(max_dist)]
+    if tail_ptr is None:
+        ids, n_ids, _keep = _among(within)
+        args += [ids, n_ids, idx.ctypes.data, dist.ctypes.data, group.ctypes.data, members.ctypes.data]
+    else:
+        args += [idx.ctypes.data, dist.ctypes.data, group.ctypes.data, members.ctypes.data, tail_ptr]
+    args += [fac.ctypes.data if facets else None, int(n_groups) if facets else 0, totals]
+    check(fn(*args))
+    out = (idx[:k], dist[:k], group[:k], members[:k],
+           {"groups": totals[0], "window": totals[1], "beyond": totals[2], "nan": totals[3]})
+    return out + (fac[:int(n_groups)],) if facets else out
+
+
 def _ptrs(vecs):
     arr = (c_f * len(vecs))()
     for i, v in enumerate(vecs):
@@ -335,6 +378,29 @@ class EmbeddingTable:
         out = (ctypes.c_uint64 * 4)()
         check(lib().mi_knn_search_compound_stats(self._h, out))
         return {"scanned": out[0], "excluded": out[1], "nan": out[2], "results": out[3]}
+
+    def set_groups(self, groups, ids=None):
+        """The group column (mi_knn_set_groups): groups[i] for row ids[i], ids=None: for the first len(groups) rows.  A group id
+        is < 2^24 or NO_GROUP (the row is a group of its own); appended rows start as NO_GROUP; the column is not saved."""
+        _set_groups(lib().mi_knn_set_groups, self._h, groups, ids)
+
+    def groups(self, ids=None) -> np.ndarray:
+        """the group of the rows `ids` (None: of every row) — NO_GROUP where none was set"""
+        return _get_groups(lib().mi_knn_get_groups, self._h, ids, len(self))
+
+    def groups_info(self) -> dict:
+        info = (ctypes.c_uint64 * 2)()
+        check(lib().mi_knn_groups_info(self._h, info))
+        return {"n_groups": info[0], "rows": info[1]}
+
+    def knn_grouped(self, reference: np.ndarray, k: int = 10, max_dist: float = float("inf"), within=None, facets: bool = False):
+        """The best hit per group (mi_knn_search_grouped): of every group the row nearest to `reference` within max_dist, the k
+        nearest of those; rows without a group stand for themselves.  within: None or the ids to search among.  Returns
+        (idx [k], dist [k], group [k], members [k], totals) with members = the group's rows within max_dist and totals =
+        {"groups": representatives within max_dist, "window", "beyond", "nan"}; NO_ID / +inf / NO_GROUP / 0 behind the last
+        hit.  facets=True appends the array of every group's count.  Exact over the whole table; k <= 4096."""
+        return _grouped_call(lib().mi_knn_search_grouped, self._h, self.dim, (), reference, k, max_dist,
+                             self.groups_info()["n_groups"] if facets else 0, facets, within=within)
 
     def knn_page(self, reference: np.ndarray, k: int = 100, after=None, max_dist: float = float("inf"), within=None):
         """The k nearest rows AFTER a cursor and WITHIN a distance (mi_knn_search_page).  after: None (from the start) or the
@@ -714,6 +780,24 @@ class ShardedTable:
                                                    n_ids, idx.ctypes.data, dist.ctypes.data))
         return idx[:k], dist[:k]
 
+    def set_groups(self, groups, ids=None):
+        """EmbeddingTable.set_groups on global ids (mi_knn_sharded_set_groups): every shard keeps the column of its own rows"""
+        _set_groups(lib().mi_knn_sharded_set_groups, self._h, groups, ids)
+
+    def groups(self, ids=None) -> np.ndarray:
+        return _get_groups(lib().mi_knn_sharded_get_groups, self._h, ids, len(self))
+
+    def groups_info(self) -> dict:
+        info = (ctypes.c_uint64 * 2)()
+        check(lib().mi_knn_sharded_groups_info(self._h, info))
+        return {"n_groups": info[0], "rows": info[1]}
+
+    def knn_grouped(self, reference: np.ndarray, k: int = 10, max_dist: float = float("inf"), within=None, facets: bool = False):
+        """EmbeddingTable.knn_grouped over all shards (mi_knn_sharded_search_grouped): global ids, a group spread over several
+        shards counted once, its members and facets summed"""
+        return _grouped_call(lib().mi_knn_sharded_search_grouped, self._h, self.dim, (), reference, k, max_dist,
+                             self.groups_info()["n_groups"] if facets else 0, facets, within=within)
+
     def knn_page(self, reference: np.ndarray, k: int = 100, after=None, max_dist: float = float("inf"), within=None):
         """EmbeddingTable.knn_page over all shards (mi_knn_sharded_search_page): global ids, summed counts"""
         return _page_call(lib().mi_knn_sharded_search_page, self._h, self.dim, (), reference, k, after, max_dist, within=within)
@@ -980,13 +1064,17 @@ class ImageIndex:
     def embeddings_of(self, paths: Sequence[str]):
         """search.rs:43-58.  Rows come back in table (id) order, whatever the request order — the
         order matters: average_slices adds in input order (search.rs:139-143)."""
+        rows = self.rows_of(paths)
+        return rows, [self.table.rows(r, 1)[0] for r in rows]
+
+    def rows_of(self, paths: Sequence[str]) -> list:
+        """the ids of the rows stored under `paths` (mi_index_rows_of), ascending, each once"""
         paths = list(paths)
         cnt = ctypes.c_size_t()
         check(lib().mi_index_rows_of(self._h, _cstrs(paths), len(paths), None, 0, ctypes.byref(cnt)))
         ids = np.empty(cnt.value, np.uint64)
         check(lib().mi_index_rows_of(self._h, _cstrs(paths), len(paths), ids.ctypes.data, cnt.value, ctypes.byref(cnt)))
-        rows = [int(i) for i in ids]
-        return rows, [self.table.rows(r, 1)[0] for r in rows]
+        return [int(i) for i in ids]
 
     def web_search_text(self, text_embedding: np.ndarray, referenced_images: Sequence[str] = (), k: int = K_REFERENCE,
                         folders: Optional[Sequence[str]] = None):
@@ -1057,6 +1145,61 @@ class ImageIndex:
         idx, dist, counts, nxt = _page_call(lib().mi_index_search_page, self._h, self.dim, lead, text_embedding, k, after, max_dist,
                                             tail_ptr=ctypes.byref(n))
         return [(int(idx[i]), self.path(int(idx[i]), web=web), float(dist[i])) for i in range(n.value)], counts, nxt
+
+    def group_name(self, group: int, web: bool = True) -> str:
+        """the directory behind a group id of web_search_grouped (mi_index_group_name), with its trailing '/'"""
+        need = ctypes.c_size_t()
+        check(lib().mi_index_group_name(self._h, int(group), int(web), None, 0, ctypes.byref(need)))
+        buf = ctypes.create_string_buffer(need.value)
+        check(lib().mi_index_group_name(self._h, int(group), int(web), buf, need.value, None))
+        return buf.value.decode()
+
+    def group_count(self) -> int:
+        n = ctypes.c_uint32()
+        check(lib().mi_index_group_count(self._h, ctypes.byref(n)))
+        return n.value
+
+    def web_search_grouped(self, text_embedding: np.ndarray, referenced_images: Sequence[str] = (), k: int = 10,
+                           max_dist: float = float("inf"), folders: Sequence[str] = (), by="folder", facets: bool = False,
+                           web: bool = True):
+        """The best picture of every folder (mi_index_search_grouped): the query refined with the marked images, the images
+        under `folders` (() = everything), one hit per group within max_dist, the k nearest of those.  by="folder": a group is
+        the image's directory.  by = an integer array, one label per row (k-means labels, duplicate components; NO_GROUP = the
+        row stands for itself): those are the groups — the array goes into the table's column, and the next by="folder" call
+        puts the folders back.  Returns ([(id, image_path, distance, group name or label, members)], totals) with totals =
+        {"groups", "window", "beyond", "nan"}; a hit without a group has the name None.  facets=True appends {name or label:
+        count} for the groups with at least one image within max_dist."""
+        refs, fs = list(referenced_images), list(folders)
+        if isinstance(by, str):
+            if by != "folder":
+                raise ValueError(f"by: 'folder' or an integer array, not {by!r}")
+            n = ctypes.c_uint32()
+            lead = (_cstrs(refs), len(refs), _cstrs(fs), len(fs))
+            out = _grouped_call(lib().mi_index_search_grouped, self._h, self.dim, lead, text_embedding, k, max_dist,
+                                self.group_count() if facets else 0, facets, tail_ptr=ctypes.byref(n))
+            n_hits, name = n.value, (lambda g: self.group_name(g, web=web))
+        else:
+            labels = np.asarray(by)
+            if labels.size != len(self):
+                raise ValueError(f"{labels.size} labels for {len(self)} rows")
+            self.table.set_groups(labels)
+            within = None
+            if fs:   # the live rows under the folders, whole path components, as mi_index_search_within finds them
+                under = [self.media_dir + f[len("media/"):] for f in fs if f.startswith("media/")]
+                under = [d if d == self.media_dir or d.endswith("/") else d + "/" for d in under]
+                within = self.rows_of(sorted(p for p in self.live_paths() if any(p.startswith(d) for d in under)))
+            q = text_embedding
+            marked = self.embeddings_of([self.media_dir + r[len("media/"):] for r in refs if r.startswith("media/")])[1] if refs else []
+            if len(marked):
+                q = refine_query(text_embedding, marked)
+            out = self.table.knn_grouped(q, k, max_dist, within=within, facets=facets)
+            n_hits, name = int((out[0] != NO_ID).sum()), int
+        idx, dist, group, members, totals = out[:5]
+        hits = [(int(idx[i]), self.path(int(idx[i]), web=web), float(dist[i]), None if group[i] == NO_GROUP else name(int(group[i])),
+                 int(members[i])) for i in range(n_hits)]
+        if not facets:
+            return hits, totals
+        return hits, totals, {name(g): int(c) for g, c in enumerate(out[5]) if c}
 
     def duplicates(self, max_dist: float, first_new: int = 0, web: bool = False, max_pairs: int = 1 << 20) -> list:
         """Groups of near-duplicate images (mi_index_duplicates): lists of paths whose embeddings are chained by cosine

@@ -562,6 +562,52 @@ int mi_knn_search_page(mi_knn* t, const float* q, uint32_t k,
                        float max_dist,                      /* +INFINITY: no bound */
                        const uint64_t* among, uint64_t n_among,
                        uint64_t* idx, float* dist, uint64_t counts[4] /* may be NULL */);
+/* ---- groups: one 32-bit group id per row, resident on the device beside the deletion bitmap --------------------------------
+ * A group is whatever the caller says it is: a folder, a component of mi_pairs_to_groups, a label of mi_knn_kmeans or
+ * mi_knn_assign.  MI_KNN_NO_GROUP marks a row that belongs to no group; such a row is a group of its own, a singleton.
+ * Appended rows start as MI_KNN_NO_GROUP, and a table whose column was never set behaves as all singletons.  The column grows
+ * with the table.  It is NOT written to MIKNN files: mi_knn_load (and mi_index_load, mi_knn_sharded_load) leave the loaded
+ * rows without a group, and the file format is unchanged.
+ *   set   ids == NULL: the first n rows in table order; otherwise groups[i] goes to row ids[i] (a later entry for the same id
+ *         wins).  Group ids are < MI_KNN_GROUPS_MAX (2^24), or MI_KNN_NO_GROUP.  An id that is not a row, or a group id out of
+ *         range: MI_ERR_INVALID, nothing written.  Deleted rows may be named.
+ *   get   the same addressing; rows never set report MI_KNN_NO_GROUP.
+ *   info  {n_groups = 1 + the largest group id ever set on this handle (0: none), rows that hold a group}. */
+#define MI_KNN_NO_GROUP 0xFFFFFFFFu
+#define MI_KNN_GROUPS_MAX (1u << 24)
+int mi_knn_set_groups(mi_knn* t, const uint64_t* ids, uint64_t n, const uint32_t* groups);
+int mi_knn_get_groups(mi_knn* t, const uint64_t* ids, uint64_t n, uint32_t* groups);
+int mi_knn_groups_info(mi_knn* t, uint64_t info[2]);
+/* The best hit per group, with facet counts ("field collapsing plus facets"), exact over the whole table, in one pass over the
+ * fp32 rows plus three short passes over 12 bytes per row.  In the terms of mi_knn_search_page:
+ *   candidates, distance, key, window   exactly that call's with no cursor: a candidate is in the window when
+ *               dist_to_u32(d) <= dist_to_u32(max_dist) (inclusive, on the key order; +INFINITY: no bound; NaN:
+ *               MI_ERR_INVALID).  A NaN distance is never in the window.
+ *   representative  of a group: its in-window row with the smallest key — among equal distances the lowest id.  Every
+ *               in-window MI_KNN_NO_GROUP row is its own representative.
+ *   result      the k representatives with the smallest keys, ascending: idx [k], dist [k] as the search reports them;
+ *               group [k] (may be NULL) the group id or MI_KNN_NO_GROUP; members [k] (may be NULL) the in-window candidates
+ *               of that group, 1 for a singleton.  Padding behind the last hit: MI_KNN_NO_ID, +inf, MI_KNN_NO_GROUP, 0.
+ *   facets      (may be NULL) facets[g] = in-window candidates of group g, for g < n_groups (mi_knn_groups_info); it needs
+ *               cap_facets >= n_groups, else MI_ERR_INVALID; entries past n_groups are left alone.  Asking for facets costs
+ *               one more copy of 4 n_groups bytes from the device.
+ *   totals      (may be NULL) {representatives in the window = matched groups + matched singletons, rows in the window, rows
+ *               beyond it and not NaN, NaN rows}; the last three are mi_knn_search_page's counts[1..3].
+ * 1 <= k <= 4096 (0: MI_ERR_INVALID, larger: MI_ERR_UNSUPPORTED); dim as for mi_knn_search_page.  Argument errors return
+ * their code, and nothing runs or is written.  An empty table or an empty candidate set: all padding, zero counts, MI_OK.
+ * Identities: (a) with every row MI_KNN_NO_GROUP the result is mi_knn_search_page(q, k, no cursor, max_dist), members = 1;
+ * (b) with all rows in one group there is one hit, the search's top-1, members = the window count; (c) sum(facets) + matched
+ * singletons = totals[1]; (d) for each hit, mi_knn_search_filtered over that group's rows with k = 1 gives the same id and
+ * the same distance bits.
+ * The call reads the fp32 rows only: the result does not depend on "prefilter", nor on "page_blocks", nor on the options
+ * "group_blocks" (mi_knn_set_option: workgroups of the reduce and mark passes, 0 = four per CU, v >= 1 = exactly
+ * min(v, keys / 256)) and "group_lds_max" (the largest n_groups whose reduce pass builds block-private tables in LDS; default
+ * and maximum 4096, 0 = always the global form).  Every per-group value is an integer min or sum: the result does not depend
+ * on the order in which rows arrive.  It works on a shard borrowed from a sharded table with that shard's ids and column.
+ * Runs on the handle's stream behind every write and search enqueued before it, and waits for its result. */
+int mi_knn_search_grouped(mi_knn* t, const float* q, uint32_t k, float max_dist, const uint64_t* among, uint64_t n_among,
+                          uint64_t* idx, float* dist, uint32_t* group /* may be NULL */, uint64_t* members /* may be NULL */,
+                          uint64_t* facets /* may be NULL */, uint64_t cap_facets, uint64_t totals[4] /* may be NULL */);
 /* host-only: pairs -> groups (connected components, union-find).  ids: every id that occurs in a pair, grouped; groups
  * ordered by their smallest id, ids ascending inside a group; group_start[g] .. group_start[g + 1] index ids
  * (group_start holds n_groups + 1 entries).  Two-call protocol: counts are always written, arrays up to their caps. */
@@ -635,6 +681,24 @@ int mi_knn_sharded_search_compound(mi_knn_sharded* t, const float* pos, uint32_t
  * mi_knn_merge's ordering and the counts are summed; the result equals the one-table result bit for bit.  Waits for its result. */
 int mi_knn_sharded_search_page(mi_knn_sharded* t, const float* q, uint32_t k, float after_dist, uint64_t after_id, float max_dist,
                                const uint64_t* among, uint64_t n_among, uint64_t* idx, float* dist, uint64_t counts[4]);
+/* The group column of a sharded table, on global ids: every id is checked first (one bad id or group id: MI_ERR_INVALID,
+ * nothing written), then each shard takes the entries of the rows it holds, as mi_knn_sharded_delete routes its ids.
+ * ids == NULL: the first n global rows.  info = {1 + the largest group id ever set on any shard, rows that hold a group}.
+ * mi_knn_sharded_rebalance re-applies the column to the destination by global id, as it re-applies deletions; the column is
+ * not saved (mi_knn_sharded_load leaves it unset). */
+int mi_knn_sharded_set_groups(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, const uint32_t* groups);
+int mi_knn_sharded_get_groups(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint32_t* groups);
+int mi_knn_sharded_groups_info(mi_knn_sharded* t, uint64_t info[2]);
+/* mi_knn_search_grouped on global ids.  Every shard returns its k best representatives on its own stream and host thread; the
+ * host merges them by group id (the smaller (distance word, global id) wins, singletons never merge), sorts and keeps k.  This
+ * is exact: in the shard that holds a group's global best, every group ranked ahead of it there also ranks ahead of it
+ * globally, so a globally top-k group is in that shard's top k.  members of the winners are gathered from every shard's
+ * per-group counts on the device (k words per shard) and summed.  facets and totals[0] need every shard's whole count array
+ * on the host — 4 n_groups bytes per shard — and are computed only when one of the two is asked for; totals[0] counts a group
+ * matched in several shards once.  The result equals the one-table result bit for bit.  Waits for its result. */
+int mi_knn_sharded_search_grouped(mi_knn_sharded* t, const float* q, uint32_t k, float max_dist, const uint64_t* among,
+                                  uint64_t n_among, uint64_t* idx, float* dist, uint32_t* group, uint64_t* members,
+                                  uint64_t* facets, uint64_t cap_facets, uint64_t totals[4]);
 /* mi_knn_assign over the whole table: every shard labels its own rows on its own stream (concurrently: no exchange is
  * needed), the results land at the rows' global ids.  labels / dist: [rows of the table]; equals the one-table result
  * bit for bit.  (k-means over a sharded table is not offered: its update needs a cross-shard reduction.) */
@@ -786,6 +850,23 @@ int mi_index_search_compound(mi_index* ix, const float* pos, uint32_t n_pos, int
 int mi_index_search_page(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
                          const char* const* folders, size_t n_folders, uint32_t k, float after_dist, uint64_t after_id,
                          float max_dist, uint64_t* idx, float* dist, uint32_t* n_results, uint64_t counts[4]);
+/* mi_knn_search_grouped over the index, grouped by the image's DIRECTORY (the path without its last component; files directly
+ * in the media directory form one group).  Group ids are assigned in first-seen order and kept in a dictionary of the index;
+ * the table's column is brought up to date lazily, before a grouped search: only the rows inserted or adopted since the last
+ * one are uploaded, everything after mi_index_load.  The text embedding is refined and `folders` restrict the candidates as in
+ * mi_index_search_page; removed paths never appear.  idx / dist [k], group / members [k] (may be NULL), *n_found (may be NULL)
+ * = results before the padding, facets / cap_facets / totals as for mi_knn_search_grouped (n_groups = mi_index_group_count).
+ * The index owns the column of its table: a caller who sets groups on mi_index_table directly (labels of mi_knn_kmeans, say)
+ * may search them with mi_knn_search_grouped, and makes the index upload its own column again, whole, on the next
+ * mi_index_search_grouped. */
+int mi_index_search_grouped(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
+                            const char* const* folders, size_t n_folders, uint32_t k, float max_dist, uint64_t* idx, float* dist,
+                            uint32_t* group, uint64_t* members, uint32_t* n_found, uint64_t* facets, uint64_t cap_facets,
+                            uint64_t totals[4]);
+/* the directory behind a group id of mi_index_search_grouped, with its trailing '/': as stored (web == 0) or as the client
+ * names it ("media/...", web != 0); mi_index_path's buffer protocol.  An unknown group: MI_ERR_INVALID. */
+int mi_index_group_name(mi_index* ix, uint32_t group, int web, char* buf, size_t cap, size_t* needed);
+int mi_index_group_count(mi_index* ix, uint32_t* n_groups); /* directories seen so far */
 /* `<dir>/embedding.miknn` + `<dir>/image_path.bin`, each through a temporary file, fsync and rename, the path file
  * last: after a crash the directory holds a consistent index (at worst the one before the save). */
 int mi_index_save(mi_index* ix, const char* dir);
