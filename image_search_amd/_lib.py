@@ -16,6 +16,17 @@ c_u64p = ctypes.POINTER(ctypes.c_uint64)
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_vp = ctypes.c_void_p
 
+
+
+class KnnWhere(ctypes.Structure):
+    """mi_knn_where: the predicate of mi_knn_search_where and its kin"""
+    _fields_ = [("all_of", ctypes.c_uint64), ("any_of", ctypes.c_uint64), ("none_of", ctypes.c_uint64),
+                ("stamp_lo", ctypes.c_int64), ("stamp_hi", ctypes.c_int64), ("group", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+c_wherep = ctypes.POINTER(KnnWhere)
+MI_KNN_WHERE_GROUP = 1
+
 # every symbol include/mi355clip.h declares: (restype, argtypes)
 SYMBOLS = {
     "mi_last_error": (ctypes.c_char_p, []),
@@ -85,6 +96,11 @@ SYMBOLS = {
     "mi_knn_groups_info": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_knn_search_grouped": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, c_vp, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp,
                                              c_vp, ctypes.c_uint64, c_vp]),
+    "mi_knn_set_attrs": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, c_vp]),
+    "mi_knn_get_attrs": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, c_vp]),
+    "mi_knn_count_where": (ctypes.c_int, [c_vp, c_wherep, c_u64p]),
+    "mi_knn_rows_where": (ctypes.c_int, [c_vp, c_wherep, c_vp, ctypes.c_uint64, c_u64p]),
+    "mi_knn_search_where": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_wherep, c_vp, c_vp, c_u64p]),
     "mi_pairs_to_groups": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_u64p,
                                           c_u64p]),
     "mi_index_duplicates": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,
@@ -121,6 +137,10 @@ SYMBOLS = {
     "mi_knn_sharded_groups_info": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_knn_sharded_search_grouped": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, c_vp, ctypes.c_uint64, c_vp, c_vp,
                                                      c_vp, c_vp, c_vp, ctypes.c_uint64, c_vp]),
+    "mi_knn_sharded_set_attrs": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, c_vp]),
+    "mi_knn_sharded_get_attrs": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, c_vp]),
+    "mi_knn_sharded_count_where": (ctypes.c_int, [c_vp, c_wherep, c_u64p]),
+    "mi_knn_sharded_search_where": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_wherep, c_vp, c_vp, c_u64p]),
     "mi_knn_sharded_assign": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_sharded_assign_multi": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp]),
     "mi_knn_sharded_search_many": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
@@ -161,6 +181,10 @@ SYMBOLS = {
     "mi_index_group_name": (ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,
                                            ctypes.POINTER(ctypes.c_size_t)]),
     "mi_index_group_count": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint32)]),
+    "mi_index_group_of": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32)]),
+    "mi_index_set_attrs": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, c_vp, c_vp]),
+    "mi_index_search_where": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_uint32, c_wherep,
+                                              c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32), c_u64p]),
     "mi_index_save": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_index_load": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_knn_merge": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),

@@ -242,6 +242,21 @@ struct mi_knn {
     bool gslots_valid = false;
     uint32_t gslots_groups = 0;
     int group_blocks = 0, group_lds_max = 4096;
+    // The attribute columns (where.hip): 64 flags (`tags`) and one ordered value (`stamp`) per row of capacity, both 0 by
+    // default.  They exist from the first mi_knn_set_attrs on (sized by `cap`, carried over by grow(), the rows they gain hold
+    // the defaults); h_tags / h_stamps = the same on the host for the rows they have been told about (what get_attrs and a
+    // rebalance read).  A table that never set attributes allocates nothing and matches as if every row held the defaults.
+    uint64_t* d_tags = nullptr;
+    int64_t* d_stamps = nullptr;
+    size_t attrs_cap = 0;
+    std::vector<uint64_t> h_tags;
+    std::vector<int64_t> h_stamps;
+    // mi_knn_search_where and its kin: [0, 2) the total (one 64-bit word), [2, 2 + chunks) the chunk counts, then offsets, of
+    // the predicate passes; the pinned word the total is copied to; rows per workgroup (option "where_chunk": 0 = 4096)
+    uint32_t* d_wcounts = nullptr;
+    size_t wcounts_cap = 0;
+    uint64_t* h_wtotal = nullptr;
+    int where_chunk = 0;
     std::mutex mu;
 };
 
@@ -325,6 +340,8 @@ void knn_search_filtered_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t
 void knn_reserve(mi_knn* t, void** p, size_t* have, size_t want, size_t elem);   // a workspace buffer of the handle holds `want` elements (may wait for searches in flight)
 void knn_filter_rows(mi_knn* t, const uint64_t* ids, uint64_t n_ids);            // ids -> t->h_flist / n_flist: live local rows, ascending, once each; MI_ERR_INVALID for an id that is not a row
 void knn_filter_upload(mi_knn* t, hipStream_t s);                                // ... -> t->d_flist
+// nq queries (contiguous at d_q) over the list in t->d_flist / n_flist (knn_filter_upload's or knn_filter_where's), on s
+void knn_filtered_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s);
 void knn_reduce_lists64(mi_knn* t, uint32_t lists, uint32_t k, uint64_t* keys_out, hipStream_t s);   // the per-wave register lists in t->d_cand (lists x k keys, k <= 64) -> the k smallest, ascending
 // the k <= 4096 smallest (key, position) of the n 32-bit keys in t->d_keys32, ascending; list (nullable): positions -> list[position]
 void knn_select_keys32(mi_knn* t, uint64_t n, uint32_t k, uint64_t* keys_out, const uint32_t* list, hipStream_t s);
@@ -350,10 +367,16 @@ void knn_search_grouped(mi_knn* t, const float* q, uint32_t k, float max_dist, c
                         std::vector<uint32_t>* cnt_out);
 // out[j] = t's count, from its last grouped search, of group[j] (0: no group, unknown group, or that search had no candidate); takes t->mu
 void knn_grouped_members(mi_knn* t, const uint32_t* group, uint32_t k, uint32_t* out);
+void knn_attrs_fit(mi_knn* t);    // knn.hip: the attribute columns cover `cap` rows (created on first use; new rows hold 0 / 0); t->mu held, device selected
+// where.hip: the predicate -> t->d_flist / t->n_flist, exactly what knn_filter_rows + knn_filter_upload leave for the ids of
+// the qualifying rows (live local rows, ascending); t->h_flist is not touched.  Runs the predicate passes on s and waits for
+// their total (8 bytes).  w checked by the caller (where_host.h); t->mu held, device selected
+void knn_filter_where(mi_knn* t, const mi_knn_where* w, hipStream_t s);
 // sharded.hip
 void sharded_place(const mi_knn_sharded* t, uint64_t r, uint32_t* s, uint64_t* local);
 uint64_t sharded_rows_of(const mi_knn_sharded* t, uint64_t total, uint32_t s);  // rows shard s holds when the table holds `total`
 void sharded_search_enqueue(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, uint64_t* idx, float* dist,
-                            const std::vector<std::vector<uint64_t>>* filter = nullptr);  // t->mu held
+                            const std::vector<std::vector<uint64_t>>* filter = nullptr,
+                            const mi_knn_where* where = nullptr);  // t->mu held
 void sharded_deliver_all(mi_knn_sharded* t);                                    // t->mu held
 }  // namespace mi

@@ -29,6 +29,7 @@
 #include "common.h"
 #include "grouped_host.h"
 #include "handles.h"
+#include "where_host.h"
 
 using namespace mi;
 
@@ -420,6 +421,66 @@ int mi_index_group_count(mi_index* ix, uint32_t* n_groups) {
         if (!ix || !n_groups) fail(MI_ERR_INVALID, "null argument");
         std::lock_guard<std::mutex> l(ix->mu);
         *n_groups = (uint32_t)ix->dirs.names.size();
+    });
+}
+
+int mi_index_group_of(mi_index* ix, const char* folder, uint32_t* group) {
+    return guarded([&] {
+        if (!ix || !folder || !group) fail(MI_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> l(ix->mu);
+        std::string dir;
+        if (!to_disk(ix, folder, &dir)) fail(MI_ERR_INVALID, "'%s' is not under media/", folder);
+        // the dictionary's keys end with their '/' (grouped_dir_of); "media/" itself is the media directory as it is stored
+        if (dir.size() > ix->media_dir.size() && dir.back() != '/') dir += '/';
+        auto it = ix->dirs.ids.find(grouped_dir_of(dir + "x"));
+        if (it == ix->dirs.ids.end()) fail(MI_ERR_INVALID, "no image was stored under '%s'", folder);
+        *group = it->second;
+    });
+}
+
+// mi_knn_set_attrs by path: every path looked up before anything is written
+int mi_index_set_attrs(mi_index* ix, const char* const* paths, size_t n, const uint64_t* tags, const int64_t* stamps) {
+    return guarded([&] {
+        if (!ix || (n && !paths)) fail(MI_ERR_INVALID, "null argument");
+        if (n == 0 || (!tags && !stamps)) return;
+        std::vector<uint64_t> ids, tg;
+        std::vector<int64_t> st;
+        {
+            std::lock_guard<std::mutex> l(ix->mu);
+            for (size_t i = 0; i < n; ++i) {
+                if (!paths[i]) fail(MI_ERR_INVALID, "path %zu is null", i);
+                auto it = ix->rows_of.find(paths[i]);
+                if (it == ix->rows_of.end()) fail(MI_ERR_INVALID, "'%s' is not a path of this index", paths[i]);
+                for (const uint64_t r : it->second) {
+                    ids.push_back(r);
+                    if (tags) tg.push_back(tags[i]);
+                    if (stamps) st.push_back(stamps[i]);
+                }
+            }
+        }
+        if (ids.empty()) return;
+        const int e = mi_knn_set_attrs(ix->table, ids.data(), ids.size(), tags ? tg.data() : nullptr, stamps ? st.data() : nullptr);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+    });
+}
+
+// web_search_text among the rows a predicate keeps: the refined query of mi_index_search, the directory groups brought up to
+// date when the predicate names one, then mi_knn_search_where — no id list anywhere
+int mi_index_search_where(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref, uint32_t k,
+                          const mi_knn_where* where, uint64_t* idx, float* dist, uint32_t* n_found, uint64_t* matched) {
+    return guarded([&] {
+        if (!ix || !text_embedding || !idx || !dist || (n_ref && !referenced_images)) fail(MI_ERR_INVALID, "null argument");
+        const char* why = "";
+        const int bad = where_check_pred(where, &why);
+        if (bad != MI_OK) fail(bad, "%s", why);
+        const std::vector<float> query = refined_query(ix, text_embedding, referenced_images, n_ref);
+        if (where->flags & MI_KNN_WHERE_GROUP) {
+            std::lock_guard<std::mutex> l(ix->mu);
+            sync_groups(ix);
+        }
+        const int e = mi_knn_search_where(ix->table, query.data(), 1, k, where, idx, dist, matched);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        if (n_found) *n_found = hits(idx, k);
     });
 }
 

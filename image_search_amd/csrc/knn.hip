@@ -15,6 +15,7 @@
 #include "common.h"
 #include "handles.h"
 #include "knn_kernels.h"
+#include "where_host.h"
 
 using namespace mi;
 
@@ -124,6 +125,35 @@ void groups_fit(mi_knn* t) {
     t->groups_cap = want;
 }
 
+// ---- the attribute columns (handles.h: d_tags, d_stamps; where.hip) -----------------------------------------------
+// 64 flags and one ordered value per row of capacity, the rows they gain hold 0 / 0; nothing in flight may use the old ones
+void attrs_fit(mi_knn* t) {
+    const size_t want = std::max<size_t>((size_t)t->cap, 64);
+    if (t->attrs_cap >= want && t->d_tags && t->d_stamps) return;
+    t->writes.sync();
+    t->reads.sync();
+    uint64_t* nt = nullptr;
+    int64_t* ns = nullptr;
+    HIP_CHECK(hipMalloc((void**)&nt, want * sizeof(uint64_t)));
+    if (hipMalloc((void**)&ns, want * sizeof(int64_t)) != hipSuccess) {
+        (void)hipFree(nt);
+        fail(MI_ERR_OOM, "no device memory for the attribute columns of %zu rows", want);
+    }
+    // fills and carry-over copies on the handle's own stream, and waited for (groups_fit: an upload enqueued on that stream
+    // next must not be overtaken by a fill on the null stream)
+    hipStream_t s = own_stream(t);
+    HIP_CHECK(hipMemsetAsync(nt, 0, want * sizeof(uint64_t), s));
+    HIP_CHECK(hipMemsetAsync(ns, 0, want * sizeof(int64_t), s));
+    if (t->d_tags) HIP_CHECK(hipMemcpyAsync(nt, t->d_tags, t->attrs_cap * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    if (t->d_stamps) HIP_CHECK(hipMemcpyAsync(ns, t->d_stamps, t->attrs_cap * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (t->d_tags) HIP_CHECK(hipFree(t->d_tags));
+    if (t->d_stamps) HIP_CHECK(hipFree(t->d_stamps));
+    t->d_tags = nt;
+    t->d_stamps = ns;
+    t->attrs_cap = want;
+}
+
 // id -> local row of this table (its own id space: base, and the block-cyclic map of a shard); false if it holds no such row
 bool local_of(const mi_knn* t, uint64_t id, uint64_t* local) {
     if (id < t->base) return false;
@@ -159,6 +189,7 @@ void grow(mi_knn* t, uint64_t want_rows) {
     t->cap = ncap;
     if (t->d_tomb) tomb_fit(t);  // the deletion bitmap keeps one bit per row of capacity
     if (t->d_groups) groups_fit(t);  // the group column one id
+    if (t->d_tags) attrs_fit(t);     // the attribute columns one word each
 }
 
 template <class K>
@@ -958,6 +989,9 @@ hipStream_t knn_own_stream(mi_knn* t) { return own_stream(t); }
 void knn_reserve(mi_knn* t, void** p, size_t* have, size_t want, size_t elem) { ensure(t, p, have, want, elem); }
 void knn_filter_rows(mi_knn* t, const uint64_t* ids, uint64_t n_ids) { filter_rows(t, ids, n_ids); }
 void knn_filter_upload(mi_knn* t, hipStream_t s) { upload_filter(t, s); }
+void knn_filtered_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
+    filtered_many(t, d_q, nq, k, d_idx, d_dist, s);
+}
 void knn_reduce_lists64(mi_knn* t, uint32_t lists, uint32_t k, uint64_t* keys_out, hipStream_t s) {
     QGroup qg;
     qg.lists = (uint64_t)lists * k;
@@ -974,6 +1008,7 @@ void knn_search_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint6
 }
 void knn_grow(mi_knn* t, uint64_t want_rows) { grow(t, want_rows); }
 void knn_groups_fit(mi_knn* t) { groups_fit(t); }
+void knn_attrs_fit(mi_knn* t) { attrs_fit(t); }
 void knn_search_one(mi_knn* t, const float* d_q, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
     search_one(t, d_q, k, d_idx, d_dist, s);
 }
@@ -992,6 +1027,17 @@ void knn_truncate(mi_knn* t, uint64_t rows) {
         for (size_t r = (size_t)rows; r < t->h_groups.size(); ++r) t->n_grouped -= t->h_groups[r] != MI_KNN_NO_GROUP;
         if (t->h_groups.size() > rows) t->h_groups.resize((size_t)rows);
         ++t->groups_epoch;
+    }
+    // ... and their attributes (a later append reuses those rows, with the defaults)
+    if (t->d_tags && rows < t->attrs_cap) {
+        DeviceGuard g(t->device);
+        t->writes.sync();
+        t->reads.sync();
+        HIP_CHECK(hipMemsetAsync(t->d_tags + rows, 0, (t->attrs_cap - (size_t)rows) * sizeof(uint64_t), own_stream(t)));
+        HIP_CHECK(hipMemsetAsync(t->d_stamps + rows, 0, (t->attrs_cap - (size_t)rows) * sizeof(int64_t), t->stream));
+        HIP_CHECK(hipStreamSynchronize(t->stream));
+        if (t->h_tags.size() > rows) t->h_tags.resize((size_t)rows);
+        if (t->h_stamps.size() > rows) t->h_stamps.resize((size_t)rows);
     }
     // the rows beyond are forgotten, their tombstones with them (a later append reuses those rows, live)
     const auto cut = std::lower_bound(t->dead.begin(), t->dead.end(), (uint32_t)std::min<uint64_t>(rows, 0xFFFFFFFFull));
@@ -1045,12 +1091,14 @@ void mi_knn_free(mi_knn* t) {
                     (void*)t->d_idx, (void*)t->d_dist, (void*)t->d_keys32, (void*)t->d_sel, (void*)t->d_mirror,
                     (void*)t->d_xx, (void*)t->d_pref_rows, (void*)t->d_pref_keys, (void*)t->d_pref_flag, (void*)t->d_scale8,
                     (void*)t->d_cfac8, (void*)t->d_rho8, (void*)t->d_g8, (void*)t->d_digits, (void*)t->d_qs, (void*)t->d_skeys, (void*)t->d_tomb, (void*)t->d_dead,
-                    (void*)t->d_flist, (void*)t->d_groups, (void*)t->d_gslots, (void*)t->d_gwin})
+                    (void*)t->d_flist, (void*)t->d_groups, (void*)t->d_gslots, (void*)t->d_gwin, (void*)t->d_tags, (void*)t->d_stamps,
+                    (void*)t->d_wcounts})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : t->pref_ev)
         if (e) (void)hipEventDestroy(e);
     if (t->h_pref_ring) (void)hipHostFree(t->h_pref_ring);
     if (t->h_flist) (void)hipHostFree(t->h_flist);
+    if (t->h_wtotal) (void)hipHostFree(t->h_wtotal);
     delete t;
 }
 
@@ -1126,8 +1174,13 @@ int mi_knn_set_option(mi_knn* t, const char* key, int value) {
             // Same answers whatever the value.
             if (value < 0 || value > 4096) fail(MI_ERR_INVALID, "group_lds_max must be in [0, 4096] (got %d)", value);
             t->group_lds_max = value;
+        } else if (k == "where_chunk") {
+            // mi_knn_search_where and its kin: rows one workgroup of the predicate passes owns.  0 (default): 4096; otherwise a
+            // multiple of 64 up to 65536.  Same answers whatever the value.
+            if (!where_chunk_ok(value)) fail(MI_ERR_INVALID, "where_chunk must be 0 or a multiple of 64 up to 65536 (got %d)", value);
+            t->where_chunk = value;
         } else {
-            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, many_segments, many_sample, compound_blocks, page_blocks, group_blocks, group_lds_max)", key);
+            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, many_segments, many_sample, compound_blocks, page_blocks, group_blocks, group_lds_max, where_chunk)", key);
         }
     });
 }

@@ -42,6 +42,7 @@
 #include "grouped_host.h"
 #include "page_host.h"
 #include "two_stage.h"
+#include "where_host.h"
 
 using namespace mi;
 
@@ -267,8 +268,9 @@ void sharded_deliver_all(mi_knn_sharded* t) {
 // halves in place, the exchange moves it as one piece — one ncclAllGather of bytes per shard (or one copy) — the merge
 // kernel reads the gathered records where they lie, and the merged record goes to the host in one copy.
 // filter (nullable): a filtered search (mi_knn_sharded_search_filtered), filter[s] = the global ids shard s holds
+// where (nullable): a predicate search (mi_knn_sharded_search_where): every shard builds its own list on the device
 void sharded_search_enqueue(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, uint64_t* idx, float* dist,
-                            const std::vector<std::vector<uint64_t>>* filter) {
+                            const std::vector<std::vector<uint64_t>>* filter, const mi_knn_where* where) {
     const uint32_t n = t->n();
     const size_t per = (size_t)nq * k;                        // results per shard
     const size_t rec = (per * 12 + 15) / 16 * 16;             // bytes of one shard's packed record
@@ -300,7 +302,10 @@ void sharded_search_enqueue(mi_knn_sharded* t, const float* q, uint32_t nq, uint
         if (filter)  // the shard's gathered search over its own ids (none: a no-id record)
             knn_search_filtered_many(sh, (const float*)sl.d_q[s].p, nq, k, (*filter)[s].data(), (*filter)[s].size(),
                                      rec_idx(sl.d_rec[s].p), rec_dist(sl.d_rec[s].p), st);
-        else
+        else if (where) {  // the predicate passes (they wait for their 8-byte total), then the same gathered search
+            knn_filter_where(sh, where, st);
+            knn_filtered_many(sh, (const float*)sl.d_q[s].p, nq, k, rec_idx(sl.d_rec[s].p), rec_dist(sl.d_rec[s].p), st);
+        } else
             knn_search_many(sh, (const float*)sl.d_q[s].p, nq, k, rec_idx(sl.d_rec[s].p), rec_dist(sl.d_rec[s].p), st);
         sh->reads.end(st);
     }
@@ -583,6 +588,56 @@ int mi_knn_sharded_search_filtered(mi_knn_sharded* t, const float* q, uint32_t n
     });
 }
 
+// the predicate calls on global ids (where.hip): count = the shards' counts summed; search = every shard's own list and
+// gathered search, the usual exchange and merge; waits for the results
+int mi_knn_sharded_count_where(mi_knn_sharded* t, const mi_knn_where* w, uint64_t* count) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = where_check_rows_args(t, w, nullptr, 0, count, &why);
+        if (bad != MI_OK) fail(bad, "%s", why);
+        std::lock_guard<std::mutex> l(t->mu);
+        sharded_deliver_all(t);
+        uint64_t sum = 0;
+        for (mi_knn* sh : t->shard) {
+            uint64_t one = 0;
+            const int e = mi_knn_count_where(sh, w, &one);
+            if (e != MI_OK) fail(e, "%s", mi_last_error());
+            sum += one;
+        }
+        *count = sum;
+    });
+}
+
+int mi_knn_sharded_search_where(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, const mi_knn_where* w, uint64_t* idx,
+                                float* dist, uint64_t* matched) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = where_check_search_args(t, q, nq, k, w, idx, dist, &why);
+        if (bad != MI_OK) fail(bad, "%s (k %u)", why, k);
+        check_sharded_search(t, q, nq, k, idx, dist);
+        std::lock_guard<std::mutex> l(t->mu);
+        if (nq) {
+            sharded_search_enqueue(t, q, nq, k, idx, dist, nullptr, w);
+            sharded_deliver_all(t);
+            if (matched) {  // every shard's list is still the one this search built
+                *matched = 0;
+                for (mi_knn* sh : t->shard) {
+                    std::lock_guard<std::mutex> ls(sh->mu);
+                    *matched += sh->n_flist;
+                }
+            }
+        } else if (matched) {
+            *matched = 0;
+            for (mi_knn* sh : t->shard) {
+                uint64_t one = 0;
+                const int e = mi_knn_count_where(sh, w, &one);
+                if (e != MI_OK) fail(e, "%s", mi_last_error());
+                *matched += one;
+            }
+        }
+    });
+}
+
 // mi_knn_search_compound on global ids: every shard answers for the rows (the ids of `among`) it holds, on its own stream and
 // host thread; the lists carry global ids and are merged with mi_knn_merge's ordering
 int mi_knn_sharded_search_compound(mi_knn_sharded* t, const float* pos, uint32_t n_pos, int mode, const float* neg,
@@ -846,6 +901,38 @@ void get_groups_locked(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint3
         for (size_t i = 0; i < mine.size(); ++i) groups[at[i]] = g[i];
     });
 }
+// the attribute columns (where.hip): the same routing.  A column that is null is neither written nor read
+void set_attrs_locked(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, const uint64_t* tags, const int64_t* stamps) {
+    route_ids(t, ids, n, [&](uint32_t s, const std::vector<uint64_t>& mine, const std::vector<uint64_t>& at) {
+        std::vector<uint64_t> tg(tags ? mine.size() : 0);
+        std::vector<int64_t> st(stamps ? mine.size() : 0);
+        for (size_t i = 0; i < mine.size(); ++i) {
+            if (tags) tg[i] = tags[at[i]];
+            if (stamps) st[i] = stamps[at[i]];
+        }
+        const int e = mi_knn_set_attrs(t->shard[s], mine.data(), mine.size(), tags ? tg.data() : nullptr, stamps ? st.data() : nullptr);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+    });
+}
+void get_attrs_locked(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint64_t* tags, int64_t* stamps) {
+    route_ids(t, ids, n, [&](uint32_t s, const std::vector<uint64_t>& mine, const std::vector<uint64_t>& at) {
+        std::vector<uint64_t> tg(mine.size());
+        std::vector<int64_t> st(mine.size());
+        const int e = mi_knn_get_attrs(t->shard[s], mine.data(), mine.size(), tg.data(), st.data());
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        for (size_t i = 0; i < mine.size(); ++i) {
+            if (tags) tags[at[i]] = tg[i];
+            if (stamps) stamps[at[i]] = st[i];
+        }
+    });
+}
+bool has_attrs_locked(mi_knn_sharded* t) {
+    for (mi_knn* sh : t->shard) {
+        std::lock_guard<std::mutex> ls(sh->mu);
+        if (sh->d_tags) return true;
+    }
+    return false;
+}
 void groups_info_locked(mi_knn_sharded* t, uint64_t info[2]) {
     info[0] = info[1] = 0;
     for (mi_knn* sh : t->shard) {
@@ -877,6 +964,28 @@ int mi_knn_sharded_get_groups(mi_knn_sharded* t, const uint64_t* ids, uint64_t n
         if (!groups) fail(MI_ERR_INVALID, "groups is null");
         std::lock_guard<std::mutex> l(t->mu);
         get_groups_locked(t, ids, n, groups);
+    });
+}
+
+int mi_knn_sharded_set_attrs(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, const uint64_t* tags, const int64_t* stamps) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = where_check_attrs_args(t, ids, n, &why);
+        if (bad != MI_OK) fail(bad, "%s", why);
+        if (n == 0 || (!tags && !stamps)) return;
+        std::lock_guard<std::mutex> l(t->mu);
+        set_attrs_locked(t, ids, n, tags, stamps);
+    });
+}
+
+int mi_knn_sharded_get_attrs(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint64_t* tags, int64_t* stamps) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = where_check_attrs_args(t, ids, n, &why);
+        if (bad != MI_OK) fail(bad, "%s", why);
+        if (n == 0) return;
+        std::lock_guard<std::mutex> l(t->mu);
+        get_attrs_locked(t, ids, n, tags, stamps);
     });
 }
 
@@ -926,6 +1035,13 @@ int mi_knn_sharded_rebalance(mi_knn_sharded* dst, mi_knn_sharded* src) {
                 std::vector<uint32_t> col((size_t)src->rows);
                 get_groups_locked(src, nullptr, src->rows, col.data());
                 set_groups_locked(dst, nullptr, src->rows, col.data());
+            }
+            if (has_attrs_locked(src) && src->rows) {  // the attribute columns the same way
+                std::vector<uint64_t> ids((size_t)src->rows), tags((size_t)src->rows);
+                std::vector<int64_t> stamps((size_t)src->rows);
+                for (size_t i = 0; i < ids.size(); ++i) ids[i] = i;
+                get_attrs_locked(src, ids.data(), ids.size(), tags.data(), stamps.data());
+                set_attrs_locked(dst, ids.data(), ids.size(), tags.data(), stamps.data());
             }
         } catch (...) {
             dst->rows = 0;

@@ -1,0 +1,214 @@
+// where.hip — the table's attribute columns (mi_knn_set_attrs / get_attrs) and the predicate calls: mi_knn_count_where,
+// mi_knn_rows_where, mi_knn_search_where.  A predicate over tags, stamp, the deletion bitmap and the group column becomes, on
+// the device, the ascending list of qualifying rows in t->d_flist — what mi_knn_search_filtered builds on the host from an
+// id list and uploads — and the search behind it is that call's own (knn_filtered_many).  The kernels: where_kernels.h.  The
+// host-only rules: where_host.h.
+//
+// One call: where_count_kernel, where_offsets_kernel, an 8-byte copy of the total to a pinned word and one wait for it (the
+// host needs n to size the list and to choose the grid and the selection path, as filtered_one does), where_emit_kernel.
+#include <algorithm>
+
+#include <mutex>
+#include <vector>
+
+#include "common.h"
+#include "handles.h"
+#include "page_host.h"
+#include "two_stage.h"
+#include "where_host.h"
+#include "where_kernels.h"
+
+using namespace mi;
+
+namespace {
+
+PageIds ids_of(const mi_knn* t) { return PageIds{t->base, t->rows, t->cyc_block, t->cyc_n, t->cyc_rank}; }
+
+// ids -> local rows, every one checked; MI_ERR_INVALID names the first that is no row
+std::vector<uint32_t> local_rows(const mi_knn* t, const uint64_t* ids, uint64_t n) {
+    std::vector<uint32_t> rows((size_t)n);
+    const PageIds m = ids_of(t);
+    for (uint64_t i = 0; i < n; ++i) {
+        uint64_t local = 0;
+        if (!page_local_of(m, ids[i], &local))
+            fail(MI_ERR_INVALID, "id %llu is not a row of this table (base %llu, %llu rows)", (unsigned long long)ids[i],
+                 (unsigned long long)t->base, (unsigned long long)t->rows);
+        rows[(size_t)i] = (uint32_t)local;
+    }
+    return rows;
+}
+
+WherePred pred_of(const mi_knn_where& w) {
+    WherePred p;
+    p.all_of = w.all_of; p.any_of = w.any_of; p.none_of = w.none_of;
+    p.lo = w.stamp_lo; p.hi = w.stamp_hi;
+    p.group = w.group;
+    p.use_group = (w.flags & MI_KNN_WHERE_GROUP) ? 1u : 0u;
+    return p;
+}
+
+// the count and offsets passes on s, and the wait for their total: the qualifying rows.  Leaves the chunk offsets in
+// t->d_wcounts + 2.  t->mu held, device selected, s ordered behind the handle's writes
+uint64_t where_total(mi_knn* t, const mi_knn_where& w, hipStream_t s) {
+    if (t->rows == 0 || where_never(w, t->d_groups != nullptr)) return 0;
+    const uint32_t chunk = where_chunk_rows(t->where_chunk), chunks = where_chunks(t->rows, chunk);
+    knn_reserve(t, (void**)&t->d_wcounts, &t->wcounts_cap, (size_t)chunks + 2, sizeof(uint32_t));
+    if (!t->h_wtotal) HIP_CHECK(hipHostMalloc((void**)&t->h_wtotal, sizeof(uint64_t), hipHostMallocDefault));
+    const unsigned long long* tomb = t->dead.empty() ? nullptr : reinterpret_cast<const unsigned long long*>(t->d_tomb);
+    hipLaunchKernelGGL(where_count_kernel, dim3(chunks), dim3(WHERE_THREADS), 0, s, pred_of(w),
+                       reinterpret_cast<const unsigned long long*>(t->d_tags), reinterpret_cast<const long long*>(t->d_stamps),
+                       t->d_groups, tomb, t->rows, chunk, t->d_wcounts + 2);
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(where_offsets_kernel, dim3(1), dim3(WHERE_SCAN_THREADS), 0, s, t->d_wcounts + 2, chunks,
+                       reinterpret_cast<unsigned long long*>(t->d_wcounts));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(t->h_wtotal, t->d_wcounts, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return *t->h_wtotal;
+}
+
+// ... and the emit pass: the rows into t->d_flist (room made first: the total is known), n_flist = their number
+void where_list(mi_knn* t, const mi_knn_where& w, hipStream_t s) {
+    const uint64_t total = where_total(t, w, s);
+    t->n_flist = (size_t)total;
+    if (total == 0) return;
+    knn_reserve(t, (void**)&t->d_flist, &t->flist_cap, (size_t)total, sizeof(uint32_t));
+    const uint32_t chunk = where_chunk_rows(t->where_chunk), chunks = where_chunks(t->rows, chunk);
+    const unsigned long long* tomb = t->dead.empty() ? nullptr : reinterpret_cast<const unsigned long long*>(t->d_tomb);
+    hipLaunchKernelGGL(where_emit_kernel, dim3(chunks), dim3(WHERE_THREADS), 0, s, pred_of(w),
+                       reinterpret_cast<const unsigned long long*>(t->d_tags), reinterpret_cast<const long long*>(t->d_stamps),
+                       t->d_groups, tomb, t->rows, chunk, t->d_wcounts + 2, t->d_flist);
+    HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+namespace mi {
+
+void knn_filter_where(mi_knn* t, const mi_knn_where* w, hipStream_t s) { where_list(t, *w, s); }
+
+}  // namespace mi
+
+extern "C" {
+
+int mi_knn_set_attrs(mi_knn* t, const uint64_t* ids, uint64_t n, const uint64_t* tags, const int64_t* stamps) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = where_check_attrs_args(t, ids, n, &why);
+        if (bad != MI_OK) fail(bad, "%s", why);
+        if (n == 0 || (!tags && !stamps)) return;
+        std::lock_guard<std::mutex> l(t->mu);
+        const std::vector<uint32_t> rows = local_rows(t, ids, n);   // every id checked before anything is written
+        DeviceGuard g(t->device);
+        hipStream_t s = knn_own_stream(t);
+        knn_attrs_fit(t);
+        if (t->h_tags.size() < t->rows) t->h_tags.resize((size_t)t->rows, 0);
+        if (t->h_stamps.size() < t->rows) t->h_stamps.resize((size_t)t->rows, 0);
+        uint32_t lo = 0xFFFFFFFFu, hi = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint32_t r = rows[(size_t)i];
+            if (tags) t->h_tags[r] = tags[i];
+            if (stamps) t->h_stamps[r] = stamps[i];
+            lo = std::min(lo, r);
+            hi = std::max(hi, r);
+        }
+        // a write that changes what searches read: behind the searches enqueued before it, ahead of every later one.  The
+        // span of rows the call names goes up in one copy per column (the host holds the columns too).
+        t->writes.begin(s);
+        t->reads.begin(s);
+        const size_t span = (size_t)(hi - lo) + 1;
+        if (tags) HIP_CHECK(hipMemcpyAsync(t->d_tags + lo, t->h_tags.data() + lo, span * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        if (stamps) HIP_CHECK(hipMemcpyAsync(t->d_stamps + lo, t->h_stamps.data() + lo, span * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        t->writes.end(s);
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int mi_knn_get_attrs(mi_knn* t, const uint64_t* ids, uint64_t n, uint64_t* tags, int64_t* stamps) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = where_check_attrs_args(t, ids, n, &why);
+        if (bad != MI_OK) fail(bad, "%s", why);
+        if (n == 0) return;
+        std::lock_guard<std::mutex> l(t->mu);
+        const std::vector<uint32_t> rows = local_rows(t, ids, n);
+        for (uint64_t i = 0; i < n; ++i) {   // rows appended since the last set hold the defaults
+            const uint32_t r = rows[(size_t)i];
+            if (tags) tags[i] = r < t->h_tags.size() ? t->h_tags[r] : 0;
+            if (stamps) stamps[i] = r < t->h_stamps.size() ? t->h_stamps[r] : 0;
+        }
+    });
+}
+
+int mi_knn_count_where(mi_knn* t, const mi_knn_where* w, uint64_t* count) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = where_check_rows_args(t, w, nullptr, 0, count, &why);
+        if (bad != MI_OK) fail(bad, "%s", why);
+        std::lock_guard<std::mutex> l(t->mu);
+        DeviceGuard g(t->device);
+        hipStream_t s = knn_own_stream(t);
+        t->writes.begin(s);
+        t->reads.begin(s);
+        Settle settle{t, s};
+        *count = where_total(t, *w, s);
+    });
+}
+
+int mi_knn_rows_where(mi_knn* t, const mi_knn_where* w, uint64_t* ids, uint64_t cap, uint64_t* count) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = where_check_rows_args(t, w, ids, cap, count, &why);
+        if (bad != MI_OK) fail(bad, "%s", why);
+        std::lock_guard<std::mutex> l(t->mu);
+        DeviceGuard g(t->device);
+        hipStream_t s = knn_own_stream(t);
+        t->writes.begin(s);
+        t->reads.begin(s);
+        Settle settle{t, s};
+        where_list(t, *w, s);
+        *count = t->n_flist;
+        const size_t take = (size_t)std::min<uint64_t>(cap, t->n_flist);
+        if (take == 0) return;
+        std::vector<uint32_t> rows(take);
+        HIP_CHECK(hipMemcpyAsync(rows.data(), t->d_flist, take * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        // a table's ids ascend with its local rows (a shard's too: block-cyclic placement keeps the order)
+        const bool cyclic = t->cyc_n > 1 && t->cyc_block;
+        for (size_t i = 0; i < take; ++i) {
+            const uint64_t r = rows[i];
+            ids[i] = t->base + (cyclic ? ((r / t->cyc_block) * t->cyc_n + t->cyc_rank) * t->cyc_block + r % t->cyc_block : r);
+        }
+    });
+}
+
+// mi_knn_search_filtered with the list built on the device: the same grouping of the queries, the same kernels behind
+int mi_knn_search_where(mi_knn* t, const float* q, uint32_t nq, uint32_t k, const mi_knn_where* w, uint64_t* idx, float* dist,
+                        uint64_t* matched) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = where_check_search_args(t, q, nq, k, w, idx, dist, &why);
+        if (bad != MI_OK) fail(bad, "%s (k %u)", why, k);
+        std::lock_guard<std::mutex> l(t->mu);
+        DeviceGuard g(t->device);
+        hipStream_t s = knn_own_stream(t);
+        constexpr uint32_t GROUP = 16;
+        knn_reserve(t, (void**)&t->d_idx, &t->idx_cap, (size_t)GROUP * k, sizeof(uint64_t));
+        knn_reserve(t, (void**)&t->d_dist, &t->dist_cap, (size_t)GROUP * k, sizeof(float));
+        t->writes.begin(s);
+        t->reads.begin(s);
+        Settle settle{t, s};
+        where_list(t, *w, s);
+        if (matched) *matched = t->n_flist;
+        for (uint32_t u0 = 0; u0 < nq; u0 += GROUP) {
+            const uint32_t ng = std::min(GROUP, nq - u0);
+            HIP_CHECK(hipMemcpyAsync(t->d_q, q + (size_t)u0 * t->dim, (size_t)ng * t->dim * sizeof(float), hipMemcpyHostToDevice, s));
+            knn_filtered_many(t, t->d_q, ng, k, t->d_idx, t->d_dist, s);
+            HIP_CHECK(hipMemcpyAsync(idx + (size_t)u0 * k, t->d_idx, (size_t)ng * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(dist + (size_t)u0 * k, t->d_dist, (size_t)ng * k * sizeof(float), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+        }
+    });
+}
+
+}  // extern "C"

@@ -139,6 +139,20 @@ inline void finish_grouped(Grouped& g) {
     g.idx.resize(n); g.dist.resize(n); g.group.resize(n); g.members.resize(n);
 }
 
+// a predicate search (mi_knn_search_where and its kin): the hits without the padding, and how many rows qualified
+struct WhereHits {
+    std::vector<uint64_t> idx;
+    std::vector<float> dist;
+    uint64_t matched = 0;
+};
+inline void finish_where(WhereHits& r) {
+    size_t n = 0;
+    while (n < r.idx.size() && r.idx[n] != MI_KNN_NO_ID) ++n;
+    r.idx.resize(n); r.dist.resize(n);
+}
+// every tag, every stamp, any group: narrow the fields that matter (flags = MI_KNN_WHERE_GROUP makes `group` count)
+inline mi_knn_where where_all() { return mi_knn_where{0, 0, 0, INT64_MIN, INT64_MAX, 0, 0}; }
+
 class EmbeddingTable {
     mi_knn* h_ = nullptr;
     uint32_t dim_;
@@ -324,6 +338,34 @@ class EmbeddingTable {
         finish_grouped(r);
         return r;
     }
+    // the attribute columns (mi_knn_set_attrs): 64 flags and one ordered value per row; nullptr keeps a column; not saved
+    void set_attrs(const std::vector<uint64_t>& ids, const std::vector<uint64_t>* tags, const std::vector<int64_t>* stamps) {
+        check(mi_knn_set_attrs(h_, ids.data(), ids.size(), tags ? tags->data() : nullptr, stamps ? stamps->data() : nullptr));
+    }
+    std::pair<std::vector<uint64_t>, std::vector<int64_t>> get_attrs(const std::vector<uint64_t>& ids) const {
+        std::vector<uint64_t> tags(ids.size());
+        std::vector<int64_t> stamps(ids.size());
+        check(mi_knn_get_attrs(h_, ids.data(), ids.size(), tags.data(), stamps.data()));
+        return {tags, stamps};
+    }
+    uint64_t count_where(const mi_knn_where& w) const { uint64_t n = 0; check(mi_knn_count_where(h_, &w, &n)); return n; }
+    // the ids of the live rows the predicate keeps, ascending (mi_knn_rows_where)
+    std::vector<uint64_t> rows_where(const mi_knn_where& w) const {
+        uint64_t n = 0;
+        check(mi_knn_rows_where(h_, &w, nullptr, 0, &n));
+        std::vector<uint64_t> ids(n);
+        check(mi_knn_rows_where(h_, &w, ids.data(), ids.size(), &n));
+        ids.resize(std::min<uint64_t>(n, ids.size()));
+        return ids;
+    }
+    // the k nearest among the rows the predicate keeps, evaluated on the device (mi_knn_search_where)
+    WhereHits knn_where(const std::vector<float>& reference, uint32_t k, const mi_knn_where& w) const {
+        WhereHits r;
+        r.idx.resize(k); r.dist.resize(k);
+        check(mi_knn_search_where(h_, reference.data(), 1, k, &w, r.idx.data(), r.dist.data(), &r.matched));
+        finish_where(r);
+        return r;
+    }
     // "prefilter" = 2 (bytes) or 1 (bf16): the two-stage exact search, same results from a quarter / a half of the bytes
     void set_option(const std::string& key, int value) { check(mi_knn_set_option(h_, key.c_str(), value)); }
 };
@@ -472,6 +514,25 @@ class ImageIndex {
         finish_grouped(r);
         return r;
     }
+    // the group id of a directory as the client names it, "media/a/b" (mi_index_group_of): search_where's "in this folder"
+    uint32_t group_of(const std::string& folder) const { uint32_t g = 0; check(mi_index_group_of(h_, folder.c_str(), &g)); return g; }
+    // attributes by stored path (mi_index_set_attrs): every row of paths[i] takes tags[i] / stamps[i]; nullptr keeps a column
+    void set_attrs(const std::vector<std::string>& paths, const std::vector<uint64_t>* tags, const std::vector<int64_t>* stamps) {
+        const auto p = ptrs(paths);
+        check(mi_index_set_attrs(h_, p.data(), p.size(), tags ? tags->data() : nullptr, stamps ? stamps->data() : nullptr));
+    }
+    // web_search_text among the images a predicate keeps (mi_index_search_where); w.group = group_of(folder) under
+    // MI_KNN_WHERE_GROUP is "in this folder" without an id list
+    WhereHits search_where(const std::vector<float>& text_embedding, const std::vector<std::string>& referenced_images, uint32_t k,
+                           const mi_knn_where& w) const {
+        WhereHits r;
+        r.idx.resize(k); r.dist.resize(k);
+        uint32_t n = 0;
+        const auto p = ptrs(referenced_images);
+        check(mi_index_search_where(h_, text_embedding.data(), p.data(), p.size(), k, &w, r.idx.data(), r.dist.data(), &n, &r.matched));
+        finish_where(r);
+        return r;
+    }
     // the directory behind a group id of search_grouped (mi_index_group_name)
     std::string group_name(uint32_t group, bool web = true) const {
         size_t need = 0;
@@ -560,6 +621,24 @@ class ShardedTable {
         check(mi_knn_sharded_search_grouped(h_, reference.data(), k, max_dist, ids, among ? among->size() : 0, r.idx.data(), r.dist.data(),
                                             r.group.data(), r.members.data(), facets ? r.facets.data() : nullptr, r.facets.size(), r.totals));
         finish_grouped(r);
+        return r;
+    }
+    // the attribute columns and predicates on global ids (mi_knn_sharded_set_attrs and its kin)
+    void set_attrs(const std::vector<uint64_t>& ids, const std::vector<uint64_t>* tags, const std::vector<int64_t>* stamps) {
+        check(mi_knn_sharded_set_attrs(h_, ids.data(), ids.size(), tags ? tags->data() : nullptr, stamps ? stamps->data() : nullptr));
+    }
+    std::pair<std::vector<uint64_t>, std::vector<int64_t>> get_attrs(const std::vector<uint64_t>& ids) const {
+        std::vector<uint64_t> tags(ids.size());
+        std::vector<int64_t> stamps(ids.size());
+        check(mi_knn_sharded_get_attrs(h_, ids.data(), ids.size(), tags.data(), stamps.data()));
+        return {tags, stamps};
+    }
+    uint64_t count_where(const mi_knn_where& w) const { uint64_t n = 0; check(mi_knn_sharded_count_where(h_, &w, &n)); return n; }
+    WhereHits knn_where(const std::vector<float>& reference, uint32_t k, const mi_knn_where& w) const {
+        WhereHits r;
+        r.idx.resize(k); r.dist.resize(k);
+        check(mi_knn_sharded_search_where(h_, reference.data(), 1, k, &w, r.idx.data(), r.dist.data(), &r.matched));
+        finish_where(r);
         return r;
     }
     // EmbeddingTable::knn_page over all shards (mi_knn_sharded_search_page): global ids, summed counts

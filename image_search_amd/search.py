@@ -16,7 +16,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import c_f, c_vp, check, lib
+from ._lib import MI_KNN_WHERE_GROUP, KnnWhere, c_f, c_vp, check, lib
 
 K_REFERENCE = 1000  # `<|1000|>` in server/src/search.rs:76
 NO_ID = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -124,6 +124,58 @@ def _grouped_call(fn, handle, dim, lead, reference, k, max_dist, n_groups, facet
     out = (idx[:k], dist[:k], group[:k], members[:k],
            {"groups": totals[0], "window": totals[1], "beyond": totals[2], "nan": totals[3]})
     return out + (fac[:int(n_groups)],) if facets else out
+
+
+STAMP_MIN, STAMP_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def make_where(all_of=0, any_of=0, none_of=0, stamp=(None, None), group=None) -> KnnWhere:
+    """The predicate of the *_where calls (mi_knn_where).  all_of / any_of / none_of: masks over the 64 tag bits (any_of = 0:
+    clause absent); stamp = (lo, hi), inclusive and signed, None = open on that side, lo > hi matches nothing; group: None (any)
+    or a group id — NO_GROUP selects the rows without a group, and a table without a group column matches nothing."""
+    lo, hi = stamp
+    w = KnnWhere(int(all_of) & 0xFFFFFFFFFFFFFFFF, int(any_of) & 0xFFFFFFFFFFFFFFFF, int(none_of) & 0xFFFFFFFFFFFFFFFF,
+                 STAMP_MIN if lo is None else int(lo), STAMP_MAX if hi is None else int(hi), 0, 0)
+    if group is not None:
+        w.group, w.flags = int(group), MI_KNN_WHERE_GROUP
+    return w
+
+
+def _set_attrs(fn, h, ids, tags, stamps):
+    a = _ids(ids)
+    tg = None if tags is None else np.ascontiguousarray(np.asarray(tags, dtype=np.uint64).reshape(-1))
+    st = None if stamps is None else np.ascontiguousarray(np.asarray(stamps, dtype=np.int64).reshape(-1))
+    for name, col in (("tags", tg), ("stamps", st)):
+        if col is not None and col.size != a.size:
+            raise ValueError(f"{col.size} {name} for {a.size} ids")
+    check(fn(h, a.ctypes.data if a.size else None, a.size, tg.ctypes.data if tg is not None and tg.size else None,
+             st.ctypes.data if st is not None and st.size else None))
+
+
+def _get_attrs(fn, h, ids, rows):
+    a = np.arange(rows, dtype=np.uint64) if ids is None else _ids(ids)
+    tags, stamps = np.zeros(max(a.size, 1), np.uint64), np.zeros(max(a.size, 1), np.int64)
+    check(fn(h, a.ctypes.data if a.size else None, a.size, tags.ctypes.data, stamps.ctypes.data))
+    return tags[:a.size], stamps[:a.size]
+
+
+def _count_where(fn, h, where) -> int:
+    n = ctypes.c_uint64()
+    check(fn(h, ctypes.byref(where), ctypes.byref(n)))
+    return n.value
+
+
+def _search_where(fn, h, dim, reference, k, where):
+    """one mi_*_search_where call -> (idx, dist, matched); reference [dim] or [nq, dim]"""
+    q = _f32(reference)
+    single = q.ndim == 1
+    q = q.reshape(-1, dim)
+    k = int(k)
+    idx, dist = np.empty((q.shape[0], max(k, 1)), np.uint64), np.empty((q.shape[0], max(k, 1)), np.float32)
+    matched = ctypes.c_uint64()
+    check(fn(h, q.ctypes.data, q.shape[0], k, ctypes.byref(where), idx.ctypes.data, dist.ctypes.data, ctypes.byref(matched)))
+    idx, dist = idx[:, :k], dist[:, :k]
+    return (idx[0], dist[0], matched.value) if single else (idx, dist, matched.value)
 
 
 def _ptrs(vecs):
@@ -401,6 +453,36 @@ class EmbeddingTable:
         hit.  facets=True appends the array of every group's count.  Exact over the whole table; k <= 4096."""
         return _grouped_call(lib().mi_knn_search_grouped, self._h, self.dim, (), reference, k, max_dist,
                              self.groups_info()["n_groups"] if facets else 0, facets, within=within)
+
+    def set_attrs(self, ids, tags=None, stamps=None):
+        """The attribute columns (mi_knn_set_attrs): tags[i] (64 flags, uint64) and stamps[i] (an ordered int64: a capture time,
+        a rating) for row ids[i]; None keeps that column.  Rows start with 0 / 0; the columns grow with the table and are not
+        saved (get_attrs() reads them back).  An id that is no row raises and writes nothing."""
+        _set_attrs(lib().mi_knn_set_attrs, self._h, ids, tags, stamps)
+
+    def get_attrs(self, ids=None):
+        """(tags, stamps) of the rows `ids` (None: of every row) — 0 / 0 where none was set"""
+        first = int(getattr(self, "_base_id", 0))
+        return _get_attrs(lib().mi_knn_get_attrs, self._h, np.arange(first, first + len(self), dtype=np.uint64) if ids is None else ids, 0)
+
+    def count_where(self, all_of=0, any_of=0, none_of=0, stamp=(None, None), group=None) -> int:
+        """how many live rows the predicate keeps (mi_knn_count_where; make_where for the arguments)"""
+        return _count_where(lib().mi_knn_count_where, self._h, make_where(all_of, any_of, none_of, stamp, group))
+
+    def rows_where(self, all_of=0, any_of=0, none_of=0, stamp=(None, None), group=None) -> np.ndarray:
+        """the ids of the live rows the predicate keeps, ascending (mi_knn_rows_where)"""
+        w = make_where(all_of, any_of, none_of, stamp, group)
+        n = ctypes.c_uint64()
+        ids = np.empty(max(len(self), 1), np.uint64)
+        check(lib().mi_knn_rows_where(self._h, ctypes.byref(w), ids.ctypes.data, len(self), ctypes.byref(n)))
+        return ids[:n.value].copy()
+
+    def knn_where(self, reference: np.ndarray, k: int = 10, all_of=0, any_of=0, none_of=0, stamp=(None, None), group=None):
+        """The k nearest among the live rows a predicate keeps (mi_knn_search_where): "like this, among my favourites, taken
+        2019-2021, not hidden, in this group".  The predicate runs on the device over the attribute columns — no id list.
+        Returns (idx, dist, matched): bit for bit what knn(reference, k, within=rows_where(...)) returns, and the number of
+        qualifying rows; NO_ID / +inf behind the last hit; k <= 4096."""
+        return _search_where(lib().mi_knn_search_where, self._h, self.dim, reference, k, make_where(all_of, any_of, none_of, stamp, group))
 
     def knn_page(self, reference: np.ndarray, k: int = 100, after=None, max_dist: float = float("inf"), within=None):
         """The k nearest rows AFTER a cursor and WITHIN a distance (mi_knn_search_page).  after: None (from the start) or the
@@ -797,6 +879,36 @@ class ShardedTable:
         shards counted once, its members and facets summed"""
         return _grouped_call(lib().mi_knn_sharded_search_grouped, self._h, self.dim, (), reference, k, max_dist,
                              self.groups_info()["n_groups"] if facets else 0, facets, within=within)
+
+    def set_attrs(self, ids, tags=None, stamps=None):
+        """EmbeddingTable.set_attrs on global ids (mi_knn_sharded_set_attrs): every shard keeps the columns of its own rows"""
+        _set_attrs(lib().mi_knn_sharded_set_attrs, self._h, ids, tags, stamps)
+
+    def get_attrs(self, ids=None):
+        return _get_attrs(lib().mi_knn_sharded_get_attrs, self._h, ids, len(self))
+
+    def count_where(self, all_of=0, any_of=0, none_of=0, stamp=(None, None), group=None) -> int:
+        """EmbeddingTable.count_where summed over the shards (mi_knn_sharded_count_where)"""
+        return _count_where(lib().mi_knn_sharded_count_where, self._h, make_where(all_of, any_of, none_of, stamp, group))
+
+    def rows_where(self, all_of=0, any_of=0, none_of=0, stamp=(None, None), group=None) -> np.ndarray:
+        """EmbeddingTable.rows_where on global ids: the shards' lists (mi_knn_rows_where on each shard), merged ascending"""
+        w = make_where(all_of, any_of, none_of, stamp, group)
+        parts = []
+        for s in range(self.info()["shards"]):
+            h = c_vp(lib().mi_knn_sharded_shard(self._h, s))
+            n = ctypes.c_uint64()
+            check(lib().mi_knn_rows_where(h, ctypes.byref(w), None, 0, ctypes.byref(n)))
+            ids = np.empty(max(n.value, 1), np.uint64)
+            check(lib().mi_knn_rows_where(h, ctypes.byref(w), ids.ctypes.data, n.value, ctypes.byref(n)))
+            parts.append(ids[:n.value])
+        return np.sort(np.concatenate(parts)) if parts else np.empty(0, np.uint64)
+
+    def knn_where(self, reference: np.ndarray, k: int = 10, all_of=0, any_of=0, none_of=0, stamp=(None, None), group=None):
+        """EmbeddingTable.knn_where over all shards (mi_knn_sharded_search_where): every shard builds its own list on its
+        device; global ids, the one-table result bit for bit"""
+        return _search_where(lib().mi_knn_sharded_search_where, self._h, self.dim, reference, k,
+                             make_where(all_of, any_of, none_of, stamp, group))
 
     def knn_page(self, reference: np.ndarray, k: int = 100, after=None, max_dist: float = float("inf"), within=None):
         """EmbeddingTable.knn_page over all shards (mi_knn_sharded_search_page): global ids, summed counts"""
@@ -1200,6 +1312,44 @@ class ImageIndex:
         if not facets:
             return hits, totals
         return hits, totals, {name(g): int(c) for g, c in enumerate(out[5]) if c}
+
+    def group_of(self, folder: str) -> int:
+        """the group id of a directory as the client names it, "media/a/b" (mi_index_group_of): web_search_where's `group`"""
+        g = ctypes.c_uint32()
+        check(lib().mi_index_group_of(self._h, folder.encode(), ctypes.byref(g)))
+        return g.value
+
+    def set_attrs(self, paths: Sequence[str], tags=None, stamps=None):
+        """EmbeddingTable.set_attrs by stored path (mi_index_set_attrs): tags[i] / stamps[i] go to every row of paths[i]; an
+        unknown path raises and writes nothing"""
+        paths = list(paths)
+        tg = None if tags is None else np.ascontiguousarray(np.asarray(tags, dtype=np.uint64).reshape(-1))
+        st = None if stamps is None else np.ascontiguousarray(np.asarray(stamps, dtype=np.int64).reshape(-1))
+        for name, col in (("tags", tg), ("stamps", st)):
+            if col is not None and col.size != len(paths):
+                raise ValueError(f"{col.size} {name} for {len(paths)} paths")
+        check(lib().mi_index_set_attrs(self._h, _cstrs(paths), len(paths), tg.ctypes.data if tg is not None and tg.size else None,
+                                       st.ctypes.data if st is not None and st.size else None))
+
+    def web_search_where(self, text_embedding: np.ndarray, referenced_images: Sequence[str] = (), k: int = 10, all_of=0, any_of=0,
+                         none_of=0, stamp=(None, None), folder: Optional[str] = None, group=None, web: bool = True):
+        """web_search_text among the images a predicate keeps (mi_index_search_where): the query refined with the marked
+        images, then tags / stamp as EmbeddingTable.knn_where takes them.  folder="media/a/b": only the images directly in that
+        directory (its group id, group_of; or pass `group`) — no id list is built.  Returns ([(id, image_path, distance)],
+        matched)."""
+        refs = list(referenced_images)
+        if folder is not None:
+            group = self.group_of(folder)
+        w = make_where(all_of, any_of, none_of, stamp, group)
+        q = _f32(text_embedding).reshape(-1)
+        if q.size != self.dim:
+            raise ValueError(f"a query of {q.size} floats for dim {self.dim}")
+        k = int(k)
+        idx, dist = np.empty(max(k, 1), np.uint64), np.empty(max(k, 1), np.float32)
+        n, matched = ctypes.c_uint32(), ctypes.c_uint64()
+        check(lib().mi_index_search_where(self._h, q.ctypes.data, _cstrs(refs), len(refs), k, ctypes.byref(w), idx.ctypes.data,
+                                          dist.ctypes.data, ctypes.byref(n), ctypes.byref(matched)))
+        return [(int(idx[i]), self.path(int(idx[i]), web=web), float(dist[i])) for i in range(n.value)], matched.value
 
     def duplicates(self, max_dist: float, first_new: int = 0, web: bool = False, max_pairs: int = 1 << 20) -> list:
         """Groups of near-duplicate images (mi_index_duplicates): lists of paths whose embeddings are chained by cosine

@@ -608,6 +608,49 @@ int mi_knn_groups_info(mi_knn* t, uint64_t info[2]);
 int mi_knn_search_grouped(mi_knn* t, const float* q, uint32_t k, float max_dist, const uint64_t* among, uint64_t n_among,
                           uint64_t* idx, float* dist, uint32_t* group /* may be NULL */, uint64_t* members /* may be NULL */,
                           uint64_t* facets /* may be NULL */, uint64_t cap_facets, uint64_t totals[4] /* may be NULL */);
+/* ---- attributes and predicates: "like this, among my favourites, taken 2019-2021, not hidden, in this folder" ---------------
+ * Two more per-row columns, resident on the device beside the deletion bitmap and the group column:
+ *   tags   one uint64_t per row: 64 flags whose meaning is the application's.  Default 0.
+ *   stamp  one int64_t per row: a capture time, a rating, any ordered value.  Default 0.
+ * They are created by the first mi_knn_set_attrs (a table that never sets attributes allocates nothing and behaves as if every
+ * row held the defaults), grow with the table (appended rows hold the defaults) and are NOT written to MIKNN files: the file
+ * format and mi_abi_version are unchanged; mi_knn_get_attrs lets the application persist them.
+ *   set   tags[i] / stamps[i] go to row ids[i]; a NULL column keeps what the rows hold; a later entry for the same id wins.  An
+ *         id that is not a row: MI_ERR_INVALID, nothing written.  Deleted rows may be set and read.
+ *   get   the same addressing; either output may be NULL. */
+int mi_knn_set_attrs(mi_knn* t, const uint64_t* ids, uint64_t n, const uint64_t* tags /* NULL: keep */,
+                     const int64_t* stamps /* NULL: keep */);
+int mi_knn_get_attrs(mi_knn* t, const uint64_t* ids, uint64_t n, uint64_t* tags /* may be NULL */, int64_t* stamps /* may be NULL */);
+/* The predicate.  A row qualifies iff it is live (not deleted) and
+ *   (tags & all_of) == all_of,   any_of == 0 || (tags & any_of) != 0,   (tags & none_of) == 0,
+ *   stamp_lo <= stamp <= stamp_hi   (signed, inclusive: lo > hi matches nothing; INT64_MIN .. INT64_MAX: every stamp), and,
+ *   with MI_KNN_WHERE_GROUP in flags, its group (mi_knn_set_groups) == group: MI_KNN_NO_GROUP selects the rows without a
+ *   group, and a table without a group column matches nothing under the flag.
+ * Any other bit in flags: MI_ERR_INVALID. */
+#define MI_KNN_WHERE_GROUP 1u
+typedef struct mi_knn_where {
+    uint64_t all_of, any_of, none_of; /* on tags; any_of == 0: clause absent */
+    int64_t stamp_lo, stamp_hi;       /* inclusive, signed; lo > hi matches nothing */
+    uint32_t group;                   /* used only with MI_KNN_WHERE_GROUP */
+    uint32_t flags;                   /* MI_KNN_WHERE_GROUP; other bits: MI_ERR_INVALID */
+} mi_knn_where;
+/* The predicate is evaluated on the device, over the columns, without the host touching a row: an ordered two-pass compaction
+ * (count per chunk of rows, offsets, emit) leaves the qualifying rows as the ascending list the gathered search reads.  No
+ * workgroup waits for another; integers only, the same list for any grid.  The host reads back one 8-byte total per call.
+ * Option "where_chunk" (mi_knn_set_option): rows per workgroup of the two passes, 0 = 4096, otherwise a multiple of 64 up to
+ * 65536; it changes no answer.
+ *   count  *count = the qualifying rows.
+ *   rows   their ids, ascending, the first `cap` of them into ids (may be NULL with cap == 0); *count = the number qualifying,
+ *          also when that exceeds cap. */
+int mi_knn_count_where(mi_knn* t, const mi_knn_where* w, uint64_t* count);
+int mi_knn_rows_where(mi_knn* t, const mi_knn_where* w, uint64_t* ids, uint64_t cap, uint64_t* count);
+/* The k nearest among the qualifying rows.  Contract: the result is bit-identical to mi_knn_search_filtered(t, q, nq, k, ids =
+ * every qualifying row) — same ids, same order, same distance bits, same MI_KNN_NO_ID / +inf padding; k <= 4096, else
+ * MI_ERR_UNSUPPORTED; nothing qualifying gives k no-id entries.  *matched (may be NULL) = the qualifying rows.  Behind the
+ * predicate passes run the filtered search's own kernels over the list.  Runs on the handle's stream behind every write and
+ * search enqueued before it, and waits for its result. */
+int mi_knn_search_where(mi_knn* t, const float* q, uint32_t nq, uint32_t k, const mi_knn_where* w, uint64_t* idx, float* dist,
+                        uint64_t* matched /* may be NULL */);
 /* host-only: pairs -> groups (connected components, union-find).  ids: every id that occurs in a pair, grouped; groups
  * ordered by their smallest id, ids ascending inside a group; group_start[g] .. group_start[g + 1] index ids
  * (group_start holds n_groups + 1 entries).  Two-call protocol: counts are always written, arrays up to their caps. */
@@ -699,6 +742,17 @@ int mi_knn_sharded_groups_info(mi_knn_sharded* t, uint64_t info[2]);
 int mi_knn_sharded_search_grouped(mi_knn_sharded* t, const float* q, uint32_t k, float max_dist, const uint64_t* among,
                                   uint64_t n_among, uint64_t* idx, float* dist, uint32_t* group, uint64_t* members,
                                   uint64_t* facets, uint64_t cap_facets, uint64_t totals[4]);
+/* The attribute columns and predicates of a sharded table, on global ids.  set / get: every id is checked first (one bad id:
+ * MI_ERR_INVALID, nothing written), then each shard takes the entries of the rows it holds, as mi_knn_sharded_set_groups
+ * routes its ids.  count_where sums the shards.  search_where: every shard turns the predicate into its own list and runs its
+ * gathered search; the packed exchange and the device merge are mi_knn_sharded_search's.  The result equals the one-table
+ * result bit for bit; *matched (may be NULL) = the qualifying rows of all shards.  mi_knn_sharded_rebalance re-applies the
+ * columns to the destination by global id; they are not saved. */
+int mi_knn_sharded_set_attrs(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, const uint64_t* tags, const int64_t* stamps);
+int mi_knn_sharded_get_attrs(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint64_t* tags, int64_t* stamps);
+int mi_knn_sharded_count_where(mi_knn_sharded* t, const mi_knn_where* w, uint64_t* count);
+int mi_knn_sharded_search_where(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, const mi_knn_where* w, uint64_t* idx,
+                                float* dist, uint64_t* matched /* may be NULL */);
 /* mi_knn_assign over the whole table: every shard labels its own rows on its own stream (concurrently: no exchange is
  * needed), the results land at the rows' global ids.  labels / dist: [rows of the table]; equals the one-table result
  * bit for bit.  (k-means over a sharded table is not offered: its update needs a cross-shard reduction.) */
@@ -867,6 +921,19 @@ int mi_index_search_grouped(mi_index* ix, const float* text_embedding, const cha
  * names it ("media/...", web != 0); mi_index_path's buffer protocol.  An unknown group: MI_ERR_INVALID. */
 int mi_index_group_name(mi_index* ix, uint32_t group, int web, char* buf, size_t cap, size_t* needed);
 int mi_index_group_count(mi_index* ix, uint32_t* n_groups); /* directories seen so far */
+/* the group id of a directory as the client names it ("media/a/b" or "media/a/b/"; "media/" = the files directly in the media
+ * directory): what MI_KNN_WHERE_GROUP takes for "in this folder" (the folder itself, not the folders below it).  A directory
+ * no image was ever stored under: MI_ERR_INVALID. */
+int mi_index_group_of(mi_index* ix, const char* folder, uint32_t* group);
+/* mi_knn_set_attrs by path: tags[i] / stamps[i] (either may be NULL: keep) go to every row stored under paths[i] (paths as
+ * mi_index_rows_of takes them).  An unknown path: MI_ERR_INVALID, nothing written. */
+int mi_index_set_attrs(mi_index* ix, const char* const* paths, size_t n, const uint64_t* tags, const int64_t* stamps);
+/* web_search_text among the rows a predicate keeps (mi_knn_search_where): the refined query of mi_index_search, no id list at
+ * all.  With MI_KNN_WHERE_GROUP the group is a directory id (mi_index_group_of): the table's group column is brought up to
+ * date first, as mi_index_search_grouped does.  Removed paths never appear (they are deleted rows of the table).  idx / dist
+ * [k], *n_found (may be NULL) = results before the padding, *matched (may be NULL) = the qualifying rows. */
+int mi_index_search_where(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref, uint32_t k,
+                          const mi_knn_where* where, uint64_t* idx, float* dist, uint32_t* n_found, uint64_t* matched);
 /* `<dir>/embedding.miknn` + `<dir>/image_path.bin`, each through a temporary file, fsync and rename, the path file
  * last: after a crash the directory holds a consistent index (at worst the one before the save). */
 int mi_index_save(mi_index* ix, const char* dir);
