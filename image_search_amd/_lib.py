@@ -101,6 +101,9 @@ SYMBOLS = {
     "mi_knn_count_where": (ctypes.c_int, [c_vp, c_wherep, c_u64p]),
     "mi_knn_rows_where": (ctypes.c_int, [c_vp, c_wherep, c_vp, ctypes.c_uint64, c_u64p]),
     "mi_knn_search_where": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_wherep, c_vp, c_vp, c_u64p]),
+    "mi_knn_search_ordered": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, c_wherep, ctypes.c_uint32, ctypes.c_int64,
+                                             ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp]),
+    "mi_knn_stamp_histogram": (ctypes.c_int, [c_vp, c_vp, ctypes.c_float, c_wherep, c_vp, ctypes.c_uint32, c_vp]),
     "mi_pairs_to_groups": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_u64p,
                                           c_u64p]),
     "mi_index_duplicates": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,
@@ -141,6 +144,9 @@ SYMBOLS = {
     "mi_knn_sharded_get_attrs": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, c_vp]),
     "mi_knn_sharded_count_where": (ctypes.c_int, [c_vp, c_wherep, c_u64p]),
     "mi_knn_sharded_search_where": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_wherep, c_vp, c_vp, c_u64p]),
+    "mi_knn_sharded_search_ordered": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, c_wherep, ctypes.c_uint32,
+                                                     ctypes.c_int64, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp]),
+    "mi_knn_sharded_stamp_histogram": (ctypes.c_int, [c_vp, c_vp, ctypes.c_float, c_wherep, c_vp, ctypes.c_uint32, c_vp]),
     "mi_knn_sharded_assign": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_sharded_assign_multi": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp]),
     "mi_knn_sharded_search_many": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
@@ -185,6 +191,11 @@ SYMBOLS = {
     "mi_index_set_attrs": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, c_vp, c_vp]),
     "mi_index_search_where": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_uint32, c_wherep,
                                               c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32), c_u64p]),
+    "mi_index_search_ordered": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_uint32,
+                                               ctypes.c_float, c_wherep, ctypes.c_uint32, ctypes.c_int64, ctypes.c_uint64, c_vp, c_vp,
+                                               c_vp, ctypes.POINTER(ctypes.c_uint32), c_vp]),
+    "mi_index_stamp_histogram": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_float, c_wherep,
+                                                c_vp, ctypes.c_uint32, c_vp]),
     "mi_index_save": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_index_load": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_knn_merge": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),

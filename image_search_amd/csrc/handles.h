@@ -372,6 +372,15 @@ void knn_attrs_fit(mi_knn* t);    // knn.hip: the attribute columns cover `cap` 
 // the qualifying rows (live local rows, ascending); t->h_flist is not touched.  Runs the predicate passes on s and waits for
 // their total (8 bytes).  w checked by the caller (where_host.h); t->mu held, device selected
 void knn_filter_where(mi_knn* t, const mi_knn_where* w, hipStream_t s);
+// ordered.hip: mi_knn_search_ordered behind its argument check (ordered_host.h); takes t->mu.  cur (nullable): the cursor as the
+// sharded call hands it to a shard (ordered_cursor_shard); otherwise it is built from (flags, after_stamp, after_id), which must
+// name a row of t.  counts: {within, before, beyond, nan}
+struct OrderedCursor;
+void knn_search_ordered(mi_knn* t, const float* q, uint32_t k, float max_dist, const mi_knn_where* w, uint32_t flags, int64_t after_stamp,
+                        uint64_t after_id, const OrderedCursor* cur, uint64_t* idx, float* dist, int64_t* stamps, uint64_t* counts);
+// ordered.hip: mi_knn_stamp_histogram behind its argument check; takes t->mu
+void knn_stamp_histogram(mi_knn* t, const float* q, float max_dist, const mi_knn_where* w, const int64_t* edges, uint32_t n_edges,
+                         uint64_t* hist);
 // sharded.hip
 void sharded_place(const mi_knn_sharded* t, uint64_t r, uint32_t* s, uint64_t* local);
 uint64_t sharded_rows_of(const mi_knn_sharded* t, uint64_t total, uint32_t s);  // rows shard s holds when the table holds `total`

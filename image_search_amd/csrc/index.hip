@@ -29,6 +29,7 @@
 #include "common.h"
 #include "grouped_host.h"
 #include "handles.h"
+#include "ordered_host.h"
 #include "where_host.h"
 
 using namespace mi;
@@ -481,6 +482,45 @@ int mi_index_search_where(mi_index* ix, const float* text_embedding, const char*
         const int e = mi_knn_search_where(ix->table, query.data(), 1, k, where, idx, dist, matched);
         if (e != MI_OK) fail(e, "%s", mi_last_error());
         if (n_found) *n_found = hits(idx, k);
+    });
+}
+
+// web_search_text as a timeline: the refined query of mi_index_search, the directory groups brought up to date when the
+// predicate names one, then mi_knn_search_ordered — the rows of removed paths are deleted rows of the table and never appear
+int mi_index_search_ordered(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref, uint32_t k,
+                            float max_dist, const mi_knn_where* where, uint32_t flags, int64_t after_stamp, uint64_t after_id,
+                            uint64_t* idx, float* dist, int64_t* stamps, uint32_t* n_found, uint64_t counts[4]) {
+    return guarded([&] {
+        if (!ix || !text_embedding || !idx || !dist || (n_ref && !referenced_images)) fail(MI_ERR_INVALID, "null argument");
+        const char* why = "";
+        const int bad = ordered_check_args(ix, text_embedding, k, max_dist, where, flags, idx, dist, &why);
+        if (bad != MI_OK) fail(bad, "%s (k %u)", why, k);
+        const std::vector<float> query = refined_query(ix, text_embedding, referenced_images, n_ref);
+        if (where && (where->flags & MI_KNN_WHERE_GROUP)) {
+            std::lock_guard<std::mutex> l(ix->mu);
+            sync_groups(ix);
+        }
+        const int e = mi_knn_search_ordered(ix->table, query.data(), k, max_dist, where, flags, after_stamp, after_id, idx, dist, stamps, counts);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        if (n_found) *n_found = hits(idx, k);
+    });
+}
+
+// the timeline facet of the same query: mi_knn_stamp_histogram behind the refined query and the group column
+int mi_index_stamp_histogram(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
+                             float max_dist, const mi_knn_where* where, const int64_t* edges, uint32_t n_edges, uint64_t* hist) {
+    return guarded([&] {
+        if (!ix || !text_embedding || (n_ref && !referenced_images)) fail(MI_ERR_INVALID, "null argument");
+        const char* why = "";
+        const int bad = ordered_check_hist_args(ix, text_embedding, max_dist, where, edges, n_edges, hist, &why);
+        if (bad != MI_OK) fail(bad, "%s (n_edges %u)", why, n_edges);
+        const std::vector<float> query = refined_query(ix, text_embedding, referenced_images, n_ref);
+        if (where && (where->flags & MI_KNN_WHERE_GROUP)) {
+            std::lock_guard<std::mutex> l(ix->mu);
+            sync_groups(ix);
+        }
+        const int e = mi_knn_stamp_histogram(ix->table, query.data(), max_dist, where, edges, n_edges, hist);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
     });
 }
 

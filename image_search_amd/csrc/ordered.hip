@@ -1,0 +1,183 @@
+// ordered.hip — host side of mi_knn_search_ordered and mi_knn_stamp_histogram: the rows within a distance in the order of their
+// stamps — "everything that looks like this, newest first, 100 at a time" — and the timeline facet over the same rows.  The
+// kernels, and why the selection key is (okey(stamp), position): ordered_kernels.h.  The host-only rules: ordered_host.h.
+//
+// One call: with a predicate its passes leave the ascending list of the rows it keeps (knn_filter_where); the query goes up;
+// the paged search's scan in its one-key-per-entry form (knn_page_scan_keys32) classifies every candidate against the bound;
+// nine short histogram passes (most of which return at once), a collect, a one-block sort and ordered_finish_kernel turn the
+// keys into ids, distances and stamps beside the counts, and the host copies that one record back in one piece.
+#include <algorithm>
+#include <cmath>
+
+#include <mutex>
+#include <vector>
+
+#include "common.h"
+#include "compound_host.h"
+#include "handles.h"
+#include "ordered_host.h"
+#include "ordered_kernels.h"
+#include "page_host.h"
+#include "two_stage.h"
+
+using namespace mi;
+
+namespace {
+
+PageIds ids_of(const mi_knn* t) { return PageIds{t->base, t->rows, t->cyc_block, t->cyc_n, t->cyc_rank}; }
+
+// What both calls share in front of their own passes: the candidates (w: the predicate's list in t->d_flist, else the table under
+// its deletion bitmap), the query, the scan (t->d_keys32 holds `cap` words: reserved by the caller).  Leaves one distance key per entry in t->d_keys32 and {-, within, beyond, nan} added
+// to d_counts (zeroed here); returns the number of entries (0: no candidate, nothing was launched behind the predicate).
+// t->mu held, device selected, s ordered behind the handle's writes and searches
+uint64_t scan_candidates(mi_knn* t, const float* q, float max_dist, const mi_knn_where* w, uint32_t k, hipStream_t s,
+                         unsigned long long* d_counts, const uint32_t** list) {
+    *list = nullptr;
+    if (w) knn_filter_where(t, w, s);
+    const uint64_t n = w ? (uint64_t)t->n_flist : t->rows;
+    if (n == 0) return 0;
+    HIP_CHECK(hipMemcpyAsync(t->d_q, q, (size_t)t->dim * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(d_counts, 0, 4 * sizeof(uint64_t), s));
+    *list = w ? t->d_flist : nullptr;
+    const uint64_t* tomb = (w || t->dead.empty()) ? nullptr : t->d_tomb;
+    knn_page_scan_keys32(t, s, n, *list, tomb, page_hi(max_dist), k, t->d_keys32, d_counts);
+    return n;
+}
+
+}  // namespace
+
+namespace mi {
+
+// the call behind the C entry points (arguments checked by ordered_check_args); throws Error.  cur (nullable): the cursor as a
+// shard takes it from the sharded call; otherwise it is built here from (flags, after_stamp, after_id), and after_id must name a
+// row of t
+void knn_search_ordered(mi_knn* t, const float* q, uint32_t k, float max_dist, const mi_knn_where* w, uint32_t flags, int64_t after_stamp,
+                        uint64_t after_id, const OrderedCursor* cur_in, uint64_t* idx, float* dist, int64_t* stamps, uint64_t* counts) {
+    std::lock_guard<std::mutex> l(t->mu);
+    if (!compound_dim_ok(t->dim)) fail(MI_ERR_UNSUPPORTED, "dim %u: the ordered search is built for dim in {128, 256, 512, 768, 1024}", t->dim);
+    OrderedCursor cur;
+    if (cur_in) cur = *cur_in;
+    else if (!ordered_cursor(ids_of(t), flags, after_stamp, after_id, &cur))
+        fail(MI_ERR_INVALID, "after_id %llu is not a row of this table (base %llu, %llu rows)", (unsigned long long)after_id,
+             (unsigned long long)t->base, (unsigned long long)t->rows);
+    if (t->rows == 0 || (w && where_never(*w, t->d_groups != nullptr))) {
+        ordered_pad(k, idx, dist, stamps, counts);
+        return;
+    }
+
+    DeviceGuard g(t->device);
+    hipStream_t s = knn_own_stream(t);
+    const OrderedRecord rec = ordered_record(k);
+    knn_reserve(t, (void**)&t->d_idx, &t->idx_cap, (rec.bytes + 7) / 8, sizeof(uint64_t));
+    knn_reserve(t, (void**)&t->d_keys, &t->keys_cap, (size_t)ORDERED_K_MAX * 2, sizeof(uint64_t));   // sorted: hi [4096] | lo [4096]
+    knn_reserve(t, (void**)&t->d_cand, &t->cand_keys, (size_t)ORDERED_K_MAX * 2, sizeof(uint64_t));  // collected: the same
+    knn_reserve(t, (void**)&t->d_sel, &t->sel_cap, ORD_SEL_WORDS, sizeof(uint32_t));
+    knn_reserve(t, (void**)&t->d_keys32, &t->keys32_cap, (size_t)std::max<uint64_t>(t->rows, t->cap), sizeof(uint32_t));
+    // behind every write and search enqueued before this call, on whichever stream
+    t->writes.begin(s);
+    t->reads.begin(s);
+    Settle settle{t, s};
+
+    unsigned char* d_rec = reinterpret_cast<unsigned char*>(t->d_idx);
+    unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(d_rec + rec.counts);
+    const uint32_t* list = nullptr;
+    const uint64_t n = scan_candidates(t, q, max_dist, w, k, s, d_counts, &list);
+    if (n == 0) {
+        ordered_pad(k, idx, dist, stamps, counts);
+        return;
+    }
+    HIP_CHECK(hipMemsetAsync(t->d_sel, 0, ORD_SEL_WORDS * sizeof(uint32_t), s));
+    uint32_t* d_hist = t->d_sel;
+    OrdState* d_states = reinterpret_cast<OrdState*>(t->d_sel + ORD_HIST_WORDS);
+    uint32_t* d_count = t->d_sel + ORD_HIST_WORDS + ORD_STATE_WORDS;
+    uint64_t* c_hi = t->d_cand;
+    uint32_t* c_lo = reinterpret_cast<uint32_t*>(t->d_cand + ORDERED_K_MAX);
+    uint64_t* s_hi = t->d_keys;
+    uint32_t* s_lo = reinterpret_cast<uint32_t*>(t->d_keys + ORDERED_K_MAX);
+    const long long* d_stamps = reinterpret_cast<const long long*>(t->d_stamps);
+    // one entry per thread and round; the grid rule (and the option) of the scan in front
+    const uint32_t blocks = page_grid(n, t->n_cu, t->page_blocks);
+    for (int p = 0; p < ORD_PASSES; ++p) {
+        hipLaunchKernelGGL(ordered_hist_kernel, dim3(blocks), dim3(256), 0, s, t->d_keys32, n, list, d_stamps, cur, k, p, d_hist, d_states,
+                           d_counts);
+        HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(ordered_collect_kernel, dim3(blocks), dim3(256), 0, s, t->d_keys32, n, list, d_stamps, cur, k, d_hist, d_states, c_hi,
+                       c_lo, d_count);
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(ordered_sort_kernel, dim3(1), dim3(1024), 0, s, c_hi, c_lo, d_count, k, s_hi, s_lo);
+    HIP_CHECK(hipGetLastError());
+    const IdMap map{t->base, t->cyc_block, t->cyc_n, t->cyc_rank};
+    hipLaunchKernelGGL(ordered_finish_kernel, dim3((k + 255) / 256), dim3(256), 0, s, s_hi, s_lo, d_count, k, t->d_keys32, list, (int)cur.desc,
+                       map, reinterpret_cast<uint64_t*>(d_rec + rec.idx), reinterpret_cast<float*>(d_rec + rec.dist),
+                       reinterpret_cast<long long*>(d_rec + rec.stamps));
+    HIP_CHECK(hipGetLastError());
+    std::vector<unsigned char> h_rec(rec.bytes);
+    HIP_CHECK(hipMemcpyAsync(h_rec.data(), d_rec, rec.bytes, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    ordered_unpack(h_rec.data(), k, idx, dist, stamps, counts);
+}
+
+// mi_knn_stamp_histogram behind its argument check; hist [n_edges + 1] is written only on success
+void knn_stamp_histogram(mi_knn* t, const float* q, float max_dist, const mi_knn_where* w, const int64_t* edges, uint32_t n_edges,
+                         uint64_t* hist) {
+    std::lock_guard<std::mutex> l(t->mu);
+    if (!compound_dim_ok(t->dim)) fail(MI_ERR_UNSUPPORTED, "dim %u: the stamp histogram is built for dim in {128, 256, 512, 768, 1024}", t->dim);
+    const size_t bins = (size_t)n_edges + 1;
+    if (t->rows == 0 || (w && where_never(*w, t->d_groups != nullptr))) {
+        std::fill(hist, hist + bins, 0ull);
+        return;
+    }
+    DeviceGuard g(t->device);
+    hipStream_t s = knn_own_stream(t);
+    knn_reserve(t, (void**)&t->d_idx, &t->idx_cap, bins + 4, sizeof(uint64_t));                       // hist [bins] | the scan's counts [4]
+    knn_reserve(t, (void**)&t->d_keys, &t->keys_cap, (size_t)ORDERED_K_MAX * 2, sizeof(uint64_t));   // the edges
+    knn_reserve(t, (void**)&t->d_keys32, &t->keys32_cap, (size_t)std::max<uint64_t>(t->rows, t->cap), sizeof(uint32_t));
+    t->writes.begin(s);
+    t->reads.begin(s);
+    Settle settle{t, s};
+
+    unsigned long long* d_hist = reinterpret_cast<unsigned long long*>(t->d_idx);
+    const uint32_t* list = nullptr;
+    const uint64_t n = scan_candidates(t, q, max_dist, w, 1, s, d_hist + bins, &list);
+    if (n == 0) {
+        std::fill(hist, hist + bins, 0ull);
+        return;
+    }
+    HIP_CHECK(hipMemsetAsync(d_hist, 0, bins * sizeof(uint64_t), s));
+    HIP_CHECK(hipMemcpyAsync(t->d_keys, edges, (size_t)n_edges * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    const uint32_t blocks = page_grid(n, t->n_cu, t->page_blocks);
+    hipLaunchKernelGGL(ordered_stamp_hist_kernel, dim3(blocks), dim3(256), 0, s, t->d_keys32, n, list,
+                       reinterpret_cast<const long long*>(t->d_stamps), reinterpret_cast<const long long*>(t->d_keys), n_edges, d_hist);
+    HIP_CHECK(hipGetLastError());
+    std::vector<uint64_t> h(bins);
+    HIP_CHECK(hipMemcpyAsync(h.data(), d_hist, bins * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    std::copy(h.begin(), h.end(), hist);
+}
+
+}  // namespace mi
+
+extern "C" {
+
+int mi_knn_search_ordered(mi_knn* t, const float* q, uint32_t k, float max_dist, const mi_knn_where* w, uint32_t flags, int64_t after_stamp,
+                          uint64_t after_id, uint64_t* idx, float* dist, int64_t* stamps, uint64_t counts[4]) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = ordered_check_args(t, q, k, max_dist, w, flags, idx, dist, &why);
+        if (bad != MI_OK) fail(bad, "%s (k %u)", why, k);
+        knn_search_ordered(t, q, k, max_dist, w, flags, after_stamp, after_id, nullptr, idx, dist, stamps, counts);
+    });
+}
+
+int mi_knn_stamp_histogram(mi_knn* t, const float* q, float max_dist, const mi_knn_where* w, const int64_t* edges, uint32_t n_edges,
+                           uint64_t* hist) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = ordered_check_hist_args(t, q, max_dist, w, edges, n_edges, hist, &why);
+        if (bad != MI_OK) fail(bad, "%s (n_edges %u)", why, n_edges);
+        knn_stamp_histogram(t, q, max_dist, w, edges, n_edges, hist);
+    });
+}
+
+}  // extern "C"

@@ -40,6 +40,7 @@
 #include "compound_host.h"
 #include "handles.h"
 #include "grouped_host.h"
+#include "ordered_host.h"
 #include "page_host.h"
 #include "two_stage.h"
 #include "where_host.h"
@@ -715,6 +716,67 @@ int mi_knn_sharded_search_page(mi_knn_sharded* t, const float* q, uint32_t k, fl
                 counts[c] = 0;
                 for (uint32_t si = 0; si < n; ++si) counts[c] += all_counts[(size_t)si * 4 + c];
             }
+    });
+}
+
+// mi_knn_search_ordered on global ids: every shard runs the call on its own rows, on its own stream and host thread.  A shard's
+// local rows ascend with their global ids, so its cursor is (okey(after_stamp), the number of its rows whose global id is <=
+// after_id) — ordered_host.h; the lists carry global ids and stamps and are merged by (okey, id), the counts are summed
+int mi_knn_sharded_search_ordered(mi_knn_sharded* t, const float* q, uint32_t k, float max_dist, const mi_knn_where* w, uint32_t flags,
+                                  int64_t after_stamp, uint64_t after_id, uint64_t* idx, float* dist, int64_t* stamps, uint64_t counts[4]) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = ordered_check_args(t, q, k, max_dist, w, flags, idx, dist, &why);
+        if (bad != MI_OK) fail(bad, "%s (k %u)", why, k);
+        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
+        std::lock_guard<std::mutex> l(t->mu);
+        const uint32_t n = t->n();
+        if ((flags & MI_KNN_ORDER_AFTER) && after_id >= t->rows)
+            fail(MI_ERR_INVALID, "after_id %llu is not a row of this table (%llu rows)", (unsigned long long)after_id, (unsigned long long)t->rows);
+        sharded_deliver_all(t);
+        std::vector<uint64_t> all_idx((size_t)n * k), all_counts((size_t)n * 4, 0);
+        std::vector<float> all_dist((size_t)n * k);
+        std::vector<int64_t> all_stamps((size_t)n * k);
+        for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
+            const OrderedCursor cur = ordered_cursor_shard(t->block, n, si, flags, after_stamp, after_id);
+            knn_search_ordered(sh, q, k, max_dist, w, flags, after_stamp, after_id, &cur, all_idx.data() + (size_t)si * k,
+                               all_dist.data() + (size_t)si * k, all_stamps.data() + (size_t)si * k, all_counts.data() + (size_t)si * 4);
+        });
+        std::vector<uint64_t> m_idx(k);
+        std::vector<float> m_dist(k);
+        std::vector<int64_t> m_stamps(k);
+        ordered_merge(all_idx.data(), all_dist.data(), all_stamps.data(), n, k, (flags & MI_KNN_ORDER_DESC) != 0, m_idx.data(), m_dist.data(),
+                      m_stamps.data());
+        std::copy(m_idx.begin(), m_idx.end(), idx);
+        std::copy(m_dist.begin(), m_dist.end(), dist);
+        if (stamps) std::copy(m_stamps.begin(), m_stamps.end(), stamps);
+        if (counts)
+            for (int c = 0; c < 4; ++c) {
+                counts[c] = 0;
+                for (uint32_t si = 0; si < n; ++si) counts[c] += all_counts[(size_t)si * 4 + c];
+            }
+    });
+}
+
+// mi_knn_stamp_histogram over all shards: every shard counts its own rows, the host sums the bins
+int mi_knn_sharded_stamp_histogram(mi_knn_sharded* t, const float* q, float max_dist, const mi_knn_where* w, const int64_t* edges,
+                                   uint32_t n_edges, uint64_t* hist) {
+    return guarded([&] {
+        const char* why = "";
+        const int bad = ordered_check_hist_args(t, q, max_dist, w, edges, n_edges, hist, &why);
+        if (bad != MI_OK) fail(bad, "%s (n_edges %u)", why, n_edges);
+        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
+        std::lock_guard<std::mutex> l(t->mu);
+        const uint32_t n = t->n();
+        const size_t bins = (size_t)n_edges + 1;
+        sharded_deliver_all(t);
+        std::vector<uint64_t> all((size_t)n * bins, 0);
+        for_each_shard(t, [&](uint32_t si, mi_knn* sh) { knn_stamp_histogram(sh, q, max_dist, w, edges, n_edges, all.data() + (size_t)si * bins); });
+        for (size_t b = 0; b < bins; ++b) {
+            uint64_t sum = 0;
+            for (uint32_t si = 0; si < n; ++si) sum += all[(size_t)si * bins + b];
+            hist[b] = sum;
+        }
     });
 }
 

@@ -153,6 +153,29 @@ inline void finish_where(WhereHits& r) {
 // every tag, every stamp, any group: narrow the fields that matter (flags = MI_KNN_WHERE_GROUP makes `group` count)
 inline mi_knn_where where_all() { return mi_knn_where{0, 0, 0, INT64_MIN, INT64_MAX, 0, 0}; }
 
+// one page of a timeline (mi_knn_search_ordered and its kin): the hits without the padding in the order of their stamps, counts =
+// {within, before, beyond, nan} of the candidates, and the cursor for the following page — has_next is false when this page came
+// back short
+struct OrderedPage {
+    std::vector<uint64_t> idx;
+    std::vector<float> dist;
+    std::vector<int64_t> stamps;
+    uint64_t counts[4] = {0, 0, 0, 0};
+    bool has_next = false;
+    int64_t next_stamp = 0;
+    uint64_t next_id = 0;
+};
+inline void finish_ordered(OrderedPage& p, uint32_t k) {
+    p.has_next = k > 0 && p.idx[k - 1] != MI_KNN_NO_ID;
+    if (p.has_next) { p.next_stamp = p.stamps[k - 1]; p.next_id = p.idx[k - 1]; }
+    size_t n = 0;
+    while (n < p.idx.size() && p.idx[n] != MI_KNN_NO_ID) ++n;
+    p.idx.resize(n); p.dist.resize(n); p.stamps.resize(n);
+}
+inline uint32_t ordered_flags(bool descending, const OrderedPage* after) {
+    return (descending ? MI_KNN_ORDER_DESC : 0u) | (after && after->has_next ? MI_KNN_ORDER_AFTER : 0u);
+}
+
 class EmbeddingTable {
     mi_knn* h_ = nullptr;
     uint32_t dim_;
@@ -366,6 +389,25 @@ class EmbeddingTable {
         finish_where(r);
         return r;
     }
+    // the rows within max_dist in the order of their stamps, a page of k after the previous page (mi_knn_search_ordered).  w = nullptr:
+    // every live row.  Page 1: after = nullptr; page n + 1: the page before
+    OrderedPage knn_ordered(const std::vector<float>& reference, uint32_t k, float max_dist = INFINITY, bool descending = false,
+                            const OrderedPage* after = nullptr, const mi_knn_where* w = nullptr) const {
+        OrderedPage p;
+        p.idx.resize(k); p.dist.resize(k); p.stamps.resize(k);
+        const bool cur = after && after->has_next;
+        check(mi_knn_search_ordered(h_, reference.data(), k, max_dist, w, ordered_flags(descending, after), cur ? after->next_stamp : 0,
+              cur ? after->next_id : 0, p.idx.data(), p.dist.data(), p.stamps.data(), p.counts));
+        finish_ordered(p, k);
+        return p;
+    }
+    // the timeline facet (mi_knn_stamp_histogram): hist[b] = the rows within max_dist with exactly b of the ascending edges <= stamp
+    std::vector<uint64_t> stamp_histogram(const std::vector<float>& reference, const std::vector<int64_t>& edges, float max_dist = INFINITY,
+                                          const mi_knn_where* w = nullptr) const {
+        std::vector<uint64_t> hist(edges.size() + 1);
+        check(mi_knn_stamp_histogram(h_, reference.data(), max_dist, w, edges.data(), (uint32_t)edges.size(), hist.data()));
+        return hist;
+    }
     // "prefilter" = 2 (bytes) or 1 (bf16): the two-stage exact search, same results from a quarter / a half of the bytes
     void set_option(const std::string& key, int value) { check(mi_knn_set_option(h_, key.c_str(), value)); }
 };
@@ -533,6 +575,31 @@ class ImageIndex {
         finish_where(r);
         return r;
     }
+    // web_search_text as a timeline (mi_index_search_ordered): the refined query, the images within max_dist newest first (or
+    // oldest first), a page of k after the previous page; w as search_where takes it, nullptr = every image
+    OrderedPage search_ordered(const std::vector<float>& text_embedding, const std::vector<std::string>& referenced_images, uint32_t k,
+                               float max_dist = INFINITY, bool descending = true, const OrderedPage* after = nullptr,
+                               const mi_knn_where* w = nullptr) const {
+        OrderedPage r;
+        r.idx.resize(k); r.dist.resize(k); r.stamps.resize(k);
+        uint32_t n = 0;
+        const auto p = ptrs(referenced_images);
+        const bool cur = after && after->has_next;
+        check(mi_index_search_ordered(h_, text_embedding.data(), p.data(), p.size(), k, max_dist, w, ordered_flags(descending, after),
+                                      cur ? after->next_stamp : 0, cur ? after->next_id : 0, r.idx.data(), r.dist.data(), r.stamps.data(), &n,
+                                      r.counts));
+        finish_ordered(r, k);
+        return r;
+    }
+    // the "matches per month" strip above it (mi_index_stamp_histogram)
+    std::vector<uint64_t> timeline_histogram(const std::vector<float>& text_embedding, const std::vector<std::string>& referenced_images,
+                                             const std::vector<int64_t>& edges, float max_dist = INFINITY, const mi_knn_where* w = nullptr) const {
+        std::vector<uint64_t> hist(edges.size() + 1);
+        const auto p = ptrs(referenced_images);
+        check(mi_index_stamp_histogram(h_, text_embedding.data(), p.data(), p.size(), max_dist, w, edges.data(), (uint32_t)edges.size(),
+                                       hist.data()));
+        return hist;
+    }
     // the directory behind a group id of search_grouped (mi_index_group_name)
     std::string group_name(uint32_t group, bool web = true) const {
         size_t need = 0;
@@ -640,6 +707,25 @@ class ShardedTable {
         check(mi_knn_sharded_search_where(h_, reference.data(), 1, k, &w, r.idx.data(), r.dist.data(), &r.matched));
         finish_where(r);
         return r;
+    }
+    // the rows within max_dist in the order of their stamps, a page of k after the previous page (EmbeddingTable::knn_ordered over all shards: mi_knn_sharded_search_ordered).  w = nullptr:
+    // every live row.  Page 1: after = nullptr; page n + 1: the page before
+    OrderedPage knn_ordered(const std::vector<float>& reference, uint32_t k, float max_dist = INFINITY, bool descending = false,
+                            const OrderedPage* after = nullptr, const mi_knn_where* w = nullptr) const {
+        OrderedPage p;
+        p.idx.resize(k); p.dist.resize(k); p.stamps.resize(k);
+        const bool cur = after && after->has_next;
+        check(mi_knn_sharded_search_ordered(h_, reference.data(), k, max_dist, w, ordered_flags(descending, after), cur ? after->next_stamp : 0,
+              cur ? after->next_id : 0, p.idx.data(), p.dist.data(), p.stamps.data(), p.counts));
+        finish_ordered(p, k);
+        return p;
+    }
+    // the timeline facet (mi_knn_sharded_stamp_histogram): hist[b] = the rows within max_dist with exactly b of the ascending edges <= stamp
+    std::vector<uint64_t> stamp_histogram(const std::vector<float>& reference, const std::vector<int64_t>& edges, float max_dist = INFINITY,
+                                          const mi_knn_where* w = nullptr) const {
+        std::vector<uint64_t> hist(edges.size() + 1);
+        check(mi_knn_sharded_stamp_histogram(h_, reference.data(), max_dist, w, edges.data(), (uint32_t)edges.size(), hist.data()));
+        return hist;
     }
     // EmbeddingTable::knn_page over all shards (mi_knn_sharded_search_page): global ids, summed counts
     Page knn_page(const std::vector<float>& reference, uint32_t k, const Page* after = nullptr, float max_dist = INFINITY,

@@ -178,6 +178,61 @@ def _search_where(fn, h, dim, reference, k, where):
     return (idx[0], dist[0], matched.value) if single else (idx, dist, matched.value)
 
 
+MI_KNN_ORDER_DESC, MI_KNN_ORDER_AFTER = 1, 2
+
+
+def _where_or_null(predicate):
+    """the keyword arguments of make_where -> a pointer to the structure, or None (NULL: every live row) when there are none"""
+    if not predicate:
+        return None, None
+    w = make_where(**predicate)
+    return ctypes.byref(w), w
+
+
+def _ordered_call(fn, handle, dim, lead, reference, k, max_dist, descending, after, predicate, n_found=False):
+    """one mi_*_search_ordered call -> (idx [k], dist [k], stamps [k], counts dict): `lead` = the arguments between the query and
+    k (the index's references); after = None or the (stamp, id) of the previous page's last hit"""
+    q = _f32(reference).reshape(-1)
+    if q.size != dim:
+        raise ValueError(f"a query of {q.size} floats for dim {dim}")
+    k = int(k)
+    idx, dist, stamps = np.empty(max(k, 1), np.uint64), np.empty(max(k, 1), np.float32), np.empty(max(k, 1), np.int64)
+    counts = (ctypes.c_uint64 * 4)()
+    wp, _keep = _where_or_null(predicate)
+    flags = (MI_KNN_ORDER_DESC if descending else 0) | (MI_KNN_ORDER_AFTER if after is not None else 0)
+    a_stamp, a_id = (0, 0) if after is None else (int(after[0]), int(after[1]))
+    args = [handle, q.ctypes.data] + list(lead) + [k, float(max_dist), wp, flags, a_stamp, a_id, idx.ctypes.data, dist.ctypes.data,
+                                                    stamps.ctypes.data]
+    if n_found:
+        args.append(None)
+    check(fn(*(args + [counts])))
+    return idx[:k], dist[:k], stamps[:k], {"within": counts[0], "before": counts[1], "beyond": counts[2], "nan": counts[3]}
+
+
+def _timeline(page, k):
+    """page(after) -> (idx, dist, stamps, counts), called until a page comes back short: yields each with the padding cut off"""
+    after = None
+    while True:
+        idx, dist, stamps, counts = page(after)
+        n = int((idx != NO_ID).sum())
+        if n:
+            yield idx[:n], dist[:n], stamps[:n], counts
+        if n < int(k):
+            return
+        after = (int(stamps[n - 1]), int(idx[n - 1]))
+
+
+def _stamp_histogram(fn, handle, dim, lead, reference, edges, max_dist, predicate):
+    q = _f32(reference).reshape(-1)
+    if q.size != dim:
+        raise ValueError(f"a query of {q.size} floats for dim {dim}")
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.int64).reshape(-1))
+    hist = np.zeros(e.size + 1, np.uint64)
+    wp, _keep = _where_or_null(predicate)
+    check(fn(*([handle, q.ctypes.data] + list(lead) + [float(max_dist), wp, e.ctypes.data if e.size else None, e.size, hist.ctypes.data])))
+    return hist
+
+
 def _ptrs(vecs):
     arr = (c_f * len(vecs))()
     for i, v in enumerate(vecs):
@@ -492,6 +547,25 @@ class EmbeddingTable:
         returned; counts = {"before", "window", "beyond", "nan"} of the candidates (they add up to their number); next = the
         cursor for the following page, None when this page came back short.  k <= 4096."""
         return _page_call(lib().mi_knn_search_page, self._h, self.dim, (), reference, k, after, max_dist, within=within)
+
+    def knn_ordered(self, reference: np.ndarray, k: int = 100, max_dist: float = float("inf"), descending: bool = False, after=None,
+                    **predicate):
+        """The rows within max_dist of the reference in the order of their stamps (mi_knn_search_ordered): ascending, or newest
+        first with descending=True; equal stamps by ascending id.  after: None (from the start) or the (stamp, id) of the
+        previous page's last hit — its row may have been deleted since.  predicate: the keyword arguments of make_where (none:
+        every live row).  Returns (idx, dist, stamps, counts): the hits in order, NO_ID / +inf / 0 behind them, and counts =
+        {"within", "before", "beyond", "nan"} ("101-200 of within").  k <= 4096."""
+        return _ordered_call(lib().mi_knn_search_ordered, self._h, self.dim, (), reference, k, max_dist, descending, after, predicate)
+
+    def timeline(self, reference: np.ndarray, k: int = 100, max_dist: float = float("inf"), descending: bool = False, **predicate):
+        """knn_ordered after knn_ordered until one comes back short: yields (idx, dist, stamps, counts) with the padding cut off.
+        Rows appended or deleted between two pages are honoured as they stand when each page is asked for."""
+        return _timeline(lambda after: self.knn_ordered(reference, k, max_dist, descending, after, **predicate), k)
+
+    def stamp_histogram(self, reference: np.ndarray, edges, max_dist: float = float("inf"), **predicate) -> np.ndarray:
+        """The timeline facet (mi_knn_stamp_histogram): hist[b] = the rows within max_dist (and the predicate) with exactly b of
+        the strictly ascending edges <= stamp; [len(edges) + 1] uint64, summing to knn_ordered's counts["within"]."""
+        return _stamp_histogram(lib().mi_knn_stamp_histogram, self._h, self.dim, (), reference, edges, max_dist, predicate)
 
     def pages(self, reference: np.ndarray, k: int = 100, max_dist: float = float("inf"), within=None):
         """knn_page after knn_page until one comes back short: yields (idx, dist, counts) with the padding cut off.  Rows
@@ -913,6 +987,25 @@ class ShardedTable:
     def knn_page(self, reference: np.ndarray, k: int = 100, after=None, max_dist: float = float("inf"), within=None):
         """EmbeddingTable.knn_page over all shards (mi_knn_sharded_search_page): global ids, summed counts"""
         return _page_call(lib().mi_knn_sharded_search_page, self._h, self.dim, (), reference, k, after, max_dist, within=within)
+
+    def knn_ordered(self, reference: np.ndarray, k: int = 100, max_dist: float = float("inf"), descending: bool = False, after=None,
+                    **predicate):
+        """EmbeddingTable.knn_ordered over all shards, global ids, summed counts.  The rows within max_dist of the reference in the order of their stamps (mi_knn_search_ordered): ascending, or newest
+        first with descending=True; equal stamps by ascending id.  after: None (from the start) or the (stamp, id) of the
+        previous page's last hit — its row may have been deleted since.  predicate: the keyword arguments of make_where (none:
+        every live row).  Returns (idx, dist, stamps, counts): the hits in order, NO_ID / +inf / 0 behind them, and counts =
+        {"within", "before", "beyond", "nan"} ("101-200 of within").  k <= 4096."""
+        return _ordered_call(lib().mi_knn_sharded_search_ordered, self._h, self.dim, (), reference, k, max_dist, descending, after, predicate)
+
+    def timeline(self, reference: np.ndarray, k: int = 100, max_dist: float = float("inf"), descending: bool = False, **predicate):
+        """knn_ordered after knn_ordered until one comes back short: yields (idx, dist, stamps, counts) with the padding cut off.
+        Rows appended or deleted between two pages are honoured as they stand when each page is asked for."""
+        return _timeline(lambda after: self.knn_ordered(reference, k, max_dist, descending, after, **predicate), k)
+
+    def stamp_histogram(self, reference: np.ndarray, edges, max_dist: float = float("inf"), **predicate) -> np.ndarray:
+        """The timeline facet (mi_knn_stamp_histogram): hist[b] = the rows within max_dist (and the predicate) with exactly b of
+        the strictly ascending edges <= stamp; [len(edges) + 1] uint64, summing to knn_ordered's counts["within"]."""
+        return _stamp_histogram(lib().mi_knn_sharded_stamp_histogram, self._h, self.dim, (), reference, edges, max_dist, predicate)
 
     def assign(self, vectors: np.ndarray):
         """EmbeddingTable.assign over all shards (mi_knn_sharded_assign): labels / dist by global row id"""
@@ -1350,6 +1443,32 @@ class ImageIndex:
         check(lib().mi_index_search_where(self._h, q.ctypes.data, _cstrs(refs), len(refs), k, ctypes.byref(w), idx.ctypes.data,
                                           dist.ctypes.data, ctypes.byref(n), ctypes.byref(matched)))
         return [(int(idx[i]), self.path(int(idx[i]), web=web), float(dist[i])) for i in range(n.value)], matched.value
+
+    def web_search_ordered(self, text_embedding: np.ndarray, referenced_images: Sequence[str] = (), k: int = 100,
+                           max_dist: float = float("inf"), descending: bool = True, after=None, folder: Optional[str] = None,
+                           web: bool = True, **predicate):
+        """web_search_text as a timeline (mi_index_search_ordered): the query refined with the marked images, the images within
+        max_dist in the order of their stamps (newest first by default), a page of k after the (stamp, id) cursor.  predicate:
+        the keyword arguments of make_where; folder="media/a/b": only the images directly in that directory.  Returns ([(id,
+        image_path, distance, stamp)], counts, next) — next = the cursor for the following page, None when this was the last."""
+        refs = list(referenced_images)
+        if folder is not None:
+            predicate["group"] = self.group_of(folder)
+        idx, dist, stamps, counts = _ordered_call(lib().mi_index_search_ordered, self._h, self.dim, (_cstrs(refs), len(refs)),
+                                                  text_embedding, k, max_dist, descending, after, predicate, n_found=True)
+        n = int((idx != NO_ID).sum())
+        nxt = (int(stamps[n - 1]), int(idx[n - 1])) if n and n == int(k) else None
+        return [(int(idx[i]), self.path(int(idx[i]), web=web), float(dist[i]), int(stamps[i])) for i in range(n)], counts, nxt
+
+    def web_timeline_histogram(self, text_embedding: np.ndarray, edges, referenced_images: Sequence[str] = (),
+                               max_dist: float = float("inf"), folder: Optional[str] = None, **predicate) -> np.ndarray:
+        """The "matches per month" strip above web_search_ordered (mi_index_stamp_histogram): EmbeddingTable.stamp_histogram
+        behind the refined query; edges are the month starts."""
+        refs = list(referenced_images)
+        if folder is not None:
+            predicate["group"] = self.group_of(folder)
+        return _stamp_histogram(lib().mi_index_stamp_histogram, self._h, self.dim, (_cstrs(refs), len(refs)), text_embedding, edges,
+                                max_dist, predicate)
 
     def duplicates(self, max_dist: float, first_new: int = 0, web: bool = False, max_pairs: int = 1 << 20) -> list:
         """Groups of near-duplicate images (mi_index_duplicates): lists of paths whose embeddings are chained by cosine

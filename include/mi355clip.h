@@ -651,6 +651,47 @@ int mi_knn_rows_where(mi_knn* t, const mi_knn_where* w, uint64_t* ids, uint64_t 
  * search enqueued before it, and waits for its result. */
 int mi_knn_search_where(mi_knn* t, const float* q, uint32_t nq, uint32_t k, const mi_knn_where* w, uint64_t* idx, float* dist,
                         uint64_t* matched /* may be NULL */);
+/* ---- ordered search: the hits within a distance in the order of their stamps -----------------------------------------------------
+ * "Everything that looks like this, newest first, 100 at a time": the rows within max_dist of q, ordered by stamp instead of by
+ * distance, one page per call, and the timeline facet ("matches per month") over the same rows.
+ *   candidates  the live rows w keeps — exactly the rows mi_knn_rows_where returns; w == NULL: every live row.
+ *   within      a candidate is within iff its distance is not NaN and <= max_dist on the search's key order (inclusive, -0
+ *               before +0): the "window" class of mi_knn_search_page without a cursor.  A row's distance has the bits
+ *               mi_knn_search reports for it.
+ *   order       okey(s) = (uint64_t)s ^ 0x8000000000000000, bitwise complemented under MI_KNN_ORDER_DESC; the result order is
+ *               (okey(stamp), id) ascending: equal stamps break by ascending id in both directions.  A table that never set
+ *               attributes holds stamp 0 everywhere and is ordered by id.
+ *   cursor      with MI_KNN_ORDER_AFTER only rows with (okey(stamp), id) > (okey(after_stamp), after_id) are returned.  after_id
+ *               must name a row of the table (deleted or not), else MI_ERR_INVALID; after_stamp is taken as given, not looked up:
+ *               pass back (stamps[k-1], idx[k-1]) of the previous page.  Page n costs what page 1 costs, no row appears twice and
+ *               no surviving row is skipped when rows are appended or deleted between pages.  A row whose STAMP is changed
+ *               between two pages may move across the cursor: it can then appear twice or not at all.
+ *   result      the first min(k, remaining) slots: idx, dist (the distance bits), stamps (may be NULL) in the result order;
+ *               MI_KNN_NO_ID / +inf / 0 behind them.
+ *   counts      (may be NULL) {within, before, beyond, nan}: candidates within the bound (the cursor does not change it); those of
+ *               them at or before the cursor (0 without the flag); candidates with a non-NaN distance above the bound; candidates
+ *               with a NaN distance.  "101-200 of `within`".
+ * 1 <= k <= 4096 (0: MI_ERR_INVALID, larger: MI_ERR_UNSUPPORTED); dim as for mi_knn_search_page; max_dist NaN, unknown flag bits
+ * and a bad w (as mi_knn_search_where judges it): MI_ERR_INVALID.  An error writes nothing to any output.  An empty table, or a
+ * predicate that keeps nothing, gives padding and zero counts.
+ * How: the predicate's list (mi_knn_search_where's passes), mi_knn_search_page's scan leaving one distance key per candidate,
+ * then integers only: a radix select over the 96-bit key (okey(stamp), position) — one short histogram pass per digit, six for
+ * the stamp and three for the position, of which those behind a decided pick return at once — a collect, a one-block sort, one
+ * packed record back.  The same answer for any grid (option "page_blocks" sizes these passes too).  Runs on the handle's stream
+ * behind every write and search enqueued before it, and waits for its result. */
+#define MI_KNN_ORDER_DESC  1u   /* largest stamp first; default: smallest first */
+#define MI_KNN_ORDER_AFTER 2u   /* (after_stamp, after_id) is a cursor */
+int mi_knn_search_ordered(mi_knn* t, const float* q, uint32_t k, float max_dist,
+                          const mi_knn_where* w /* may be NULL: every live row */,
+                          uint32_t flags, int64_t after_stamp, uint64_t after_id,
+                          uint64_t* idx, float* dist, int64_t* stamps /* may be NULL */,
+                          uint64_t counts[4] /* may be NULL */);
+/* The timeline facet: hist[b] = the rows within (as above) with exactly b edges <= stamp — hist[0] is "before edges[0]",
+ * hist[n_edges] "at or after the last edge"; sum(hist) == within.  edges: strictly ascending, 1 <= n_edges <= 4096, else
+ * MI_ERR_INVALID (edges, not a bucket width: calendar months are not equal-width).  hist: [n_edges + 1], written only on
+ * success. */
+int mi_knn_stamp_histogram(mi_knn* t, const float* q, float max_dist, const mi_knn_where* w /* may be NULL */,
+                           const int64_t* edges, uint32_t n_edges, uint64_t* hist /* [n_edges + 1] */);
 /* host-only: pairs -> groups (connected components, union-find).  ids: every id that occurs in a pair, grouped; groups
  * ordered by their smallest id, ids ascending inside a group; group_start[g] .. group_start[g + 1] index ids
  * (group_start holds n_groups + 1 entries).  Two-call protocol: counts are always written, arrays up to their caps. */
@@ -753,6 +794,15 @@ int mi_knn_sharded_get_attrs(mi_knn_sharded* t, const uint64_t* ids, uint64_t n,
 int mi_knn_sharded_count_where(mi_knn_sharded* t, const mi_knn_where* w, uint64_t* count);
 int mi_knn_sharded_search_where(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, const mi_knn_where* w, uint64_t* idx,
                                 float* dist, uint64_t* matched /* may be NULL */);
+/* mi_knn_search_ordered / mi_knn_stamp_histogram on global ids: every shard runs the call on its own rows, on its own stream and
+ * host thread; a shard that does not hold after_id starts at its first row whose global id is larger.  The host merges the
+ * shards' lists by (okey(stamp), id) and sums the counts and the histograms: the result equals the one-table result bit for
+ * bit.  after_id must be a global row id of the table (deleted or not). */
+int mi_knn_sharded_search_ordered(mi_knn_sharded* t, const float* q, uint32_t k, float max_dist, const mi_knn_where* w, uint32_t flags,
+                                  int64_t after_stamp, uint64_t after_id, uint64_t* idx, float* dist, int64_t* stamps,
+                                  uint64_t counts[4]);
+int mi_knn_sharded_stamp_histogram(mi_knn_sharded* t, const float* q, float max_dist, const mi_knn_where* w, const int64_t* edges,
+                                   uint32_t n_edges, uint64_t* hist);
 /* mi_knn_assign over the whole table: every shard labels its own rows on its own stream (concurrently: no exchange is
  * needed), the results land at the rows' global ids.  labels / dist: [rows of the table]; equals the one-table result
  * bit for bit.  (k-means over a sharded table is not offered: its update needs a cross-shard reduction.) */
@@ -934,6 +984,16 @@ int mi_index_set_attrs(mi_index* ix, const char* const* paths, size_t n, const u
  * [k], *n_found (may be NULL) = results before the padding, *matched (may be NULL) = the qualifying rows. */
 int mi_index_search_where(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref, uint32_t k,
                           const mi_knn_where* where, uint64_t* idx, float* dist, uint32_t* n_found, uint64_t* matched);
+/* web_search_text as a timeline (mi_knn_search_ordered / mi_knn_stamp_histogram): the refined query of mi_index_search, a
+ * predicate as mi_index_search_where takes it (where may be NULL; with MI_KNN_WHERE_GROUP the group is a directory id and the
+ * group column is brought up to date first), the cursor and the flags of mi_knn_search_ordered.  Removed paths never appear.
+ * idx / dist [k], stamps [k] (may be NULL), *n_found (may be NULL) = results before the padding, counts (may be NULL) as for
+ * mi_knn_search_ordered. */
+int mi_index_search_ordered(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref, uint32_t k,
+                            float max_dist, const mi_knn_where* where, uint32_t flags, int64_t after_stamp, uint64_t after_id,
+                            uint64_t* idx, float* dist, int64_t* stamps, uint32_t* n_found, uint64_t counts[4]);
+int mi_index_stamp_histogram(mi_index* ix, const float* text_embedding, const char* const* referenced_images, size_t n_ref,
+                             float max_dist, const mi_knn_where* where, const int64_t* edges, uint32_t n_edges, uint64_t* hist);
 /* `<dir>/embedding.miknn` + `<dir>/image_path.bin`, each through a temporary file, fsync and rename, the path file
  * last: after a crash the directory holds a consistent index (at worst the one before the save). */
 int mi_index_save(mi_index* ix, const char* dir);
