@@ -203,6 +203,9 @@ struct mi_knn {
     // "join_cap"; its buffers live for the call only), and {candidates, pairs, strips, tiles} of the last call.
     uint32_t join_cap = 1u << 22;
     uint64_t join_stats[4] = {0, 0, 0, 0};
+    // mi_knn_density / mi_knn_dbscan (density.hip): {candidates pass 1, pairs within, tiles pass 1, candidates pass 2, tiles
+    // visited pass 2, tiles skipped pass 2, unions that merged, stage-1 launches} of the last call
+    uint64_t dbscan_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // mi_knn_assign (assign.hip): {candidates, live rows labelled, stage-1 launches, tiles} of the last assign
     uint64_t assign_stats[4] = {0, 0, 0, 0};
     // mi_knn_assign_multi (assign_multi.hip): {candidates, (row, label) hits written, stage-1 launches, tiles} of the last call

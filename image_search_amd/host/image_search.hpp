@@ -222,6 +222,43 @@ class EmbeddingTable {
     }
     // {candidate pairs, pairs accepted, strips run, tiles visited} of the last near_pairs
     std::vector<uint64_t> near_pairs_stats() const { std::vector<uint64_t> v(4); check(mi_knn_near_pairs_stats(h_, v.data())); return v; }
+    // how crowded it is around every row (mi_knn_density): the pairs of near_pairs(max_dist) that contain the row, by local row;
+    // 0 for a deleted row and for an outlier.  No pair list is built
+    std::vector<uint32_t> neighbor_counts(float max_dist) const {
+        std::vector<uint32_t> counts(size());
+        uint32_t none = 0;
+        check(mi_knn_density(h_, max_dist, counts.empty() ? &none : counts.data()));
+        return counts;
+    }
+    // density clusters without a k (mi_knn_dbscan), arrays by local row: labels 0 .. C - 1 in the order of the clusters' smallest
+    // core ids (-1: noise or deleted, as scikit-learn numbers them), cluster = the id of the cluster's smallest core row, via =
+    // a core's own id / the core a border row joined through, via_dist = +0 / that pair's distance bits / +inf, counts = the
+    // neighbours within, summary = {clusters, core rows, border rows, noise rows}.  The labels fit set_groups
+    struct Dbscan {
+        std::vector<int64_t> labels;
+        std::vector<uint64_t> cluster, via;
+        std::vector<float> via_dist;
+        std::vector<uint32_t> counts;
+        uint64_t summary[4] = {0, 0, 0, 0};
+    };
+    Dbscan dbscan(float max_dist, uint32_t min_pts = 5) const {
+        Dbscan r;
+        const uint64_t n = size();
+        r.cluster.resize(n + 1); r.via.resize(n + 1); r.via_dist.resize(n + 1); r.counts.resize(n + 1);   // (+ 1: never a null pointer)
+        check(mi_knn_dbscan(h_, max_dist, min_pts, r.cluster.data(), r.via.data(), r.via_dist.data(), r.counts.data(), r.summary));
+        r.cluster.resize(n); r.via.resize(n); r.via_dist.resize(n); r.counts.resize(n);
+        std::vector<uint64_t> names;
+        for (uint64_t c : r.cluster) if (c != MI_KNN_NO_ID) names.push_back(c);
+        std::sort(names.begin(), names.end());
+        names.erase(std::unique(names.begin(), names.end()), names.end());
+        r.labels.assign(n, -1);
+        for (uint64_t i = 0; i < n; ++i)
+            if (r.cluster[i] != MI_KNN_NO_ID) r.labels[i] = (int64_t)(std::lower_bound(names.begin(), names.end(), r.cluster[i]) - names.begin());
+        return r;
+    }
+    // {candidates pass 1, pairs within, tiles pass 1, candidates pass 2, tiles visited pass 2, tiles skipped pass 2, unions that
+    // merged, stage-1 launches} of the last neighbor_counts / dbscan
+    std::vector<uint64_t> dbscan_stats() const { std::vector<uint64_t> v(8); check(mi_knn_dbscan_stats(h_, v.data())); return v; }
     // label every row by the nearest of C vectors (mi_knn_assign): for a live row what a table of the vectors answers to
     // knn(row, 1), id and distance bits; MI_KNN_NO_LABEL / +inf for a deleted row.  vectors: [C * dim]
     struct Assignment { std::vector<uint32_t> labels; std::vector<float> dist; };
@@ -619,6 +656,23 @@ class ImageIndex {
         check(mi_index_duplicates(h_, max_dist, first_new, max_pairs, ids.data(), ids.size(), start.data(), start.size(), &n_ids, &n_groups));
         std::vector<std::vector<std::string>> out;
         for (const auto& g : groups_from(ids, start)) {
+            out.emplace_back();
+            for (uint64_t id : g) out.back().push_back(path(id, web));
+        }
+        return out;
+    }
+    // the themes that are really there as lists of paths (mi_index_themes), what a /themes handler returns: the largest
+    // cluster first, equal sizes by their first row; removed paths never appear.  *n_noise (may be null): the live rows in no theme
+    std::vector<std::vector<std::string>> themes(float max_dist, uint32_t min_pts = 5, bool web = false, uint64_t* n_noise = nullptr) const {
+        uint64_t n_ids = 0, n_groups = 0, noise = 0;
+        std::vector<uint64_t> ids(size() + 1), start(size() + 1);   // every row in a theme of its own still fits: one call, not two
+        check(mi_index_themes(h_, max_dist, min_pts, ids.data(), ids.size(), start.data(), start.size(), &n_ids, &n_groups, &noise));
+        ids.resize(n_ids); start.resize(n_groups + 1);
+        if (n_noise) *n_noise = noise;
+        auto groups = groups_from(ids, start);
+        std::stable_sort(groups.begin(), groups.end(), [](const auto& x, const auto& y) { return x.size() > y.size(); });
+        std::vector<std::vector<std::string>> out;
+        for (const auto& g : groups) {
             out.emplace_back();
             for (uint64_t id : g) out.back().push_back(path(id, web));
         }

@@ -375,6 +375,40 @@ class EmbeddingTable:
         check(lib().mi_knn_near_pairs_stats(self._h, out))
         return {"candidates": out[0], "pairs": out[1], "strips": out[2], "tiles": out[3]}
 
+    def neighbor_counts(self, max_dist: float) -> np.ndarray:
+        """How crowded is it around every row (mi_knn_density): counts [rows] uint32 = the pairs of near_pairs(max_dist) that
+        contain the row, the row itself not counted; 0 for a deleted row — and for an outlier.  No pair list is built."""
+        counts = np.empty(len(self), np.uint32)
+        check(lib().mi_knn_density(self._h, float(max_dist), counts.ctypes.data))
+        return counts
+
+    def dbscan(self, max_dist: float, min_pts: int = 5) -> dict:
+        """Density clusters without a k (mi_knn_dbscan) over the pairs of near_pairs(max_dist), which never leave the device.
+        A row is a core when it has at least min_pts - 1 neighbours within max_dist (scikit-learn's min_samples: the row
+        itself counts); clusters are the components of the core rows; a non-core row beside a core is a border row of the
+        cluster of its nearest core (distance key, then row); the rest is noise.  Arrays by local row:
+        labels (int64: 0 .. C - 1 in the order of the clusters' smallest core ids, -1 noise or deleted, as scikit-learn numbers
+        them), cluster (uint64: the id of the cluster's smallest core row, NO_ID), via (uint64: a core's own id, the core a
+        border row joined through, NO_ID), via_dist (float32: +0, that pair's distance bits, +inf), counts (uint32: the
+        neighbours within), summary {"clusters", "core", "border", "noise"}.
+        labels.astype(np.uint32) fits set_groups (-1 becomes NO_GROUP: a row of its own), so knn_grouped then answers "the best
+        picture of each theme"."""
+        n = len(self)
+        cluster, via = np.empty(n, np.uint64), np.empty(n, np.uint64)
+        via_dist, counts = np.empty(n, np.float32), np.empty(n, np.uint32)
+        summary = np.zeros(4, np.uint64)
+        check(lib().mi_knn_dbscan(self._h, float(max_dist), int(min_pts), cluster.ctypes.data, via.ctypes.data, via_dist.ctypes.data,
+                                  counts.ctypes.data, summary.ctypes.data))
+        return {"labels": dense_labels(cluster), "cluster": cluster, "via": via, "via_dist": via_dist, "counts": counts,
+                "summary": dict(zip(("clusters", "core", "border", "noise"), (int(v) for v in summary)))}
+
+    def dbscan_stats(self) -> dict:
+        """mi_knn_dbscan_stats, of the last neighbor_counts / dbscan on this table"""
+        out = (ctypes.c_uint64 * 8)()
+        check(lib().mi_knn_dbscan_stats(self._h, out))
+        return dict(zip(("candidates_pass1", "pairs", "tiles_pass1", "candidates_pass2", "tiles_visited", "tiles_skipped",
+                         "unions_merged", "launches"), (int(v) for v in out)))
+
     def assign(self, vectors: np.ndarray):
         """Label every row by the nearest of C vectors (mi_knn_assign): (labels [rows] uint32, dist [rows] f32) — for a live
         row what a table of the vectors answers to knn(row, 1), id and distance bits; NO_LABEL / +inf for a deleted row."""
@@ -679,6 +713,15 @@ def clusters_of(labels, keys) -> list:
         if int(lab) != int(NO_LABEL):
             by.setdefault(int(lab), []).append(key)
     return [by[lab] for lab in sorted(by, key=lambda c: (-len(by[c]), c))]
+
+
+def dense_labels(cluster) -> np.ndarray:
+    """cluster ids as dbscan reports them (NO_ID: none) -> int64 labels 0 .. C - 1 in the order of the ids, -1 where none"""
+    cluster = np.asarray(cluster, np.uint64).reshape(-1)
+    labels = np.full(cluster.size, -1, np.int64)
+    has = cluster != NO_ID
+    labels[has] = np.searchsorted(np.unique(cluster[has]), cluster[has])
+    return labels
 
 
 def _groups(ids: np.ndarray, starts: np.ndarray) -> list:
@@ -1481,6 +1524,21 @@ class ImageIndex:
         check(lib().mi_index_duplicates(self._h, float(max_dist), int(first_new), max_pairs, ids.ctypes.data if ids.size else None,
                                         ids.size, starts.ctypes.data, starts.size, ctypes.byref(n_ids), ctypes.byref(n_groups)))
         return [[self.path(int(i), web=web) for i in g] for g in _groups(ids, starts)]
+
+    def themes(self, max_dist: float, min_pts: int = 5, web: bool = False):
+        """The events / themes that are really there, however many, and the odd pictures (mi_index_themes: EmbeddingTable.dbscan
+        on the index's table): (lists of paths, the largest cluster first, equal sizes by their first row, paths ordered by
+        row id inside a list; the paths of the noise rows).  Removed paths are in neither."""
+        n_ids, n_groups, n_noise = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        n = len(self.table)
+        ids, starts = np.empty(n, np.uint64), np.empty(n + 1, np.uint64)
+        check(lib().mi_index_themes(self._h, float(max_dist), int(min_pts), ids.ctypes.data if n else None, n, starts.ctypes.data,
+                                    starts.size, ctypes.byref(n_ids), ctypes.byref(n_groups), ctypes.byref(n_noise)))
+        ids, starts = ids[:n_ids.value], starts[:n_groups.value + 1]
+        groups = sorted(_groups(ids, starts), key=lambda g: (-len(g), int(g[0])))
+        out = set(int(i) for i in ids) | set(int(i) for i in self.table.deleted())
+        noise = [r for r in range(n) if r not in out]   # n_noise.value of them
+        return [[self.path(int(i), web=web) for i in g] for g in groups], [self.path(r, web=web) for r in noise]
 
     def label(self, vectors: np.ndarray, names: Optional[Sequence[str]] = None, web: bool = False) -> dict:
         """"Tag my library" (EmbeddingTable.assign): {path: (label, distance)} for every path that has not been removed;

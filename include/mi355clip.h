@@ -352,6 +352,37 @@ int mi_knn_near_pairs(mi_knn* t, float max_dist, uint64_t first_new, uint64_t* a
 /* of the last mi_knn_near_pairs on this handle: out = {candidate pairs stage 1 passed to stage 2, pairs accepted,
  * strips run (re-runs after an overflow included), tiles visited} */
 int mi_knn_near_pairs_stats(mi_knn* t, uint64_t out[4]);
+/* Density ("how crowded is it around every image?") and DBSCAN ("which themes are really there, however many, and which
+ * pictures belong to none?") on the join's tiles; the pairs never leave the device, so a dense theme costs no pair list.
+ * Let W be the pairs (a < b, d) that mi_knn_near_pairs(t, max_dist, first_new = 0) reports: live rows only, d the bits
+ * mi_knn_search reports with q = row a for row b, a NaN never within.  Arrays are indexed by local row (rows = mi_knn_size,
+ * deleted rows counted), as mi_knn_assign's are; ids go through the table's base / block-cyclic map.
+ *   deg[r]     the number of pairs of W that contain r (the row itself is not counted); 0 for a deleted row.
+ *   core       r is live and deg[r] + 1 >= min_pts (scikit-learn's min_samples: the point itself counts).
+ *   clusters   the connected components of the graph on the core rows whose edges are the pairs of W with both ends core; a
+ *              cluster is named by the id of its smallest core row.
+ *   border     a live non-core row with a core neighbour in W: it belongs to the cluster of the core neighbour c that minimises
+ *              (the search's 32-bit key of the pair's d — so -0 comes before +0 —, row of c); d is the pair's distance as W holds
+ *              it whichever end the border row is.  This fixes what classic DBSCAN leaves to the visiting order.
+ *   noise      every other live row.  A deleted row is nothing at all.
+ * mi_knn_density: counts [rows] = deg.
+ * mi_knn_dbscan: cluster [rows] = the id of the row's cluster, MI_KNN_NO_ID for noise and deleted rows; via [rows] (may be
+ * NULL) = a core row: its own id, a border row: the core it joined through, else MI_KNN_NO_ID; via_dist [rows] (may be NULL) =
+ * core: +0.0f, border: that pair's distance bits, else +inf; counts [rows] (may be NULL) = deg; summary = {clusters, core rows,
+ * border rows, noise rows}.  The result does not depend on arrival order, grid or strip size.
+ * max_dist NaN or < 0, min_pts == 0, a null handle or a null required pointer: MI_ERR_INVALID.  dim, mirror, "join_cap" and
+ * stream ordering: as mi_knn_near_pairs (two tile passes for mi_knn_dbscan, one for mi_knn_density; 16 bytes of device memory
+ * per row beside the join's buffers, plus the result arrays, freed before the call returns).  An error writes nothing.  An
+ * empty table is valid (no clusters); with min_pts == 1 every live row is a core, a lone one a cluster of one.  Should the
+ * bounded retry loops of the device's disjoint-set forest ever run out (they never should), the call fails with MI_ERR_HIP. */
+int mi_knn_density(mi_knn* t, float max_dist, uint32_t* counts);
+int mi_knn_dbscan(mi_knn* t, float max_dist, uint32_t min_pts, uint64_t* cluster, uint64_t* via, float* via_dist,
+                  uint32_t* counts, uint64_t summary[4]);
+/* of the last mi_knn_density / mi_knn_dbscan on this handle: out = {candidate pairs pass 1, pairs within, tiles pass 1,
+ * candidate pairs pass 2, tiles visited pass 2, tiles skipped pass 2 (both blocks must hold a row with a neighbour and one a
+ * core: exact), unions that merged two trees, stage-1 launches of both passes (re-runs after an overflow included)}.  The tile
+ * counts are those of the launches whose candidates were consumed: visited + skipped = the triangle's tiles. */
+int mi_knn_dbscan_stats(mi_knn* t, uint64_t out[8]);
 /* Label every row by its nearest of C vectors ("tag my library" with C text embeddings; the inner step of k-means): the
  * search turned round.  For every row r of the table (rows = mi_knn_size, deleted rows counted):
  *   r live     labels[r], dist[r] = the first entry of mi_knn_search(T_v, q = row r, k = 1) where T_v holds exactly the C
@@ -1012,6 +1043,10 @@ int mi_index_live_paths(mi_index* ix, char* buf, size_t cap, size_t* needed);
  * max_pairs bounds the join (MI_ERR_UNSUPPORTED beyond it). */
 int mi_index_duplicates(mi_index* ix, float max_dist, uint64_t first_new, uint64_t max_pairs, uint64_t* ids,
                         uint64_t cap_ids, uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups);
+/* themes of table `image`: mi_knn_dbscan on mi_index_table in mi_index_duplicates' output shape — the clusters ordered by
+ * their smallest id, ids ascending inside; noise is not listed, *n_noise counts it; removed paths are in neither. */
+int mi_index_themes(mi_index* ix, float max_dist, uint32_t min_pts, uint64_t* ids, uint64_t cap_ids, uint64_t* group_start,
+                    uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups, uint64_t* n_noise);
 
 /* ------------------------------------------------------------ query refinement */
 
