@@ -95,14 +95,12 @@ struct Assign {
         dispatch_nch(t->dim, [&](auto nch) { run<decltype(nch)::value>(count_changed, changed); });
     }
 
-    // t->mu held, device selected, arguments checked, the table not empty
-    void setup(mi_knn* table, uint32_t n_vec) {
-        t = table;
+    // inside the call's frame (declared after this object: the stream is idle before the scratch memory goes); arguments
+    // checked, the table not empty
+    void setup(const TableCall& call, uint32_t n_vec) {
+        t = call.t;
         C = n_vec;
-        s = knn_own_stream(t);
-        // behind every write and search enqueued before this call, on whichever stream
-        t->writes.begin(s);
-        t->reads.begin(s);
+        s = call.s;
         n_rows = (uint32_t)t->rows;
         n_cb = (C + TILE - 1) / TILE;
         thr = 2.0f * eps2(t->dim);   // the join's bound, unchanged (join_kernels.h): both operands are rounded to bf16
@@ -135,10 +133,9 @@ void assign_local(mi_knn* t, const float* vectors, uint32_t C, uint32_t* labels,
     std::lock_guard<std::mutex> l(t->mu);
     for (uint64_t& v : t->assign_stats) v = 0;
     if (t->rows == 0) return;
-    DeviceGuard g(t->device);
     Assign a;
-    a.setup(t, C);
-    Settle settle{t, a.s};
+    TableCall call(t);
+    a.setup(call, C);
     HIP_CHECK(hipMemcpyAsync(a.d_vec, vectors, (size_t)C * t->dim * sizeof(float), hipMemcpyHostToDevice, a.s));
     a.run();
     HIP_CHECK(hipMemcpyAsync(labels, a.d_labels, (size_t)a.n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, a.s));
@@ -239,10 +236,9 @@ int mi_knn_kmeans(mi_knn* t, float* centroids, uint32_t C, uint32_t max_iters, u
         std::lock_guard<std::mutex> l(t->mu);
         for (uint64_t& v : t->assign_stats) v = 0;
         if (t->rows == 0) return;
-        DeviceGuard g(t->device);
         Assign a;
-        a.setup(t, C);
-        Settle settle{t, a.s};
+        TableCall call(t);
+        a.setup(call, C);
         const size_t cbytes = (size_t)C * t->dim * sizeof(float);
         HIP_CHECK(hipMemcpyAsync(a.d_vec, centroids, cbytes, hipMemcpyHostToDevice, a.s));
         uint32_t it = 0;
@@ -280,7 +276,7 @@ int mi_knn_sharded_assign(mi_knn_sharded* t, const float* vectors, uint32_t C, u
             std::vector<uint32_t> lab(rows);
             std::vector<float> dd(dist ? rows : 0);
             assign_local(sh, vectors, C, lab.data(), dist ? dd.data() : nullptr);
-            const IdMap map{sh->base, sh->cyc_block, sh->cyc_n, sh->cyc_rank};
+            const IdMap map = knn_id_map(sh);
             for (uint64_t r = 0; r < rows; ++r) {
                 const uint64_t id = id_of_local(map, r);
                 labels[id] = lab[r];

@@ -131,16 +131,14 @@ struct AssignMulti {
         dispatch_nch(t->dim, [&](auto nch) { run<decltype(nch)::value>(labels, dist); });
     }
 
-    // t->mu held, device selected, arguments checked, the table not empty
-    void setup(mi_knn* table, uint32_t n_vec, uint32_t n_lab, float md) {
-        t = table;
+    // inside the call's frame (declared after this object: the stream is idle before the scratch memory goes); arguments
+    // checked, the table not empty
+    void setup(const TableCall& call, uint32_t n_vec, uint32_t n_lab, float md) {
+        t = call.t;
         C = n_vec;
         m = n_lab;
         max_dist = md;
-        s = knn_own_stream(t);
-        // behind every write and search enqueued before this call, on whichever stream
-        t->writes.begin(s);
-        t->reads.begin(s);
+        s = call.s;
         n_rows = (uint32_t)t->rows;
         n_cb = (C + TILE - 1) / TILE;
         const float e2 = eps2(t->dim);   // the join's bound, unchanged (join_kernels.h): both operands are rounded to bf16
@@ -183,10 +181,9 @@ void assign_multi_local(mi_knn* t, const float* vectors, uint32_t C, uint32_t m,
     std::lock_guard<std::mutex> l(t->mu);
     for (uint64_t& v : t->assign_multi_stats) v = 0;
     if (t->rows == 0) return;
-    DeviceGuard g(t->device);
     AssignMulti a;
-    a.setup(t, C, m, max_dist);
-    Settle settle{t, a.s};
+    TableCall call(t);
+    a.setup(call, C, m, max_dist);
     HIP_CHECK(hipMemcpyAsync(a.d_vec, vectors, (size_t)C * t->dim * sizeof(float), hipMemcpyHostToDevice, a.s));
     a.run(labels, dist);
 }
@@ -224,7 +221,7 @@ int mi_knn_sharded_assign_multi(mi_knn_sharded* t, const float* vectors, uint32_
             std::vector<uint32_t> lab(rows * m);
             std::vector<float> dd(dist ? rows * m : 0);
             assign_multi_local(sh, vectors, C, m, max_dist, lab.data(), dist ? dd.data() : nullptr);
-            const IdMap map{sh->base, sh->cyc_block, sh->cyc_n, sh->cyc_rank};
+            const IdMap map = knn_id_map(sh);
             for (uint64_t r = 0; r < rows; ++r) {
                 const uint64_t id = id_of_local(map, r);
                 std::memcpy(labels + id * m, lab.data() + r * m, m * sizeof(uint32_t));

@@ -1,5 +1,5 @@
 // compound_host.h — the host-only pieces of mi_knn_search_compound (compound.hip): the argument rules, the term set as the
-// scan wants it (padded to 2 / 4 / 8 resident terms with their roles and thresholds), the grid rule of "compound_blocks",
+// scan wants it (padded to 2 / 4 / 8 resident terms with their roles and thresholds), the per-CU factor of "compound_blocks",
 // the layout of the one record the device writes, and how it (or "no candidate") reaches the caller's arrays.  No HIP in
 // here: tests/cpp/test_compound_host.cpp runs it under the sanitizers.
 #pragma once
@@ -38,8 +38,6 @@ inline int compound_check_args(const void* t, const float* pos, uint32_t n_pos, 
     return MI_OK;
 }
 
-inline bool compound_dim_ok(uint32_t dim) { return dim == 128 || dim == 256 || dim == 512 || dim == 768 || dim == 1024; }
-
 // The resident term set: the T = n_pos + n_neg terms, positives first, then copies of the first positive term up to 2 / 4 / 8
 // (a repeated positive term changes no maximum and no minimum).  neg_mask bit u = term u is negative; within[u] its threshold.
 struct CompoundSet {
@@ -63,13 +61,8 @@ inline CompoundSet compound_set(const float* pos, uint32_t n_pos, const float* n
     return c;
 }
 
-// workgroups of the scan over n rows or list entries (a workgroup = 4 waves, a wave's tile = 64): option 0 = the batched
-// search's grid, v >= 1 = exactly min(v, needed)
-inline uint32_t compound_grid(uint64_t n, int n_cu, int option) {
-    const uint64_t n_tiles = (n + 63) / 64, needed = std::max<uint64_t>(1, (n_tiles + 3) / 4);
-    const uint64_t want = option >= 1 ? (uint64_t)option : (uint64_t)std::max(n_cu, 1) * 2;
-    return (uint32_t)std::min(want, needed);
-}
+// the scan's workgroups with "compound_blocks" = 0: the batched search's grid, two per CU (scan_grid of scan_call.h)
+constexpr uint32_t COMPOUND_BLOCKS_PER_CU = 2;
 
 // The record: idx [k] u64 | stats [4] u64 = {excluded, NaN scores, -, results written} | dist [k] f32 | term_dist [k][T] f32
 struct CompoundRecord {

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.h"
+#include "ids.h"
 
 namespace mi {
 
@@ -146,16 +147,14 @@ int mi_knn_merge(const uint64_t* idx_in, const float* dist_in, uint32_t lists, u
 int mi_knn_sharded_place(uint32_t block_rows, uint32_t n_shards, uint64_t row, uint32_t* shard, uint64_t* local) {
     return guarded([&] {
         if (block_rows == 0 || n_shards == 0 || !shard || !local) fail(MI_ERR_INVALID, "bad argument");
-        const uint64_t blk = row / block_rows;
-        *shard = (uint32_t)(blk % n_shards);
-        *local = (blk / n_shards) * block_rows + row % block_rows;
+        cyclic_place(block_rows, n_shards, row, shard, local);
     });
 }
 
 int mi_knn_sharded_id(uint32_t block_rows, uint32_t n_shards, uint32_t shard, uint64_t local, uint64_t* row) {
     return guarded([&] {
         if (block_rows == 0 || n_shards == 0 || shard >= n_shards || !row) fail(MI_ERR_INVALID, "bad argument");
-        *row = ((local / block_rows) * n_shards + shard) * block_rows + local % block_rows;
+        *row = id_of_local(IdMap{0, block_rows, n_shards, shard}, local);
     });
 }
 

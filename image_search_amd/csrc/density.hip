@@ -117,14 +117,9 @@ void density_run(mi_knn* t, float max_dist, uint32_t min_pts, bool want_via, boo
     const uint64_t rows = t->rows;
     if (rows >= (1ull << 32)) fail(MI_ERR_UNSUPPORTED, "at most 2^32 - 1 rows (got %llu)", (unsigned long long)rows);
     if (rows == 0) return;
-    DeviceGuard g(t->device);
-    hipStream_t s = knn_own_stream(t);
-    // behind every write and search enqueued before this call, on whichever stream
-    t->writes.begin(s);
-    t->reads.begin(s);
-
     Scratch scratch;
-    Settle settle{t, s};
+    TableCall call(t);
+    hipStream_t s = call.s;
     Density d;
     d.t = t; d.s = s;
     d.n_rows = (uint32_t)rows;
@@ -176,7 +171,7 @@ void density_run(mi_knn* t, float max_dist, uint32_t min_pts, bool want_via, boo
     uint64_t* d_cluster = (uint64_t*)scratch.get(rows * sizeof(uint64_t));
     uint64_t* d_via = want_via ? (uint64_t*)scratch.get(rows * sizeof(uint64_t)) : nullptr;
     float* d_via_dist = want_via_dist ? (float*)scratch.get(rows * sizeof(float)) : nullptr;
-    const IdMap map{t->base, t->cyc_block, t->cyc_n, t->cyc_rank};
+    const IdMap map = knn_id_map(t);
     hipLaunchKernelGGL(density_finish_kernel, dim3((d.n_rows + 255) / 256), dim3(256), 0, s, d.d_deg, d.d_parent, d.d_bkey, d.tomb, d.n_rows,
                        min_pts, map, d_cluster, d_via, d_via_dist, d.d_words);
     HIP_CHECK(hipGetLastError());
@@ -267,7 +262,7 @@ int mi_index_themes(mi_index* ix, float max_dist, uint32_t min_pts, uint64_t* id
         IdMap map;
         {
             std::lock_guard<std::mutex> l(t->mu);
-            map = IdMap{t->base, t->cyc_block, t->cyc_n, t->cyc_rank};
+            map = knn_id_map(t);
         }
         std::vector<uint64_t> row_ids(out.cluster.size());
         for (size_t r = 0; r < row_ids.size(); ++r) row_ids[r] = id_of_local(map, r);

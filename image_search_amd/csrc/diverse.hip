@@ -96,13 +96,9 @@ int mi_knn_search_diverse(mi_knn* t, const float* q, uint32_t k, uint32_t pool, 
             return;
         }
 
-        DeviceGuard g(t->device);
-        hipStream_t s = knn_own_stream(t);
-        // behind every write and search enqueued before this call, on whichever stream
-        t->writes.begin(s);
-        t->reads.begin(s);
         Scratch scratch;
-        Settle settle{t, s};
+        TableCall call(t);
+        hipStream_t s = call.s;
 
         const DiverseRecord rec = diverse_record(k, pool);
         Carve a;

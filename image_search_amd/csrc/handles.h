@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.h"
+#include "ids.h"
 
 namespace mi {
 typedef unsigned short bf16_t;
@@ -331,6 +332,9 @@ void clip_ensure_workspace(mi_clip* m, size_t n);   // frees and reallocates: wa
 void clip_ensure_copy_stream(mi_clip* m);
 void clip_forward(mi_clip* m, const float* d_img, size_t n, float* d_out, hipStream_t s, hipStream_t front = nullptr);
 // knn.hip
+IdMap knn_id_map(const mi_knn* t);                  // the table's id space (ids.h): what its kernels emit and its calls accept
+// ids (nullable: the first n rows) -> local rows, every one checked; MI_ERR_INVALID names the first that is no row.  t->mu held
+std::vector<uint32_t> knn_local_rows(const mi_knn* t, const uint64_t* ids, uint64_t n);
 hipStream_t knn_own_stream(mi_knn* t);
 void knn_grow(mi_knn* t, uint64_t want_rows);       // may reallocate: waits for the handle's pending work
 void knn_search_one(mi_knn* t, const float* d_q, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s);

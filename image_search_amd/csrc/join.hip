@@ -99,7 +99,7 @@ struct Join {
 // first_new (an id of the table, one past its last id, or 0 = everything) -> local row
 uint32_t local_first_new(const mi_knn* t, uint64_t first_new) {
     if (first_new == 0) return 0;
-    const IdMap map{t->base, t->cyc_block, t->cyc_n, t->cyc_rank};
+    const IdMap map = knn_id_map(t);
     if (first_new == id_of_local(map, t->rows)) return (uint32_t)t->rows;
     // (ids are monotone in the local ordinal: a binary search serves the plain and the block-cyclic map alike)
     uint64_t lo = 0, hi = t->rows;
@@ -122,14 +122,9 @@ void near_pairs(mi_knn* t, float max_dist, uint64_t first_new_id, uint64_t user_
     const uint32_t fn = local_first_new(t, first_new_id);
     check_mirror_dim(t->dim, "the join's");
     if (t->rows < 2 || fn >= t->rows) return;
-    DeviceGuard g(t->device);
-    hipStream_t s = knn_own_stream(t);
-    // behind every write and search enqueued before this call, on whichever stream
-    t->writes.begin(s);
-    t->reads.begin(s);
-
     Scratch scratch;
-    Settle settle{t, s};
+    TableCall call(t);
+    hipStream_t s = call.s;
     Join j;
     j.t = t; j.s = s;
     j.n_rows = (uint32_t)t->rows; j.first_new = fn;
@@ -218,7 +213,7 @@ int mi_knn_near_pairs(mi_knn* t, float max_dist, uint64_t first_new, uint64_t* a
             fail(MI_ERR_UNSUPPORTED, "more than %llu pairs lie within %g: lower max_dist or raise cap", (unsigned long long)cap,
                  (double)max_dist);
         }
-        const IdMap map{t->base, t->cyc_block, t->cyc_n, t->cyc_rank};
+        const IdMap map = knn_id_map(t);
         for (size_t i = 0; i < pairs.size(); ++i) {
             a[i] = id_of_local(map, pairs[i].a);
             b[i] = id_of_local(map, pairs[i].b);
@@ -267,7 +262,7 @@ int mi_index_duplicates(mi_index* ix, float max_dist, uint64_t first_new, uint64
         if (over)
             fail(MI_ERR_UNSUPPORTED, "more than %llu pairs lie within %g: lower max_dist or raise max_pairs",
                  (unsigned long long)max_pairs, (double)max_dist);
-        const IdMap map{t->base, t->cyc_block, t->cyc_n, t->cyc_rank};
+        const IdMap map = knn_id_map(t);
         std::vector<uint64_t> pa(pairs.size()), pb(pairs.size());
         for (size_t i = 0; i < pairs.size(); ++i) { pa[i] = id_of_local(map, pairs[i].a); pb[i] = id_of_local(map, pairs[i].b); }
         std::vector<uint64_t> gids, starts;

@@ -81,16 +81,12 @@ int mi_knn_kmeans_seed(mi_knn* t, uint32_t C, uint64_t seed, const uint64_t* amo
             out = v ^ (v >> 31);
         }
 
-        DeviceGuard g(t->device);
-        hipStream_t s = knn_own_stream(t);
-        // behind every write and search enqueued before this call, on whichever stream
-        t->writes.begin(s);
-        t->reads.begin(s);
         std::vector<uint32_t> picks(C);
         uint32_t h_state[2] = {0, 0};
         unsigned long long total = 0;
         Scratch scratch;
-        Settle settle{t, s};
+        TableCall call(t);
+        hipStream_t s = call.s;
         // a chunk: as many positions as keep the chunk sums within what one pick scans
         const uint32_t per = (uint32_t)(((uint64_t)S + (uint64_t)KMPP_CHUNK * KMPP_MAX_CHUNKS - 1) / ((uint64_t)KMPP_CHUNK * KMPP_MAX_CHUNKS));
         const uint32_t chunk = KMPP_CHUNK * std::max(1u, per);

@@ -23,8 +23,6 @@ namespace {
 
 constexpr int MAX_BATCH_Q = 8;
 
-IdMap id_map(const mi_knn* t) { return IdMap{t->base, t->cyc_block, t->cyc_n, t->cyc_rank}; }
-
 void ensure(mi_knn* t, void** p, size_t* have, size_t want, size_t elem) {
     if (*have >= want) return;
     t->reads.sync();  // a search still in flight uses the buffer freed here
@@ -65,11 +63,13 @@ void tomb_fit(mi_knn* t) {
     t->reads.sync();
     uint64_t* nb = nullptr;
     HIP_CHECK(hipMalloc((void**)&nb, std::max<size_t>(want, 1) * sizeof(uint64_t)));
-    HIP_CHECK(hipMemset(nb, 0, std::max<size_t>(want, 1) * sizeof(uint64_t)));
-    if (t->d_tomb) {
-        HIP_CHECK(hipMemcpy(nb, t->d_tomb, t->tomb_words * sizeof(uint64_t), hipMemcpyDeviceToDevice));
-        HIP_CHECK(hipFree(t->d_tomb));
-    }
+    // the fill and the carry-over copy on the handle's own stream, and waited for (groups_fit: the bits set on that stream
+    // next must not be overtaken by a fill on the null stream)
+    hipStream_t s = own_stream(t);
+    HIP_CHECK(hipMemsetAsync(nb, 0, std::max<size_t>(want, 1) * sizeof(uint64_t), s));
+    if (t->d_tomb) HIP_CHECK(hipMemcpyAsync(nb, t->d_tomb, t->tomb_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (t->d_tomb) HIP_CHECK(hipFree(t->d_tomb));
     t->d_tomb = nb;
     t->tomb_words = std::max<size_t>(want, 1);
 }
@@ -98,7 +98,7 @@ void tomb_rebuild(mi_knn* t) {
     tomb_fit(t);
     t->writes.sync();
     t->reads.sync();
-    HIP_CHECK(hipMemset(t->d_tomb, 0, t->tomb_words * sizeof(uint64_t)));
+    HIP_CHECK(hipMemsetAsync(t->d_tomb, 0, t->tomb_words * sizeof(uint64_t), own_stream(t)));   // (the stream the bits are set on)
     std::vector<uint32_t> rows;
     rows.swap(t->dead);
     tomb_add(t, rows, own_stream(t));
@@ -152,21 +152,6 @@ void attrs_fit(mi_knn* t) {
     t->d_tags = nt;
     t->d_stamps = ns;
     t->attrs_cap = want;
-}
-
-// id -> local row of this table (its own id space: base, and the block-cyclic map of a shard); false if it holds no such row
-bool local_of(const mi_knn* t, uint64_t id, uint64_t* local) {
-    if (id < t->base) return false;
-    const uint64_t off = id - t->base;
-    uint64_t l = off;
-    if (t->cyc_n > 1 && t->cyc_block) {
-        const uint64_t b = off / t->cyc_block;
-        if (b % t->cyc_n != t->cyc_rank) return false;
-        l = (b / t->cyc_n) * t->cyc_block + off % t->cyc_block;
-    }
-    if (l >= t->rows) return false;
-    *local = l;
-    return true;
 }
 
 void grow(mi_knn* t, uint64_t want_rows) {
@@ -632,7 +617,7 @@ void two_stage(mi_knn* t, const float* d_q, uint32_t k, uint64_t* d_idx, float* 
     // the single pass, every kernel of it returning at once unless the query's fallback word is set
     if (k <= 64) one_pass<WaveTopReg>(t, d_q, k, nullptr, t->d_keys, s, fallback, gy, qg);
     else select_pass(t, d_q, k, t->d_keys, s, fallback, gy);
-    hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, gy), dim3(256), 0, s, t->d_keys, k, id_map(t),
+    hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, gy), dim3(256), 0, s, t->d_keys, k, knn_id_map(t),
                        d_idx, d_dist, (size_t)qg.out, (size_t)(gy > 1 ? k : 0), t->d_pref_keys, fallback, qg.flags);
     HIP_CHECK(hipGetLastError());
 }
@@ -671,7 +656,7 @@ void search_batched_two_stage(mi_knn* t, const float* d_q, uint32_t nq, uint32_t
 void search_one(mi_knn* t, const float* d_q, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
     if (t->rows == 0) {  // nothing stored: k "none" entries
         hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, 1), dim3(256), 0, s,
-                           (const uint64_t*)nullptr, k, id_map(t), d_idx, d_dist, (size_t)0, (size_t)0);
+                           (const uint64_t*)nullptr, k, knn_id_map(t), d_idx, d_dist, (size_t)0, (size_t)0);
         HIP_CHECK(hipGetLastError());
         return;
     }
@@ -698,7 +683,7 @@ void search_one(mi_knn* t, const float* d_q, uint32_t k, uint64_t* d_idx, float*
     // TOMB) measured 13 % slower than the plain scan the select path runs
     if ((k > 64 || tomb_of(t)) && k <= 4096 && t->select_path) {
         select_pass(t, d_q, k, t->d_keys, s);
-        hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, 1), dim3(256), 0, s, t->d_keys, k, id_map(t),
+        hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, 1), dim3(256), 0, s, t->d_keys, k, knn_id_map(t),
                            d_idx, d_dist, (size_t)0, (size_t)0);
         HIP_CHECK(hipGetLastError());
         return;
@@ -711,7 +696,7 @@ void search_one(mi_knn* t, const float* d_q, uint32_t k, uint64_t* d_idx, float*
         else if (kp <= 256) one_pass<WaveTopLds<256>>(t, d_q, kp, lo, out, s);
         else one_pass<WaveTopLds<1024>>(t, d_q, kp, lo, out, s);
     }
-    hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, 1), dim3(256), 0, s, t->d_keys, k, id_map(t),
+    hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, 1), dim3(256), 0, s, t->d_keys, k, knn_id_map(t),
                        d_idx, d_dist, (size_t)0, (size_t)0);
     HIP_CHECK(hipGetLastError());
 }
@@ -753,7 +738,7 @@ void search_batched(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint64
         launch_merge<WaveTopReg>(t->d_cand, lists, k, lpb, t->d_tmp, nq, cstride, (size_t)mid * k, s);
         launch_merge<WaveTopReg>(t->d_tmp, mid, k, mid, t->d_keys, nq, (size_t)mid * k, k, s);
     }
-    hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, nq), dim3(256), 0, s, t->d_keys, k, id_map(t),
+    hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, nq), dim3(256), 0, s, t->d_keys, k, knn_id_map(t),
                        d_idx, d_dist, (size_t)k, (size_t)k);
     HIP_CHECK(hipGetLastError());
 }
@@ -804,14 +789,7 @@ uint32_t* flist_reserve(mi_knn* t, size_t want) {
 // ids -> t->h_flist [0, n_flist): the local rows they name, ascending, once each, deleted rows left out; MI_ERR_INVALID (and
 // the list untouched) when an id is not a row of the table
 void filter_rows(mi_knn* t, const uint64_t* ids, uint64_t n_ids) {
-    std::vector<uint32_t> rows((size_t)n_ids);
-    for (uint64_t i = 0; i < n_ids; ++i) {
-        uint64_t local = 0;
-        if (!local_of(t, ids[i], &local))
-            fail(MI_ERR_INVALID, "id %llu is not a row of this table (base %llu, %llu rows)", (unsigned long long)ids[i],
-                 (unsigned long long)t->base, (unsigned long long)t->rows);
-        rows[i] = (uint32_t)local;
-    }
+    std::vector<uint32_t> rows = knn_local_rows(t, ids, n_ids);
     // From rows / 1024 ids on, a bitmap over the rows (zeroed, marked, emitted: O(rows / 64 + n_ids)) instead of a sort
     // (O(n_ids log n_ids)): at 10 M rows the sort took 4 ms for 10^5 scattered ids and 570 ms for 10^7.
     if (n_ids >= t->rows / 1024) {
@@ -916,7 +894,7 @@ bool filter_takes_lists(const mi_knn* t, uint32_t n, uint32_t k) {
 
 void filtered_one(mi_knn* t, const float* d_q, uint32_t n, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
     if (n == 0) {  // nothing qualifies: k "none" entries
-        hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, 1), dim3(256), 0, s, (const uint64_t*)nullptr, k, id_map(t),
+        hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, 1), dim3(256), 0, s, (const uint64_t*)nullptr, k, knn_id_map(t),
                            d_idx, d_dist, (size_t)0, (size_t)0);
         HIP_CHECK(hipGetLastError());
         return;
@@ -925,7 +903,7 @@ void filtered_one(mi_knn* t, const float* d_q, uint32_t n, uint32_t k, uint64_t*
     if (!filter_takes_lists(t, n, k)) gather_select(t, d_q, n, k, t->d_keys, s);
     else if (k <= 64) gather_lists<WaveTopReg>(t, d_q, n, k, t->d_keys, s);
     else gather_lists<WaveTopLds<1024>>(t, d_q, n, k, t->d_keys, s);
-    hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, 1), dim3(256), 0, s, t->d_keys, k, id_map(t), d_idx, d_dist,
+    hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, 1), dim3(256), 0, s, t->d_keys, k, knn_id_map(t), d_idx, d_dist,
                        (size_t)0, (size_t)0);
     HIP_CHECK(hipGetLastError());
 }
@@ -951,7 +929,7 @@ void filtered_batched(mi_knn* t, const float* d_q, uint32_t nq, uint32_t n, uint
         launch_merge<WaveTopReg>(t->d_cand, lists, k, lpb, t->d_tmp, nq, cstride, (size_t)mid * k, s);
         launch_merge<WaveTopReg>(t->d_tmp, mid, k, mid, t->d_keys, nq, (size_t)mid * k, k, s);
     }
-    hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, nq), dim3(256), 0, s, t->d_keys, k, id_map(t), d_idx, d_dist,
+    hipLaunchKernelGGL(knn_finalize_kernel, dim3((k + 255) / 256, nq), dim3(256), 0, s, t->d_keys, k, knn_id_map(t), d_idx, d_dist,
                        (size_t)k, (size_t)k);
     HIP_CHECK(hipGetLastError());
 }
@@ -984,6 +962,20 @@ void knn_search_filtered_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t
     filter_rows(t, ids, n_ids);
     upload_filter(t, s);
     filtered_many(t, d_q, nq, k, d_idx, d_dist, s);
+}
+IdMap knn_id_map(const mi_knn* t) { return IdMap{t->base, t->cyc_block, t->cyc_n, t->cyc_rank}; }
+std::vector<uint32_t> knn_local_rows(const mi_knn* t, const uint64_t* ids, uint64_t n) {
+    if (!ids && n > t->rows) fail(MI_ERR_INVALID, "%llu rows asked of a table of %llu", (unsigned long long)n, (unsigned long long)t->rows);
+    std::vector<uint32_t> rows((size_t)n);
+    const IdMap m = knn_id_map(t);
+    for (uint64_t i = 0; i < n; ++i) {
+        uint64_t local = i;
+        if (ids && !local_of_id(m, t->rows, ids[i], &local))
+            fail(MI_ERR_INVALID, "id %llu is not a row of this table (base %llu, %llu rows)", (unsigned long long)ids[i],
+                 (unsigned long long)t->base, (unsigned long long)t->rows);
+        rows[(size_t)i] = (uint32_t)local;
+    }
+    return rows;
 }
 hipStream_t knn_own_stream(mi_knn* t) { return own_stream(t); }
 void knn_reserve(mi_knn* t, void** p, size_t* have, size_t want, size_t elem) { ensure(t, p, have, want, elem); }
@@ -1324,14 +1316,7 @@ int mi_knn_delete(mi_knn* t, const uint64_t* ids, uint64_t n, uint64_t* newly) {
         if (!ids) fail(MI_ERR_INVALID, "ids is null");
         std::lock_guard<std::mutex> l(t->mu);
         // every id is checked before anything changes: a call with one bad id deletes nothing
-        std::vector<uint32_t> rows((size_t)n);
-        for (uint64_t i = 0; i < n; ++i) {
-            uint64_t local = 0;
-            if (!local_of(t, ids[i], &local))
-                fail(MI_ERR_INVALID, "id %llu is not a row of this table (base %llu, %llu rows)", (unsigned long long)ids[i],
-                     (unsigned long long)t->base, (unsigned long long)t->rows);
-            rows[i] = (uint32_t)local;
-        }
+        std::vector<uint32_t> rows = knn_local_rows(t, ids, n);
         std::sort(rows.begin(), rows.end());
         rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
         std::vector<uint32_t> fresh;
@@ -1356,7 +1341,7 @@ int mi_knn_deleted(mi_knn* t, uint64_t* ids, uint64_t cap, uint64_t* count) {
         std::lock_guard<std::mutex> l(t->mu);
         *count = t->dead.size();
         if (!ids) return;
-        const IdMap m = id_map(t);  // monotone in the local row: ascending rows give ascending ids
+        const IdMap m = knn_id_map(t);  // monotone in the local row: ascending rows give ascending ids
         for (uint64_t i = 0; i < std::min<uint64_t>(cap, t->dead.size()); ++i) ids[i] = id_of_local(m, t->dead[i]);
     });
 }

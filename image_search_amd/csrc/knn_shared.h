@@ -1,12 +1,14 @@
 // knn_shared.h — the search's arithmetic that other translation units build on: the vector types, the 16-lane sum and
 // RowAcc (the summation order that defines "the search's bits"), the 64-bit keys and the register form of the per-wave top-k
 // (WaveTopReg), the bf16 mirror (knn_mirror_kernel) and
-// the row ids of a shard.  Everything here is a template or inline, so any number of translation units may include it;
+// the row ids of a shard (ids.h).  Everything here is a template or inline, so any number of translation units may include it;
 // knn_kernels.h includes it and keeps the search's own kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "ids.h"
 
 namespace mi {
 
@@ -156,15 +158,6 @@ __global__ __launch_bounds__(256) void knn_mirror_kernel(const float* __restrict
         const bool any_bad = ((bm >> (lane & 48)) & 0xFFFFull) != 0ull;
         if (live && i == 0) xx[r] = (any_bad || !(s >= 1.0e-30f && s <= 1.0e30f)) ? -1.0f : s;
     }
-}
-
-// Row ids of a shard.  Plain: id = base + local ordinal.  Block-cyclic (a shard of mi_knn_sharded: global row r lives in
-// block r / B, blocks are dealt round-robin to the n shards): id = base + ((local / B) * n + rank) * B + local % B —
-// monotone in the local ordinal, so "(distance asc, local asc)" inside a shard IS "(distance asc, id asc)".
-struct IdMap { uint64_t base; uint32_t block, n, rank; };
-__host__ __device__ inline uint64_t id_of_local(const IdMap& m, uint64_t local) {
-    if (m.n <= 1 || m.block == 0) return m.base + local;
-    return m.base + ((local / m.block) * m.n + m.rank) * m.block + local % m.block;
 }
 
 }  // namespace mi

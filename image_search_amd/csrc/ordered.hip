@@ -13,35 +13,30 @@
 #include <vector>
 
 #include "common.h"
-#include "compound_host.h"
 #include "handles.h"
 #include "ordered_host.h"
 #include "ordered_kernels.h"
 #include "page_host.h"
+#include "scan_call.h"
 #include "two_stage.h"
 
 using namespace mi;
 
 namespace {
 
-PageIds ids_of(const mi_knn* t) { return PageIds{t->base, t->rows, t->cyc_block, t->cyc_n, t->cyc_rank}; }
-
-// What both calls share in front of their own passes: the candidates (w: the predicate's list in t->d_flist, else the table under
-// its deletion bitmap), the query, the scan (t->d_keys32 holds `cap` words: reserved by the caller).  Leaves one distance key per entry in t->d_keys32 and {-, within, beyond, nan} added
-// to d_counts (zeroed here); returns the number of entries (0: no candidate, nothing was launched behind the predicate).
-// t->mu held, device selected, s ordered behind the handle's writes and searches
-uint64_t scan_candidates(mi_knn* t, const float* q, float max_dist, const mi_knn_where* w, uint32_t k, hipStream_t s,
-                         unsigned long long* d_counts, const uint32_t** list) {
-    *list = nullptr;
+// What both calls share in front of their own passes: the candidates (w: the predicate's list, built here on the device, else the
+// table under its deletion bitmap), the query, the scan.  Leaves one distance key per entry in keys32 (the caller's scan_keys32
+// of the table's rows) and {-, within, beyond, nan} added to d_counts (zeroed here); n == 0: no candidate, nothing was launched
+// behind the predicate.  t->mu held, inside the call's frame
+ScanSet scan_candidates(mi_knn* t, const float* q, float max_dist, const mi_knn_where* w, uint32_t k, hipStream_t s, uint32_t* keys32,
+                        unsigned long long* d_counts) {
     if (w) knn_filter_where(t, w, s);
-    const uint64_t n = w ? (uint64_t)t->n_flist : t->rows;
-    if (n == 0) return 0;
+    const ScanSet c = scan_set(t, s, w ? SCAN_DEVICE_LIST : SCAN_TABLE);
+    if (c.n == 0) return c;
     HIP_CHECK(hipMemcpyAsync(t->d_q, q, (size_t)t->dim * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemsetAsync(d_counts, 0, 4 * sizeof(uint64_t), s));
-    *list = w ? t->d_flist : nullptr;
-    const uint64_t* tomb = (w || t->dead.empty()) ? nullptr : t->d_tomb;
-    knn_page_scan_keys32(t, s, n, *list, tomb, page_hi(max_dist), k, t->d_keys32, d_counts);
-    return n;
+    knn_page_scan_keys32(t, s, c.n, c.list, c.tomb, page_hi(max_dist), k, keys32, d_counts);
+    return c;
 }
 
 }  // namespace
@@ -54,10 +49,10 @@ namespace mi {
 void knn_search_ordered(mi_knn* t, const float* q, uint32_t k, float max_dist, const mi_knn_where* w, uint32_t flags, int64_t after_stamp,
                         uint64_t after_id, const OrderedCursor* cur_in, uint64_t* idx, float* dist, int64_t* stamps, uint64_t* counts) {
     std::lock_guard<std::mutex> l(t->mu);
-    if (!compound_dim_ok(t->dim)) fail(MI_ERR_UNSUPPORTED, "dim %u: the ordered search is built for dim in {128, 256, 512, 768, 1024}", t->dim);
+    check_scan_dim(t->dim, "the ordered search");
     OrderedCursor cur;
     if (cur_in) cur = *cur_in;
-    else if (!ordered_cursor(ids_of(t), flags, after_stamp, after_id, &cur))
+    else if (!ordered_cursor(knn_id_map(t), t->rows, flags, after_stamp, after_id, &cur))
         fail(MI_ERR_INVALID, "after_id %llu is not a row of this table (base %llu, %llu rows)", (unsigned long long)after_id,
              (unsigned long long)t->base, (unsigned long long)t->rows);
     if (t->rows == 0 || (w && where_never(*w, t->d_groups != nullptr))) {
@@ -65,23 +60,19 @@ void knn_search_ordered(mi_knn* t, const float* q, uint32_t k, float max_dist, c
         return;
     }
 
-    DeviceGuard g(t->device);
-    hipStream_t s = knn_own_stream(t);
+    TableCall call(t);
+    hipStream_t s = call.s;
     const OrderedRecord rec = ordered_record(k);
-    knn_reserve(t, (void**)&t->d_idx, &t->idx_cap, (rec.bytes + 7) / 8, sizeof(uint64_t));
+    unsigned char* d_rec = scan_record(t, rec.bytes);
     knn_reserve(t, (void**)&t->d_keys, &t->keys_cap, (size_t)ORDERED_K_MAX * 2, sizeof(uint64_t));   // sorted: hi [4096] | lo [4096]
     knn_reserve(t, (void**)&t->d_cand, &t->cand_keys, (size_t)ORDERED_K_MAX * 2, sizeof(uint64_t));  // collected: the same
     knn_reserve(t, (void**)&t->d_sel, &t->sel_cap, ORD_SEL_WORDS, sizeof(uint32_t));
-    knn_reserve(t, (void**)&t->d_keys32, &t->keys32_cap, (size_t)std::max<uint64_t>(t->rows, t->cap), sizeof(uint32_t));
-    // behind every write and search enqueued before this call, on whichever stream
-    t->writes.begin(s);
-    t->reads.begin(s);
-    Settle settle{t, s};
+    uint32_t* keys32 = scan_keys32(t, t->rows);
 
-    unsigned char* d_rec = reinterpret_cast<unsigned char*>(t->d_idx);
     unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(d_rec + rec.counts);
-    const uint32_t* list = nullptr;
-    const uint64_t n = scan_candidates(t, q, max_dist, w, k, s, d_counts, &list);
+    const ScanSet c = scan_candidates(t, q, max_dist, w, k, s, keys32, d_counts);
+    const uint64_t n = c.n;
+    const uint32_t* list = c.list;
     if (n == 0) {
         ordered_pad(k, idx, dist, stamps, counts);
         return;
@@ -96,64 +87,54 @@ void knn_search_ordered(mi_knn* t, const float* q, uint32_t k, float max_dist, c
     uint32_t* s_lo = reinterpret_cast<uint32_t*>(t->d_keys + ORDERED_K_MAX);
     const long long* d_stamps = reinterpret_cast<const long long*>(t->d_stamps);
     // one entry per thread and round; the grid rule (and the option) of the scan in front
-    const uint32_t blocks = page_grid(n, t->n_cu, t->page_blocks);
+    const uint32_t blocks = scan_grid(n, t->n_cu, t->page_blocks, PAGE_BLOCKS_PER_CU);
     for (int p = 0; p < ORD_PASSES; ++p) {
-        hipLaunchKernelGGL(ordered_hist_kernel, dim3(blocks), dim3(256), 0, s, t->d_keys32, n, list, d_stamps, cur, k, p, d_hist, d_states,
+        hipLaunchKernelGGL(ordered_hist_kernel, dim3(blocks), dim3(256), 0, s, keys32, n, list, d_stamps, cur, k, p, d_hist, d_states,
                            d_counts);
         HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(ordered_collect_kernel, dim3(blocks), dim3(256), 0, s, t->d_keys32, n, list, d_stamps, cur, k, d_hist, d_states, c_hi,
+    hipLaunchKernelGGL(ordered_collect_kernel, dim3(blocks), dim3(256), 0, s, keys32, n, list, d_stamps, cur, k, d_hist, d_states, c_hi,
                        c_lo, d_count);
     HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(ordered_sort_kernel, dim3(1), dim3(1024), 0, s, c_hi, c_lo, d_count, k, s_hi, s_lo);
     HIP_CHECK(hipGetLastError());
-    const IdMap map{t->base, t->cyc_block, t->cyc_n, t->cyc_rank};
-    hipLaunchKernelGGL(ordered_finish_kernel, dim3((k + 255) / 256), dim3(256), 0, s, s_hi, s_lo, d_count, k, t->d_keys32, list, (int)cur.desc,
-                       map, reinterpret_cast<uint64_t*>(d_rec + rec.idx), reinterpret_cast<float*>(d_rec + rec.dist),
+    hipLaunchKernelGGL(ordered_finish_kernel, dim3((k + 255) / 256), dim3(256), 0, s, s_hi, s_lo, d_count, k, keys32, list, (int)cur.desc,
+                       knn_id_map(t), reinterpret_cast<uint64_t*>(d_rec + rec.idx), reinterpret_cast<float*>(d_rec + rec.dist),
                        reinterpret_cast<long long*>(d_rec + rec.stamps));
     HIP_CHECK(hipGetLastError());
-    std::vector<unsigned char> h_rec(rec.bytes);
-    HIP_CHECK(hipMemcpyAsync(h_rec.data(), d_rec, rec.bytes, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    ordered_unpack(h_rec.data(), k, idx, dist, stamps, counts);
+    ordered_unpack(scan_record_fetch(d_rec, rec.bytes, s).data(), k, idx, dist, stamps, counts);
 }
 
 // mi_knn_stamp_histogram behind its argument check; hist [n_edges + 1] is written only on success
 void knn_stamp_histogram(mi_knn* t, const float* q, float max_dist, const mi_knn_where* w, const int64_t* edges, uint32_t n_edges,
                          uint64_t* hist) {
     std::lock_guard<std::mutex> l(t->mu);
-    if (!compound_dim_ok(t->dim)) fail(MI_ERR_UNSUPPORTED, "dim %u: the stamp histogram is built for dim in {128, 256, 512, 768, 1024}", t->dim);
+    check_scan_dim(t->dim, "the stamp histogram");
     const size_t bins = (size_t)n_edges + 1;
     if (t->rows == 0 || (w && where_never(*w, t->d_groups != nullptr))) {
         std::fill(hist, hist + bins, 0ull);
         return;
     }
-    DeviceGuard g(t->device);
-    hipStream_t s = knn_own_stream(t);
-    knn_reserve(t, (void**)&t->d_idx, &t->idx_cap, bins + 4, sizeof(uint64_t));                       // hist [bins] | the scan's counts [4]
+    TableCall call(t);
+    hipStream_t s = call.s;
+    unsigned char* d_rec = scan_record(t, (bins + 4) * sizeof(uint64_t));                             // hist [bins] | the scan's counts [4]
     knn_reserve(t, (void**)&t->d_keys, &t->keys_cap, (size_t)ORDERED_K_MAX * 2, sizeof(uint64_t));   // the edges
-    knn_reserve(t, (void**)&t->d_keys32, &t->keys32_cap, (size_t)std::max<uint64_t>(t->rows, t->cap), sizeof(uint32_t));
-    t->writes.begin(s);
-    t->reads.begin(s);
-    Settle settle{t, s};
+    uint32_t* keys32 = scan_keys32(t, t->rows);
 
-    unsigned long long* d_hist = reinterpret_cast<unsigned long long*>(t->d_idx);
-    const uint32_t* list = nullptr;
-    const uint64_t n = scan_candidates(t, q, max_dist, w, 1, s, d_hist + bins, &list);
-    if (n == 0) {
+    unsigned long long* d_hist = reinterpret_cast<unsigned long long*>(d_rec);
+    const ScanSet c = scan_candidates(t, q, max_dist, w, 1, s, keys32, d_hist + bins);
+    if (c.n == 0) {
         std::fill(hist, hist + bins, 0ull);
         return;
     }
     HIP_CHECK(hipMemsetAsync(d_hist, 0, bins * sizeof(uint64_t), s));
     HIP_CHECK(hipMemcpyAsync(t->d_keys, edges, (size_t)n_edges * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    const uint32_t blocks = page_grid(n, t->n_cu, t->page_blocks);
-    hipLaunchKernelGGL(ordered_stamp_hist_kernel, dim3(blocks), dim3(256), 0, s, t->d_keys32, n, list,
+    const uint32_t blocks = scan_grid(c.n, t->n_cu, t->page_blocks, PAGE_BLOCKS_PER_CU);
+    hipLaunchKernelGGL(ordered_stamp_hist_kernel, dim3(blocks), dim3(256), 0, s, keys32, c.n, c.list,
                        reinterpret_cast<const long long*>(t->d_stamps), reinterpret_cast<const long long*>(t->d_keys), n_edges, d_hist);
     HIP_CHECK(hipGetLastError());
-    std::vector<uint64_t> h(bins);
-    HIP_CHECK(hipMemcpyAsync(h.data(), d_hist, bins * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    std::copy(h.begin(), h.end(), hist);
+    // hist is written only on success: the bins come to the host first
+    std::memcpy(hist, scan_record_fetch(d_rec, bins * sizeof(uint64_t), s).data(), bins * sizeof(uint64_t));
 }
 
 }  // namespace mi

@@ -99,22 +99,22 @@ inline uint32_t ordered_bin(const int64_t* edges, uint32_t n_edges, int64_t stam
     return lo;
 }
 
-// one table: false when MI_KNN_ORDER_AFTER is set and after_id names no row of it (deleted or not)
-inline bool ordered_cursor(const PageIds& m, uint32_t flags, int64_t after_stamp, uint64_t after_id, OrderedCursor* c) {
+// one table of `rows` rows: false when MI_KNN_ORDER_AFTER is set and after_id names no row of it (deleted or not)
+inline bool ordered_cursor(const IdMap& m, uint64_t rows, uint32_t flags, int64_t after_stamp, uint64_t after_id, OrderedCursor* c) {
     const bool desc = (flags & MI_KNN_ORDER_DESC) != 0;
     *c = OrderedCursor{0, 0, 0, desc ? 1u : 0u};
     if (!(flags & MI_KNN_ORDER_AFTER)) return true;
     uint64_t local = 0;
-    if (!page_local_of(m, after_id, &local)) return false;
+    if (!local_of_id(m, rows, after_id, &local)) return false;
     *c = OrderedCursor{ordered_okey(after_stamp, desc), local + 1, 1, desc ? 1u : 0u};
     return true;
 }
 // shard s of n (blocks of `block` rows dealt round-robin) under a cursor at global row after_row: the shard's rows at or below
-// it are its first page_shard_rows_below rows, whether it holds the cursor's row or not
+// it are the rows it holds of a table of after_row + 1 rows, whether it holds the cursor's row or not
 inline OrderedCursor ordered_cursor_shard(uint32_t block, uint32_t n, uint32_t s, uint32_t flags, int64_t after_stamp, uint64_t after_row) {
     const bool desc = (flags & MI_KNN_ORDER_DESC) != 0;
     if (!(flags & MI_KNN_ORDER_AFTER)) return OrderedCursor{0, 0, 0, desc ? 1u : 0u};
-    return OrderedCursor{ordered_okey(after_stamp, desc), page_shard_rows_below(block, n, s, after_row), 1, desc ? 1u : 0u};
+    return OrderedCursor{ordered_okey(after_stamp, desc), cyclic_rows_of(block, n, s, after_row + 1), 1, desc ? 1u : 0u};
 }
 
 // The record: idx [k] u64 | counts [4] u64 as the device leaves them = {before, within, beyond, nan} | stamps [k] i64 | dist [k] f32

@@ -12,15 +12,17 @@
 #include <vector>
 
 #include "common.h"
-#include "compound_host.h"
 #include "handles.h"
 #include "page_host.h"
 #include "page_kernels.h"
+#include "scan_call.h"
 #include "two_stage.h"
 
 using namespace mi;
 
 namespace {
+
+static_assert(PAGE_K_MAX <= SCAN_K_MAX, "the shared selection delivers every k the call accepts");
 
 template <int NCH>
 void launch_scan(mi_knn* t, uint32_t blocks, hipStream_t s, uint64_t n, const uint32_t* list, const uint64_t* tomb, uint64_t first_key,
@@ -34,8 +36,6 @@ void launch_scan(mi_knn* t, uint32_t blocks, hipStream_t s, uint64_t n, const ui
     HIP_CHECK(hipGetLastError());
 }
 
-PageIds page_ids(const mi_knn* t) { return PageIds{t->base, t->rows, t->cyc_block, t->cyc_n, t->cyc_rank}; }
-
 }  // namespace
 
 namespace mi {
@@ -45,7 +45,7 @@ namespace mi {
 // selected, the query in t->d_q
 void knn_page_scan_keys32(mi_knn* t, hipStream_t s, uint64_t n, const uint32_t* list, const uint64_t* tomb, uint64_t hi, uint32_t k,
                           uint32_t* keys32, unsigned long long* counts) {
-    const uint32_t blocks = page_grid(n, t->n_cu, t->page_blocks);
+    const uint32_t blocks = scan_grid(n, t->n_cu, t->page_blocks, PAGE_BLOCKS_PER_CU);
     dispatch_nch(t->dim, [&](auto nch) { launch_scan<decltype(nch)::value>(t, blocks, s, n, list, tomb, 0, hi, k, nullptr, keys32, counts); });
 }
 
@@ -54,53 +54,38 @@ void knn_page_scan_keys32(mi_knn* t, hipStream_t s, uint64_t n, const uint32_t* 
 void knn_search_page(mi_knn* t, const float* q, uint32_t k, bool cursor_is_id, float after_dist, uint64_t after_id, uint64_t first_key,
                      float max_dist, const uint64_t* among, uint64_t n_among, uint64_t* idx, float* dist, uint64_t* counts) {
     std::lock_guard<std::mutex> l(t->mu);
-    if (!compound_dim_ok(t->dim)) fail(MI_ERR_UNSUPPORTED, "dim %u: the paged search is built for dim in {128, 256, 512, 768, 1024}", t->dim);
+    check_scan_dim(t->dim, "the paged search");
+    const ScanFrom from = among ? SCAN_HOST_IDS : SCAN_TABLE;
     if (among) knn_filter_rows(t, among, n_among);   // every id checked before anything runs
-    if (cursor_is_id && !page_first_key(page_ids(t), after_dist, after_id, &first_key))
+    if (cursor_is_id && !page_first_key(knn_id_map(t), t->rows, after_dist, after_id, &first_key))
         fail(MI_ERR_INVALID, "after_id %llu is not a row of this table (base %llu, %llu rows)", (unsigned long long)after_id,
              (unsigned long long)t->base, (unsigned long long)t->rows);
     const uint64_t hi = page_hi(max_dist);
-    const uint64_t n = among ? (uint64_t)t->n_flist : t->rows;
+    const uint64_t n = scan_count(t, from);
     if (n == 0) {
         page_pad(k, idx, dist, counts);
         return;
     }
 
-    DeviceGuard g(t->device);
-    hipStream_t s = knn_own_stream(t);
+    TableCall call(t);
+    hipStream_t s = call.s;
     const PageRecord rec = page_record(k);
-    const uint32_t blocks = page_grid(n, t->n_cu, t->page_blocks), lists = blocks * 4;
-    knn_reserve(t, (void**)&t->d_idx, &t->idx_cap, (rec.bytes + 7) / 8, sizeof(uint64_t));
-    knn_reserve(t, (void**)&t->d_keys, &t->keys_cap, (size_t)PAGE_K_MAX, sizeof(uint64_t));
-    if (k <= 64) knn_reserve(t, (void**)&t->d_cand, &t->cand_keys, (size_t)lists * k, sizeof(uint64_t));
-    else knn_reserve(t, (void**)&t->d_keys32, &t->keys32_cap, (size_t)std::max<uint64_t>(n, t->cap), sizeof(uint32_t));
-    // behind every write and search enqueued before this call, on whichever stream
-    t->writes.begin(s);
-    t->reads.begin(s);
-    Settle settle{t, s};
+    const uint32_t blocks = scan_grid(n, t->n_cu, t->page_blocks, PAGE_BLOCKS_PER_CU);
+    unsigned char* d_rec = scan_record(t, rec.bytes);
+    const ScanSelect sel = scan_select_reserve(t, n, k, blocks * 4);
 
-    unsigned char* d_rec = reinterpret_cast<unsigned char*>(t->d_idx);
     unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(d_rec + rec.counts);
     HIP_CHECK(hipMemcpyAsync(t->d_q, q, (size_t)t->dim * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemsetAsync(d_counts, 0, 4 * sizeof(uint64_t), s));
-    if (among) knn_filter_upload(t, s);
-    const uint32_t* list = among ? t->d_flist : nullptr;
-    const uint64_t* tomb = (among || t->dead.empty()) ? nullptr : t->d_tomb;
-    uint64_t* cand = k <= 64 ? t->d_cand : nullptr;
-    uint32_t* all_keys = k <= 64 ? nullptr : t->d_keys32;
+    const ScanSet c = scan_set(t, s, from);
     dispatch_nch(t->dim, [&](auto nch) {
-        launch_scan<decltype(nch)::value>(t, blocks, s, n, list, tomb, first_key, hi, k, cand, all_keys, d_counts);
+        launch_scan<decltype(nch)::value>(t, blocks, s, n, c.list, c.tomb, first_key, hi, k, sel.cand, sel.all_keys, d_counts);
     });
-    if (k <= 64) knn_reduce_lists64(t, lists, k, t->d_keys, s);
-    else knn_select_keys32(t, n, k, t->d_keys, list, s);
-    const IdMap map{t->base, t->cyc_block, t->cyc_n, t->cyc_rank};
-    hipLaunchKernelGGL(knn_page_finish_kernel, dim3((k + 255) / 256), dim3(256), 0, s, t->d_keys, k, map,
+    scan_select(t, sel, c.list, s);
+    hipLaunchKernelGGL(knn_page_finish_kernel, dim3((k + 255) / 256), dim3(256), 0, s, t->d_keys, k, knn_id_map(t),
                        reinterpret_cast<uint64_t*>(d_rec + rec.idx), reinterpret_cast<float*>(d_rec + rec.dist));
     HIP_CHECK(hipGetLastError());
-    std::vector<unsigned char> h_rec(rec.bytes);
-    HIP_CHECK(hipMemcpyAsync(h_rec.data(), d_rec, rec.bytes, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    page_unpack(h_rec.data(), k, idx, dist, counts);
+    page_unpack(scan_record_fetch(d_rec, rec.bytes, s).data(), k, idx, dist, counts);
 }
 
 }  // namespace mi

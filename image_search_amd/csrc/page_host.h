@@ -1,8 +1,8 @@
 // page_host.h — the host-only pieces of mi_knn_search_page (page.hip): the argument rules, the search's key transform as the
 // host needs it (the cursor and the bound are keys), the cursor -> first_key rule for a table, for a shard of a block-cyclic
-// table and for the sharded call, the `hi` rule, the grid rule of "page_blocks", and the layout of the one record the device
-// writes with how it (or "no candidate") reaches the caller's arrays.  No HIP in here: tests/cpp/test_page_host.cpp runs it
-// under the sanitizers.
+// table and for the sharded call (on the id space of ids.h), the `hi` rule, the per-CU factor of "page_blocks", and the layout
+// of the one record the device writes with how it (or "no candidate") reaches the caller's arrays.  No HIP in here:
+// tests/cpp/test_page_host.cpp runs it under the sanitizers.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -12,6 +12,7 @@
 #include <limits>
 
 #include "../../include/mi355clip.h"
+#include "ids.h"
 
 namespace mi {
 
@@ -41,26 +42,6 @@ inline int page_check_args(const void* t, const float* q, uint32_t k, float afte
     return MI_OK;
 }
 
-// The id space of a table: plain (id = base + local) or a shard of a block-cyclic table (IdMap of knn_shared.h).
-struct PageIds {
-    uint64_t base, rows;
-    uint32_t block, n, rank;
-};
-// id -> local row, deleted or not; false if the table holds no such row
-inline bool page_local_of(const PageIds& m, uint64_t id, uint64_t* local) {
-    if (id < m.base) return false;
-    const uint64_t off = id - m.base;
-    uint64_t l = off;
-    if (m.n > 1 && m.block) {
-        const uint64_t b = off / m.block;
-        if (b % m.n != m.rank) return false;
-        l = (b / m.n) * m.block + off % m.block;
-    }
-    if (l >= m.rows) return false;
-    *local = l;
-    return true;
-}
-
 // The scan's lower end is INCLUSIVE: a candidate is past the cursor iff key >= first_key.  `below` = the table's local rows
 // whose id is <= after_id: with the cursor's own row in the table that is its local row + 1, i.e. first_key = cursor key + 1
 // (the carry into the distance word at row 0xFFFFFFFF is the right answer: nothing of that distance is left).  A shard that
@@ -68,34 +49,22 @@ inline bool page_local_of(const PageIds& m, uint64_t id, uint64_t* local) {
 // as given (-0 and +0 differ); after_dist is not NaN, so the sum cannot wrap.
 inline uint64_t page_first_key_at(float after_dist, uint64_t below) { return ((uint64_t)page_dist_key(after_dist) << 32) + below; }
 
-// one table: false when after_id names no row of it (MI_ERR_INVALID); no cursor (MI_KNN_NO_ID): 0, after_dist ignored
-inline bool page_first_key(const PageIds& m, float after_dist, uint64_t after_id, uint64_t* first_key) {
+// one table of `rows` rows (ids.h): false when after_id names no row of it (MI_ERR_INVALID); no cursor (MI_KNN_NO_ID): 0,
+// after_dist ignored.  A shard under the sharded call: page_first_key_at(after_dist, cyclic_rows_of(.., after_id + 1)).
+inline bool page_first_key(const IdMap& m, uint64_t rows, float after_dist, uint64_t after_id, uint64_t* first_key) {
     *first_key = 0;
     if (after_id == MI_KNN_NO_ID) return true;
     uint64_t local = 0;
-    if (!page_local_of(m, after_id, &local)) return false;
+    if (!local_of_id(m, rows, after_id, &local)) return false;
     *first_key = page_first_key_at(after_dist, local + 1);
     return true;
-}
-
-// mi_knn_sharded_place's arithmetic (global row r lives in block r / block, block b on shard b % n at local block b / n): the
-// local rows of shard s whose global row is <= after_row = the rows s holds of a table of after_row + 1 rows.  A shard's local
-// rows ascend with their global ids, so these are its FIRST rows.
-inline uint64_t page_shard_rows_below(uint32_t block, uint32_t n, uint32_t s, uint64_t after_row) {
-    const uint64_t total = after_row + 1, full = total / block, rem = total % block;
-    return (full / n + (s < full % n ? 1 : 0)) * block + (s == full % n ? rem : 0);
 }
 
 // the upper end, inclusive, on the key order: every row part of the bound's distance
 inline uint64_t page_hi(float max_dist) { return ((uint64_t)page_dist_key(max_dist) << 32) | 0xFFFFFFFFull; }
 
-// workgroups of the scan over n rows or list entries (a workgroup = 4 waves, a wave's tile = 64): the rule of
-// "compound_blocks" — option 0 = the default grid, v >= 1 = exactly min(v, needed)
-inline uint32_t page_grid(uint64_t n, int n_cu, int option) {
-    const uint64_t n_tiles = (n + 63) / 64, needed = std::max<uint64_t>(1, (n_tiles + 3) / 4);
-    const uint64_t want = option >= 1 ? (uint64_t)option : (uint64_t)std::max(n_cu, 1) * 4;
-    return (uint32_t)std::min(want, needed);
-}
+// the scan's workgroups with "page_blocks" = 0: the single pass's grid, four per CU (scan_grid of scan_call.h)
+constexpr uint32_t PAGE_BLOCKS_PER_CU = 4;
 
 // The record: idx [k] u64 | counts [4] u64 = {before, window, beyond, nan} | dist [k] f32
 struct PageRecord {

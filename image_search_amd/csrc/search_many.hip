@@ -118,7 +118,7 @@ struct SearchMany {
             piece = overflowed ? std::max(1u, piece / 2) : (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_rt, cand_cap / (2 * per_tile)));
             br = end;
         }
-        const IdMap map{t->base, t->cyc_block, t->cyc_n, t->cyc_rank};
+        const IdMap map = knn_id_map(t);
         hipLaunchKernelGGL(search_many_finalize_kernel, dim3((n_s + 255) / 256), dim3(256), 0, s, d_slot, q_tomb, q_local0, n_s, m,
                            self_drop ? 1u : 0u, map, d_idx, d_dist, d_hits);
         HIP_CHECK(hipGetLastError());
@@ -168,16 +168,14 @@ struct SearchMany {
         for (int i = 0; i < 4; ++i) t->search_many_stats[i] = stats[i];
     }
 
-    // t->mu held, device selected, arguments checked, the table not empty; nq = the queries of the call
-    void setup(mi_knn* table, uint32_t nq, uint32_t n_keep, bool drop) {
-        t = table;
+    // inside the call's frame (declared after this object: the stream is idle before the scratch memory goes); arguments
+    // checked, the table not empty; nq = the queries of the call
+    void setup(const TableCall& call, uint32_t nq, uint32_t n_keep, bool drop) {
+        t = call.t;
         k = n_keep;
         self_drop = drop;
         m = k + (drop ? 1u : 0u);
-        s = knn_own_stream(t);
-        // behind every write and search enqueued before this call, on whichever stream
-        t->writes.begin(s);
-        t->reads.begin(s);
+        s = call.s;
         n_cols = (uint32_t)t->rows;
         n_cb = (n_cols + TILE - 1) / TILE;
         thr = 2.0f * eps2(t->dim);   // the join's bound, unchanged (join_kernels.h): both operands are rounded to bf16
@@ -229,10 +227,9 @@ void search_many_local(mi_knn* t, const float* q, uint32_t nq, uint32_t k, uint6
         pad(idx, dist, (size_t)nq * k);
         return;
     }
-    DeviceGuard g(t->device);
     SearchMany a;
-    a.setup(t, nq, k, false);
-    Settle settle{t, a.s};
+    TableCall call(t);
+    a.setup(call, nq, k, false);
     a.run_queries(q, nq, idx, dist);
 }
 
@@ -269,10 +266,9 @@ int mi_knn_neighbors(mi_knn* t, uint64_t first, uint64_t n, uint32_t k, uint64_t
                  (unsigned long long)(first + n), (unsigned long long)t->base, (unsigned long long)t->rows);
         for (uint64_t& v : t->search_many_stats) v = 0;
         if (n == 0) return;
-        DeviceGuard g(t->device);
         SearchMany a;
-        a.setup(t, (uint32_t)n, k, true);
-        Settle settle{t, a.s};
+        TableCall call(t);
+        a.setup(call, (uint32_t)n, k, true);
         a.run_rows((uint32_t)(first - t->base), (uint32_t)n, idx, dist);
     });
 }

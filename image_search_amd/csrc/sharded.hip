@@ -242,20 +242,45 @@ void fsync_dir_of(const std::string& path) {
     if (d) { (void)fsync(fileno(d)); std::fclose(d); }
 }
 
+// A list of global ids, every one checked against t->rows before anything runs, dealt to the shards that hold them (in the
+// list's order).  listed == false: the caller gave no list, every shard answers for all its rows.
+struct ShardIds {
+    std::vector<std::vector<uint64_t>> per;   // [shard]
+    bool listed;
+    // what shard s's call takes: null = no list; a shard that holds none of the ids gets an empty candidate set, not "every row"
+    const uint64_t* of(uint32_t s) const {
+        static const uint64_t none = 0;
+        return !listed ? nullptr : per[s].empty() ? &none : per[s].data();
+    }
+    uint64_t n_of(uint32_t s) const { return per[s].size(); }
+};
+ShardIds route_list(const mi_knn_sharded* t, const uint64_t* ids, uint64_t n_ids) {
+    ShardIds r{std::vector<std::vector<uint64_t>>(t->n()), ids != nullptr};
+    for (uint64_t i = 0; i < n_ids; ++i) {
+        if (ids[i] >= t->rows)
+            fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)ids[i], (unsigned long long)t->rows);
+        uint32_t s; uint64_t local;
+        sharded_place(t, ids[i], &s, &local);
+        r.per[s].push_back(ids[i]);
+    }
+    return r;
+}
+
+// out[c] = the sum over the n shards of all[shard][c], the four counters of a scan call
+void sum_counts4(const std::vector<uint64_t>& all, uint32_t n, uint64_t out[4]) {
+    for (int c = 0; c < 4; ++c) {
+        out[c] = 0;
+        for (uint32_t si = 0; si < n; ++si) out[c] += all[(size_t)si * 4 + c];
+    }
+}
+
 }  // namespace
 
 namespace mi {
 
-void sharded_place(const mi_knn_sharded* t, uint64_t r, uint32_t* s, uint64_t* local) {
-    const uint64_t blk = r / t->block;
-    *s = (uint32_t)(blk % t->n());
-    *local = (blk / t->n()) * t->block + r % t->block;
-}
+void sharded_place(const mi_knn_sharded* t, uint64_t r, uint32_t* s, uint64_t* local) { cyclic_place(t->block, t->n(), r, s, local); }
 
-uint64_t sharded_rows_of(const mi_knn_sharded* t, uint64_t total, uint32_t s) {
-    const uint64_t full = total / t->block, rem = total % t->block, n = t->n();
-    return (full / n + (s < full % n ? 1 : 0)) * t->block + (s == full % n ? rem : 0);
-}
+uint64_t sharded_rows_of(const mi_knn_sharded* t, uint64_t total, uint32_t s) { return cyclic_rows_of(t->block, t->n(), s, total); }
 
 void sharded_deliver_all(mi_knn_sharded* t) {
     for (int i = 0; i < mi_knn_sharded::N_SLOTS; ++i) deliver(t->slots[(t->next_slot + i) % mi_knn_sharded::N_SLOTS]);  // oldest first
@@ -575,16 +600,9 @@ int mi_knn_sharded_search_filtered(mi_knn_sharded* t, const float* q, uint32_t n
         if (k > 4096) fail(MI_ERR_UNSUPPORTED, "a filtered search takes k <= 4096 (got %u)", k);
         if (n_ids && !ids) fail(MI_ERR_INVALID, "ids is null");
         std::lock_guard<std::mutex> l(t->mu);
-        std::vector<std::vector<uint64_t>> per(t->n());
-        for (uint64_t i = 0; i < n_ids; ++i) {  // every id checked before anything runs
-            if (ids[i] >= t->rows)
-                fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)ids[i], (unsigned long long)t->rows);
-            uint32_t s; uint64_t local;
-            sharded_place(t, ids[i], &s, &local);
-            per[s].push_back(ids[i]);
-        }
+        const ShardIds among = route_list(t, ids, n_ids);
         if (nq == 0) return;
-        sharded_search_enqueue(t, q, nq, k, idx, dist, &per);
+        sharded_search_enqueue(t, q, nq, k, idx, dist, &among.per);
         sharded_deliver_all(t);
     });
 }
@@ -651,21 +669,12 @@ int mi_knn_sharded_search_compound(mi_knn_sharded* t, const float* pos, uint32_t
         if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
         std::lock_guard<std::mutex> l(t->mu);
         const uint32_t n = t->n();
-        std::vector<std::vector<uint64_t>> per(n);
-        for (uint64_t i = 0; i < n_among; ++i) {  // every id checked before anything runs
-            if (among[i] >= t->rows)
-                fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)among[i], (unsigned long long)t->rows);
-            uint32_t s; uint64_t local;
-            sharded_place(t, among[i], &s, &local);
-            per[s].push_back(among[i]);
-        }
+        const ShardIds mine = route_list(t, among, n_among);
         sharded_deliver_all(t);
         std::vector<uint64_t> all_idx((size_t)n * k);
         std::vector<float> all_dist((size_t)n * k);
-        const uint64_t none = 0;   // a shard that holds none of the ids: an empty candidate set, not "every row"
         for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
-            const uint64_t* ids = among ? (per[si].empty() ? &none : per[si].data()) : nullptr;
-            knn_search_compound(sh, pos, n_pos, mode, neg, neg_within, n_neg, k, ids, per[si].size(), all_idx.data() + (size_t)si * k,
+            knn_search_compound(sh, pos, n_pos, mode, neg, neg_within, n_neg, k, mine.of(si), mine.n_of(si), all_idx.data() + (size_t)si * k,
                                 all_dist.data() + (size_t)si * k, nullptr);
         });
         merge_lists(all_idx.data(), all_dist.data(), n, k, idx, dist);
@@ -685,37 +694,23 @@ int mi_knn_sharded_search_page(mi_knn_sharded* t, const float* q, uint32_t k, fl
         if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
         std::lock_guard<std::mutex> l(t->mu);
         const uint32_t n = t->n();
-        std::vector<std::vector<uint64_t>> per(n);
-        for (uint64_t i = 0; i < n_among; ++i) {  // every id checked before anything runs
-            if (among[i] >= t->rows)
-                fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)among[i], (unsigned long long)t->rows);
-            uint32_t s; uint64_t local;
-            sharded_place(t, among[i], &s, &local);
-            per[s].push_back(among[i]);
-        }
+        const ShardIds mine = route_list(t, among, n_among);
         if (after_id != MI_KNN_NO_ID && after_id >= t->rows)
             fail(MI_ERR_INVALID, "after_id %llu is not a row of this table (%llu rows)", (unsigned long long)after_id, (unsigned long long)t->rows);
         sharded_deliver_all(t);
         std::vector<uint64_t> all_idx((size_t)n * k), all_counts((size_t)n * 4, 0);
         std::vector<float> all_dist((size_t)n * k);
-        const uint64_t none = 0;   // a shard that holds none of the ids: an empty candidate set, not "every row"
         for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
-            const uint64_t* ids = among ? (per[si].empty() ? &none : per[si].data()) : nullptr;
-            const uint64_t first_key =
-                after_id == MI_KNN_NO_ID ? 0 : page_first_key_at(after_dist, page_shard_rows_below(t->block, n, si, after_id));
-            knn_search_page(sh, q, k, false, 0.0f, MI_KNN_NO_ID, first_key, max_dist, ids, per[si].size(), all_idx.data() + (size_t)si * k,
-                            all_dist.data() + (size_t)si * k, all_counts.data() + (size_t)si * 4);
+            const uint64_t first_key = after_id == MI_KNN_NO_ID ? 0 : page_first_key_at(after_dist, sharded_rows_of(t, after_id + 1, si));
+            knn_search_page(sh, q, k, false, 0.0f, MI_KNN_NO_ID, first_key, max_dist, mine.of(si), mine.n_of(si),
+                            all_idx.data() + (size_t)si * k, all_dist.data() + (size_t)si * k, all_counts.data() + (size_t)si * 4);
         });
         std::vector<uint64_t> m_idx(k);
         std::vector<float> m_dist(k);
         merge_lists(all_idx.data(), all_dist.data(), n, k, m_idx.data(), m_dist.data());
         std::copy(m_idx.begin(), m_idx.end(), idx);
         std::copy(m_dist.begin(), m_dist.end(), dist);
-        if (counts)
-            for (int c = 0; c < 4; ++c) {
-                counts[c] = 0;
-                for (uint32_t si = 0; si < n; ++si) counts[c] += all_counts[(size_t)si * 4 + c];
-            }
+        if (counts) sum_counts4(all_counts, n, counts);
     });
 }
 
@@ -750,11 +745,7 @@ int mi_knn_sharded_search_ordered(mi_knn_sharded* t, const float* q, uint32_t k,
         std::copy(m_idx.begin(), m_idx.end(), idx);
         std::copy(m_dist.begin(), m_dist.end(), dist);
         if (stamps) std::copy(m_stamps.begin(), m_stamps.end(), stamps);
-        if (counts)
-            for (int c = 0; c < 4; ++c) {
-                counts[c] = 0;
-                for (uint32_t si = 0; si < n; ++si) counts[c] += all_counts[(size_t)si * 4 + c];
-            }
+        if (counts) sum_counts4(all_counts, n, counts);
     });
 }
 
@@ -800,26 +791,17 @@ int mi_knn_sharded_search_grouped(mi_knn_sharded* t, const float* q, uint32_t k,
         }
         if (facets && cap_facets < n_groups)
             fail(MI_ERR_INVALID, "facets holds %llu entries, the table has %llu groups", (unsigned long long)cap_facets, (unsigned long long)n_groups);
-        std::vector<std::vector<uint64_t>> per(n);
-        for (uint64_t i = 0; i < n_among; ++i) {  // every id checked before anything runs
-            if (among[i] >= t->rows)
-                fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)among[i], (unsigned long long)t->rows);
-            uint32_t s; uint64_t local;
-            sharded_place(t, among[i], &s, &local);
-            per[s].push_back(among[i]);
-        }
+        const ShardIds mine = route_list(t, among, n_among);
         sharded_deliver_all(t);
         const bool sums = facets || totals;
         std::vector<uint64_t> all_idx((size_t)n * k), all_totals((size_t)n * 4, 0);
         std::vector<float> all_dist((size_t)n * k);
         std::vector<uint32_t> all_group((size_t)n * k);
         std::vector<std::vector<uint32_t>> cnt(n);
-        const uint64_t none = 0;   // a shard that holds none of the ids: an empty candidate set, not "every row"
         for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
-            const uint64_t* ids = among ? (per[si].empty() ? &none : per[si].data()) : nullptr;
-            knn_search_grouped(sh, q, k, max_dist, ids, per[si].size(), all_idx.data() + (size_t)si * k, all_dist.data() + (size_t)si * k,
-                               all_group.data() + (size_t)si * k, nullptr, nullptr, 0, all_totals.data() + (size_t)si * 4,
-                               sums ? &cnt[si] : nullptr);
+            knn_search_grouped(sh, q, k, max_dist, mine.of(si), mine.n_of(si), all_idx.data() + (size_t)si * k,
+                               all_dist.data() + (size_t)si * k, all_group.data() + (size_t)si * k, nullptr, nullptr, 0,
+                               all_totals.data() + (size_t)si * 4, sums ? &cnt[si] : nullptr);
         });
         std::vector<uint64_t> m_idx(k);
         std::vector<float> m_dist(k);
@@ -843,11 +825,8 @@ int mi_knn_sharded_search_grouped(mi_knn_sharded* t, const float* q, uint32_t k,
             for (uint32_t si = 0; si < n; ++si) reps[si] = all_totals[(size_t)si * 4];
             const uint64_t total_reps = grouped_sum_counts(cnt, reps.data(), n_groups, facets);
             if (totals) {
-                totals[0] = total_reps;
-                for (int c = 1; c < 4; ++c) {
-                    totals[c] = 0;
-                    for (uint32_t si = 0; si < n; ++si) totals[c] += all_totals[(size_t)si * 4 + c];
-                }
+                sum_counts4(all_totals, n, totals);
+                totals[0] = total_reps;   // representatives are counted per group over all shards, not per shard
             }
         }
     });
@@ -867,14 +846,7 @@ int mi_knn_sharded_sync(mi_knn_sharded* t) {
 namespace {
 // t->mu held: every id checked first (a call with one bad id deletes nothing), then each shard takes its own ids
 uint64_t delete_locked(mi_knn_sharded* t, const uint64_t* ids, uint64_t n) {
-    std::vector<std::vector<uint64_t>> per(t->n());
-    for (uint64_t i = 0; i < n; ++i) {
-        if (ids[i] >= t->rows)
-            fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)ids[i], (unsigned long long)t->rows);
-        uint32_t s; uint64_t local;
-        sharded_place(t, ids[i], &s, &local);
-        per[s].push_back(ids[i]);
-    }
+    const std::vector<std::vector<uint64_t>> per = route_list(t, ids, n).per;
     uint64_t newly = 0;
     for (uint32_t s = 0; s < t->n(); ++s) {
         if (per[s].empty()) continue;

@@ -12,6 +12,7 @@
 #include "common.h"
 #include "handles.h"
 #include "knn_shared.h"
+#include "scan_call.h"   // Settle, the frame of a call (TableCall), the dim rule
 
 namespace mi {
 
@@ -29,21 +30,12 @@ struct Scratch {
     }
 };
 
-// whatever happens, the handle's stream is idle and its order words say so when the call leaves
-struct Settle {
-    mi_knn* t; hipStream_t s;
-    ~Settle() { (void)hipStreamSynchronize(s); t->reads.pending = false; }
-};
-
 // The bound of a first stage with BOTH operands rounded to bf16 (derived in join_kernels.h):
 // |coarse - exact| <= eps2 on the cosine of every pair the mirror does not mark.
 inline float eps2(uint32_t dim) { return 0x1p-7f + 0x1p-16f + 4.1f * (float)(dim + 8) * 0x1p-24f + 2e-6f; }
 
 // `whose`: "the join's", "the assign's", ... for the message
-inline void check_mirror_dim(uint32_t dim, const char* whose) {
-    if (dim % 128 != 0 || (dim / 64 != 2 && dim / 64 != 4 && dim / 64 != 8 && dim / 64 != 12 && dim / 64 != 16))
-        fail(MI_ERR_UNSUPPORTED, "dim %u: %s bf16 mirror is built for dim in {128, 256, 512, 768, 1024}", dim, whose);
-}
+inline void check_mirror_dim(uint32_t dim, const char* whose) { check_scan_dim(dim, (std::string(whose) + " bf16 mirror").c_str()); }
 
 // f(std::integral_constant<int, NCH>) with NCH = dim / 64; dim has passed check_mirror_dim
 template <class F>

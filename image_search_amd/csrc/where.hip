@@ -13,30 +13,13 @@
 
 #include "common.h"
 #include "handles.h"
-#include "page_host.h"
-#include "two_stage.h"
+#include "scan_call.h"
 #include "where_host.h"
 #include "where_kernels.h"
 
 using namespace mi;
 
 namespace {
-
-PageIds ids_of(const mi_knn* t) { return PageIds{t->base, t->rows, t->cyc_block, t->cyc_n, t->cyc_rank}; }
-
-// ids -> local rows, every one checked; MI_ERR_INVALID names the first that is no row
-std::vector<uint32_t> local_rows(const mi_knn* t, const uint64_t* ids, uint64_t n) {
-    std::vector<uint32_t> rows((size_t)n);
-    const PageIds m = ids_of(t);
-    for (uint64_t i = 0; i < n; ++i) {
-        uint64_t local = 0;
-        if (!page_local_of(m, ids[i], &local))
-            fail(MI_ERR_INVALID, "id %llu is not a row of this table (base %llu, %llu rows)", (unsigned long long)ids[i],
-                 (unsigned long long)t->base, (unsigned long long)t->rows);
-        rows[(size_t)i] = (uint32_t)local;
-    }
-    return rows;
-}
 
 WherePred pred_of(const mi_knn_where& w) {
     WherePred p;
@@ -98,29 +81,18 @@ int mi_knn_set_attrs(mi_knn* t, const uint64_t* ids, uint64_t n, const uint64_t*
         if (bad != MI_OK) fail(bad, "%s", why);
         if (n == 0 || (!tags && !stamps)) return;
         std::lock_guard<std::mutex> l(t->mu);
-        const std::vector<uint32_t> rows = local_rows(t, ids, n);   // every id checked before anything is written
-        DeviceGuard g(t->device);
-        hipStream_t s = knn_own_stream(t);
+        const std::vector<uint32_t> rows = knn_local_rows(t, ids, n);   // every id checked before anything is written
+        TableCall call(t);
         knn_attrs_fit(t);
         if (t->h_tags.size() < t->rows) t->h_tags.resize((size_t)t->rows, 0);
         if (t->h_stamps.size() < t->rows) t->h_stamps.resize((size_t)t->rows, 0);
-        uint32_t lo = 0xFFFFFFFFu, hi = 0;
         for (uint64_t i = 0; i < n; ++i) {
             const uint32_t r = rows[(size_t)i];
             if (tags) t->h_tags[r] = tags[i];
             if (stamps) t->h_stamps[r] = stamps[i];
-            lo = std::min(lo, r);
-            hi = std::max(hi, r);
         }
-        // a write that changes what searches read: behind the searches enqueued before it, ahead of every later one.  The
-        // span of rows the call names goes up in one copy per column (the host holds the columns too).
-        t->writes.begin(s);
-        t->reads.begin(s);
-        const size_t span = (size_t)(hi - lo) + 1;
-        if (tags) HIP_CHECK(hipMemcpyAsync(t->d_tags + lo, t->h_tags.data() + lo, span * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        if (stamps) HIP_CHECK(hipMemcpyAsync(t->d_stamps + lo, t->h_stamps.data() + lo, span * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        t->writes.end(s);
-        HIP_CHECK(hipStreamSynchronize(s));
+        upload_span(call, rows, {{tags ? t->d_tags : nullptr, t->h_tags.data(), sizeof(uint64_t)},
+                                 {stamps ? t->d_stamps : nullptr, t->h_stamps.data(), sizeof(int64_t)}});
     });
 }
 
@@ -131,7 +103,7 @@ int mi_knn_get_attrs(mi_knn* t, const uint64_t* ids, uint64_t n, uint64_t* tags,
         if (bad != MI_OK) fail(bad, "%s", why);
         if (n == 0) return;
         std::lock_guard<std::mutex> l(t->mu);
-        const std::vector<uint32_t> rows = local_rows(t, ids, n);
+        const std::vector<uint32_t> rows = knn_local_rows(t, ids, n);
         for (uint64_t i = 0; i < n; ++i) {   // rows appended since the last set hold the defaults
             const uint32_t r = rows[(size_t)i];
             if (tags) tags[i] = r < t->h_tags.size() ? t->h_tags[r] : 0;
@@ -146,12 +118,8 @@ int mi_knn_count_where(mi_knn* t, const mi_knn_where* w, uint64_t* count) {
         const int bad = where_check_rows_args(t, w, nullptr, 0, count, &why);
         if (bad != MI_OK) fail(bad, "%s", why);
         std::lock_guard<std::mutex> l(t->mu);
-        DeviceGuard g(t->device);
-        hipStream_t s = knn_own_stream(t);
-        t->writes.begin(s);
-        t->reads.begin(s);
-        Settle settle{t, s};
-        *count = where_total(t, *w, s);
+        TableCall call(t);
+        *count = where_total(t, *w, call.s);
     });
 }
 
@@ -161,11 +129,8 @@ int mi_knn_rows_where(mi_knn* t, const mi_knn_where* w, uint64_t* ids, uint64_t 
         const int bad = where_check_rows_args(t, w, ids, cap, count, &why);
         if (bad != MI_OK) fail(bad, "%s", why);
         std::lock_guard<std::mutex> l(t->mu);
-        DeviceGuard g(t->device);
-        hipStream_t s = knn_own_stream(t);
-        t->writes.begin(s);
-        t->reads.begin(s);
-        Settle settle{t, s};
+        TableCall call(t);
+        hipStream_t s = call.s;
         where_list(t, *w, s);
         *count = t->n_flist;
         const size_t take = (size_t)std::min<uint64_t>(cap, t->n_flist);
@@ -174,11 +139,8 @@ int mi_knn_rows_where(mi_knn* t, const mi_knn_where* w, uint64_t* ids, uint64_t 
         HIP_CHECK(hipMemcpyAsync(rows.data(), t->d_flist, take * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         // a table's ids ascend with its local rows (a shard's too: block-cyclic placement keeps the order)
-        const bool cyclic = t->cyc_n > 1 && t->cyc_block;
-        for (size_t i = 0; i < take; ++i) {
-            const uint64_t r = rows[i];
-            ids[i] = t->base + (cyclic ? ((r / t->cyc_block) * t->cyc_n + t->cyc_rank) * t->cyc_block + r % t->cyc_block : r);
-        }
+        const IdMap map = knn_id_map(t);
+        for (size_t i = 0; i < take; ++i) ids[i] = id_of_local(map, rows[i]);
     });
 }
 
@@ -190,14 +152,11 @@ int mi_knn_search_where(mi_knn* t, const float* q, uint32_t nq, uint32_t k, cons
         const int bad = where_check_search_args(t, q, nq, k, w, idx, dist, &why);
         if (bad != MI_OK) fail(bad, "%s (k %u)", why, k);
         std::lock_guard<std::mutex> l(t->mu);
-        DeviceGuard g(t->device);
-        hipStream_t s = knn_own_stream(t);
+        TableCall call(t);
+        hipStream_t s = call.s;
         constexpr uint32_t GROUP = 16;
         knn_reserve(t, (void**)&t->d_idx, &t->idx_cap, (size_t)GROUP * k, sizeof(uint64_t));
         knn_reserve(t, (void**)&t->d_dist, &t->dist_cap, (size_t)GROUP * k, sizeof(float));
-        t->writes.begin(s);
-        t->reads.begin(s);
-        Settle settle{t, s};
         where_list(t, *w, s);
         if (matched) *matched = t->n_flist;
         for (uint32_t u0 = 0; u0 < nq; u0 += GROUP) {

@@ -1,5 +1,5 @@
 // The host-only pieces of mi_knn_search_compound (image_search_amd/csrc/compound_host.h) as a stand-alone program: the
-// argument rules, the padding of the term set, the grid rule, the record's layout and the copy into caller arrays of exactly
+// argument rules, the padding of the term set, the dim and grid rules (scan_call.h's), the record's layout and the copy into caller arrays of exactly
 // k and k x T elements.  Built with -fsanitize=address,undefined (tests/test_compound_host.py) every array is heap memory of
 // its exact size, so a read or write one element too far is reported.
 #include <cmath>
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../image_search_amd/csrc/compound_host.h"
+#include "../../image_search_amd/csrc/scan_call.h"
 
 using namespace mi;
 
@@ -45,8 +46,8 @@ static void args() {
     EXPECT(chk(&t, v, 1, 0, v, w_neg, 0xFFFFFFFFu, 1, nullptr, 0, &o, &o) == MI_ERR_UNSUPPORTED);   // the count is judged before a threshold is read
     EXPECT(chk(&t, v, 1, 0, nullptr, nullptr, 0, 4097, nullptr, 0, &o, &o) == MI_ERR_UNSUPPORTED);
     EXPECT(why && why[0] != '\0');
-    for (uint32_t dim : {128u, 256u, 512u, 768u, 1024u}) EXPECT(compound_dim_ok(dim));
-    for (uint32_t dim : {0u, 64u, 192u, 384u, 2048u}) EXPECT(!compound_dim_ok(dim));
+    for (uint32_t dim : {128u, 256u, 512u, 768u, 1024u}) EXPECT(scan_dim_ok(dim));
+    for (uint32_t dim : {0u, 64u, 192u, 384u, 2048u}) EXPECT(!scan_dim_ok(dim));
 }
 
 static void term_set(uint32_t n_pos, uint32_t n_neg, uint32_t dim) {
@@ -67,6 +68,8 @@ static void term_set(uint32_t n_pos, uint32_t n_neg, uint32_t dim) {
     }
     EXPECT((c.neg_mask >> c.padded) == 0);
 }
+
+static uint32_t compound_grid(uint64_t n, int n_cu, int option) { return scan_grid(n, n_cu, option, COMPOUND_BLOCKS_PER_CU); }
 
 static void grid() {
     EXPECT(compound_grid(1, 256, 0) == 1 && compound_grid(64, 256, 0) == 1 && compound_grid(257, 256, 0) == 2);

@@ -81,29 +81,29 @@ static void okey() {
 }
 
 static void cursor() {
-    const PageIds plain{100, 50, 0, 0, 0};
+    const IdMap plain{100, 0, 0, 0};   // 50 rows
     OrderedCursor c;
-    EXPECT(ordered_cursor(plain, 0, 7, 12345, &c) && c.on == 0 && c.desc == 0);              // no flag: after_* are not looked at
+    EXPECT(ordered_cursor(plain, 50, 0, 7, 12345, &c) && c.on == 0 && c.desc == 0);              // no flag: after_* are not looked at
     EXPECT(ordered_past(c, 0, 0));
-    EXPECT(ordered_cursor(plain, MI_KNN_ORDER_DESC, 7, 12345, &c) && c.on == 0 && c.desc == 1);
-    EXPECT(!ordered_cursor(plain, MI_KNN_ORDER_AFTER, 7, 99, &c));                            // below the base
-    EXPECT(!ordered_cursor(plain, MI_KNN_ORDER_AFTER, 7, 150, &c));                           // past the last row
-    EXPECT(!ordered_cursor(plain, MI_KNN_ORDER_AFTER, 7, MI_KNN_NO_ID, &c));
-    EXPECT(ordered_cursor(plain, MI_KNN_ORDER_AFTER, 7, 110, &c) && c.on == 1 && c.first_row == 11 && c.okey == ordered_okey(7, false));
+    EXPECT(ordered_cursor(plain, 50, MI_KNN_ORDER_DESC, 7, 12345, &c) && c.on == 0 && c.desc == 1);
+    EXPECT(!ordered_cursor(plain, 50, MI_KNN_ORDER_AFTER, 7, 99, &c));                            // below the base
+    EXPECT(!ordered_cursor(plain, 50, MI_KNN_ORDER_AFTER, 7, 150, &c));                           // past the last row
+    EXPECT(!ordered_cursor(plain, 50, MI_KNN_ORDER_AFTER, 7, MI_KNN_NO_ID, &c));
+    EXPECT(ordered_cursor(plain, 50, MI_KNN_ORDER_AFTER, 7, 110, &c) && c.on == 1 && c.first_row == 11 && c.okey == ordered_okey(7, false));
     // inside the group of stamp 7: rows up to the cursor's are behind it, the next one is past it; other stamps by their order
     EXPECT(!ordered_past(c, ordered_okey(7, false), 0) && !ordered_past(c, ordered_okey(7, false), 10));
     EXPECT(ordered_past(c, ordered_okey(7, false), 11) && ordered_past(c, ordered_okey(8, false), 0));
     EXPECT(!ordered_past(c, ordered_okey(6, false), 49) && !ordered_past(c, ordered_okey(-8, false), 49));
-    EXPECT(ordered_cursor(plain, MI_KNN_ORDER_AFTER | MI_KNN_ORDER_DESC, 7, 149, &c) && c.first_row == 50 && c.desc == 1);
+    EXPECT(ordered_cursor(plain, 50, MI_KNN_ORDER_AFTER | MI_KNN_ORDER_DESC, 7, 149, &c) && c.first_row == 50 && c.desc == 1);
     EXPECT(ordered_past(c, ordered_okey(6, true), 0) && !ordered_past(c, ordered_okey(8, true), 49));   // descending: smaller stamps follow
     EXPECT(!ordered_past(c, ordered_okey(7, true), 49));
     // the extremes as the cursor's stamp
-    EXPECT(ordered_cursor(plain, MI_KNN_ORDER_AFTER, INT64_MAX, 100, &c) && c.okey == UINT64_MAX);
+    EXPECT(ordered_cursor(plain, 50, MI_KNN_ORDER_AFTER, INT64_MAX, 100, &c) && c.okey == UINT64_MAX);
     EXPECT(ordered_past(c, UINT64_MAX, 1) && !ordered_past(c, UINT64_MAX, 0) && !ordered_past(c, UINT64_MAX - 1, 49));
     // a shard of a block-cyclic table: the cursor's own row
-    const PageIds shard{0, 40, 8, 3, 1};   // blocks of 8 rows over 3 shards, this is shard 1: global rows 8..15, 32..39, ...
-    EXPECT(ordered_cursor(shard, MI_KNN_ORDER_AFTER, 0, 33, &c) && c.first_row == 10);
-    EXPECT(!ordered_cursor(shard, MI_KNN_ORDER_AFTER, 0, 16, &c));   // lives on shard 2
+    const IdMap shard{0, 8, 3, 1};   // 40 rows; blocks of 8 rows over 3 shards, this is shard 1: global rows 8..15, 32..39, ...
+    EXPECT(ordered_cursor(shard, 40, MI_KNN_ORDER_AFTER, 0, 33, &c) && c.first_row == 10);
+    EXPECT(!ordered_cursor(shard, 40, MI_KNN_ORDER_AFTER, 0, 16, &c));   // lives on shard 2
 }
 
 static void shard_cursor() {

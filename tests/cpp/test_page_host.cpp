@@ -1,7 +1,7 @@
 // The host-only pieces of mi_knn_search_page (image_search_amd/csrc/page_host.h) as a stand-alone program: the argument rules
 // in the contract's order, the key transform, the cursor -> first_key rule for a plain table, for a shard of a block-cyclic
-// table and for the sharded call (against a brute-force placement of every row), the `hi` rule, the grid rule, the record's
-// layout and the copy into caller arrays of exactly k elements.  Built with -fsanitize=address,undefined
+// table and for the sharded call (against a brute-force placement of every row), the `hi` rule, the grid rule (scan_call.h's,
+// at the paged search's factor), the record's layout and the copy into caller arrays of exactly k elements.  Built with -fsanitize=address,undefined
 // (tests/test_page_host.py) every array is heap memory of its exact size, so a read or write one element too far is reported.
 #include <cmath>
 #include <cstdio>
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../image_search_amd/csrc/page_host.h"
+#include "../../image_search_amd/csrc/scan_call.h"
 
 using namespace mi;
 
@@ -54,43 +55,36 @@ static void keys() {
     EXPECT(page_hi(0.25f) + 1 == ((uint64_t)page_dist_key(std::nextafterf(0.25f, 1.0f)) << 32));
 }
 
-// id of a local row, as IdMap / id_of_local (knn_shared.h) places it
-static uint64_t id_of(const PageIds& m, uint64_t local) {
-    if (m.n <= 1 || m.block == 0) return m.base + local;
-    return m.base + ((local / m.block) * m.n + m.rank) * m.block + local % m.block;
-}
-
-static void cursor_one_table(const PageIds& m) {
-    // every row's id maps back; the ids between the rows' and the ids around the range do not
-    std::vector<char> held(m.rows * std::max(m.n, 1u) + 2 * (m.block ? m.block : 1) + 4, 0);
-    for (uint64_t l = 0; l < m.rows; ++l) {
-        uint64_t back = ~0ull;
-        EXPECT(page_local_of(m, id_of(m, l), &back) && back == l);
-        held[id_of(m, l) - m.base] = 1;
+// (the id space itself — id <-> local row, the placement arithmetic — is tests/cpp/test_ids_host.cpp's)
+static void cursor_one_table(const IdMap& m, uint64_t rows) {
+    // a cursor at every row's id; none at the ids between the rows' and around the range
+    std::vector<char> held(rows * std::max(m.n, 1u) + 2 * (m.block ? m.block : 1) + 4, 0);
+    for (uint64_t l = 0; l < rows; ++l) {
+        held[id_of_local(m, l) - m.base] = 1;
         uint64_t fk = 1;
-        EXPECT(page_first_key(m, 0.25f, id_of(m, l), &fk));
+        EXPECT(page_first_key(m, rows, 0.25f, id_of_local(m, l), &fk));
         EXPECT(fk == (((uint64_t)page_dist_key(0.25f) << 32) | l) + 1);          // the cursor key + 1
     }
     for (uint64_t off = 0; off < held.size(); ++off) {
-        uint64_t l = 0, fk = 1;
-        EXPECT(page_local_of(m, m.base + off, &l) == (held[off] != 0));
-        EXPECT(page_first_key(m, 0.5f, m.base + off, &fk) == (held[off] != 0));
+        uint64_t fk = 1;
+        EXPECT(page_first_key(m, rows, 0.5f, m.base + off, &fk) == (held[off] != 0));
     }
-    uint64_t l = 0, fk = 1;
-    if (m.base) EXPECT(!page_local_of(m, m.base - 1, &l) && !page_first_key(m, 0.5f, m.base - 1, &fk));
-    EXPECT(page_first_key(m, NAN, NO, &fk) && fk == 0);                           // no cursor: from the start, after_dist ignored
+    uint64_t fk = 1;
+    if (m.base) EXPECT(!page_first_key(m, rows, 0.5f, m.base - 1, &fk));
+    EXPECT(page_first_key(m, rows, NAN, NO, &fk) && fk == 0);                     // no cursor: from the start, after_dist ignored
     // -0 and +0 are different cursors
-    if (m.rows) {
+    if (rows) {
         uint64_t a = 0, b = 0;
-        EXPECT(page_first_key(m, -0.0f, id_of(m, 0), &a) && page_first_key(m, 0.0f, id_of(m, 0), &b) && a + (1ull << 32) == b);
+        EXPECT(page_first_key(m, rows, -0.0f, id_of_local(m, 0), &a) && page_first_key(m, rows, 0.0f, id_of_local(m, 0), &b) &&
+               a + (1ull << 32) == b);
     }
 }
 
 static void first_key_carry() {
     // the last possible row of a distance: + 1 carries into the distance word, i.e. "nothing of that distance is left"
-    const PageIds m{0, 0x100000000ull, 0, 0, 0};
+    const IdMap m{0, 0, 0, 0};
     uint64_t fk = 0;
-    EXPECT(page_first_key(m, 0.25f, 0xFFFFFFFFull, &fk) && fk == ((uint64_t)(page_dist_key(0.25f) + 1) << 32));
+    EXPECT(page_first_key(m, 0x100000000ull, 0.25f, 0xFFFFFFFFull, &fk) && fk == ((uint64_t)(page_dist_key(0.25f) + 1) << 32));
     EXPECT(page_first_key_at(INFINITY, 0x100000000ull) == 0xFF80000100000000ull);   // the largest cursor does not wrap
     EXPECT(page_first_key_at(-INFINITY, 0) == ((uint64_t)page_dist_key(-INFINITY) << 32));
 }
@@ -110,16 +104,18 @@ static void cursor_sharded(uint32_t block, uint32_t n, uint64_t rows) {
         EXPECT(local == below[s]);        // a shard's local rows ascend with their global ids
         ++below[s];
         for (uint32_t u = 0; u < n; ++u) {
-            EXPECT(page_shard_rows_below(block, n, u, after) == below[u]);
+            EXPECT(cyclic_rows_of(block, n, u, after + 1) == below[u]);
             // the shard that holds the cursor's row gets what the one-table rule gives it
             if (u == s) {
-                const PageIds m{0, rows, block, n, u};
+                const IdMap m{0, block, n, u};
                 uint64_t fk = 0;
-                EXPECT(page_first_key(m, 0.125f, after, &fk) && fk == page_first_key_at(0.125f, below[u]));
+                EXPECT(page_first_key(m, rows, 0.125f, after, &fk) && fk == page_first_key_at(0.125f, below[u]));
             }
         }
     }
 }
+
+static uint32_t page_grid(uint64_t n, int n_cu, int option) { return scan_grid(n, n_cu, option, PAGE_BLOCKS_PER_CU); }
 
 static void grid() {
     EXPECT(page_grid(1, 256, 0) == 1 && page_grid(64, 256, 0) == 1 && page_grid(257, 256, 0) == 2);
@@ -154,11 +150,11 @@ static void record(uint32_t k, bool with_counts) {
 int main() {
     args();
     keys();
-    cursor_one_table(PageIds{0, 300, 0, 0, 0});
-    cursor_one_table(PageIds{1ull << 33, 130, 0, 0, 0});
-    cursor_one_table(PageIds{0, 0, 0, 0, 0});
-    for (uint32_t rank = 0; rank < 3; ++rank) cursor_one_table(PageIds{0, 100, 16, 3, rank});   // a shard with a ragged last block
-    cursor_one_table(PageIds{1000, 64, 64, 2, 1});
+    cursor_one_table(IdMap{0, 0, 0, 0}, 300);
+    cursor_one_table(IdMap{1ull << 33, 0, 0, 0}, 130);
+    cursor_one_table(IdMap{0, 0, 0, 0}, 0);
+    for (uint32_t rank = 0; rank < 3; ++rank) cursor_one_table(IdMap{0, 16, 3, rank}, 100);   // a shard with a ragged last block
+    cursor_one_table(IdMap{1000, 64, 2, 1}, 64);
     first_key_carry();
     cursor_sharded(16, 2, 200);
     cursor_sharded(64, 3, 1000);
