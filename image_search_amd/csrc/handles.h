@@ -204,6 +204,12 @@ struct mi_knn {
     // "join_cap"; its buffers live for the call only), and {candidates, pairs, strips, tiles} of the last call.
     uint32_t join_cap = 1u << 22;
     uint64_t join_stats[4] = {0, 0, 0, 0};
+    // The join with another table (mi_knn_near_pairs_between, join_between.hip), this table as the row side: {candidates, pairs,
+    // stage-1 launches, tiles} of the last call; the column side goes through a staged copy even on this table's own device
+    // (option "join_stage": what a column side on another device always takes); the column side is walked in chunks of that
+    // many rows, staged or not (option "join_stage_rows": 0 = what the staging budget holds)
+    uint64_t between_stats[4] = {0, 0, 0, 0};
+    int join_stage = 0, join_stage_rows = 0;
     // mi_knn_density / mi_knn_dbscan (density.hip): {candidates pass 1, pairs within, tiles pass 1, candidates pass 2, tiles
     // visited pass 2, tiles skipped pass 2, unions that merged, stage-1 launches} of the last call
     uint64_t dbscan_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -321,6 +327,7 @@ struct mi_knn_sharded {
     struct { uint64_t searches = 0, collectives = 0, copies = 0, merges = 0; } stats;   // mi_knn_sharded_stats
     uint64_t generation = 0;                  // of the files last saved or loaded (mi_knn_sharded_save)
     std::vector<hipEvent_t> ev_src;           // [device ordinal]: the peer copies of the last append_device from that device
+    uint64_t join_stats[4] = {0, 0, 0, 0};    // mi_knn_sharded_near_pairs_stats: summed over every shard and shard pair of the last call
     std::mutex mu;
     uint32_t n() const { return (uint32_t)shard.size(); }
 };
@@ -388,6 +395,11 @@ void knn_search_ordered(mi_knn* t, const float* q, uint32_t k, float max_dist, c
 // ordered.hip: mi_knn_stamp_histogram behind its argument check; takes t->mu
 void knn_stamp_histogram(mi_knn* t, const float* q, float max_dist, const mi_knn_where* w, const int64_t* edges, uint32_t n_edges,
                          uint64_t* hist);
+// join.hip: the self-join of mi_knn_near_pairs with first_new as a LOCAL row (0 = everything, >= rows = nothing): pairs as local
+// rows a < b with the join's distance, ascending by (a, b); *over = more than user_cap qualify (out is then partial).  Takes
+// t->mu and leaves the call's figures in t->join_stats
+struct JoinPair { uint32_t a, b; float d; };
+void knn_near_pairs_local(mi_knn* t, float max_dist, uint64_t first_new_local, uint64_t user_cap, std::vector<JoinPair>* out, bool* over);
 // sharded.hip
 void sharded_place(const mi_knn_sharded* t, uint64_t r, uint32_t* s, uint64_t* local);
 uint64_t sharded_rows_of(const mi_knn_sharded* t, uint64_t total, uint32_t s);  // rows shard s holds when the table holds `total`

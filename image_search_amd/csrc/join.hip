@@ -16,8 +16,6 @@ using namespace mi;
 
 namespace {
 
-struct JoinPair { uint32_t a, b; float d; };
-
 struct Join {
     mi_knn* t;
     hipStream_t s;
@@ -113,13 +111,16 @@ uint32_t local_first_new(const mi_knn* t, uint64_t first_new) {
     return (uint32_t)lo;
 }
 
-// the join itself: pairs as local rows, ascending by (a, b); *over = more than user_cap pairs qualify (out is then partial)
-void near_pairs(mi_knn* t, float max_dist, uint64_t first_new_id, uint64_t user_cap, std::vector<JoinPair>* out, bool* over) {
+// the join itself: pairs as local rows, ascending by (a, b); *over = more than user_cap pairs qualify (out is then partial).
+// first_new_id: an id (local_first_new), or with first_new_is_local the local row itself (what a shard of the sharded join is
+// handed: the number of its rows below the global bound)
+void near_pairs(mi_knn* t, float max_dist, uint64_t first_new_id, uint64_t user_cap, std::vector<JoinPair>* out, bool* over,
+                bool first_new_is_local = false) {
     out->clear();
     *over = false;
     std::lock_guard<std::mutex> l(t->mu);
     for (uint64_t& v : t->join_stats) v = 0;
-    const uint32_t fn = local_first_new(t, first_new_id);
+    const uint32_t fn = first_new_is_local ? (uint32_t)std::min<uint64_t>(first_new_id, t->rows) : local_first_new(t, first_new_id);
     check_mirror_dim(t->dim, "the join's");
     if (t->rows < 2 || fn >= t->rows) return;
     Scratch scratch;
@@ -195,6 +196,12 @@ void write_groups(const std::vector<uint64_t>& gids, const std::vector<uint64_t>
 }
 
 }  // namespace
+
+namespace mi {
+void knn_near_pairs_local(mi_knn* t, float max_dist, uint64_t first_new_local, uint64_t user_cap, std::vector<JoinPair>* out, bool* over) {
+    near_pairs(t, max_dist, first_new_local, user_cap, out, over, true);
+}
+}  // namespace mi
 
 extern "C" {
 

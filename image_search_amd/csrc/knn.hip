@@ -1135,6 +1135,17 @@ int mi_knn_set_option(mi_knn* t, const char* key, int value) {
             // full tile, 2^14): a strip that finds more is redone in smaller pieces.  Same answers whatever the value.
             if (value < (1 << 14)) fail(MI_ERR_INVALID, "join_cap must be >= 16384 (got %d)", value);
             t->join_cap = (uint32_t)value;
+        } else if (k == "join_stage") {
+            // mi_knn_near_pairs_between / mi_knn_sharded_near_pairs with this table as the row side: 1 = the column side goes
+            // through the staged copy even when it lives on this table's device (what a column side on another device always
+            // takes); 0 (default): it is read where it lies.  Same answers either way.
+            if (value < 0 || value > 1) fail(MI_ERR_INVALID, "join_stage must be 0 or 1 (got %d)", value);
+            t->join_stage = value;
+        } else if (k == "join_stage_rows") {
+            // ... rows of one column chunk (staged or read where it lies), rounded up to whole tiles of 128.  0 (default): what
+            // the staging budget (256 MiB of fp32 rows) holds.  Same answers whatever the value.
+            if (value < 0) fail(MI_ERR_INVALID, "join_stage_rows must be >= 0 (got %d)", value);
+            t->join_stage_rows = value;
         } else if (k == "many_segments") {
             // mi_knn_search_many / mi_knn_neighbors: column segments of a stage-1 launch.  0 (default): from the query and column
             // tile counts; v >= 1: exactly min(v, column tiles).  Same answers whatever the value.
@@ -1172,7 +1183,7 @@ int mi_knn_set_option(mi_knn* t, const char* key, int value) {
             if (!where_chunk_ok(value)) fail(MI_ERR_INVALID, "where_chunk must be 0 or a multiple of 64 up to 65536 (got %d)", value);
             t->where_chunk = value;
         } else {
-            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, many_segments, many_sample, compound_blocks, page_blocks, group_blocks, group_lds_max, where_chunk)", key);
+            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, join_stage, join_stage_rows, many_segments, many_sample, compound_blocks, page_blocks, group_blocks, group_lds_max, where_chunk)", key);
         }
     });
 }

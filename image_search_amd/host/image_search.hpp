@@ -222,6 +222,18 @@ class EmbeddingTable {
     }
     // {candidate pairs, pairs accepted, strips run, tiles visited} of the last near_pairs
     std::vector<uint64_t> near_pairs_stats() const { std::vector<uint64_t> v(4); check(mi_knn_near_pairs_stats(h_, v.data())); return v; }
+    // the join with another table (mi_knn_near_pairs_between): every pair of a live row of this table (a, the query) and a live
+    // row of `other` (b) with cosine distance <= max_dist, ascending by (a, b); neither table changes
+    NearPairs near_pairs_with(const EmbeddingTable& other, float max_dist, uint64_t cap = 1ull << 20) const {
+        NearPairs r;
+        r.a.resize(cap); r.b.resize(cap); r.dist.resize(cap);
+        uint64_t n = 0;
+        check(mi_knn_near_pairs_between(h_, other.h_, max_dist, r.a.data(), r.b.data(), r.dist.data(), cap, &n));
+        r.a.resize(n); r.b.resize(n); r.dist.resize(n);
+        return r;
+    }
+    // {candidate pairs, pairs accepted, stage-1 launches, tiles computed} of the last near_pairs_with
+    std::vector<uint64_t> near_pairs_with_stats() const { std::vector<uint64_t> v(4); check(mi_knn_near_pairs_between_stats(h_, v.data())); return v; }
     // how crowded it is around every row (mi_knn_density): the pairs of near_pairs(max_dist) that contain the row, by local row;
     // 0 for a deleted row and for an outlier.  No pair list is built
     std::vector<uint32_t> neighbor_counts(float max_dist) const {
@@ -661,6 +673,18 @@ class ImageIndex {
         }
         return out;
     }
+    // "skip what I already have" (mi_index_matches): (path here, path in `other`, distance) of every pair of images within
+    // max_dist, ordered by this index's row, then the other's; removed paths never appear
+    struct Match { std::string mine, theirs; float dist; };
+    std::vector<Match> matches(const ImageIndex& other, float max_dist, bool web = false, uint64_t max_pairs = 1ull << 20) const {
+        std::vector<uint64_t> a(max_pairs), b(max_pairs);
+        std::vector<float> d(max_pairs);
+        uint64_t n = 0;
+        check(mi_index_matches(h_, other.h_, max_dist, a.data(), b.data(), d.data(), max_pairs, &n));
+        std::vector<Match> out;
+        for (uint64_t i = 0; i < n; ++i) out.push_back(Match{path(a[i], web), other.path(b[i], web), d[i]});
+        return out;
+    }
     // the themes that are really there as lists of paths (mi_index_themes), what a /themes handler returns: the largest
     // cluster first, equal sizes by their first row; removed paths never appear.  *n_noise (may be null): the live rows in no theme
     std::vector<std::vector<std::string>> themes(float max_dist, uint32_t min_pts = 5, bool web = false, uint64_t* n_noise = nullptr) const {
@@ -711,6 +735,18 @@ class ShardedTable {
     void set_option(const std::string& key, int value) { check(mi_knn_sharded_set_option(h_, key.c_str(), value)); }
     // {searches, ncclAllGather calls, transport copies, device merges} issued so far
     std::vector<uint64_t> stats() const { std::vector<uint64_t> v(4); check(mi_knn_sharded_stats(h_, v.data())); return v; }
+    // EmbeddingTable::near_pairs over all shards (mi_knn_sharded_near_pairs): the one table's ids and distance bits, pairs that
+    // cross shards included; first_new: only pairs whose larger id is >= first_new
+    EmbeddingTable::NearPairs near_pairs(float max_dist, uint64_t first_new = 0, uint64_t cap = 1ull << 20) const {
+        EmbeddingTable::NearPairs r;
+        r.a.resize(cap); r.b.resize(cap); r.dist.resize(cap);
+        uint64_t n = 0;
+        check(mi_knn_sharded_near_pairs(h_, max_dist, first_new, r.a.data(), r.b.data(), r.dist.data(), cap, &n));
+        r.a.resize(n); r.b.resize(n); r.dist.resize(n);
+        return r;
+    }
+    // {candidate pairs, pairs accepted, stage-1 launches, tiles} of the last near_pairs, summed over shards and shard pairs
+    std::vector<uint64_t> near_pairs_stats() const { std::vector<uint64_t> v(4); check(mi_knn_sharded_near_pairs_stats(h_, v.data())); return v; }
     // EmbeddingTable::assign_multi over all shards (mi_knn_sharded_assign_multi): labels / dist [rows * m] by global row id
     std::pair<std::vector<uint32_t>, std::vector<float>> assign_multi(const std::vector<float>& vectors, uint32_t C, uint32_t m,
                                                                       float max_dist = INFINITY) const {

@@ -233,6 +233,16 @@ def _stamp_histogram(fn, handle, dim, lead, reference, edges, max_dist, predicat
     return hist
 
 
+def _pairs_call(fn, lead, cap: int):
+    """fn(*lead, a, b, dist, cap, &count) of the join calls -> (a, b, dist) cut to the pairs found"""
+    a, b = np.empty(cap, np.uint64), np.empty(cap, np.uint64)
+    dist = np.empty(cap, np.float32)
+    n = ctypes.c_uint64()
+    check(fn(*lead, a.ctypes.data if cap else None, b.ctypes.data if cap else None, dist.ctypes.data if cap else None, cap,
+             ctypes.byref(n)))
+    return a[:n.value].copy(), b[:n.value].copy(), dist[:n.value].copy()
+
+
 def _ptrs(vecs):
     arr = (c_f * len(vecs))()
     for i, v in enumerate(vecs):
@@ -374,6 +384,19 @@ class EmbeddingTable:
         out = (ctypes.c_uint64 * 4)()
         check(lib().mi_knn_near_pairs_stats(self._h, out))
         return {"candidates": out[0], "pairs": out[1], "strips": out[2], "tiles": out[3]}
+
+    def near_pairs_with(self, other: "EmbeddingTable", max_dist: float, cap: int = 1 << 20):
+        """The join with another table (mi_knn_near_pairs_between): every pair of a live row of this table and a live row of
+        `other` with cosine distance <= max_dist as (a, b, dist) — a: ids of this table, b: ids of `other`, ascending by
+        (a, b); dist is what other.knn(row a of this table) reports for row b, bit for bit.  Neither table changes.  More
+        than `cap` pairs: MiError (MI_ERR_UNSUPPORTED)."""
+        return _pairs_call(lib().mi_knn_near_pairs_between, (self._h, other._h, float(max_dist)), cap)
+
+    def near_pairs_with_stats(self):
+        """mi_knn_near_pairs_between_stats, of the last near_pairs_with on this table"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_near_pairs_between_stats(self._h, out))
+        return {"candidates": out[0], "pairs": out[1], "launches": out[2], "tiles": out[3]}
 
     def neighbor_counts(self, max_dist: float) -> np.ndarray:
         """How crowded is it around every row (mi_knn_density): counts [rows] uint32 = the pairs of near_pairs(max_dist) that
@@ -1050,6 +1073,24 @@ class ShardedTable:
         the strictly ascending edges <= stamp; [len(edges) + 1] uint64, summing to knn_ordered's counts["within"]."""
         return _stamp_histogram(lib().mi_knn_sharded_stamp_histogram, self._h, self.dim, (), reference, edges, max_dist, predicate)
 
+    def near_pairs(self, max_dist: float, first_new: int = 0, cap: int = 1 << 20):
+        """EmbeddingTable.near_pairs over all shards (mi_knn_sharded_near_pairs): every pair of live rows a < b (global ids)
+        within max_dist whose larger id is >= first_new, pairs that cross shards included; ids and distance bits are those
+        of one table holding the same rows."""
+        return _pairs_call(lib().mi_knn_sharded_near_pairs, (self._h, float(max_dist), int(first_new)), cap)
+
+    def near_pairs_stats(self):
+        """mi_knn_sharded_near_pairs_stats: the last near_pairs, summed over every shard and shard pair"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_sharded_near_pairs_stats(self._h, out))
+        return {"candidates": out[0], "pairs": out[1], "launches": out[2], "tiles": out[3]}
+
+    def duplicates(self, max_dist: float, first_new: int = 0, cap: int = 1 << 20) -> list:
+        """Groups of near-duplicate rows: near_pairs through pairs_to_groups — lists of global ids chained by distances
+        <= max_dist, ascending inside a group, the groups by their first id."""
+        a, b, _ = self.near_pairs(max_dist, first_new, cap)
+        return pairs_to_groups(a, b)
+
     def assign(self, vectors: np.ndarray):
         """EmbeddingTable.assign over all shards (mi_knn_sharded_assign): labels / dist by global row id"""
         v = _f32(vectors).reshape(-1, self.dim)
@@ -1524,6 +1565,12 @@ class ImageIndex:
         check(lib().mi_index_duplicates(self._h, float(max_dist), int(first_new), max_pairs, ids.ctypes.data if ids.size else None,
                                         ids.size, starts.ctypes.data, starts.size, ctypes.byref(n_ids), ctypes.byref(n_groups)))
         return [[self.path(int(i), web=web) for i in g] for g in _groups(ids, starts)]
+
+    def matches(self, other: "ImageIndex", max_dist: float, web: bool = False, max_pairs: int = 1 << 20) -> list:
+        """"Skip what I already have" (mi_index_matches): (path here, path in `other`, distance) for every pair of images
+        within max_dist, ordered by this index's row id, then the other's; removed paths never appear."""
+        a, b, d = _pairs_call(lib().mi_index_matches, (self._h, other._h, float(max_dist)), max_pairs)
+        return [(self.path(int(x), web=web), other.path(int(y), web=web), float(z)) for x, y, z in zip(a, b, d)]
 
     def themes(self, max_dist: float, min_pts: int = 5, web: bool = False):
         """The events / themes that are really there, however many, and the odd pictures (mi_index_themes: EmbeddingTable.dbscan

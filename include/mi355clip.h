@@ -352,6 +352,25 @@ int mi_knn_near_pairs(mi_knn* t, float max_dist, uint64_t first_new, uint64_t* a
 /* of the last mi_knn_near_pairs on this handle: out = {candidate pairs stage 1 passed to stage 2, pairs accepted,
  * strips run (re-runs after an overflow included), tiles visited} */
 int mi_knn_near_pairs_stats(mi_knn* t, uint64_t out[4]);
+/* The join of TWO tables ("which pictures on this card, or in that other library, do I already have?" — the reference has one
+ * table in one server, server/src/main.rs, and could only answer this by inserting the other rows first): every pair of a
+ * live row of `t` and a live row of `other` with cosine distance <= max_dist.  a[i]: an id of t; b[i]: an id of other (the two
+ * id spaces are unrelated and may overlap); dist[i] = what mi_knn_search on `other` with q = row a[i] of t reports for row
+ * b[i], bit for bit: the row of t is the query.  Ascending by (a, b).  Neither table is changed.  Stage 1 is the self-join's
+ * bf16 tile with a row operand (t, where the work runs) and a column operand (other); the same bound decides what stage 2
+ * re-evaluates from the fp32 rows (dim as mi_knn_near_pairs requires, MI_ERR_UNSUPPORTED otherwise).  `other` on t's device
+ * is read where it lies; on another device (or with option "join_stage" = 1 on t) its rows pass through a staged copy on t's
+ * device.  Either way `other` is walked in column chunks of at most 256 MiB of fp32 rows (option "join_stage_rows": rows
+ * per chunk; same answers whatever the value): what the staged copy holds at a time.  Memory beyond that is mi_knn_near_pairs' (t's "join_cap").  Takes both handles' locks; runs on t's stream behind
+ * every write and search enqueued on either table before it, and waits for its results.
+ * a, b, dist: [cap] (may be NULL when cap = 0); *count = number of pairs.  More than cap pairs qualify: MI_ERR_UNSUPPORTED,
+ * *count = cap + 1, the call stops early (the cap protocol of mi_knn_near_pairs).  t == other, a null handle, dims that
+ * differ, max_dist NaN or < 0: MI_ERR_INVALID.  An empty table on either side: 0 pairs. */
+int mi_knn_near_pairs_between(mi_knn* t, mi_knn* other, float max_dist, uint64_t* a, uint64_t* b, float* dist, uint64_t cap,
+                              uint64_t* count);
+/* of the last mi_knn_near_pairs_between with t as its first table: out = {candidate pairs stage 1 passed to stage 2, pairs
+ * accepted, stage-1 launches (re-runs after an overflow included), tiles computed} */
+int mi_knn_near_pairs_between_stats(mi_knn* t, uint64_t out[4]);
 /* Density ("how crowded is it around every image?") and DBSCAN ("which themes are really there, however many, and which
  * pictures belong to none?") on the join's tiles; the pairs never leave the device, so a dense theme costs no pair list.
  * Let W be the pairs (a < b, d) that mi_knn_near_pairs(t, max_dist, first_new = 0) reports: live rows only, d the bits
@@ -846,6 +865,19 @@ int mi_knn_sharded_assign_multi(mi_knn_sharded* t, const float* vectors, uint32_
  * mi_knn_sharded_assign_multi), the per-shard lists are merged with mi_knn_merge's ordering; equals the one-table result
  * bit for bit */
 int mi_knn_sharded_search_many(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, uint64_t* idx, float* dist);
+/* mi_knn_near_pairs over the whole table (the reference's one table in one server, server/src/main.rs, at the size that needs
+ * several GPUs): every pair of live rows a < b (global ids) with cosine distance <= max_dist whose larger id is >= first_new,
+ * ascending by (a, b) — ids and distance bits are those of mi_knn_near_pairs on ONE table that holds the same rows in id
+ * order.  A pair whose rows live in different shards is found by joining the two shards (mi_knn_near_pairs_between's
+ * primitive, the row with the smaller id as the query); the S self-joins run side by side, then the S (S - 1) / 2 shard
+ * pairs in round-robin rounds in which no shard occurs twice, the row side alternating between the shards; a column side on
+ * another device is staged on the row side's device.  first_new: 0 (all pairs) or any id up to one past the last row
+ * (beyond: MI_ERR_INVALID); it need not belong to a particular shard.  cap, *count, the errors and the early stop (checked
+ * between launches across the whole call): as mi_knn_near_pairs. */
+int mi_knn_sharded_near_pairs(mi_knn_sharded* t, float max_dist, uint64_t first_new, uint64_t* a, uint64_t* b, float* dist,
+                              uint64_t cap, uint64_t* count);
+/* of the last mi_knn_sharded_near_pairs: {candidates, pairs, stage-1 launches, tiles} summed over every shard and shard pair */
+int mi_knn_sharded_near_pairs_stats(mi_knn_sharded* t, uint64_t out[4]);
 /* Change the layout of a LIVE table: every row of `src` into the empty `dst` (another shard count, device set or block
  * size), block by block, device to device — a plain copy where source and destination shard share a GPU,
  * hipMemcpyPeerAsync over xGMI where they do not; nothing passes through the host.  src is unchanged. */
@@ -1043,6 +1075,11 @@ int mi_index_live_paths(mi_index* ix, char* buf, size_t cap, size_t* needed);
  * max_pairs bounds the join (MI_ERR_UNSUPPORTED beyond it). */
 int mi_index_duplicates(mi_index* ix, float max_dist, uint64_t first_new, uint64_t max_pairs, uint64_t* ids,
                         uint64_t cap_ids, uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups);
+/* "skip what I already have" at import: mi_knn_near_pairs_between on the two indexes' tables (the reference, one table in one
+ * server — server/src/main.rs — can only compare paths).  a[i]: a row id of ix, b[i]: a row id of other (mi_index_path names
+ * them), ascending by (a, b); removed paths are deleted rows and never reported. */
+int mi_index_matches(mi_index* ix, mi_index* other, float max_dist, uint64_t* a, uint64_t* b, float* dist, uint64_t cap,
+                     uint64_t* count);
 /* themes of table `image`: mi_knn_dbscan on mi_index_table in mi_index_duplicates' output shape — the clusters ordered by
  * their smallest id, ids ascending inside; noise is not listed, *n_noise counts it; removed paths are in neither. */
 int mi_index_themes(mi_index* ix, float max_dist, uint32_t min_pts, uint64_t* ids, uint64_t cap_ids, uint64_t* group_start,
