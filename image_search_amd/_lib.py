@@ -93,6 +93,10 @@ SYMBOLS = {
     "mi_knn_kmeans_seed": (ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, c_vp,
                                           ctypes.POINTER(ctypes.c_double)]),
     "mi_knn_kmeans_seed_stats": (ctypes.c_int, [c_vp, c_u64p]),
+    "mi_knn_summarize": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mi_knn_summarize_stats": (ctypes.c_int, [c_vp, c_u64p]),
+    "mi_index_folder_overview": (ctypes.c_int, [c_vp, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                ctypes.POINTER(ctypes.c_uint32)]),
     "mi_knn_search_diverse": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, ctypes.c_uint64,
                                              c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32)]),
     "mi_knn_search_diverse_stats": (ctypes.c_int, [c_vp, c_u64p]),

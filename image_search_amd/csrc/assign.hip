@@ -11,6 +11,7 @@
 #include "common.h"
 #include "handles.h"
 #include "assign_kernels.h"
+#include "kmeans_update.h"
 #include "two_stage.h"
 
 using namespace mi;
@@ -143,53 +144,13 @@ void assign_local(mi_knn* t, const float* vectors, uint32_t C, uint32_t* labels,
     HIP_CHECK(hipStreamSynchronize(a.s));
 }
 
-// one update: d_labels / d_dist -> d_vec, in an order the row ids fix (assign_kernels.h)
-struct Update {
-    uint32_t n_waves = 0, chunk = 0, max_segs = 0;
-    uint32_t *d_hist = nullptr, *d_total = nullptr, *d_start = nullptr, *d_seg = nullptr, *d_sorted = nullptr;
-    float *d_inv = nullptr, *d_part = nullptr;
-
-    template <int NCH>
-    void setup(Assign& a) {
-        const uint32_t n = a.n_rows, C = a.C;
-        n_waves = std::max<uint32_t>(1u, std::min<uint32_t>({4096u, (1u << 24) / (C + 1), (n + 1023) / 1024}));
-        n_waves = (n_waves + 3) / 4 * 4;
-        chunk = ((n + n_waves - 1) / n_waves + 63) / 64 * 64;
-        max_segs = n / KM_SEG + C;
-        d_hist = (uint32_t*)a.scratch.get((size_t)n_waves * (C + 1) * sizeof(uint32_t));
-        d_total = (uint32_t*)a.scratch.get((size_t)(C + 2) * sizeof(uint32_t));
-        d_start = (uint32_t*)a.scratch.get((size_t)(C + 2) * sizeof(uint32_t));
-        d_seg = (uint32_t*)a.scratch.get((size_t)(C + 2) * sizeof(uint32_t));
-        d_sorted = (uint32_t*)a.scratch.get((size_t)n * sizeof(uint32_t));
-        d_inv = (float*)a.scratch.get((size_t)n * sizeof(float));
-        d_part = (float*)a.scratch.get((size_t)max_segs * a.t->dim * sizeof(float));
-        hipLaunchKernelGGL((km_inv_norm_kernel<NCH>), dim3(group16_blocks(a.t, n)), dim3(256), 0, a.s, a.t->table, n, d_inv);
-        HIP_CHECK(hipGetLastError());
-    }
-
-    template <int NCH>
-    void run(Assign& a) {
-        const uint32_t n = a.n_rows, C = a.C;
-        hipStream_t s = a.s;
-        HIP_CHECK(hipMemsetAsync(d_hist, 0, (size_t)n_waves * (C + 1) * sizeof(uint32_t), s));
-        hipLaunchKernelGGL(km_hist_kernel, dim3(n_waves / 4), dim3(256), 0, s, a.d_labels, a.d_dist, n, C, chunk, d_hist);
-        hipLaunchKernelGGL(km_scan_kernel, dim3((C + 1 + 255) / 256), dim3(256), 0, s, d_hist, n_waves, C, d_total);
-        hipLaunchKernelGGL(km_offsets_kernel, dim3(1), dim3(1024), 0, s, d_total, C, d_start, d_seg);
-        hipLaunchKernelGGL(km_place_kernel, dim3(n_waves / 4), dim3(256), 0, s, a.d_labels, a.d_dist, n, C, chunk, d_hist, d_start,
-                           d_sorted);
-        hipLaunchKernelGGL((km_sum_kernel<NCH>), dim3(std::max(max_segs, 1u)), dim3(256), 0, s, a.t->table, d_inv, d_sorted, d_start,
-                           d_seg, C, d_part);
-        const uint64_t el = (uint64_t)C * a.t->dim;
-        hipLaunchKernelGGL(km_centroid_kernel, dim3((uint32_t)((el + 255) / 256)), dim3(256), 0, s, d_part, d_total, d_seg, C,
-                           a.t->dim, a.d_vec);
-        HIP_CHECK(hipGetLastError());
-    }
-};
-
 template <int NCH>
 void kmeans_loop(Assign& a, uint32_t max_iters, uint32_t* iters_run, uint64_t* changed_last) {
-    Update u;
-    if (max_iters > 0) u.setup<NCH>(a);
+    KmUpdate u;   // d_labels / d_dist -> d_vec (kmeans_update.h)
+    if (max_iters > 0) {
+        u.alloc(a.scratch, a.n_rows, a.C, a.t->dim);
+        u.inv_norms<NCH>(a.t, a.s, a.n_rows);
+    }
     uint32_t it = 0;
     uint64_t changed = 0;
     for (;;) {
@@ -200,7 +161,7 @@ void kmeans_loop(Assign& a, uint32_t max_iters, uint32_t* iters_run, uint64_t* c
             a.run(true, &changed);
         }
         if ((it > 0 && changed == 0) || it == max_iters) break;
-        u.run<NCH>(a);
+        u.run<NCH>(a.t, a.s, a.d_labels, a.d_dist, a.n_rows, a.C, a.d_vec);
         ++it;
     }
     *iters_run = it;

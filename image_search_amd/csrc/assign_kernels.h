@@ -39,6 +39,8 @@
 #include "common.h"
 #include "tile128.h"
 
+// (assign.hip and summary.hip both include this file: the kernels that are no templates are static, one copy per translation
+// unit)
 namespace mi {
 
 constexpr int ASG_LDS = TILE_IMGS + 3 * TILE * 4;               // the tile's images + row weights, column weights, row maxima
@@ -167,10 +169,10 @@ __global__ __launch_bounds__(256) void assign_rescore_kernel(const float* __rest
 
 // best -> labels / dist (deleted rows: MI_KNN_NO_LABEL, +inf).  prev (nullable): the previous assign's labels, the rows
 // that differ are counted into *changed (an integer count: the same whatever the order).  prev may be `labels` itself.
-__global__ __launch_bounds__(256) void assign_finalize_kernel(const unsigned long long* __restrict__ best,
-                                                              const uint64_t* __restrict__ tomb, uint32_t n_rows,
-                                                              const uint32_t* prev, uint32_t* labels, float* __restrict__ dist,
-                                                              unsigned long long* __restrict__ changed) {
+static __global__ __launch_bounds__(256) void assign_finalize_kernel(const unsigned long long* __restrict__ best,
+                                                                     const uint64_t* __restrict__ tomb, uint32_t n_rows,
+                                                                     const uint32_t* prev, uint32_t* labels, float* __restrict__ dist,
+                                                                     unsigned long long* __restrict__ changed) {
     const uint32_t r = blockIdx.x * 256 + threadIdx.x;
     bool diff = false;
     if (r < n_rows) {
@@ -226,8 +228,8 @@ __device__ __forceinline__ uint32_t km_bucket(const uint32_t* __restrict__ label
 }
 
 // wave w of the grid owns rows [w * chunk, (w + 1) * chunk) and the counters hist[w][0 .. C]
-__global__ __launch_bounds__(256) void km_hist_kernel(const uint32_t* __restrict__ labels, const float* __restrict__ dist,
-                                                      uint32_t n_rows, uint32_t C, uint32_t chunk, uint32_t* __restrict__ hist) {
+static __global__ __launch_bounds__(256) void km_hist_kernel(const uint32_t* __restrict__ labels, const float* __restrict__ dist,
+                                                             uint32_t n_rows, uint32_t C, uint32_t chunk, uint32_t* __restrict__ hist) {
     const uint32_t w = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
     const uint64_t lo = (uint64_t)w * chunk, hi = lo + chunk < n_rows ? lo + chunk : n_rows;
     uint32_t* h = hist + (size_t)w * (C + 1);
@@ -235,7 +237,8 @@ __global__ __launch_bounds__(256) void km_hist_kernel(const uint32_t* __restrict
 }
 
 // per bucket: hist[w][c] -> the number of members in the chunks before w; total[c] = all of them
-__global__ __launch_bounds__(256) void km_scan_kernel(uint32_t* __restrict__ hist, uint32_t n_waves, uint32_t C, uint32_t* __restrict__ total) {
+static __global__ __launch_bounds__(256) void km_scan_kernel(uint32_t* __restrict__ hist, uint32_t n_waves, uint32_t C,
+                                                             uint32_t* __restrict__ total) {
     const uint32_t c = blockIdx.x * 256 + threadIdx.x;
     if (c > C) return;
     uint32_t run = 0;
@@ -249,8 +252,8 @@ __global__ __launch_bounds__(256) void km_scan_kernel(uint32_t* __restrict__ his
 
 // one workgroup: start[c] = members in the buckets before c (start[C + 1] = all rows), seg[c] = segments of the clusters
 // before c (seg[C] = all segments; the bucket C has none)
-__global__ __launch_bounds__(1024) void km_offsets_kernel(const uint32_t* __restrict__ total, uint32_t C, uint32_t* __restrict__ start,
-                                                          uint32_t* __restrict__ seg) {
+static __global__ __launch_bounds__(1024) void km_offsets_kernel(const uint32_t* __restrict__ total, uint32_t C, uint32_t* __restrict__ start,
+                                                                 uint32_t* __restrict__ seg) {
     __shared__ uint32_t s_rows[1024], s_segs[1024];
     const uint32_t n = C + 1, per = (n + 1023) / 1024, t = threadIdx.x;
     const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
@@ -275,9 +278,9 @@ __global__ __launch_bounds__(1024) void km_offsets_kernel(const uint32_t* __rest
 
 // the stable placement: wave w walks its rows 64 at a time in order; the lanes of one bucket take consecutive slots in
 // lane order.  Lane 0 alone reads and advances the wave's counters (one thread, program order).
-__global__ __launch_bounds__(256) void km_place_kernel(const uint32_t* __restrict__ labels, const float* __restrict__ dist,
-                                                       uint32_t n_rows, uint32_t C, uint32_t chunk, uint32_t* hist,
-                                                       const uint32_t* __restrict__ start, uint32_t* __restrict__ sorted) {
+static __global__ __launch_bounds__(256) void km_place_kernel(const uint32_t* __restrict__ labels, const float* __restrict__ dist,
+                                                              uint32_t n_rows, uint32_t C, uint32_t chunk, uint32_t* hist,
+                                                              const uint32_t* __restrict__ start, uint32_t* __restrict__ sorted) {
     const uint32_t w = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
     const uint64_t lo = (uint64_t)w * chunk, hi = lo + chunk < n_rows ? lo + chunk : n_rows;
     uint32_t* h = hist + (size_t)w * (C + 1);
@@ -343,9 +346,9 @@ __global__ __launch_bounds__(256) void km_sum_kernel(const float* __restrict__ t
 }
 
 // thread (c, j): the cluster's segments in order, divided by its size; an empty cluster keeps its centroid
-__global__ __launch_bounds__(256) void km_centroid_kernel(const float* __restrict__ part, const uint32_t* __restrict__ total,
-                                                          const uint32_t* __restrict__ seg, uint32_t C, uint32_t dim,
-                                                          float* __restrict__ centroids) {
+static __global__ __launch_bounds__(256) void km_centroid_kernel(const float* __restrict__ part, const uint32_t* __restrict__ total,
+                                                                 const uint32_t* __restrict__ seg, uint32_t C, uint32_t dim,
+                                                                 float* __restrict__ centroids) {
     const uint64_t at = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (at >= (uint64_t)C * dim) return;
     const uint32_t c = (uint32_t)(at / dim), j = (uint32_t)(at % dim);

@@ -224,6 +224,8 @@ struct mi_knn {
     int many_segments = 0, many_sample = 0;
     // mi_knn_kmeans_seed (kmeans_seed.hip): {candidates, passes run, fallback picks, 0} of the last call
     uint64_t kmeans_seed_stats[4] = {0, 0, 0, 0};
+    // mi_knn_summarize (summary.hip): {segments summed, workgroups of the distance pass, rows read by it, 0} of the last call
+    uint64_t summarize_stats[4] = {0, 0, 0, 0};
     // mi_knn_search_diverse (diverse.hip): {pool entries P, candidate pairs, conflicting pairs, pool entries hidden} of the last call
     uint64_t diverse_stats[4] = {0, 0, 0, 0};
     // mi_knn_search_compound (compound.hip): {rows or list entries scanned, rows excluded by a negative term, rows with a NaN

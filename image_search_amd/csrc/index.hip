@@ -30,6 +30,7 @@
 #include "grouped_host.h"
 #include "handles.h"
 #include "ordered_host.h"
+#include "summary_host.h"
 #include "where_host.h"
 
 using namespace mi;
@@ -436,6 +437,39 @@ int mi_index_group_of(mi_index* ix, const char* folder, uint32_t* group) {
         auto it = ix->dirs.ids.find(grouped_dir_of(dir + "x"));
         if (it == ix->dirs.ids.end()) fail(MI_ERR_INVALID, "no image was stored under '%s'", folder);
         *group = it->second;
+    });
+}
+
+// the folders at a glance: the table's column brought up to date, then mi_knn_summarize over it (labels = NULL) with one group
+// per directory; results land in buffers of the call, the first min(cap, directories) entries reach the caller
+int mi_index_folder_overview(mi_index* ix, uint32_t cap, uint64_t* count, uint64_t* cover, float* cover_dist, uint64_t* odd,
+                             float* odd_dist, uint64_t* measured, uint64_t* spread, uint32_t* n_groups) {
+    return guarded([&] {
+        if (!ix || !n_groups) fail(MI_ERR_INVALID, "null argument");
+        size_t n_dirs = 0;
+        {
+            std::lock_guard<std::mutex> l(ix->mu);
+            n_dirs = ix->dirs.names.size();
+            if (n_dirs > SUMMARY_MAX_C) fail(MI_ERR_UNSUPPORTED, "%zu directories: a summary holds at most %u groups", n_dirs, SUMMARY_MAX_C);
+            if (n_dirs) sync_groups(ix);
+        }
+        if (n_dirs == 0) { *n_groups = 0; return; }
+        const uint32_t C = (uint32_t)n_dirs;
+        std::vector<uint64_t> u64((size_t)C * 5);
+        std::vector<float> f32((size_t)C * 2);
+        uint64_t *h_count = u64.data(), *h_cover = h_count + C, *h_odd = h_cover + C, *h_measured = h_odd + C, *h_spread = h_measured + C;
+        const int e = mi_knn_summarize(ix->table, nullptr, C, nullptr, h_count, h_cover, f32.data(), h_odd, f32.data() + C, h_measured,
+                                       h_spread, nullptr, nullptr);
+        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        const size_t n = std::min<size_t>(cap, C);
+        if (count) std::copy(h_count, h_count + n, count);
+        if (cover) std::copy(h_cover, h_cover + n, cover);
+        if (cover_dist) std::copy(f32.data(), f32.data() + n, cover_dist);
+        if (odd) std::copy(h_odd, h_odd + n, odd);
+        if (odd_dist) std::copy(f32.data() + C, f32.data() + C + n, odd_dist);
+        if (measured) std::copy(h_measured, h_measured + n, measured);
+        if (spread) std::copy(h_spread, h_spread + n, spread);
+        *n_groups = C;
     });
 }
 

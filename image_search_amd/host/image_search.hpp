@@ -339,6 +339,33 @@ class EmbeddingTable {
     }
     // {candidates, passes run, fallback picks, 0} of the last kmeans_seed
     std::vector<uint64_t> kmeans_seed_stats() const { std::vector<uint64_t> v(4); check(mi_knn_kmeans_seed_stats(h_, v.data())); return v; }
+    // what every group looks like (mi_knn_summarize).  labels: one per local row (kmeans / assign labels, dbscan's dense labels,
+    // anything; a value >= C belongs to nothing), nullptr: the table's group column.  centroids [C * dim] = the mean of x / |x|
+    // over a group's members, bit-identical to kmeans' update; cover / odd = the ids of the member nearest to the centroid (the
+    // group's exact medoid for unit vectors) and of the farthest, MI_KNN_NO_ID / +inf where there is none; spread = the measured
+    // members' distances summed as integers of 2^-30; dist [rows] = a member's distance to its centroid with assign's bits;
+    // totals = {members, live rows with a label >= C, unusable live rows with a label < C, non-empty groups}
+    struct Summary {
+        std::vector<float> centroids, cover_dist, odd_dist, dist;
+        std::vector<uint64_t> count, cover, odd, measured, spread;
+        uint64_t totals[4] = {0, 0, 0, 0};
+        double mean_dist(uint32_t c) const { return measured[c] ? std::ldexp((double)spread[c] / (double)measured[c], -30) : NAN; }
+    };
+    Summary summarize(const std::vector<uint32_t>* labels, uint32_t C) const {
+        uint64_t n = 0;
+        check(mi_knn_size(h_, &n));
+        if (labels && labels->size() != n) throw std::invalid_argument("summarize: one label per row");
+        Summary r;
+        r.centroids.resize((size_t)C * dim_); r.cover_dist.resize(C); r.odd_dist.resize(C); r.dist.resize(n + 1);   // (+ 1: never a null pointer)
+        r.count.resize(C); r.cover.resize(C); r.odd.resize(C); r.measured.resize(C); r.spread.resize(C);
+        check(mi_knn_summarize(h_, labels && n ? labels->data() : nullptr, C, r.centroids.data(), r.count.data(), r.cover.data(),
+                               r.cover_dist.data(), r.odd.data(), r.odd_dist.data(), r.measured.data(), r.spread.data(), r.dist.data(),
+                               r.totals));
+        r.dist.resize(n);
+        return r;
+    }
+    // {segments summed, workgroups of the distance pass, rows read by it, 0} of the last summarize
+    std::vector<uint64_t> summarize_stats() const { std::vector<uint64_t> v(4); check(mi_knn_summarize_stats(h_, v.data())); return v; }
     // the k best DISTINCT results (mi_knn_search_diverse): the first `pool` results of knn(query) walked in order, an entry
     // within cosine distance min_gap of an earlier kept one hidden behind it.  idx / dist / hidden [k] (padding MI_KNN_NO_ID /
     // +inf / 0 behind n_kept), rep [pool]: per pool rank its slot, MI_KNN_NO_LABEL when left over.  pool = 0: min(4096, max(4 k, 64))
@@ -699,6 +726,35 @@ class ImageIndex {
         for (const auto& g : groups) {
             out.emplace_back();
             for (uint64_t id : g) out.back().push_back(path(id, web));
+        }
+        return out;
+    }
+    // the folders at a glance (mi_index_folder_overview): per directory that holds an image its name, how many images, the
+    // cover (the image nearest to the folder's centroid: its medoid) and the odd one out (the farthest; empty when no distance
+    // is a number) as paths with their distances, and the mean distance; the largest folder first
+    struct FolderOverview { std::string folder, cover, odd_one_out; uint64_t images = 0; float cover_dist = INFINITY, odd_dist = INFINITY; double mean_dist = NAN; };
+    std::vector<FolderOverview> folder_overview(bool web = false) const {
+        uint32_t C = 0;
+        check(mi_index_group_count(h_, &C));
+        std::vector<uint64_t> count(C + 1), cover(C + 1), odd(C + 1), measured(C + 1), spread(C + 1);
+        std::vector<float> cover_dist(C + 1), odd_dist(C + 1);
+        uint32_t n = 0;
+        check(mi_index_folder_overview(h_, C, count.data(), cover.data(), cover_dist.data(), odd.data(), odd_dist.data(), measured.data(),
+                                       spread.data(), &n));
+        std::vector<uint32_t> order;
+        for (uint32_t g = 0; g < std::min(C, n); ++g) if (count[g]) order.push_back(g);
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return count[x] > count[y]; });
+        std::vector<FolderOverview> out;
+        for (uint32_t g : order) {
+            FolderOverview o;
+            o.folder = group_name(g, web);
+            o.images = count[g];
+            o.cover = path(cover[g], web);
+            o.cover_dist = cover_dist[g];
+            if (odd[g] != MI_KNN_NO_ID) o.odd_one_out = path(odd[g], web);
+            o.odd_dist = odd_dist[g];
+            if (measured[g]) o.mean_dist = std::ldexp((double)spread[g] / (double)measured[g], -30);
+            out.push_back(o);
         }
         return out;
     }

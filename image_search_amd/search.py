@@ -689,6 +689,74 @@ class EmbeddingTable:
         return {"centroids": cent, "labels": labels, "dist": dist, "iters": iters.value, "changed": changed.value,
                 "objective": obj.value}
 
+    def summarize(self, labels=None, n_groups: Optional[int] = None) -> dict:
+        """What every group looks like (mi_knn_summarize).  labels: one per local row (kmeans / assign labels, dbscan's dense
+        labels with -1 for noise, duplicate components, anything; NO_LABEL or any value >= n_groups = belongs to nothing), or
+        None: the table's group column, read on the device.  n_groups defaults to the largest label that is not NO_LABEL,
+        plus one, or to groups_info()["n_groups"].  A member is a live row with a label < n_groups whose distance to itself
+        is a number.  Returns dict(centroids [C, dim] = the mean of x / |x| over the members, summed in kmeans' order and
+        bit-identical to its update; count [C]; cover / cover_dist [C] = the member nearest to the centroid (the group's exact
+        medoid for unit vectors), NO_ID / +inf for an empty group; odd / odd_dist [C] = the farthest member; measured [C] =
+        members with a non-NaN distance; spread [C] = their distances summed as integers of 2^-30; mean_dist [C] float64 =
+        spread / measured * 2^-30, NaN where nothing was measured; dist [rows] = a member's distance to its centroid with
+        assign's bits, NaN for an unusable row of a group, +inf otherwise; totals {"members", "outside", "unusable",
+        "groups"}).  cover and odd are ids; every array indexed by row is indexed by local row."""
+        n = len(self)
+        lab = None
+        if labels is not None:
+            lab = np.ascontiguousarray(np.asarray(labels).reshape(-1).astype(np.uint32))
+            if lab.size != n:
+                raise ValueError(f"{lab.size} labels for {n} rows")
+            if n_groups is None:
+                has = lab[lab != NO_LABEL]
+                n_groups = int(has.max()) + 1 if has.size else 1
+        elif n_groups is None:
+            n_groups = max(int(self.groups_info()["n_groups"]), 1)
+        C = int(n_groups)
+        m = max(C, 0)
+        cent = np.empty((m, self.dim), np.float32)
+        count, cover, odd, measured, spread = (np.empty(m, np.uint64) for _ in range(5))
+        cover_dist, odd_dist, dist = np.empty(m, np.float32), np.empty(m, np.float32), np.empty(n, np.float32)
+        totals = np.zeros(4, np.uint64)
+        check(lib().mi_knn_summarize(self._h, lab.ctypes.data if lab is not None and n else None, C, cent.ctypes.data, count.ctypes.data,
+                                     cover.ctypes.data, cover_dist.ctypes.data, odd.ctypes.data, odd_dist.ctypes.data,
+                                     measured.ctypes.data, spread.ctypes.data, dist.ctypes.data if n else None, totals.ctypes.data))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = np.where(measured > 0, spread.astype(np.float64) / measured.astype(np.float64) * 2.0 ** -30, np.nan)
+        return {"centroids": cent, "count": count, "cover": cover, "cover_dist": cover_dist, "odd": odd, "odd_dist": odd_dist,
+                "measured": measured, "spread": spread, "mean_dist": mean, "dist": dist,
+                "totals": dict(zip(("members", "outside", "unusable", "groups"), (int(v) for v in totals)))}
+
+    def summarize_stats(self) -> dict:
+        """mi_knn_summarize_stats, of the last summarize on this table"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_summarize_stats(self._h, out))
+        return {"segments": out[0], "workgroups": out[1], "rows": out[2]}
+
+
+def dist_keys(dist) -> np.ndarray:
+    """the search's 32-bit order of distances: ascending with the distance, -0 in front of +0, every NaN last"""
+    d = np.ascontiguousarray(np.asarray(dist, np.float32).reshape(-1))
+    b = d.view(np.uint32)
+    key = np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+    key[np.isnan(d)] = np.uint32(0xFFFFFFFF)
+    return key
+
+
+def typical_order(labels, dist, n_groups: Optional[int] = None) -> list:
+    """"Most typical first": labels [rows] and the dist [rows] summarize returned -> per group 0 .. C - 1 its members' local rows
+    ordered by (distance key, row): the cover first, NaN distances last.  Rows whose dist is +inf (no member: deleted,
+    unlabelled) are left out."""
+    lab = np.asarray(labels).reshape(-1).astype(np.uint32)
+    d = np.asarray(dist, np.float32).reshape(-1)
+    if n_groups is None:
+        has = lab[lab != NO_LABEL]
+        n_groups = int(has.max()) + 1 if has.size else 0
+    rows = np.flatnonzero((lab < n_groups) & ~np.isposinf(d))
+    order = rows[np.lexsort((rows, dist_keys(d[rows]), lab[rows]))]
+    cuts = np.searchsorted(lab[order], np.arange(n_groups + 1))
+    return [order[cuts[c]:cuts[c + 1]] for c in range(n_groups)]
+
 
 def drop_self(idx: np.ndarray, dist: np.ndarray, self_ids) -> tuple:
     """knn_many(rows, k + 1) -> the k nearest OTHER rows: from row i of idx / dist [n, k + 1] the entry whose id is
@@ -1648,6 +1716,55 @@ class ImageIndex:
         res = self.table.kmeans(int(k), max_iters=max_iters, seed=seed, init=init, sample=sample)
         rows = [r for r in range(res["labels"].size) if res["labels"][r] != NO_LABEL]
         return clusters_of(res["labels"][rows], [self.path(r, web=web) for r in rows])
+
+    def _overview(self, res: dict, names, web: bool) -> list:
+        out = []
+        for g in sorted(range(len(names)), key=lambda c: (-int(res["count"][c]), c)):
+            if int(res["count"][g]) == 0:
+                continue
+            cover, odd = int(res["cover"][g]), int(res["odd"][g])
+            mean = float(res["mean_dist"][g])
+            out.append({"group": names[g], "images": int(res["count"][g]), "cover": self.path(cover, web=web),
+                        "cover_dist": float(res["cover_dist"][g]), "odd_one_out": None if odd == int(NO_ID) else self.path(odd, web=web),
+                        "odd_dist": float(res["odd_dist"][g]), "mean_dist": mean})
+        return out
+
+    def folder_overview(self, web: bool = False) -> list:
+        """The folders at a glance (mi_index_folder_overview): per directory that holds an image {folder, images, cover,
+        cover_dist, odd_one_out, odd_dist, mean_dist}, the largest first, equal sizes by directory id.  cover = the image
+        nearest to the folder's centroid (its medoid), odd_one_out = the farthest; removed paths count nowhere."""
+        C = self.group_count()
+        n = ctypes.c_uint32()
+        count, cover, odd, measured, spread = (np.empty(C, np.uint64) for _ in range(5))
+        cover_dist, odd_dist = np.empty(C, np.float32), np.empty(C, np.float32)
+        check(lib().mi_index_folder_overview(self._h, C, count.ctypes.data, cover.ctypes.data, cover_dist.ctypes.data, odd.ctypes.data,
+                                             odd_dist.ctypes.data, measured.ctypes.data, spread.ctypes.data, ctypes.byref(n)))
+        C = min(C, n.value)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = np.where(measured > 0, spread.astype(np.float64) / measured.astype(np.float64) * 2.0 ** -30, np.nan)
+        res = {"count": count[:C], "cover": cover, "cover_dist": cover_dist, "odd": odd, "odd_dist": odd_dist, "mean_dist": mean}
+        out = self._overview(res, [self.group_name(g, web=web) for g in range(C)], web)
+        for o in out:
+            o["folder"] = o.pop("group")
+        return out
+
+    def cluster_overview(self, k: int, max_iters: int = 20, seed: int = 0, web: bool = False, init: str = "uniform",
+                         sample: Optional[int] = None) -> list:
+        """"Group my library into k themes and show me each": EmbeddingTable.kmeans, then summarize over its labels — per
+        non-empty cluster {group (the label), images, cover, cover_dist, odd_one_out, odd_dist, mean_dist}, largest first."""
+        res = self.table.kmeans(int(k), max_iters=max_iters, seed=seed, init=init, sample=sample)
+        C = res["centroids"].shape[0]
+        return self._overview(self.table.summarize(res["labels"], C), list(range(C)), web)
+
+    def theme_overview(self, max_dist: float, min_pts: int = 5, web: bool = False) -> list:
+        """The themes that are really there, each with its cover (EmbeddingTable.dbscan, its dense labels, then summarize):
+        per theme {group (the dense label), images, cover, cover_dist, odd_one_out, odd_dist, mean_dist}, largest first.
+        Noise belongs to no theme."""
+        labels = self.table.dbscan(max_dist, min_pts)["labels"]
+        C = int(labels.max()) + 1 if labels.size and labels.max() >= 0 else 0
+        if C == 0:
+            return []
+        return self._overview(self.table.summarize(labels.astype(np.uint32), C), list(range(C)), web)
 
     def save(self, directory: str):
         check(lib().mi_index_save(self._h, directory.encode()))

@@ -506,6 +506,43 @@ int mi_knn_kmeans_seed(mi_knn* t, uint32_t C, uint64_t seed, const uint64_t* amo
 /* of the last mi_knn_kmeans_seed on this handle: out = {candidates S, passes over the candidates (the usable pass and one per
  * seed: C + 1), fallback picks, 0} */
 int mi_knn_kmeans_seed_stats(mi_knn* t, uint64_t out[4]);
+/* What a group looks like once it exists ("your 40 themes", "your folders"): per group its centroid, its cover picture, the
+ * picture that does not belong and how tight it is — for ANY grouping: mi_knn_kmeans / mi_knn_assign labels, mi_knn_dbscan themes
+ * (dense labels), mi_pairs_to_groups components, the index's directories or a caller's own column.  labels: [rows] by local row
+ * (rows = mi_knn_size, deleted rows counted), as mi_knn_assign's arrays are, or NULL: the table's group column
+ * (mi_knn_set_groups), read where it lies.  Ids go through the table's base / block-cyclic map, as mi_knn_dbscan's do.
+ *   member of c   a live row with label c < C that is usable: mi_knn_search(q = the row) reports a non-NaN distance for the row
+ *                 itself (mi_knn_kmeans_seed's "usable").  A label >= C (MI_KNN_NO_LABEL, MI_KNN_NO_GROUP) belongs to nothing.
+ *   count[c]      the number of members.
+ *   centroid[c]   S / count[c], S = the sum of x / |x| over the members in exactly the order of mi_knn_kmeans' update (members
+ *                 ascending by row, fixed segments, segments in order): bit-identical to that update.  All zeros if empty.
+ *   dist[r]       a member: the distance mi_knn_search over a table holding the C centroids under ids 0 .. C-1 reports with
+ *                 q = row r for entry label[r], to the bit (mi_knn_assign's arithmetic); NaN for an unusable live row with a
+ *                 label < C; +inf for every other row.
+ *   cover[c]      the member with the smallest (32-bit distance key, id) — NaN sorts last, -0 before +0, among equal keys the
+ *                 lowest id; cover_dist[c] its distance.  Empty group: MI_KNN_NO_ID, +inf.  For unit vectors
+ *                 sum_j (1 - x_i . x_j) = n - x_i . S, so the member nearest to the centroid is the group's exact medoid (the
+ *                 smallest total cosine distance to the other members) in real arithmetic.
+ *   odd[c]        the member with the largest key among those whose distance is not NaN, the lowest id among equal keys;
+ *                 odd_dist[c] its distance.  None: MI_KNN_NO_ID, +inf.
+ *   measured[c]   the members whose distance is not NaN.
+ *   spread[c]     the sum over those of w(d) = floor(min(max(d, 0), 2) * 2^30), exact in uint64 (mi_knn_kmeans_seed's weight):
+ *                 the mean distance is spread / measured * 2^-30.
+ *   totals        {members, live rows with a label >= C, unusable live rows with a label < C, non-empty groups}.
+ * centroids: [C][dim]; count, cover, cover_dist, odd, odd_dist, measured, spread: [C] each; dist: [rows]; every output pointer
+ * may be NULL.  1 <= C <= 65536 (MI_ERR_UNSUPPORTED above, MI_ERR_INVALID for 0 or a null handle).  labels == NULL on a table
+ * whose group column was never set is valid: every row belongs to nothing.  dim as mi_knn_near_pairs requires.  An empty table
+ * succeeds with zero counts and the padding above.  An argument error writes nothing.  The call reads the fp32 rows only: the
+ * result does not depend on "prefilter".  Every per-group value except the centroid is an integer min, max or sum and the
+ * centroid's order is fixed by the row ids: the same table and labels give the same bits on every call.  Two reads of the
+ * member rows; device memory beside the outputs: 8 bytes per row, the k-means update's buffers and 32 bytes per group, freed
+ * before the call returns.  Runs on the handle's stream behind every write and search enqueued before it, and waits for its
+ * results. */
+int mi_knn_summarize(mi_knn* t, const uint32_t* labels /* [rows] or NULL */, uint32_t C, float* centroids, uint64_t* count,
+                     uint64_t* cover, float* cover_dist, uint64_t* odd, float* odd_dist, uint64_t* measured, uint64_t* spread,
+                     float* dist, uint64_t totals[4]);
+/* of the last mi_knn_summarize on this handle: out = {segments summed, workgroups of the distance pass, rows read by it, 0} */
+int mi_knn_summarize_stats(mi_knn* t, uint64_t out[4]);
 /* The k best DISTINCT results of a search ("the grid without the same shot ten times"): the search's own list with
  * near-duplicates collapsed behind the best of them, greedily, and how many look-alikes stand behind each kept result.
  *   pool        L = the result of mi_knn_search(t, q, 1, pool) when among == NULL, else of mi_knn_search_filtered(t, q, 1,
@@ -1084,6 +1121,13 @@ int mi_index_matches(mi_index* ix, mi_index* other, float max_dist, uint64_t* a,
  * their smallest id, ids ascending inside; noise is not listed, *n_noise counts it; removed paths are in neither. */
 int mi_index_themes(mi_index* ix, float max_dist, uint32_t min_pts, uint64_t* ids, uint64_t cap_ids, uint64_t* group_start,
                     uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups, uint64_t* n_noise);
+/* The folders at a glance (mi_knn_summarize over the directory groups of mi_index_search_grouped): for directory g <
+ * min(cap, *n_groups) its number of images count[g], its cover and odd one out (row ids: mi_index_path names them) with their
+ * distances to the folder's centroid, measured[g] and spread[g] as mi_knn_summarize defines them.  Removed paths are deleted
+ * rows: they count nowhere.  Every array may be NULL; *n_groups = the directories seen so far (mi_index_group_name names them).
+ * More than 65536 directories: MI_ERR_UNSUPPORTED.  An index without a row succeeds with *n_groups = 0. */
+int mi_index_folder_overview(mi_index* ix, uint32_t cap, uint64_t* count, uint64_t* cover, float* cover_dist, uint64_t* odd,
+                             float* odd_dist, uint64_t* measured, uint64_t* spread, uint32_t* n_groups);
 
 /* ------------------------------------------------------------ query refinement */
 
