@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void density_count_kernel(const float* __restr
 }
 
 // one workgroup per 128-row block: act[block] = (some deg > 0) | (some core) << 1; parent[r] = r; bkey[r] = ~0
-__global__ __launch_bounds__(TILE) void density_blocks_kernel(const uint32_t* __restrict__ deg, const uint64_t* __restrict__ tomb,
+static __global__ __launch_bounds__(TILE) void density_blocks_kernel(const uint32_t* __restrict__ deg, const uint64_t* __restrict__ tomb,
                                                               uint32_t n_rows, uint32_t min_pts, uint32_t* __restrict__ parent,
                                                               unsigned long long* __restrict__ bkey, uint8_t* __restrict__ act) {
     __shared__ uint32_t bits;
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(256) void density_link_kernel(const float* __restri
 }
 
 // pass 3: per row, what the contract names (mi355clip.h).  via / via_dist may be null; counts are deg as it stands.
-__global__ __launch_bounds__(256) void density_finish_kernel(const uint32_t* __restrict__ deg, const uint32_t* __restrict__ parent,
+static __global__ __launch_bounds__(256) void density_finish_kernel(const uint32_t* __restrict__ deg, const uint32_t* __restrict__ parent,
                                                              const unsigned long long* __restrict__ bkey,
                                                              const uint64_t* __restrict__ tomb, uint32_t n_rows, uint32_t min_pts,
                                                              IdMap map, uint64_t* __restrict__ cluster, uint64_t* __restrict__ via,

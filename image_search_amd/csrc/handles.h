@@ -330,6 +330,7 @@ struct mi_knn_sharded {
     uint64_t generation = 0;                  // of the files last saved or loaded (mi_knn_sharded_save)
     std::vector<hipEvent_t> ev_src;           // [device ordinal]: the peer copies of the last append_device from that device
     uint64_t join_stats[4] = {0, 0, 0, 0};    // mi_knn_sharded_near_pairs_stats: summed over every shard and shard pair of the last call
+    uint64_t dbscan_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // mi_knn_sharded_dbscan_stats: mi_knn::dbscan_stats summed the same way, plus the forest merge
     std::mutex mu;
     uint32_t n() const { return (uint32_t)shard.size(); }
 };

@@ -2,11 +2,9 @@
 // mi_index_matches).  The kernels: join_between_kernels.h; the rules without HIP in them: join_between_host.h.
 //
 // One primitive (join_between) joins table A, the row side, on whose device and stream the work runs, with table B, the column
-// side.  B is a sequence of column chunks, each described by pointers that are valid on A's device: B's own mirror, rows and
-// deletion bits when it lives there, or a staged copy — the fp32 rows of chunk [c0, c1) copied into the call's
-// scratch (device to device, or peer to peer from another GPU), mirrored there with knn_mirror_kernel, its deletion words
-// built from B's host list.  Strips of tile rows, the candidate buffer, the halving after an overflow (rect_stages) and the
-// early stop behind user_cap are the self-join's (join.hip).
+// side.  B is a sequence of column chunks, direct or staged, walked in strips of tile rows: join_between_walk.h, which the
+// density passes across shards (density_sharded.hip) share.  The candidate buffer, the halving after an overflow (rect_stages)
+// and the early stop behind user_cap are the self-join's (join.hip).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -21,6 +19,7 @@
 #include "handles.h"
 #include "join_between_host.h"
 #include "join_between_kernels.h"
+#include "join_between_walk.h"
 #include "two_stage.h"
 
 using namespace mi;
@@ -28,15 +27,6 @@ using namespace mi;
 static_assert(BETWEEN_TILE == (uint32_t)TILE, "join_between_host.h counts the tiles of tile128.h");
 
 namespace {
-
-// one column chunk as stage 1 and stage 2 see it: n rows that start at B's local row `off`; fn: the bound on its own rows
-struct ColChunk {
-    const uint16_t* mirror;
-    const float* xx;
-    const uint64_t* tomb;
-    const float* rows;
-    uint32_t n, off, fn;
-};
 
 struct Cross {
     mi_knn* a;
@@ -102,22 +92,12 @@ struct Cross {
         rect_stages(br0, br1, bc0, bc1, cand_cap, overflowed, stage1, stage2);
     }
 
-    // the chunk in `col` against all of A: the rectangles (fn_a, col.fn) leave, in strips of tile rows
+    // the chunk in `col` against all of A
     template <int NCH>
     void run_chunk() {
-        TileRect rects[2];
-        const uint32_t n_rects = between_rects(n_a, col.n, fn_a, col.fn, rects);
-        for (uint32_t i = 0; i < n_rects && !over; ++i) {
-            const TileRect& r = rects[i];
-            uint32_t strip = between_strip(r.c1 - r.c0);
-            for (uint32_t br = r.r0; br < r.r1 && !over;) {
-                const uint32_t end = std::min(r.r1, br + strip);
-                bool overflowed = false;
-                rect<NCH>(br, end, r.c0, r.c1, &overflowed);
-                if (overflowed) strip = std::max(1u, strip / 2);
-                br = end;
-            }
-        }
+        between_strips(n_a, col.n, fn_a, col.fn,
+                       [&](uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) { rect<NCH>(br0, br1, bc0, bc1, overflowed); },
+                       [&] { return over; });
     }
 };
 
@@ -159,56 +139,10 @@ void join_between(mi_knn* a, mi_knn* b, float max_dist, uint64_t fn_a, uint64_t 
     j.d_pairs = (uint2*)scratch.get((size_t)j.cand_cap * sizeof(uint2));
     j.d_dist = (float*)scratch.get((size_t)j.cand_cap * sizeof(float));
     j.d_count = (unsigned long long*)scratch.get(2 * sizeof(unsigned long long));
-    const uint64_t n_b = b->rows, bound_b = std::min<uint64_t>(fn_b, n_b);
-
-    // B in column chunks of whole tiles: what a staged chunk's scratch holds, and a block of columns whose mirror stays in the
-    // last-level cache while the row strips pass over it (a direct column side is cut the same way, by pointer)
-    const bool staged = b->device != a->device || a->join_stage;
-    const uint32_t chunk_rows = (uint32_t)std::min<uint64_t>(between_chunk_rows(a->dim, (uint32_t)a->join_stage_rows),
-                                                             (n_b + TILE - 1) / TILE * TILE);
-    const size_t words = (chunk_rows + 63) / 64;
-    TableMirror tb{nullptr, nullptr, nullptr};
-    float* st_rows = nullptr;
-    uint16_t* st_mirror = nullptr;
-    float* st_xx = nullptr;
-    uint64_t* st_tomb = nullptr;
-    std::vector<uint64_t> h_tomb;
-    if (!staged) {
-        tb = table_mirror(b, s, scratch);
-    } else {
-        st_rows = (float*)scratch.get((size_t)chunk_rows * a->dim * sizeof(float));
-        st_mirror = (uint16_t*)scratch.get((size_t)chunk_rows * a->dim * sizeof(uint16_t));
-        st_xx = (float*)scratch.get((size_t)chunk_rows * sizeof(float));
-        if (!b->dead.empty()) st_tomb = (uint64_t*)scratch.get(words * sizeof(uint64_t));
-    }
-    const uint32_t n_chunks = between_n_chunks(n_b, chunk_rows);
-    for (uint32_t ci = 0; ci < n_chunks && !j.over; ++ci) {
-        uint64_t c0, c1;
-        between_chunk(n_b, chunk_rows, ci, &c0, &c1);
-        const uint32_t cn = (uint32_t)(c1 - c0), cfn = between_chunk_bound(bound_b, c0, c1);
-        if (j.fn_a >= j.n_a && cfn >= cn) continue;   // nothing of this chunk qualifies
-        if (!staged) {
-            // direct: B where it lies (c0 is a multiple of 128: whole deletion words)
-            j.col = ColChunk{tb.mirror + c0 * a->dim, tb.xx + c0, tb.tomb ? tb.tomb + c0 / 64 : nullptr, b->table + c0 * a->dim, cn,
-                             (uint32_t)c0, cfn};
-        } else {
-            // staged: the chunk's fp32 rows into this call's scratch on A's device, mirrored there
-            const size_t bytes = (size_t)cn * a->dim * sizeof(float);
-            const float* src = b->table + c0 * a->dim;
-            if (b->device == a->device) HIP_CHECK(hipMemcpyAsync(st_rows, src, bytes, hipMemcpyDeviceToDevice, s));
-            else HIP_CHECK(hipMemcpyPeerAsync(st_rows, a->device, src, b->device, bytes, s));
-            mirror_rows(a, s, st_rows, 0, cn, st_mirror, st_xx);
-            const uint64_t* tomb = nullptr;
-            const auto d0 = std::lower_bound(b->dead.begin(), b->dead.end(), (uint32_t)c0);
-            const auto d1 = std::lower_bound(d0, b->dead.end(), (uint32_t)std::min<uint64_t>(c1, 0xFFFFFFFFull));
-            if (d0 != d1) {
-                h_tomb.assign(words, 0ull);
-                for (auto it = d0; it != d1; ++it) h_tomb[(*it - c0) >> 6] |= 1ull << ((*it - c0) & 63);
-                HIP_CHECK(hipMemcpyAsync(st_tomb, h_tomb.data(), words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-                tomb = st_tomb;
-            }
-            j.col = ColChunk{st_mirror, st_xx, tomb, st_rows, cn, (uint32_t)c0, cfn};
-        }
+    // B chunk by chunk (join_between_walk.h: direct or staged)
+    ColumnWalk walk(a, b, s, scratch);
+    for (uint32_t ci = 0; ci < walk.n_chunks && !j.over; ++ci) {
+        if (!walk.chunk(ci, j.n_a, j.fn_a, fn_b, &j.col)) continue;   // nothing of this chunk qualifies
         dispatch_nch(a->dim, [&](auto nch) { j.template run_chunk<decltype(nch)::value>(); });
         HIP_CHECK(hipStreamSynchronize(s));   // (staged: the scratch and h_tomb are free for the next chunk)
     }
@@ -322,28 +256,13 @@ int mi_knn_sharded_near_pairs(mi_knn_sharded* t, float max_dist, uint64_t first_
         // the shard pairs, round by round: the pairs of a round share no shard, each on a host thread of its own
         for (const std::vector<ShardPair>& round : between_schedule(S)) {
             if (over) break;
-            std::vector<int> codes(round.size(), MI_OK);
-            std::vector<std::string> msgs(round.size());
-            std::vector<std::thread> threads;
-            for (size_t pi = 0; pi < round.size(); ++pi) {
-                threads.emplace_back([&, pi] {
-                    const uint32_t ra = round[pi].first, cb = round[pi].second;
-                    try {
-                        std::vector<JoinPair> pairs;
-                        bool piece_over = false;
-                        uint64_t stats[4];
-                        join_between(t->shard[ra], t->shard[cb], max_dist, fn[ra], fn[cb], true, cap, &total, &pairs, stats, &piece_over);
-                        take(pairs, t->shard[ra], t->shard[cb], stats, piece_over);
-                    } catch (const Error& e) {
-                        codes[pi] = e.code; msgs[pi] = e.what();
-                    } catch (const std::exception& e) {
-                        codes[pi] = MI_ERR_INVALID; msgs[pi] = e.what();
-                    }
-                });
-            }
-            for (std::thread& th : threads) th.join();
-            for (size_t pi = 0; pi < round.size(); ++pi)
-                if (codes[pi] != MI_OK) fail(codes[pi], "shards %u x %u: %s", round[pi].first, round[pi].second, msgs[pi].c_str());
+            for_each_shard_pair(round, [&](uint32_t ra, uint32_t cb) {
+                std::vector<JoinPair> pairs;
+                bool piece_over = false;
+                uint64_t stats[4];
+                join_between(t->shard[ra], t->shard[cb], max_dist, fn[ra], fn[cb], true, cap, &total, &pairs, stats, &piece_over);
+                take(pairs, t->shard[ra], t->shard[cb], stats, piece_over);
+            });
         }
         if (over || res.size() > cap) fail_over(cap, max_dist, count);
         sort_pairs(&res);

@@ -7,6 +7,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "common.h"
@@ -160,6 +161,29 @@ void for_each_shard(mi_knn_sharded* t, F&& f) {
     for (std::thread& th : threads) th.join();
     for (uint32_t si = 0; si < n; ++si)
         if (codes[si] != MI_OK) fail(codes[si], "shard %u: %s", si, msgs[si].c_str());
+}
+
+// f(row shard, column shard) for every shard pair of one round of between_schedule (join_between_host.h: the pairs of a round
+// share no shard), each on a host thread of its own; the first pair that failed is reported.  t->mu held.
+template <class F>
+void for_each_shard_pair(const std::vector<std::pair<uint32_t, uint32_t>>& round, F&& f) {
+    std::vector<int> codes(round.size(), MI_OK);
+    std::vector<std::string> msgs(round.size());
+    std::vector<std::thread> threads;
+    for (size_t pi = 0; pi < round.size(); ++pi) {
+        threads.emplace_back([&, pi] {
+            try {
+                f(round[pi].first, round[pi].second);
+            } catch (const Error& e) {
+                codes[pi] = e.code; msgs[pi] = e.what();
+            } catch (const std::exception& e) {
+                codes[pi] = MI_ERR_INVALID; msgs[pi] = e.what();
+            }
+        });
+    }
+    for (std::thread& th : threads) th.join();
+    for (size_t pi = 0; pi < round.size(); ++pi)
+        if (codes[pi] != MI_OK) fail(codes[pi], "shards %u x %u: %s", round[pi].first, round[pi].second, msgs[pi].c_str());
 }
 
 }  // namespace mi

@@ -258,6 +258,11 @@ class EmbeddingTable {
         const uint64_t n = size();
         r.cluster.resize(n + 1); r.via.resize(n + 1); r.via_dist.resize(n + 1); r.counts.resize(n + 1);   // (+ 1: never a null pointer)
         check(mi_knn_dbscan(h_, max_dist, min_pts, r.cluster.data(), r.via.data(), r.via_dist.data(), r.counts.data(), r.summary));
+        dbscan_trim_and_label(r, n);
+        return r;
+    }
+    // the arrays cut back to n rows and the dense labels from the cluster ids (shared with ShardedTable::dbscan)
+    static void dbscan_trim_and_label(Dbscan& r, uint64_t n) {
         r.cluster.resize(n); r.via.resize(n); r.via_dist.resize(n); r.counts.resize(n);
         std::vector<uint64_t> names;
         for (uint64_t c : r.cluster) if (c != MI_KNN_NO_ID) names.push_back(c);
@@ -266,7 +271,6 @@ class EmbeddingTable {
         r.labels.assign(n, -1);
         for (uint64_t i = 0; i < n; ++i)
             if (r.cluster[i] != MI_KNN_NO_ID) r.labels[i] = (int64_t)(std::lower_bound(names.begin(), names.end(), r.cluster[i]) - names.begin());
-        return r;
     }
     // {candidates pass 1, pairs within, tiles pass 1, candidates pass 2, tiles visited pass 2, tiles skipped pass 2, unions that
     // merged, stage-1 launches} of the last neighbor_counts / dbscan
@@ -803,6 +807,25 @@ class ShardedTable {
     }
     // {candidate pairs, pairs accepted, stage-1 launches, tiles} of the last near_pairs, summed over shards and shard pairs
     std::vector<uint64_t> near_pairs_stats() const { std::vector<uint64_t> v(4); check(mi_knn_sharded_near_pairs_stats(h_, v.data())); return v; }
+    // EmbeddingTable::neighbor_counts over all shards (mi_knn_sharded_density): by global row id, pairs that cross shards counted
+    std::vector<uint32_t> neighbor_counts(float max_dist) const {
+        std::vector<uint32_t> counts(size() + 1);   // (+ 1: never a null pointer)
+        check(mi_knn_sharded_density(h_, max_dist, counts.data()));
+        counts.pop_back();
+        return counts;
+    }
+    // EmbeddingTable::dbscan over all shards (mi_knn_sharded_dbscan): arrays by global row id, bit for bit what one table
+    // holding the same rows returns
+    EmbeddingTable::Dbscan dbscan(float max_dist, uint32_t min_pts = 5) const {
+        EmbeddingTable::Dbscan r;
+        const uint64_t n = size();
+        r.cluster.resize(n + 1); r.via.resize(n + 1); r.via_dist.resize(n + 1); r.counts.resize(n + 1);
+        check(mi_knn_sharded_dbscan(h_, max_dist, min_pts, r.cluster.data(), r.via.data(), r.via_dist.data(), r.counts.data(), r.summary));
+        EmbeddingTable::dbscan_trim_and_label(r, n);
+        return r;
+    }
+    // mi_knn_dbscan_stats' eight fields of the last neighbor_counts / dbscan, summed over shards and shard pairs
+    std::vector<uint64_t> dbscan_stats() const { std::vector<uint64_t> v(8); check(mi_knn_sharded_dbscan_stats(h_, v.data())); return v; }
     // EmbeddingTable::assign_multi over all shards (mi_knn_sharded_assign_multi): labels / dist [rows * m] by global row id
     std::pair<std::vector<uint32_t>, std::vector<float>> assign_multi(const std::vector<float>& vectors, uint32_t C, uint32_t m,
                                                                       float max_dist = INFINITY) const {

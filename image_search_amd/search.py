@@ -1153,6 +1153,34 @@ class ShardedTable:
         check(lib().mi_knn_sharded_near_pairs_stats(self._h, out))
         return {"candidates": out[0], "pairs": out[1], "launches": out[2], "tiles": out[3]}
 
+    def neighbor_counts(self, max_dist: float) -> np.ndarray:
+        """EmbeddingTable.neighbor_counts over all shards (mi_knn_sharded_density): counts [rows] uint32 by global row id, the
+        pairs that cross shards counted; no pair list is built."""
+        counts = np.empty(len(self), np.uint32)
+        check(lib().mi_knn_sharded_density(self._h, float(max_dist), counts.ctypes.data))
+        return counts
+
+    def dbscan(self, max_dist: float, min_pts: int = 5) -> dict:
+        """EmbeddingTable.dbscan over all shards (mi_knn_sharded_dbscan): the same dict, arrays by global row id — bit for bit
+        what one table holding the same rows returns, whatever the shard count, block size or staging.  The pairs never leave
+        the devices; labels.astype(np.uint32) fits set_groups."""
+        n = len(self)
+        cluster, via = np.empty(n, np.uint64), np.empty(n, np.uint64)
+        via_dist, counts = np.empty(n, np.float32), np.empty(n, np.uint32)
+        summary = np.zeros(4, np.uint64)
+        check(lib().mi_knn_sharded_dbscan(self._h, float(max_dist), int(min_pts), cluster.ctypes.data, via.ctypes.data,
+                                          via_dist.ctypes.data, counts.ctypes.data, summary.ctypes.data))
+        return {"labels": dense_labels(cluster), "cluster": cluster, "via": via, "via_dist": via_dist, "counts": counts,
+                "summary": dict(zip(("clusters", "core", "border", "noise"), (int(v) for v in summary)))}
+
+    def dbscan_stats(self) -> dict:
+        """mi_knn_sharded_dbscan_stats: the last neighbor_counts / dbscan, summed over every shard and shard pair (unions_merged
+        also counts the final merge of the shards' forests)"""
+        out = (ctypes.c_uint64 * 8)()
+        check(lib().mi_knn_sharded_dbscan_stats(self._h, out))
+        return dict(zip(("candidates_pass1", "pairs", "tiles_pass1", "candidates_pass2", "tiles_visited", "tiles_skipped",
+                         "unions_merged", "launches"), (int(v) for v in out)))
+
     def duplicates(self, max_dist: float, first_new: int = 0, cap: int = 1 << 20) -> list:
         """Groups of near-duplicate rows: near_pairs through pairs_to_groups — lists of global ids chained by distances
         <= max_dist, ascending inside a group, the groups by their first id."""

@@ -915,6 +915,26 @@ int mi_knn_sharded_near_pairs(mi_knn_sharded* t, float max_dist, uint64_t first_
                               uint64_t cap, uint64_t* count);
 /* of the last mi_knn_sharded_near_pairs: {candidates, pairs, stage-1 launches, tiles} summed over every shard and shard pair */
 int mi_knn_sharded_near_pairs_stats(mi_knn_sharded* t, uint64_t out[4]);
+/* mi_knn_density / mi_knn_dbscan over the whole table: every definition there (deg, core, clusters, border, noise, via,
+ * via_dist, summary) applied to the pairs W that mi_knn_sharded_near_pairs(t, max_dist, first_new = 0) reports, with "row" read
+ * as global row — a cluster is named by the id of its smallest core row in the whole table, a border row joins the core that
+ * minimises (distance key, global row of the core) whichever shard that core lies in.  Arrays are [rows of the table], indexed
+ * by global row as mi_knn_sharded_assign's labels are.  The result equals, bit for bit, mi_knn_dbscan's for ONE table that
+ * holds the same rows, for any shard count, block size, chunking ("join_stage", "join_stage_rows") and arrival order: devices
+ * exchange degrees (summed), border keys (64-bit minima) and disjoint-set forests (united) through copies only, never through
+ * pointers or atomics across devices.  The pairs never leave the devices.  Memory per shard beside the join's buffers: 12 bytes
+ * per local row and 4 bytes per row of the WHOLE table (the shard's forest over global rows), plus one more such array on the
+ * first shard's device and the result arrays, freed before the call returns.
+ * The argument rules and errors are mi_knn_density's / mi_knn_dbscan's; a table without shards: MI_ERR_INVALID; 2^32 or more
+ * rows in the table: MI_ERR_UNSUPPORTED; dim as mi_knn_sharded_near_pairs requires.  An error writes nothing.  An empty
+ * table and empty shards are valid. */
+int mi_knn_sharded_density(mi_knn_sharded* t, float max_dist, uint32_t* counts);
+int mi_knn_sharded_dbscan(mi_knn_sharded* t, float max_dist, uint32_t min_pts, uint64_t* cluster, uint64_t* via, float* via_dist,
+                          uint32_t* counts, uint64_t summary[4]);
+/* of the last mi_knn_sharded_density / mi_knn_sharded_dbscan: the eight fields of mi_knn_dbscan_stats summed over every shard
+ * and shard pair.  "unions that merged" also counts the final merge of the shards' forests, so it is >= core rows - clusters
+ * (two shards may each merge the same two components). */
+int mi_knn_sharded_dbscan_stats(mi_knn_sharded* t, uint64_t out[8]);
 /* Change the layout of a LIVE table: every row of `src` into the empty `dst` (another shard count, device set or block
  * size), block by block, device to device — a plain copy where source and destination shard share a GPU,
  * hipMemcpyPeerAsync over xGMI where they do not; nothing passes through the host.  src is unchanged. */
