@@ -359,4 +359,102 @@ static __global__ __launch_bounds__(256) void km_centroid_kernel(const float* __
     centroids[at] = s / (float)n;
 }
 
+// ---- the same update on exact integer sums (option "kmeans_fixed_sum"; always across shards) ---------------------------
+// A member row r adds q = (|v| < 2) ? rint(v * 2^30) : 0 per component, v = x[r][j] * inv[r] (the float path's product;
+// the scaling is exact, the rounding to nearest even, a NaN or inf v fails the comparison), into a 64-bit sum: |q| < 2^31
+// and fewer than 2^32 members keep |S| < 2^63.  Integer sums are the same in any order, so the segments, the waves of a
+// segment and the shards of a table may be added as they come; centroid = (float)((double)S * 2^-30 / (double)n).  The
+// rules restated for the host: kmeans_fixed_host.h.
+__device__ __forceinline__ long long km_quant(float v) {
+    return fabsf(v) < 2.0f ? (long long)(int)rintf(v * 0x1p30f) : 0ll;   // |rint| <= 2^31 - 128: it fits 32 bits
+}
+
+// workgroup g = segment g, as in km_sum_kernel -> ipart[g][dim]; a thread keeps 4 * NT 64-bit sums
+template <int NCH>
+__global__ __launch_bounds__(256) void km_sum_fixed_kernel(const float* __restrict__ table, const float* __restrict__ inv,
+                                                           const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ start,
+                                                           const uint32_t* __restrict__ seg, uint32_t C, long long* __restrict__ ipart) {
+    constexpr int DIM = NCH * 64, NT = (DIM + 255) / 256;
+    __shared__ __attribute__((aligned(16))) long long sh[3][NT * 256];   // waves 1 .. 3; wave 0 adds from its registers
+    const uint32_t g = blockIdx.x;
+    if (g >= seg[C]) return;
+    uint32_t lo = 0, hi = C;   // the last c with seg[c] <= g
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (seg[mid] <= g) lo = mid; else hi = mid;
+    }
+    const uint32_t c = lo;
+    const uint32_t first = start[c] + (g - seg[c]) * KM_SEG;
+    const uint32_t n = min((uint32_t)KM_SEG, start[c + 1] - first);
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    long long acc[NT][4];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[t][e] = 0;
+#pragma unroll 4
+    for (uint32_t m = wib; m < n; m += 4) {
+        const uint32_t r = sorted[first + m];
+        const float s = inv[r];
+        const f32x4* p = reinterpret_cast<const f32x4*>(table + (uint64_t)r * DIM) + lane;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+            if (4 * lane + 256 * t < DIM) {
+                const f32x4 v = p[64 * t] * s;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[t][e] += km_quant(v[e]);
+            }
+    }
+    if (wib != 0) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sh[wib - 1][256 * t + 4 * lane + e] = acc[t][e];
+    }
+    __syncthreads();
+    if (wib == 0) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+            if (4 * lane + 256 * t < DIM) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int j = 256 * t + 4 * lane + e;
+                    ipart[(size_t)g * DIM + j] = acc[t][e] + sh[0][j] + sh[1][j] + sh[2][j];
+                }
+            }
+    }
+}
+
+// thread (c, j): S[c][j] = the cluster's segments added; thread (c, 0) writes n[c]
+static __global__ __launch_bounds__(256) void km_reduce_fixed_kernel(const long long* __restrict__ ipart, const uint32_t* __restrict__ total,
+                                                                     const uint32_t* __restrict__ seg, uint32_t C, uint32_t dim,
+                                                                     long long* __restrict__ S, uint32_t* __restrict__ cnt) {
+    const uint64_t at = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (at >= (uint64_t)C * dim) return;
+    const uint32_t c = (uint32_t)(at / dim), j = (uint32_t)(at % dim);
+    long long s = 0;
+    for (uint32_t g = seg[c]; g < seg[c + 1]; ++g) s += ipart[(size_t)g * dim + j];
+    S[at] = s;
+    if (j == 0) cnt[c] = total[c];
+}
+
+// another shard's sums and counts added into this one's: S[i] += S_in[i] for i < n_S, cnt[c] += cnt_in[c] for c < n_cnt
+static __global__ __launch_bounds__(256) void km_merge_fixed_kernel(long long* __restrict__ S, const long long* __restrict__ S_in, uint64_t n_S,
+                                                                    uint32_t* __restrict__ cnt, const uint32_t* __restrict__ cnt_in,
+                                                                    uint32_t n_cnt) {
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n_S; i += stride) S[i] += S_in[i];
+    for (uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x; c < n_cnt; c += stride) cnt[c] += cnt_in[c];
+}
+
+// thread (c, j): the sum as a double, scaled back and divided by the cluster's size; an empty cluster keeps its centroid
+static __global__ __launch_bounds__(256) void km_centroid_fixed_kernel(const long long* __restrict__ S, const uint32_t* __restrict__ cnt,
+                                                                       uint32_t C, uint32_t dim, float* __restrict__ centroids) {
+    const uint64_t at = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (at >= (uint64_t)C * dim) return;
+    const uint32_t n = cnt[at / dim];
+    if (n == 0) return;
+    centroids[at] = (float)((double)S[at] * 0x1p-30 / (double)n);
+}
+
 }  // namespace mi

@@ -224,6 +224,9 @@ struct mi_knn {
     int many_segments = 0, many_sample = 0;
     // mi_knn_kmeans_seed (kmeans_seed.hip): {candidates, passes run, fallback picks, 0} of the last call
     uint64_t kmeans_seed_stats[4] = {0, 0, 0, 0};
+    // the update of mi_knn_kmeans and the centroids of mi_knn_summarize on exact integer sums of 2^-30 instead of the float
+    // chains (option "kmeans_fixed_sum": 0 = the float sums; kmeans_update.h)
+    int kmeans_fixed_sum = 0;
     // mi_knn_summarize (summary.hip): {segments summed, workgroups of the distance pass, rows read by it, 0} of the last call
     uint64_t summarize_stats[4] = {0, 0, 0, 0};
     // mi_knn_search_diverse (diverse.hip): {pool entries P, candidate pairs, conflicting pairs, pool entries hidden} of the last call
@@ -331,6 +334,9 @@ struct mi_knn_sharded {
     std::vector<hipEvent_t> ev_src;           // [device ordinal]: the peer copies of the last append_device from that device
     uint64_t join_stats[4] = {0, 0, 0, 0};    // mi_knn_sharded_near_pairs_stats: summed over every shard and shard pair of the last call
     uint64_t dbscan_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // mi_knn_sharded_dbscan_stats: mi_knn::dbscan_stats summed the same way, plus the forest merge
+    // mi_knn_sharded_kmeans_stats: {updates run, bytes copied between shards, segments summed in the last update (all shards),
+    // merge launches} of the last call
+    uint64_t kmeans_stats[4] = {0, 0, 0, 0};
     std::mutex mu;
     uint32_t n() const { return (uint32_t)shard.size(); }
 };

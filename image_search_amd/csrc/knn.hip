@@ -1156,6 +1156,12 @@ int mi_knn_set_option(mi_knn* t, const char* key, int value) {
             // Same answers whatever the value (a sparser sample hands stage 2 more candidates).
             if (value < 0) fail(MI_ERR_INVALID, "many_sample must be >= 0 (got %d)", value);
             t->many_sample = value;
+        } else if (k == "kmeans_fixed_sum") {
+            // mi_knn_kmeans' update and mi_knn_summarize's centroids: 0 (default) = the float sums in the order the row ids fix;
+            // 1 = exact integer sums of 2^-30 (assign_kernels.h), the arithmetic mi_knn_sharded_kmeans always takes: a sharded
+            // table holding the same rows then returns the same bits.
+            if (value < 0 || value > 1) fail(MI_ERR_INVALID, "kmeans_fixed_sum must be 0 or 1 (got %d)", value);
+            t->kmeans_fixed_sum = value;
         } else if (k == "compound_blocks") {
             // mi_knn_search_compound: workgroups of its scan.  0 (default): the grid the batched search takes; v >= 1: exactly
             // min(v, tiles / 4) — a small table can then make a wave walk several tiles.  Same answers whatever the value.
@@ -1183,7 +1189,7 @@ int mi_knn_set_option(mi_knn* t, const char* key, int value) {
             if (!where_chunk_ok(value)) fail(MI_ERR_INVALID, "where_chunk must be 0 or a multiple of 64 up to 65536 (got %d)", value);
             t->where_chunk = value;
         } else {
-            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, join_stage, join_stage_rows, many_segments, many_sample, compound_blocks, page_blocks, group_blocks, group_lds_max, where_chunk)", key);
+            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, join_stage, join_stage_rows, many_segments, many_sample, kmeans_fixed_sum, compound_blocks, page_blocks, group_blocks, group_lds_max, where_chunk)", key);
         }
     });
 }

@@ -58,7 +58,7 @@ int mi_knn_summarize(mi_knn* t, const uint32_t* labels, uint32_t C, float* centr
         unsigned long long* d_slots = (unsigned long long*)scratch.get((size_t)SUMMARY_PLANES * C * sizeof(unsigned long long));
         unsigned long long* d_words = (unsigned long long*)scratch.get(SW_WORDS * sizeof(unsigned long long));
         KmUpdate u;
-        u.alloc(scratch, n, C, dim);
+        u.alloc(scratch, n, C, dim, t->kmeans_fixed_sum != 0);
         HIP_CHECK(hipMemsetAsync(d_cent, 0, (size_t)C * dim * sizeof(float), s));   // (the update leaves an empty group's alone)
         HIP_CHECK(hipMemsetAsync(d_slots, 0xFF, (size_t)C * sizeof(unsigned long long), s));
         HIP_CHECK(hipMemsetAsync(d_slots + C, 0, (size_t)(SUMMARY_PLANES - 1) * C * sizeof(unsigned long long), s));

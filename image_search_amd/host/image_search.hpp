@@ -826,6 +826,18 @@ class ShardedTable {
     }
     // mi_knn_dbscan_stats' eight fields of the last neighbor_counts / dbscan, summed over shards and shard pairs
     std::vector<uint64_t> dbscan_stats() const { std::vector<uint64_t> v(8); check(mi_knn_sharded_dbscan_stats(h_, v.data())); return v; }
+    // EmbeddingTable::kmeans over all shards (mi_knn_sharded_kmeans): labels / dist by global row id; bit for bit what one
+    // table holding the same rows returns with its option "kmeans_fixed_sum" = 1
+    EmbeddingTable::KMeans kmeans(std::vector<float>& centroids, uint32_t C, uint32_t max_iters = 20) const {
+        const uint64_t n = size();
+        EmbeddingTable::KMeans r;
+        r.assignment.labels.resize(n); r.assignment.dist.resize(n);
+        check(mi_knn_sharded_kmeans(h_, centroids.data(), C, max_iters, r.assignment.labels.data(), r.assignment.dist.data(), &r.iters,
+                                    &r.changed, &r.objective));
+        return r;
+    }
+    // {updates run, bytes copied between shards, segments summed in the last update, merge launches} of the last kmeans
+    std::vector<uint64_t> kmeans_stats() const { std::vector<uint64_t> v(4); check(mi_knn_sharded_kmeans_stats(h_, v.data())); return v; }
     // EmbeddingTable::assign_multi over all shards (mi_knn_sharded_assign_multi): labels / dist [rows * m] by global row id
     std::pair<std::vector<uint32_t>, std::vector<float>> assign_multi(const std::vector<float>& vectors, uint32_t C, uint32_t m,
                                                                       float max_dist = INFINITY) const {

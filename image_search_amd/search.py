@@ -308,6 +308,7 @@ class EmbeddingTable:
     def set_option(self, key: str, value: int):
         """mi_knn_set_option: "prefilter" = 1 turns on the two-stage exact search (bf16 mirror, + 50 % memory)."""
         check(lib().mi_knn_set_option(self._h, key.encode(), int(value)))
+        self._options = {**getattr(self, "_options", {}), key: int(value)}   # (what a call that overrides one restores)
 
     def prefilter_stats(self):
         """(rows re-evaluated by stage 2, fell back to the single pass) of the most recent single-query search"""
@@ -661,8 +662,11 @@ class EmbeddingTable:
         check(lib().mi_knn_kmeans_seed_stats(self._h, out))
         return {"candidates": out[0], "passes": out[1], "fallbacks": out[2]}
 
-    def kmeans(self, k_or_centroids, max_iters: int = 20, seed: int = 0, init: str = "uniform", sample: Optional[int] = None) -> dict:
-        """Spherical k-means over the live rows (mi_knn_kmeans).  k_or_centroids: the initial centroids [C, dim], or an int
+    def kmeans(self, k_or_centroids, max_iters: int = 20, seed: int = 0, init: str = "uniform", sample: Optional[int] = None,
+               fixed_sum: Optional[bool] = None) -> dict:
+        """Spherical k-means over the live rows (mi_knn_kmeans).  fixed_sum: None leaves the table's option
+        "kmeans_fixed_sum" as it is; a bool sets it for this call (True: the update on exact integer sums, what
+        ShardedTable.kmeans computes) and restores what set_option last set.  k_or_centroids: the initial centroids [C, dim], or an int
         k.  init = "uniform": k distinct live rows picked with np.random.default_rng(seed); init = "kmeans++": the rows
         kmeans_seed(k, seed) picks — among all live rows, or, where there are more than `sample` of them (None =
         max(64 k, 16 384)), among a seeded uniform subset of that size.  Returns dict(centroids, labels, dist, iters,
@@ -684,8 +688,15 @@ class EmbeddingTable:
         n = len(self)
         labels, dist = np.empty(n, np.uint32), np.empty(n, np.float32)
         iters, changed, obj = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_double()
-        check(lib().mi_knn_kmeans(self._h, cent.ctypes.data, cent.shape[0], int(max_iters), labels.ctypes.data, dist.ctypes.data,
-                                  ctypes.byref(iters), ctypes.byref(changed), ctypes.byref(obj)))
+        before = int(getattr(self, "_options", {}).get("kmeans_fixed_sum", 0))
+        if fixed_sum is not None:
+            check(lib().mi_knn_set_option(self._h, b"kmeans_fixed_sum", int(bool(fixed_sum))))
+        try:
+            check(lib().mi_knn_kmeans(self._h, cent.ctypes.data, cent.shape[0], int(max_iters), labels.ctypes.data, dist.ctypes.data,
+                                      ctypes.byref(iters), ctypes.byref(changed), ctypes.byref(obj)))
+        finally:
+            if fixed_sum is not None:
+                check(lib().mi_knn_set_option(self._h, b"kmeans_fixed_sum", before))
         return {"centroids": cent, "labels": labels, "dist": dist, "iters": iters.value, "changed": changed.value,
                 "objective": obj.value}
 
@@ -1180,6 +1191,37 @@ class ShardedTable:
         check(lib().mi_knn_sharded_dbscan_stats(self._h, out))
         return dict(zip(("candidates_pass1", "pairs", "tiles_pass1", "candidates_pass2", "tiles_visited", "tiles_skipped",
                          "unions_merged", "launches"), (int(v) for v in out)))
+
+    def kmeans(self, k_or_centroids, max_iters: int = 20, seed: int = 0, init: str = "uniform") -> dict:
+        """EmbeddingTable.kmeans over all shards (mi_knn_sharded_kmeans): the same dict, labels / dist by global row id — bit
+        for bit what one table holding the same rows returns with fixed_sum=True, whatever the shard count, block size or
+        devices.  An int k starts from the rows EmbeddingTable.kmeans(k, seed) picks over the same data.  Only sums, counts
+        and centroids cross between the shards."""
+        if init == "kmeans++":
+            raise ValueError('init = "kmeans++" is not offered on a sharded table: the seeding draws every row against the rows '
+                             'drawn so far on one device (mi_knn_kmeans_seed) and has no form that runs across shards; seed on '
+                             'one table, or pass the centroids')
+        if init != "uniform":
+            raise ValueError(f'init = {init!r}: "uniform"')
+        if isinstance(k_or_centroids, (int, np.integer)):
+            rows = initial_centroid_rows(len(self), self.deleted(), int(k_or_centroids), seed)
+            cent = np.concatenate([self.rows(int(r), 1) for r in rows]) if rows.size else np.empty((0, self.dim), np.float32)
+        else:
+            cent = np.array(k_or_centroids, dtype=np.float32, order="C").reshape(-1, self.dim)
+        n = len(self)
+        labels, dist = np.empty(n, np.uint32), np.empty(n, np.float32)
+        iters, changed, obj = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_double()
+        check(lib().mi_knn_sharded_kmeans(self._h, cent.ctypes.data, cent.shape[0], int(max_iters), labels.ctypes.data,
+                                          dist.ctypes.data, ctypes.byref(iters), ctypes.byref(changed), ctypes.byref(obj)))
+        return {"centroids": cent, "labels": labels, "dist": dist, "iters": iters.value, "changed": changed.value,
+                "objective": obj.value}
+
+    def kmeans_stats(self) -> dict:
+        """mi_knn_sharded_kmeans_stats, of the last kmeans: bytes_exchanged = updates * (shards - 1) * C * (8 dim + 4) inward
+        (sums and counts) + updates * (shards - 1) * C * dim * 4 outward (centroids)"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_sharded_kmeans_stats(self._h, out))
+        return dict(zip(("updates", "bytes_exchanged", "segments", "merge_launches"), (int(v) for v in out)))
 
     def duplicates(self, max_dist: float, first_new: int = 0, cap: int = 1 << 20) -> list:
         """Groups of near-duplicate rows: near_pairs through pairs_to_groups — lists of global ids chained by distances

@@ -472,7 +472,17 @@ int mi_knn_neighbors(mi_knn* t, uint64_t first, uint64_t n, uint32_t k, uint64_t
  * *objective = sum of dist over the live rows with a non-NaN distance, in double, in row order (any of the three may be
  * NULL).  Deterministic: the sums run in an order fixed by the row ids (rows bucketed by label, fixed segments, segments in
  * order), so the same table, centroids and max_iters give the same bits.  max_iters = 0: one assign, centroids untouched.
- * Rows, labels and sums stay on the device between iterations.  Arguments and errors as mi_knn_assign. */
+ * Rows, labels and sums stay on the device between iterations.  Arguments and errors as mi_knn_assign.
+ * Option "kmeans_fixed_sum" (mi_knn_set_option; 0 = default, 1 = on, anything else MI_ERR_INVALID) replaces the float sums of
+ * this update, and of mi_knn_summarize's centroids, by exact integer sums.  For a member row r and component j:
+ *   v = x[r][j] * inv[r]                     the fp32 product the float sum adds, inv[r] = 1 / |x[r]|
+ *   q = (|v| < 2) ? rint(v * 2^30) : 0       to nearest, ties to even; the scaling is exact; |q| < 2^31 (a NaN or inf v,
+ *                                            which no member row produces, fails the comparison)
+ *   S[c][j] = sum of q as int64              fewer than 2^32 members: |S| < 2^63
+ *   centroid[c][j] = (float)((double)S[c][j] * 2^-30 / (double)n_c), an empty cluster keeps its centroid
+ * Membership, the stop rule and everything else are unchanged.  The result no longer depends on any summation order, which
+ * is what mi_knn_sharded_kmeans rests on; a component's error is half a unit of 2^-30 per member before the division and
+ * does not grow with n_c.  At 0 nothing changes: the launches and bits of the float path. */
 int mi_knn_kmeans(mi_knn* t, float* centroids, uint32_t C, uint32_t max_iters, uint32_t* labels, float* dist,
                   uint32_t* iters_run, uint64_t* changed_last, double* objective);
 /* k-means++ seeding on the device ("what mi_knn_kmeans should start from"): C rows, each drawn with probability proportional
@@ -935,6 +945,24 @@ int mi_knn_sharded_dbscan(mi_knn_sharded* t, float max_dist, uint32_t min_pts, u
  * and shard pair.  "unions that merged" also counts the final merge of the shards' forests, so it is >= core rows - clusters
  * (two shards may each merge the same two components). */
 int mi_knn_sharded_dbscan_stats(mi_knn_sharded* t, uint64_t out[8]);
+/* mi_knn_kmeans over the whole table, always on the exact integer sums of option "kmeans_fixed_sum" (defined at mi_knn_kmeans;
+ * the shards' option is not consulted).  Per iteration every shard assigns its own rows and sums them per cluster on its own
+ * device; the sums S_s [C][dim] int64 and sizes n_s [C] uint32 of shards 1 .. S-1 are copied to the first shard's device (in
+ * chunks of at most 16 MB) and added into the first shard's, the centroids are formed there and copied back to every shard.
+ * Integer adds give the same sum in any order, so centroids, labels, dist, *iters_run, *changed_last and *objective (summed
+ * in double in GLOBAL row order) equal, bit for bit, mi_knn_kmeans' on ONE table that holds the same rows with
+ * "kmeans_fixed_sum" = 1 — for any shard count, block size and devices.  labels / dist: [rows of the table] by global row, as
+ * mi_knn_sharded_assign's; either may be NULL.  Bytes that cross between shards per update:
+ * (S - 1) * C * (8 * dim + 4) inward and (S - 1) * C * dim * 4 outward, nothing else; a shard without rows takes part with
+ * zeros.  Streams are ordered by events; the host waits only where mi_knn_kmeans does (an assign's counts).
+ * Arguments and errors as mi_knn_kmeans (they are checked first, and an error writes nothing); a table without shards:
+ * MI_ERR_INVALID; 2^32 or more rows in the table: MI_ERR_UNSUPPORTED.  An empty table: MI_OK, zeros in *iters_run,
+ * *changed_last and *objective, centroids untouched. */
+int mi_knn_sharded_kmeans(mi_knn_sharded* t, float* centroids, uint32_t C, uint32_t max_iters, uint32_t* labels, float* dist,
+                          uint32_t* iters_run, uint64_t* changed_last, double* objective);
+/* of the last mi_knn_sharded_kmeans: {updates run, bytes copied between shards, segments summed in the last update (all
+ * shards), merge launches} */
+int mi_knn_sharded_kmeans_stats(mi_knn_sharded* t, uint64_t out[4]);
 /* Change the layout of a LIVE table: every row of `src` into the empty `dst` (another shard count, device set or block
  * size), block by block, device to device — a plain copy where source and destination shard share a GPU,
  * hipMemcpyPeerAsync over xGMI where they do not; nothing passes through the host.  src is unchanged. */
