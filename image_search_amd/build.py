@@ -13,7 +13,7 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libmi355clip.so")
-SOURCES = ["core.hip", "knn.hip", "vit.hip", "preprocess.hip", "pipeline.hip", "sharded.hip", "index.hip", "join.hip", "assign.hip",
+SOURCES = ["core.hip", "knn.hip", "vit.hip", "preprocess.hip", "pipeline.hip", "sharded.hip", "sharded_calls.hip", "index.hip", "join.hip", "assign.hip",
            "assign_multi.hip", "search_many.hip", "kmeans_seed.hip", "diverse.hip", "compound.hip", "page.hip",
            "grouped.hip", "where.hip", "ordered.hip", "density.hip", "join_between.hip", "summary.hip", "density_sharded.hip",
            "kmeans_sharded.hip"]

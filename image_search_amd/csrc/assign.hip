@@ -6,7 +6,6 @@
 #include <cstring>
 
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "common.h"
@@ -14,6 +13,7 @@
 #include "assign_call.h"
 #include "assign_kernels.h"
 #include "kmeans_update.h"
+#include "sharded_call.h"
 #include "two_stage.h"
 
 using namespace mi;
@@ -117,13 +117,10 @@ int mi_knn_kmeans(mi_knn* t, float* centroids, uint32_t C, uint32_t max_iters, u
 
 int mi_knn_sharded_assign(mi_knn_sharded* t, const float* vectors, uint32_t C, uint32_t* labels, float* dist) {
     return guarded([&] {
-        if (!t) fail(MI_ERR_INVALID, "null table handle");
-        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
+        ShardedCall call(t);
         check_args(t->shard[0], vectors, C, labels, true);
-        std::lock_guard<std::mutex> l(t->mu);
-        sharded_deliver_all(t);
         // every shard on its own stream; results land at the rows' global ids
-        for_each_shard(t, [&](uint32_t, mi_knn* sh) {
+        call.for_each_shard([&](uint32_t, mi_knn* sh) {
             const uint64_t rows = sh->rows;
             std::vector<uint32_t> lab(rows);
             std::vector<float> dd(dist ? rows : 0);

@@ -10,12 +10,12 @@
 #include <cstring>
 
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "common.h"
 #include "handles.h"
 #include "assign_multi_kernels.h"
+#include "sharded_call.h"
 #include "two_stage.h"
 
 using namespace mi;
@@ -210,13 +210,10 @@ int mi_knn_assign_multi_stats(mi_knn* t, uint64_t out[4]) {
 int mi_knn_sharded_assign_multi(mi_knn_sharded* t, const float* vectors, uint32_t C, uint32_t m, float max_dist, uint32_t* labels,
                                 float* dist) {
     return guarded([&] {
-        if (!t) fail(MI_ERR_INVALID, "null table handle");
-        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
+        ShardedCall call(t);
         check_args(t->shard[0], vectors, C, m, max_dist, labels);
-        std::lock_guard<std::mutex> l(t->mu);
-        sharded_deliver_all(t);
         // every shard on its own stream; results land at the rows' global ids
-        for_each_shard(t, [&](uint32_t, mi_knn* sh) {
+        call.for_each_shard([&](uint32_t, mi_knn* sh) {
             const uint64_t rows = sh->rows;
             std::vector<uint32_t> lab(rows * m);
             std::vector<float> dd(dist ? rows * m : 0);

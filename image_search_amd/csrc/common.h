@@ -42,6 +42,12 @@ int guarded(F&& f) noexcept {
     }
 }
 
+// what a public mi_* call made inside the library returned: its code and message go on as they are (`as`: the code to report
+// in its place)
+inline void call_ok(int e, int as = MI_OK) {
+    if (e != MI_OK) fail(as != MI_OK ? as : e, "%s", mi_last_error());
+}
+
 // Select `device` and require it to be a gfx950 part: there is no fallback path.
 void use_device(int device);
 

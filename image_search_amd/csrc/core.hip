@@ -7,6 +7,7 @@
 
 #include "common.h"
 #include "ids.h"
+#include "sharded_call.h"   // merge_lists
 
 namespace mi {
 
@@ -32,38 +33,6 @@ void use_device(int device) {
 }  // namespace mi
 
 using namespace mi;
-
-namespace {
-
-// ordering of results: (distance asc, id asc), NaN last — the same 32-bit monotone
-// image of the distance the kernels use (knn_kernels.h dist_to_u32).
-inline uint32_t dist_key(float d) {
-    uint32_t b;
-    std::memcpy(&b, &d, 4);
-    if (d != d) return 0xFFFFFFFFu;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-}  // namespace
-
-namespace mi {
-// global top-k of `lists` candidate lists of k (id, distance) entries under (distance asc, id asc), NaN last
-void merge_lists(const uint64_t* idx_in, const float* dist_in, uint32_t lists, uint32_t k, uint64_t* idx, float* dist) {
-    struct Ent { uint32_t key; uint64_t id; float d; };
-    std::vector<Ent> all;
-    all.reserve((size_t)lists * k);
-    for (size_t i = 0; i < (size_t)lists * k; ++i)
-        if (idx_in[i] != MI_KNN_NO_ID) all.push_back({dist_key(dist_in[i]), idx_in[i], dist_in[i]});
-    const size_t keep = std::min<size_t>(k, all.size());
-    std::partial_sort(all.begin(), all.begin() + keep, all.end(), [](const Ent& a, const Ent& b) {
-        return a.key < b.key || (a.key == b.key && a.id < b.id);
-    });
-    for (uint32_t i = 0; i < k; ++i) {
-        if (i < keep) { idx[i] = all[i].id; dist[i] = all[i].d; }
-        else { idx[i] = MI_KNN_NO_ID; dist[i] = INFINITY; }
-    }
-}
-}  // namespace mi
 
 extern "C" {
 
@@ -103,12 +72,10 @@ int mi_refine(const float* text, const float* const* selected, size_t m, size_t 
             return;
         }
         std::vector<float> sel(len);
-        int rc = mi_average_slices(selected, m, len, sel.data());
-        if (rc != MI_OK) fail(rc, "%s", mi_last_error());
+        call_ok(mi_average_slices(selected, m, len, sel.data()));
         const float* two[2] = {sel.data(), text};
         std::vector<float> res(len);
-        rc = mi_average_slices(two, 2, len, res.data());
-        if (rc != MI_OK) fail(rc, "%s", mi_last_error());
+        call_ok(mi_average_slices(two, 2, len, res.data()));
         if (len) std::memcpy(out, res.data(), len * sizeof(float));
     });
 }

@@ -22,6 +22,7 @@
 #include "density_sharded_kernels.h"
 #include "handles.h"
 #include "join_between_walk.h"
+#include "sharded_call.h"
 #include "two_stage.h"
 
 using namespace mi;
@@ -30,11 +31,6 @@ namespace {
 
 constexpr uint32_t MERGE_CHUNK = 1u << 22;   // forest entries copied to shard 0's device at a time (16 MB)
 
-void copy_between(void* dst, int dst_dev, const void* src, int src_dev, size_t bytes, hipStream_t s) {
-    if (bytes == 0) return;
-    if (dst_dev == src_dev) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
-    else HIP_CHECK(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, s));
-}
 uint32_t row_blocks(const mi_knn* t, uint64_t n) {
     return std::max<uint32_t>(1u, (uint32_t)std::min<uint64_t>((uint64_t)t->n_cu * 8, (n + 255) / 256));
 }
@@ -265,9 +261,9 @@ void cross_piece(ShardState& A, ShardState& B, const Params& p) {
 }
 
 template <int PASS>
-void cross_rounds(mi_knn_sharded* t, std::vector<std::unique_ptr<ShardState>>& st, const Params& p) {
-    for (const std::vector<ShardPair>& round : between_schedule(t->n()))
-        for_each_shard_pair(round, [&](uint32_t ra, uint32_t cb) { cross_piece<PASS>(*st[ra], *st[cb], p); });
+void cross_rounds(ShardedCall& call, std::vector<std::unique_ptr<ShardState>>& st, const Params& p) {
+    for (const std::vector<ShardPair>& round : between_schedule(call.n))
+        call.for_each_shard_pair(round, [&](uint32_t ra, uint32_t cb) { cross_piece<PASS>(*st[ra], *st[cb], p); });
 }
 
 struct ShardedDensityOut {
@@ -278,22 +274,23 @@ struct ShardedDensityOut {
 };
 
 // min_pts == 0: the degrees only (mi_knn_sharded_density).  Everything lands in `out`, by global row; the caller's arrays are
-// written by the caller once this has returned.  t->mu held.
-void sharded_density_run(mi_knn_sharded* t, float max_dist, uint32_t min_pts, bool want_via, bool want_via_dist, bool want_counts,
+// written by the caller once the frame has left.
+void sharded_density_run(ShardedCall& call, float max_dist, uint32_t min_pts, bool want_via, bool want_via_dist, bool want_counts,
                          ShardedDensityOut* out) {
+    mi_knn_sharded* t = call.t;
     for (uint64_t& v : t->dbscan_stats) v = 0;
     check_mirror_dim(t->dim, "the density pass's");
     if (!sharded_density_rows_ok(t->rows)) fail(MI_ERR_UNSUPPORTED, "at most 2^32 - 1 rows (got %llu)", (unsigned long long)t->rows);
-    sharded_deliver_all(t);
+    call.ready();
     const uint64_t G = t->rows;
     if (G == 0) return;
-    const uint32_t S = t->n();
+    const uint32_t S = call.n;
     const Params p{max_dist, 1.0f - (max_dist + eps2(t->dim)), min_pts, (uint32_t)G};
     std::vector<std::unique_ptr<ShardState>> st(S);
     for (uint32_t si = 0; si < S; ++si) st[si].reset(new ShardState);
 
     // the shards' state and their self pieces of pass 1, side by side
-    for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
+    call.for_each_shard([&](uint32_t si, mi_knn* sh) {
         std::lock_guard<std::mutex> l(sh->mu);
         ShardState& x = *st[si];
         x.sh = sh;
@@ -319,11 +316,11 @@ void sharded_density_run(mi_knn_sharded* t, float max_dist, uint32_t min_pts, bo
         x.tm = table_mirror(sh, s, x.scratch);
         self_piece<1>(x, p, s);
     });
-    cross_rounds<1>(t, st, p);
+    cross_rounds<1>(call, st, p);
 
     if (min_pts == 0) {
         out->counts.assign(G, 0u);
-        for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
+        call.for_each_shard([&](uint32_t si, mi_knn* sh) {
             ShardState& x = *st[si];
             if (x.n_rows == 0) return;
             std::lock_guard<std::mutex> l(sh->mu);
@@ -342,7 +339,7 @@ void sharded_density_run(mi_knn_sharded* t, float max_dist, uint32_t min_pts, bo
     }
 
     // between the passes: the activity bytes and the border keys' init, then the self pieces of pass 2
-    for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
+    call.for_each_shard([&](uint32_t si, mi_knn* sh) {
         ShardState& x = *st[si];
         if (x.n_rows == 0) return;
         std::lock_guard<std::mutex> l(sh->mu);
@@ -359,7 +356,7 @@ void sharded_density_run(mi_knn_sharded* t, float max_dist, uint32_t min_pts, bo
         x.blocks.index();
         self_piece<2>(x, p, s);
     });
-    cross_rounds<2>(t, st, p);
+    cross_rounds<2>(call, st, p);
 
     // forest s into forest 0 on shard 0's device (shard 0 holds row 0: it is not empty), the roots, and the roots back
     uint32_t* d_root = nullptr;
@@ -395,7 +392,7 @@ void sharded_density_run(mi_knn_sharded* t, float max_dist, uint32_t min_pts, bo
     if (want_via_dist) res.via_dist.assign(G, 0.0f);
     if (want_counts) res.counts.assign(G, 0u);
     std::vector<unsigned long long> words((size_t)S * DW_WORDS, 0ull);
-    for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
+    call.for_each_shard([&](uint32_t si, mi_knn* sh) {
         ShardState& x = *st[si];
         if (x.n_rows == 0) return;
         std::lock_guard<std::mutex> l(sh->mu);
@@ -453,11 +450,10 @@ int mi_knn_sharded_density(mi_knn_sharded* t, float max_dist, uint32_t* counts) 
         const char* why = "";
         const int bad = density_check_args(t, max_dist, counts, &why);
         if (bad != MI_OK) fail(bad, "%s", why);
-        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
         ShardedDensityOut out;
         {
-            std::lock_guard<std::mutex> l(t->mu);
-            sharded_density_run(t, max_dist, 0, false, false, true, &out);
+            ShardedCall call(t);
+            sharded_density_run(call, max_dist, 0, false, false, true, &out);
         }
         copy_out(out.counts, counts);
     });
@@ -469,11 +465,10 @@ int mi_knn_sharded_dbscan(mi_knn_sharded* t, float max_dist, uint32_t min_pts, u
         const char* why = "";
         const int bad = dbscan_check_args(t, max_dist, min_pts, cluster, summary, &why);
         if (bad != MI_OK) fail(bad, "%s", why);
-        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
         ShardedDensityOut out;
         {
-            std::lock_guard<std::mutex> l(t->mu);
-            sharded_density_run(t, max_dist, min_pts, via != nullptr, via_dist != nullptr, counts != nullptr, &out);
+            ShardedCall call(t);
+            sharded_density_run(call, max_dist, min_pts, via != nullptr, via_dist != nullptr, counts != nullptr, &out);
         }
         copy_out(out.cluster, cluster);
         copy_out(out.via, via);

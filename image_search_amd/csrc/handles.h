@@ -416,4 +416,14 @@ void sharded_search_enqueue(mi_knn_sharded* t, const float* q, uint32_t nq, uint
                             const std::vector<std::vector<uint64_t>>* filter = nullptr,
                             const mi_knn_where* where = nullptr);  // t->mu held
 void sharded_deliver_all(mi_knn_sharded* t);                                    // t->mu held
+// sharded_calls.hip: the predicate's count and the columns the shards keep for their own rows (mi_knn_sharded_rebalance carries
+// them over with these), behind the argument checks of their public calls; t->mu held.  ids == nullptr: the first n rows
+uint64_t sharded_count_where(mi_knn_sharded* t, const mi_knn_where* w);
+uint64_t sharded_delete(mi_knn_sharded* t, const uint64_t* ids, uint64_t n);     // every id checked first; returns the newly deleted
+std::vector<uint64_t> sharded_deleted(mi_knn_sharded* t);                        // the deleted global ids, ascending
+void sharded_set_groups(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, const uint32_t* groups);
+void sharded_get_groups(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint32_t* groups);
+void sharded_groups_info(mi_knn_sharded* t, uint64_t info[2]);
+void sharded_set_attrs(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, const uint64_t* tags, const int64_t* stamps);
+void sharded_get_attrs(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint64_t* tags, int64_t* stamps);
 }  // namespace mi

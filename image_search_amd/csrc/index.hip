@@ -78,8 +78,7 @@ void sync_groups(mi_index* ix) {
     if (rows > ix->groups_uploaded) {
         std::vector<uint64_t> ids((size_t)(rows - ix->groups_uploaded));
         for (size_t i = 0; i < ids.size(); ++i) ids[i] = ix->groups_uploaded + i;
-        const int e = mi_knn_set_groups(ix->table, ids.data(), ids.size(), ix->row_dir.data() + ix->groups_uploaded);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_set_groups(ix->table, ids.data(), ids.size(), ix->row_dir.data() + ix->groups_uploaded));
     }
     ix->groups_uploaded = rows;
     ix->groups_epoch = table_groups_epoch(ix->table);
@@ -111,12 +110,10 @@ std::vector<float> refined_query(mi_index* ix, const float* text_embedding, cons
         std::vector<float> sel(marked.size() * ix->dim);
         std::vector<const float*> ptr(marked.size());
         for (size_t i = 0; i < marked.size(); ++i) {
-            const int e = mi_knn_get_rows(ix->table, marked[i], 1, &sel[i * ix->dim]);
-            if (e != MI_OK) fail(e, "%s", mi_last_error());
+            call_ok(mi_knn_get_rows(ix->table, marked[i], 1, &sel[i * ix->dim]));
             ptr[i] = &sel[i * ix->dim];
         }
-        const int e = mi_refine(text_embedding, ptr.data(), ptr.size(), ix->dim, query.data());
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_refine(text_embedding, ptr.data(), ptr.size(), ix->dim, query.data()));
     }
     return query;
 }
@@ -168,8 +165,7 @@ int mi_index_create(uint32_t dim, int device, const char* media_dir, mi_index** 
         ix = new mi_index();
         ix->dim = dim;
         ix->media_dir = media_dir ? media_dir : "";
-        const int e = mi_knn_create(dim, device, &ix->table);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_create(dim, device, &ix->table));
         *out = ix;
     });
     if (rc != MI_OK && ix) { delete ix; }
@@ -225,8 +221,7 @@ int mi_index_insert(mi_index* ix, const char* const* paths, const float* embeddi
         if (!paths || !embeddings) fail(MI_ERR_INVALID, "null argument");
         for (size_t i = 0; i < n; ++i)
             if (!paths[i]) fail(MI_ERR_INVALID, "path %zu is null", i);
-        const int e = mi_knn_append(ix->table, embeddings, n);  // the rows first: a failure leaves the path column untouched
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_append(ix->table, embeddings, n));  // the rows first: a failure leaves the path column untouched
         for (size_t i = 0; i < n; ++i) add_path(ix, paths[i]);
     });
 }
@@ -237,8 +232,7 @@ int mi_index_adopt(mi_index* ix, const char* const* paths, size_t n) {
         if (!ix || (n && !paths)) fail(MI_ERR_INVALID, "null argument");
         std::lock_guard<std::mutex> l(ix->mu);
         uint64_t rows = 0;
-        const int e = mi_knn_size(ix->table, &rows);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_size(ix->table, &rows));
         if (ix->paths.size() + n != rows)
             fail(MI_ERR_INVALID, "%zu paths for %llu rows without one (the table holds %llu rows, the path column %zu)", n,
                  (unsigned long long)(rows - ix->paths.size()), (unsigned long long)rows, ix->paths.size());
@@ -292,8 +286,7 @@ int mi_index_search(mi_index* ix, const float* text_embedding, const char* const
     return guarded([&] {
         if (!ix || !text_embedding || !idx || !dist || (n_ref && !referenced_images)) fail(MI_ERR_INVALID, "null argument");
         const std::vector<float> query = refined_query(ix, text_embedding, referenced_images, n_ref);
-        const int e = mi_knn_search(ix->table, query.data(), 1, k, idx, dist);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_search(ix->table, query.data(), 1, k, idx, dist));
         if (n_found) *n_found = hits(idx, k);
     });
 }
@@ -307,8 +300,7 @@ int mi_index_search_within(mi_index* ix, const float* text_embedding, const char
             fail(MI_ERR_INVALID, "null argument");
         const std::vector<uint64_t> ids = folder_rows(ix, folders, n_folders);
         const std::vector<float> query = refined_query(ix, text_embedding, referenced_images, n_ref);
-        const int e = mi_knn_search_filtered(ix->table, query.data(), 1, k, ids.data(), ids.size(), idx, dist);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_search_filtered(ix->table, query.data(), 1, k, ids.data(), ids.size(), idx, dist));
         if (n_found) *n_found = hits(idx, k);
     });
 }
@@ -326,9 +318,8 @@ int mi_index_search_diverse(mi_index* ix, const float* text_embedding, const cha
         const std::vector<float> query = refined_query(ix, text_embedding, referenced_images, n_ref);
         const uint64_t none = 0;   // folders that match nothing are an empty row set, not "the whole table"
         const uint64_t* among = n_folders ? (ids.empty() ? &none : ids.data()) : nullptr;
-        const int e = mi_knn_search_diverse(ix->table, query.data(), k, pool, min_gap, among, ids.size(), idx, dist, hidden, nullptr,
-                                            n_found);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_search_diverse(ix->table, query.data(), k, pool, min_gap, among, ids.size(), idx, dist, hidden, nullptr,
+                                      n_found));
     });
 }
 
@@ -343,8 +334,7 @@ int mi_index_search_compound(mi_index* ix, const float* pos, uint32_t n_pos, int
         if (n_folders) ids = folder_rows(ix, folders, n_folders);
         const uint64_t none = 0;   // folders that match nothing are an empty row set, not "the whole table"
         const uint64_t* among = n_folders ? (ids.empty() ? &none : ids.data()) : nullptr;
-        const int e = mi_knn_search_compound(ix->table, pos, n_pos, mode, neg, neg_within, n_neg, k, among, ids.size(), idx, dist, term_dist);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_search_compound(ix->table, pos, n_pos, mode, neg, neg_within, n_neg, k, among, ids.size(), idx, dist, term_dist));
         if (n_found) *n_found = hits(idx, k);
     });
 }
@@ -362,8 +352,7 @@ int mi_index_search_page(mi_index* ix, const float* text_embedding, const char* 
         const std::vector<float> query = refined_query(ix, text_embedding, referenced_images, n_ref);
         const uint64_t none = 0;   // folders that match nothing are an empty row set, not "the whole table"
         const uint64_t* among = n_folders ? (ids.empty() ? &none : ids.data()) : nullptr;
-        const int e = mi_knn_search_page(ix->table, query.data(), k, after_dist, after_id, max_dist, among, ids.size(), idx, dist, counts);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_search_page(ix->table, query.data(), k, after_dist, after_id, max_dist, among, ids.size(), idx, dist, counts));
         if (n_results) *n_results = hits(idx, k);
     });
 }
@@ -390,13 +379,12 @@ int mi_index_search_grouped(mi_index* ix, const float* text_embedding, const cha
         // the table may know more groups than the index has directories (labels a caller once set on it): its facets go through
         // a buffer of the table's size, the directories' part reaches the caller
         uint64_t info[2] = {0, 0};
-        if (mi_knn_groups_info(ix->table, info) != MI_OK) fail(MI_ERR_INVALID, "%s", mi_last_error());
+        call_ok(mi_knn_groups_info(ix->table, info), MI_ERR_INVALID);
         std::vector<uint64_t> all(facets ? (size_t)std::max<uint64_t>(info[0], 1) : 0);
         const uint64_t none = 0;   // folders that match nothing are an empty row set, not "the whole table"
         const uint64_t* among = n_folders ? (ids.empty() ? &none : ids.data()) : nullptr;
-        const int e = mi_knn_search_grouped(ix->table, query.data(), k, max_dist, among, ids.size(), idx, dist, group, members,
-                                            facets ? all.data() : nullptr, all.size(), totals);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_search_grouped(ix->table, query.data(), k, max_dist, among, ids.size(), idx, dist, group, members,
+                                      facets ? all.data() : nullptr, all.size(), totals));
         if (facets) std::copy(all.begin(), all.begin() + std::min(n_dirs, all.size()), facets);
         if (n_found) *n_found = hits(idx, k);
     });
@@ -458,9 +446,8 @@ int mi_index_folder_overview(mi_index* ix, uint32_t cap, uint64_t* count, uint64
         std::vector<uint64_t> u64((size_t)C * 5);
         std::vector<float> f32((size_t)C * 2);
         uint64_t *h_count = u64.data(), *h_cover = h_count + C, *h_odd = h_cover + C, *h_measured = h_odd + C, *h_spread = h_measured + C;
-        const int e = mi_knn_summarize(ix->table, nullptr, C, nullptr, h_count, h_cover, f32.data(), h_odd, f32.data() + C, h_measured,
-                                       h_spread, nullptr, nullptr);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_summarize(ix->table, nullptr, C, nullptr, h_count, h_cover, f32.data(), h_odd, f32.data() + C, h_measured,
+                                 h_spread, nullptr, nullptr));
         const size_t n = std::min<size_t>(cap, C);
         if (count) std::copy(h_count, h_count + n, count);
         if (cover) std::copy(h_cover, h_cover + n, cover);
@@ -494,8 +481,7 @@ int mi_index_set_attrs(mi_index* ix, const char* const* paths, size_t n, const u
             }
         }
         if (ids.empty()) return;
-        const int e = mi_knn_set_attrs(ix->table, ids.data(), ids.size(), tags ? tg.data() : nullptr, stamps ? st.data() : nullptr);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_set_attrs(ix->table, ids.data(), ids.size(), tags ? tg.data() : nullptr, stamps ? st.data() : nullptr));
     });
 }
 
@@ -513,8 +499,7 @@ int mi_index_search_where(mi_index* ix, const float* text_embedding, const char*
             std::lock_guard<std::mutex> l(ix->mu);
             sync_groups(ix);
         }
-        const int e = mi_knn_search_where(ix->table, query.data(), 1, k, where, idx, dist, matched);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_search_where(ix->table, query.data(), 1, k, where, idx, dist, matched));
         if (n_found) *n_found = hits(idx, k);
     });
 }
@@ -534,8 +519,7 @@ int mi_index_search_ordered(mi_index* ix, const float* text_embedding, const cha
             std::lock_guard<std::mutex> l(ix->mu);
             sync_groups(ix);
         }
-        const int e = mi_knn_search_ordered(ix->table, query.data(), k, max_dist, where, flags, after_stamp, after_id, idx, dist, stamps, counts);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_search_ordered(ix->table, query.data(), k, max_dist, where, flags, after_stamp, after_id, idx, dist, stamps, counts));
         if (n_found) *n_found = hits(idx, k);
     });
 }
@@ -553,8 +537,7 @@ int mi_index_stamp_histogram(mi_index* ix, const float* text_embedding, const ch
             std::lock_guard<std::mutex> l(ix->mu);
             sync_groups(ix);
         }
-        const int e = mi_knn_stamp_histogram(ix->table, query.data(), max_dist, where, edges, n_edges, hist);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_stamp_histogram(ix->table, query.data(), max_dist, where, edges, n_edges, hist));
     });
 }
 
@@ -564,8 +547,7 @@ int mi_index_save(mi_index* ix, const char* dir) {
         std::lock_guard<std::mutex> l(ix->mu);
         if (::mkdir(dir, 0777) != 0 && errno != EEXIST) fail(MI_ERR_IO, "cannot create directory %s", dir);
         const std::string d(dir);
-        const int e = mi_knn_save(ix->table, (d + "/embedding.miknn").c_str());  // tmp + fsync + rename inside
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_save(ix->table, (d + "/embedding.miknn").c_str()));  // tmp + fsync + rename inside
         // image_path.bin: "MIPATHv1", u64 rows, u32 media_dir length + bytes, then per row u32 length + bytes
         const std::string tmp = d + "/image_path.bin.tmp", fin = d + "/image_path.bin";
         const int fd = ::open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
@@ -633,8 +615,7 @@ int mi_index_load(mi_index* ix, const char* dir) {
             throw;
         }
         std::fclose(f);
-        const int e = mi_knn_load(ix->table, (d + "/embedding.miknn").c_str());
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_load(ix->table, (d + "/embedding.miknn").c_str()));
         uint64_t rows = 0;
         (void)mi_knn_size(ix->table, &rows);
         // the embedding file is written first: it may be NEWER than the path file (a crash between the two renames);
@@ -645,9 +626,9 @@ int mi_index_load(mi_index* ix, const char* dir) {
         // the removed rows are the table's deleted ones (saved in embedding.miknn): no lookup finds them
         uint64_t n_dead = 0;
         std::vector<uint64_t> dead;
-        if (mi_knn_deleted(ix->table, nullptr, 0, &n_dead) != MI_OK) fail(MI_ERR_INVALID, "%s", mi_last_error());
+        call_ok(mi_knn_deleted(ix->table, nullptr, 0, &n_dead), MI_ERR_INVALID);
         dead.resize(n_dead);
-        if (n_dead && mi_knn_deleted(ix->table, dead.data(), n_dead, &n_dead) != MI_OK) fail(MI_ERR_INVALID, "%s", mi_last_error());
+        if (n_dead) call_ok(mi_knn_deleted(ix->table, dead.data(), n_dead, &n_dead), MI_ERR_INVALID);
         std::vector<uint8_t> gone(paths.size(), 0);
         for (uint64_t id : dead)
             if (id < gone.size()) gone[id] = 1;
@@ -685,8 +666,7 @@ int mi_index_remove(mi_index* ix, const char* const* paths, size_t n, uint64_t* 
         }
         if (ids.empty()) return;
         uint64_t newly = 0;
-        const int e = mi_knn_delete(ix->table, ids.data(), ids.size(), &newly);  // the rows first: a failure changes nothing
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
+        call_ok(mi_knn_delete(ix->table, ids.data(), ids.size(), &newly));  // the rows first: a failure changes nothing
         for (uint64_t id : ids) ix->removed[id] = 1;
         for (size_t i = 0; i < n; ++i) {
             ix->rows_of.erase(paths[i]);

@@ -20,6 +20,7 @@
 #include "join_between_host.h"
 #include "join_between_kernels.h"
 #include "join_between_walk.h"
+#include "sharded_call.h"
 #include "two_stage.h"
 
 using namespace mi;
@@ -214,14 +215,12 @@ int mi_knn_sharded_near_pairs(mi_knn_sharded* t, float max_dist, uint64_t first_
         const char* why = "";
         const int bad = sharded_join_check_args(t, max_dist, a, b, dist, cap, count, &why);
         if (bad != MI_OK) fail(bad, "%s (max_dist %g, cap %llu)", why, (double)max_dist, (unsigned long long)cap);
-        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
-        std::lock_guard<std::mutex> l(t->mu);
+        ShardedCall call(t);
         if (first_new > t->rows)
             fail(MI_ERR_INVALID, "first_new %llu lies beyond one past the last row (%llu rows)", (unsigned long long)first_new,
                  (unsigned long long)t->rows);
         for (uint64_t& v : t->join_stats) v = 0;
-        sharded_deliver_all(t);
-        const uint32_t S = t->n();
+        const uint32_t S = call.n;
         std::vector<uint64_t> fn(S);
         for (uint32_t si = 0; si < S; ++si) fn[si] = shard_first_new(t->block, S, si, first_new);
         std::atomic<uint64_t> total{0};
@@ -240,7 +239,7 @@ int mi_knn_sharded_near_pairs(mi_knn_sharded* t, float max_dist, uint64_t first_
             }
         };
         // the S self-joins, side by side
-        for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
+        call.for_each_shard([&](uint32_t si, mi_knn* sh) {
             std::vector<JoinPair> pairs;
             bool piece_over = false;
             knn_near_pairs_local(sh, max_dist, fn[si], cap, &pairs, &piece_over);
@@ -256,7 +255,7 @@ int mi_knn_sharded_near_pairs(mi_knn_sharded* t, float max_dist, uint64_t first_
         // the shard pairs, round by round: the pairs of a round share no shard, each on a host thread of its own
         for (const std::vector<ShardPair>& round : between_schedule(S)) {
             if (over) break;
-            for_each_shard_pair(round, [&](uint32_t ra, uint32_t cb) {
+            call.for_each_shard_pair(round, [&](uint32_t ra, uint32_t cb) {
                 std::vector<JoinPair> pairs;
                 bool piece_over = false;
                 uint64_t stats[4];

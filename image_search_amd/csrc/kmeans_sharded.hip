@@ -21,6 +21,7 @@
 #include "handles.h"
 #include "kmeans_fixed_host.h"
 #include "kmeans_update.h"
+#include "sharded_call.h"
 #include "two_stage.h"
 
 using namespace mi;
@@ -28,12 +29,6 @@ using namespace mi;
 namespace {
 
 constexpr uint64_t MERGE_CHUNK = 1ull << 21;   // 64-bit sums copied to shard 0's device at a time (16 MB)
-
-void copy_between(void* dst, int dst_dev, const void* src, int src_dev, size_t bytes, hipStream_t s) {
-    if (bytes == 0) return;
-    if (dst_dev == src_dev) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
-    else HIP_CHECK(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, s));
-}
 
 // one shard's state for the call; its device memory lives in a.scratch, on the shard's device
 struct KmShard {
@@ -115,22 +110,23 @@ void update_round(mi_knn_sharded* t, std::vector<std::unique_ptr<KmShard>>& st, 
     }
 }
 
-// t->mu held; arguments checked; everything lands in `out`, by global row
-void sharded_kmeans_run(mi_knn_sharded* t, const float* centroids, uint32_t C, uint32_t max_iters, ShardedKmeansOut* out) {
+// arguments checked; everything lands in `out`, by global row
+void sharded_kmeans_run(ShardedCall& call, const float* centroids, uint32_t C, uint32_t max_iters, ShardedKmeansOut* out) {
+    mi_knn_sharded* t = call.t;
     for (uint64_t& v : t->kmeans_stats) v = 0;
     check_mirror_dim(t->dim, "the assign's");
     if (!km_fixed_rows_ok(t->rows)) fail(MI_ERR_UNSUPPORTED, "at most 2^32 - 1 rows (got %llu)", (unsigned long long)t->rows);
-    sharded_deliver_all(t);
+    call.ready();
     const uint64_t G = t->rows;
     if (G == 0) return;
-    const uint32_t S = t->n(), dim = t->dim;
+    const uint32_t S = call.n, dim = t->dim;
     const size_t cbytes = (size_t)C * dim * sizeof(float);
     std::vector<std::unique_ptr<KmShard>> st(S);
     for (uint32_t si = 0; si < S; ++si) st[si].reset(new KmShard);
     Drain drain{st};
 
     // the shards' state: the rows' mirror and 1 / |x| once, the start centroids
-    for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
+    call.for_each_shard([&](uint32_t si, mi_knn* sh) {
         std::lock_guard<std::mutex> l(sh->mu);
         KmShard& x = *st[si];
         x.sh = sh;
@@ -179,7 +175,7 @@ void sharded_kmeans_run(mi_knn_sharded* t, const float* centroids, uint32_t C, u
     std::vector<uint64_t> ch(S);
     for (;;) {
         std::fill(ch.begin(), ch.end(), 0);
-        for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
+        call.for_each_shard([&](uint32_t si, mi_knn* sh) {
             KmShard& x = *st[si];
             if (x.n_rows == 0) return;
             std::lock_guard<std::mutex> l(sh->mu);
@@ -204,7 +200,7 @@ void sharded_kmeans_run(mi_knn_sharded* t, const float* centroids, uint32_t C, u
     res.dist.assign(G, 0.0f);
     if (it > 0) res.centroids.resize((size_t)C * dim);
     std::vector<uint32_t> segs(S, 0);
-    for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
+    call.for_each_shard([&](uint32_t si, mi_knn* sh) {
         KmShard& x = *st[si];
         if (x.n_rows == 0) return;
         std::lock_guard<std::mutex> l(sh->mu);
@@ -244,11 +240,10 @@ int mi_knn_sharded_kmeans(mi_knn_sharded* t, float* centroids, uint32_t C, uint3
         if (!centroids) fail(MI_ERR_INVALID, "vectors is null");
         if (C == 0) fail(MI_ERR_INVALID, "C must be >= 1");
         if (C > ASSIGN_MAX_C) fail(MI_ERR_UNSUPPORTED, "at most %u vectors (got %u)", ASSIGN_MAX_C, C);
-        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
         ShardedKmeansOut out;
         {
-            std::lock_guard<std::mutex> l(t->mu);
-            sharded_kmeans_run(t, centroids, C, max_iters, &out);
+            ShardedCall call(t);
+            sharded_kmeans_run(call, centroids, C, max_iters, &out);
         }
         if (labels && !out.labels.empty()) std::memcpy(labels, out.labels.data(), out.labels.size() * sizeof(uint32_t));
         if (dist && !out.dist.empty()) std::memcpy(dist, out.dist.data(), out.dist.size() * sizeof(float));

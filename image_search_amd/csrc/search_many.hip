@@ -11,20 +11,15 @@
 // column ranges — only its emit pass: the strip's thresholds stay valid for every piece.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "common.h"
 #include "handles.h"
 #include "search_many_kernels.h"
+#include "sharded_call.h"
 #include "two_stage.h"
-
-namespace mi {
-void merge_lists(const uint64_t* idx_in, const float* dist_in, uint32_t lists, uint32_t k, uint64_t* idx, float* dist);   // core.hip
-}
 
 using namespace mi;
 
@@ -275,29 +270,12 @@ int mi_knn_neighbors(mi_knn* t, uint64_t first, uint64_t n, uint32_t k, uint64_t
 
 int mi_knn_sharded_search_many(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, uint64_t* idx, float* dist) {
     return guarded([&] {
-        if (!t) fail(MI_ERR_INVALID, "null table handle");
-        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
+        ShardedCall call(t);
         check_args(t->shard[0], q, nq, k, idx, dist);
-        std::lock_guard<std::mutex> l(t->mu);
-        sharded_deliver_all(t);
-        // every shard on its own stream; the lists carry global ids
-        const uint32_t n = t->n();
-        const size_t el = (size_t)nq * k;
-        std::vector<uint64_t> all_idx(el * n);
-        std::vector<float> all_dist(el * n);
-        for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
-            search_many_local(sh, q, nq, k, all_idx.data() + el * si, all_dist.data() + el * si);
-        });
-        // mi_knn_merge's ordering, query by query
-        std::vector<uint64_t> li((size_t)n * k);
-        std::vector<float> ld((size_t)n * k);
-        for (uint32_t u = 0; u < nq; ++u) {
-            for (uint32_t si = 0; si < n; ++si) {
-                std::memcpy(li.data() + (size_t)si * k, all_idx.data() + el * si + (size_t)u * k, k * sizeof(uint64_t));
-                std::memcpy(ld.data() + (size_t)si * k, all_dist.data() + el * si + (size_t)u * k, k * sizeof(float));
-            }
-            merge_lists(li.data(), ld.data(), n, k, idx + (size_t)u * k, dist + (size_t)u * k);
-        }
+        // every shard on its own stream; the lists carry global ids and meet in mi_knn_merge's ordering, query by query
+        ShardLists<> all(call.n, nq, k);
+        call.for_each_shard([&](uint32_t si, mi_knn* sh) { search_many_local(sh, q, nq, k, all.idx(si), all.dist(si)); });
+        merge_shard_lists(all, idx, dist);
     });
 }
 

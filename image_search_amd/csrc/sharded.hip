@@ -37,19 +37,11 @@
 #include <vector>
 
 #include "common.h"
-#include "compound_host.h"
 #include "handles.h"
-#include "grouped_host.h"
-#include "ordered_host.h"
-#include "page_host.h"
-#include "two_stage.h"
+#include "sharded_call.h"
 #include "where_host.h"
 
 using namespace mi;
-
-namespace mi {
-void merge_lists(const uint64_t* idx_in, const float* dist_in, uint32_t lists, uint32_t k, uint64_t* idx, float* dist);   // core.hip
-}
 
 namespace {
 
@@ -242,38 +234,6 @@ void fsync_dir_of(const std::string& path) {
     if (d) { (void)fsync(fileno(d)); std::fclose(d); }
 }
 
-// A list of global ids, every one checked against t->rows before anything runs, dealt to the shards that hold them (in the
-// list's order).  listed == false: the caller gave no list, every shard answers for all its rows.
-struct ShardIds {
-    std::vector<std::vector<uint64_t>> per;   // [shard]
-    bool listed;
-    // what shard s's call takes: null = no list; a shard that holds none of the ids gets an empty candidate set, not "every row"
-    const uint64_t* of(uint32_t s) const {
-        static const uint64_t none = 0;
-        return !listed ? nullptr : per[s].empty() ? &none : per[s].data();
-    }
-    uint64_t n_of(uint32_t s) const { return per[s].size(); }
-};
-ShardIds route_list(const mi_knn_sharded* t, const uint64_t* ids, uint64_t n_ids) {
-    ShardIds r{std::vector<std::vector<uint64_t>>(t->n()), ids != nullptr};
-    for (uint64_t i = 0; i < n_ids; ++i) {
-        if (ids[i] >= t->rows)
-            fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)ids[i], (unsigned long long)t->rows);
-        uint32_t s; uint64_t local;
-        sharded_place(t, ids[i], &s, &local);
-        r.per[s].push_back(ids[i]);
-    }
-    return r;
-}
-
-// out[c] = the sum over the n shards of all[shard][c], the four counters of a scan call
-void sum_counts4(const std::vector<uint64_t>& all, uint32_t n, uint64_t out[4]) {
-    for (int c = 0; c < 4; ++c) {
-        out[c] = 0;
-        for (uint32_t si = 0; si < n; ++si) out[c] += all[(size_t)si * 4 + c];
-    }
-}
-
 }  // namespace
 
 namespace mi {
@@ -404,8 +364,7 @@ int mi_knn_sharded_create(uint32_t dim, const int* devices, int n_dev, uint32_t 
         t->devices.assign(devices, devices + n_dev);
         for (int s = 0; s < n_dev; ++s) {
             mi_knn* h = nullptr;
-            const int e = mi_knn_create(dim, devices[s], &h);
-            if (e != MI_OK) fail(e, "%s", mi_last_error());
+            call_ok(mi_knn_create(dim, devices[s], &h));
             h->cyc_block = block_rows; h->cyc_n = (uint32_t)n_dev; h->cyc_rank = (uint32_t)s;
             t->shard.push_back(h);
         }
@@ -476,8 +435,7 @@ int mi_knn_sharded_set_option(mi_knn_sharded* t, const char* key, int value) {
         if (!t || !key) fail(MI_ERR_INVALID, "null argument");
         std::lock_guard<std::mutex> l(t->mu);
         for (mi_knn* s : t->shard) {  // the options of mi_knn_set_option, applied to every shard
-            const int e = mi_knn_set_option(s, key, value);
-            if (e != MI_OK) fail(e, "%s", mi_last_error());
+            call_ok(mi_knn_set_option(s, key, value));
         }
     });
 }
@@ -489,8 +447,7 @@ int mi_knn_sharded_reserve(mi_knn_sharded* t, uint64_t rows) {
         for (uint32_t s = 0; s < t->n(); ++s) {
             // whole blocks: the shard that owns the last, partial block must be able to fill it
             const uint64_t mine = (sharded_rows_of(t, rows, s) + t->block - 1) / t->block * t->block;
-            const int e = mi_knn_reserve(t->shard[s], mine);
-            if (e != MI_OK) fail(e, "%s", mi_last_error());
+            call_ok(mi_knn_reserve(t->shard[s], mine));
         }
     });
 }
@@ -506,8 +463,7 @@ int mi_knn_sharded_append(mi_knn_sharded* t, const float* rows, uint64_t n, uint
             for_runs(t, t->rows, n, [&](uint64_t r, uint64_t len, uint32_t s, uint64_t local) {
                 if (local != t->shard[s]->rows) fail(MI_ERR_INVALID, "shard %u out of step (%llu rows, expected %llu)", s,
                                                      (unsigned long long)t->shard[s]->rows, (unsigned long long)local);
-                const int e = mi_knn_append(t->shard[s], rows + (r - t->rows) * t->dim, len);
-                if (e != MI_OK) fail(e, "%s", mi_last_error());
+                call_ok(mi_knn_append(t->shard[s], rows + (r - t->rows) * t->dim, len));
             });
         } catch (...) {
             roll_back(t);  // the shards that took their runs give them back: the table stays usable
@@ -539,8 +495,7 @@ int mi_knn_sharded_append_synthetic(mi_knn_sharded* t, uint64_t seed, uint64_t f
         std::lock_guard<std::mutex> l(t->mu);
         try {
             for_runs(t, t->rows, n, [&](uint64_t r, uint64_t len, uint32_t s, uint64_t) {
-                const int e = mi_knn_append_synthetic(t->shard[s], seed, first_row + (r - t->rows), len);
-                if (e != MI_OK) fail(e, "%s", mi_last_error());
+                call_ok(mi_knn_append_synthetic(t->shard[s], seed, first_row + (r - t->rows), len));
             });
         } catch (...) {
             roll_back(t);
@@ -559,8 +514,7 @@ int mi_knn_sharded_get_rows(mi_knn_sharded* t, uint64_t first, uint64_t n, float
         if (first + n > t->rows) fail(MI_ERR_INVALID, "rows [%llu,%llu) out of range (size %llu)", (unsigned long long)first,
                                       (unsigned long long)(first + n), (unsigned long long)t->rows);
         for_runs(t, first, n, [&](uint64_t r, uint64_t len, uint32_t s, uint64_t local) {
-            const int e = mi_knn_get_rows(t->shard[s], local, len, out + (r - first) * t->dim);
-            if (e != MI_OK) fail(e, "%s", mi_last_error());
+            call_ok(mi_knn_get_rows(t->shard[s], local, len, out + (r - first) * t->dim));
         });
     });
 }
@@ -599,34 +553,15 @@ int mi_knn_sharded_search_filtered(mi_knn_sharded* t, const float* q, uint32_t n
         check_sharded_search(t, q, nq, k, idx, dist);
         if (k > 4096) fail(MI_ERR_UNSUPPORTED, "a filtered search takes k <= 4096 (got %u)", k);
         if (n_ids && !ids) fail(MI_ERR_INVALID, "ids is null");
-        std::lock_guard<std::mutex> l(t->mu);
-        const ShardIds among = route_list(t, ids, n_ids);
+        ShardedCall call(t, ids, n_ids);
         if (nq == 0) return;
-        sharded_search_enqueue(t, q, nq, k, idx, dist, &among.per);
-        sharded_deliver_all(t);
+        sharded_search_enqueue(t, q, nq, k, idx, dist, &call.ids.ids);
+        call.ready();
     });
 }
 
-// the predicate calls on global ids (where.hip): count = the shards' counts summed; search = every shard's own list and
-// gathered search, the usual exchange and merge; waits for the results
-int mi_knn_sharded_count_where(mi_knn_sharded* t, const mi_knn_where* w, uint64_t* count) {
-    return guarded([&] {
-        const char* why = "";
-        const int bad = where_check_rows_args(t, w, nullptr, 0, count, &why);
-        if (bad != MI_OK) fail(bad, "%s", why);
-        std::lock_guard<std::mutex> l(t->mu);
-        sharded_deliver_all(t);
-        uint64_t sum = 0;
-        for (mi_knn* sh : t->shard) {
-            uint64_t one = 0;
-            const int e = mi_knn_count_where(sh, w, &one);
-            if (e != MI_OK) fail(e, "%s", mi_last_error());
-            sum += one;
-        }
-        *count = sum;
-    });
-}
-
+// the predicate search on global ids (where.hip): every shard's own list and gathered search, the usual exchange and merge;
+// waits for the results.  matched = the shards' counts summed (mi_knn_sharded_count_where: sharded_calls.hip)
 int mi_knn_sharded_search_where(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, const mi_knn_where* w, uint64_t* idx,
                                 float* dist, uint64_t* matched) {
     return guarded([&] {
@@ -634,10 +569,10 @@ int mi_knn_sharded_search_where(mi_knn_sharded* t, const float* q, uint32_t nq, 
         const int bad = where_check_search_args(t, q, nq, k, w, idx, dist, &why);
         if (bad != MI_OK) fail(bad, "%s (k %u)", why, k);
         check_sharded_search(t, q, nq, k, idx, dist);
-        std::lock_guard<std::mutex> l(t->mu);
+        ShardedCall call(t);
         if (nq) {
             sharded_search_enqueue(t, q, nq, k, idx, dist, nullptr, w);
-            sharded_deliver_all(t);
+            call.ready();
             if (matched) {  // every shard's list is still the one this search built
                 *matched = 0;
                 for (mi_knn* sh : t->shard) {
@@ -646,188 +581,7 @@ int mi_knn_sharded_search_where(mi_knn_sharded* t, const float* q, uint32_t nq, 
                 }
             }
         } else if (matched) {
-            *matched = 0;
-            for (mi_knn* sh : t->shard) {
-                uint64_t one = 0;
-                const int e = mi_knn_count_where(sh, w, &one);
-                if (e != MI_OK) fail(e, "%s", mi_last_error());
-                *matched += one;
-            }
-        }
-    });
-}
-
-// mi_knn_search_compound on global ids: every shard answers for the rows (the ids of `among`) it holds, on its own stream and
-// host thread; the lists carry global ids and are merged with mi_knn_merge's ordering
-int mi_knn_sharded_search_compound(mi_knn_sharded* t, const float* pos, uint32_t n_pos, int mode, const float* neg,
-                                   const float* neg_within, uint32_t n_neg, uint32_t k, const uint64_t* among, uint64_t n_among,
-                                   uint64_t* idx, float* dist) {
-    return guarded([&] {
-        const char* why = "";
-        const int bad = compound_check_args(t, pos, n_pos, mode, neg, neg_within, n_neg, k, among, n_among, idx, dist, &why);
-        if (bad != MI_OK) fail(bad, "%s (n_pos %u, n_neg %u, mode %d, k %u)", why, n_pos, n_neg, mode, k);
-        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
-        std::lock_guard<std::mutex> l(t->mu);
-        const uint32_t n = t->n();
-        const ShardIds mine = route_list(t, among, n_among);
-        sharded_deliver_all(t);
-        std::vector<uint64_t> all_idx((size_t)n * k);
-        std::vector<float> all_dist((size_t)n * k);
-        for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
-            knn_search_compound(sh, pos, n_pos, mode, neg, neg_within, n_neg, k, mine.of(si), mine.n_of(si), all_idx.data() + (size_t)si * k,
-                                all_dist.data() + (size_t)si * k, nullptr);
-        });
-        merge_lists(all_idx.data(), all_dist.data(), n, k, idx, dist);
-    });
-}
-
-// mi_knn_search_page on global ids: every shard answers for the rows (the ids of `among`) it holds, on its own stream and host
-// thread.  A shard's local rows ascend with their global ids, so its window opens at (after_dist, the number of its rows whose
-// global id is <= after_id) — page_host.h; the lists carry global ids and are merged with mi_knn_merge's ordering, the counts
-// are summed
-int mi_knn_sharded_search_page(mi_knn_sharded* t, const float* q, uint32_t k, float after_dist, uint64_t after_id, float max_dist,
-                               const uint64_t* among, uint64_t n_among, uint64_t* idx, float* dist, uint64_t counts[4]) {
-    return guarded([&] {
-        const char* why = "";
-        const int bad = page_check_args(t, q, k, after_dist, after_id, max_dist, among, n_among, idx, dist, &why);
-        if (bad != MI_OK) fail(bad, "%s (k %u)", why, k);
-        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
-        std::lock_guard<std::mutex> l(t->mu);
-        const uint32_t n = t->n();
-        const ShardIds mine = route_list(t, among, n_among);
-        if (after_id != MI_KNN_NO_ID && after_id >= t->rows)
-            fail(MI_ERR_INVALID, "after_id %llu is not a row of this table (%llu rows)", (unsigned long long)after_id, (unsigned long long)t->rows);
-        sharded_deliver_all(t);
-        std::vector<uint64_t> all_idx((size_t)n * k), all_counts((size_t)n * 4, 0);
-        std::vector<float> all_dist((size_t)n * k);
-        for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
-            const uint64_t first_key = after_id == MI_KNN_NO_ID ? 0 : page_first_key_at(after_dist, sharded_rows_of(t, after_id + 1, si));
-            knn_search_page(sh, q, k, false, 0.0f, MI_KNN_NO_ID, first_key, max_dist, mine.of(si), mine.n_of(si),
-                            all_idx.data() + (size_t)si * k, all_dist.data() + (size_t)si * k, all_counts.data() + (size_t)si * 4);
-        });
-        std::vector<uint64_t> m_idx(k);
-        std::vector<float> m_dist(k);
-        merge_lists(all_idx.data(), all_dist.data(), n, k, m_idx.data(), m_dist.data());
-        std::copy(m_idx.begin(), m_idx.end(), idx);
-        std::copy(m_dist.begin(), m_dist.end(), dist);
-        if (counts) sum_counts4(all_counts, n, counts);
-    });
-}
-
-// mi_knn_search_ordered on global ids: every shard runs the call on its own rows, on its own stream and host thread.  A shard's
-// local rows ascend with their global ids, so its cursor is (okey(after_stamp), the number of its rows whose global id is <=
-// after_id) — ordered_host.h; the lists carry global ids and stamps and are merged by (okey, id), the counts are summed
-int mi_knn_sharded_search_ordered(mi_knn_sharded* t, const float* q, uint32_t k, float max_dist, const mi_knn_where* w, uint32_t flags,
-                                  int64_t after_stamp, uint64_t after_id, uint64_t* idx, float* dist, int64_t* stamps, uint64_t counts[4]) {
-    return guarded([&] {
-        const char* why = "";
-        const int bad = ordered_check_args(t, q, k, max_dist, w, flags, idx, dist, &why);
-        if (bad != MI_OK) fail(bad, "%s (k %u)", why, k);
-        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
-        std::lock_guard<std::mutex> l(t->mu);
-        const uint32_t n = t->n();
-        if ((flags & MI_KNN_ORDER_AFTER) && after_id >= t->rows)
-            fail(MI_ERR_INVALID, "after_id %llu is not a row of this table (%llu rows)", (unsigned long long)after_id, (unsigned long long)t->rows);
-        sharded_deliver_all(t);
-        std::vector<uint64_t> all_idx((size_t)n * k), all_counts((size_t)n * 4, 0);
-        std::vector<float> all_dist((size_t)n * k);
-        std::vector<int64_t> all_stamps((size_t)n * k);
-        for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
-            const OrderedCursor cur = ordered_cursor_shard(t->block, n, si, flags, after_stamp, after_id);
-            knn_search_ordered(sh, q, k, max_dist, w, flags, after_stamp, after_id, &cur, all_idx.data() + (size_t)si * k,
-                               all_dist.data() + (size_t)si * k, all_stamps.data() + (size_t)si * k, all_counts.data() + (size_t)si * 4);
-        });
-        std::vector<uint64_t> m_idx(k);
-        std::vector<float> m_dist(k);
-        std::vector<int64_t> m_stamps(k);
-        ordered_merge(all_idx.data(), all_dist.data(), all_stamps.data(), n, k, (flags & MI_KNN_ORDER_DESC) != 0, m_idx.data(), m_dist.data(),
-                      m_stamps.data());
-        std::copy(m_idx.begin(), m_idx.end(), idx);
-        std::copy(m_dist.begin(), m_dist.end(), dist);
-        if (stamps) std::copy(m_stamps.begin(), m_stamps.end(), stamps);
-        if (counts) sum_counts4(all_counts, n, counts);
-    });
-}
-
-// mi_knn_stamp_histogram over all shards: every shard counts its own rows, the host sums the bins
-int mi_knn_sharded_stamp_histogram(mi_knn_sharded* t, const float* q, float max_dist, const mi_knn_where* w, const int64_t* edges,
-                                   uint32_t n_edges, uint64_t* hist) {
-    return guarded([&] {
-        const char* why = "";
-        const int bad = ordered_check_hist_args(t, q, max_dist, w, edges, n_edges, hist, &why);
-        if (bad != MI_OK) fail(bad, "%s (n_edges %u)", why, n_edges);
-        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
-        std::lock_guard<std::mutex> l(t->mu);
-        const uint32_t n = t->n();
-        const size_t bins = (size_t)n_edges + 1;
-        sharded_deliver_all(t);
-        std::vector<uint64_t> all((size_t)n * bins, 0);
-        for_each_shard(t, [&](uint32_t si, mi_knn* sh) { knn_stamp_histogram(sh, q, max_dist, w, edges, n_edges, all.data() + (size_t)si * bins); });
-        for (size_t b = 0; b < bins; ++b) {
-            uint64_t sum = 0;
-            for (uint32_t si = 0; si < n; ++si) sum += all[(size_t)si * bins + b];
-            hist[b] = sum;
-        }
-    });
-}
-
-// mi_knn_search_grouped on global ids: every shard answers with its k best representatives (global ids, its own column); the
-// host merges them by group id (grouped_host.h: grouped_merge).  members of the winners: every shard gathers its counts of the
-// k winning groups on the device, the host sums k words per shard.  facets / totals[0] need the shards' whole count arrays.
-int mi_knn_sharded_search_grouped(mi_knn_sharded* t, const float* q, uint32_t k, float max_dist, const uint64_t* among,
-                                  uint64_t n_among, uint64_t* idx, float* dist, uint32_t* group, uint64_t* members,
-                                  uint64_t* facets, uint64_t cap_facets, uint64_t totals[4]) {
-    return guarded([&] {
-        const char* why = "";
-        const int bad = grouped_check_args(t, q, k, max_dist, among, n_among, idx, dist, &why);
-        if (bad != MI_OK) fail(bad, "%s (k %u)", why, k);
-        if (t->shard.empty()) fail(MI_ERR_INVALID, "a table without shards");
-        std::lock_guard<std::mutex> l(t->mu);
-        const uint32_t n = t->n();
-        uint64_t n_groups = 0;
-        for (mi_knn* sh : t->shard) {
-            std::lock_guard<std::mutex> ls(sh->mu);
-            n_groups = std::max<uint64_t>(n_groups, sh->n_groups);
-        }
-        if (facets && cap_facets < n_groups)
-            fail(MI_ERR_INVALID, "facets holds %llu entries, the table has %llu groups", (unsigned long long)cap_facets, (unsigned long long)n_groups);
-        const ShardIds mine = route_list(t, among, n_among);
-        sharded_deliver_all(t);
-        const bool sums = facets || totals;
-        std::vector<uint64_t> all_idx((size_t)n * k), all_totals((size_t)n * 4, 0);
-        std::vector<float> all_dist((size_t)n * k);
-        std::vector<uint32_t> all_group((size_t)n * k);
-        std::vector<std::vector<uint32_t>> cnt(n);
-        for_each_shard(t, [&](uint32_t si, mi_knn* sh) {
-            knn_search_grouped(sh, q, k, max_dist, mine.of(si), mine.n_of(si), all_idx.data() + (size_t)si * k,
-                               all_dist.data() + (size_t)si * k, all_group.data() + (size_t)si * k, nullptr, nullptr, 0,
-                               all_totals.data() + (size_t)si * 4, sums ? &cnt[si] : nullptr);
-        });
-        std::vector<uint64_t> m_idx(k);
-        std::vector<float> m_dist(k);
-        std::vector<uint32_t> m_group(k);
-        grouped_merge(all_idx.data(), all_dist.data(), all_group.data(), n, k, m_idx.data(), m_dist.data(), m_group.data());
-        if (members) {
-            std::vector<uint32_t> part((size_t)n * k, 0);
-            for_each_shard(t, [&](uint32_t si, mi_knn* sh) { knn_grouped_members(sh, m_group.data(), k, part.data() + (size_t)si * k); });
-            for (uint32_t j = 0; j < k; ++j) {
-                uint64_t m = m_idx[j] == MI_KNN_NO_ID ? 0 : m_group[j] == MI_KNN_NO_GROUP ? 1 : 0;
-                if (m_group[j] != MI_KNN_NO_GROUP)
-                    for (uint32_t si = 0; si < n; ++si) m += part[(size_t)si * k + j];
-                members[j] = m;
-            }
-        }
-        std::copy(m_idx.begin(), m_idx.end(), idx);
-        std::copy(m_dist.begin(), m_dist.end(), dist);
-        if (group) std::copy(m_group.begin(), m_group.end(), group);
-        if (sums) {
-            std::vector<uint64_t> reps(n);
-            for (uint32_t si = 0; si < n; ++si) reps[si] = all_totals[(size_t)si * 4];
-            const uint64_t total_reps = grouped_sum_counts(cnt, reps.data(), n_groups, facets);
-            if (totals) {
-                sum_counts4(all_totals, n, totals);
-                totals[0] = total_reps;   // representatives are counted per group over all shards, not per shard
-            }
+            *matched = sharded_count_where(t, w);
         }
     });
 }
@@ -837,197 +591,6 @@ int mi_knn_sharded_sync(mi_knn_sharded* t) {
         if (!t) fail(MI_ERR_INVALID, "null table handle");
         std::lock_guard<std::mutex> l(t->mu);
         sharded_deliver_all(t);
-    });
-}
-
-}  // extern "C"
-
-// ---- deleted rows: every shard is an mi_knn whose ids are the global ones (base 0, the block-cyclic map) ------------
-namespace {
-// t->mu held: every id checked first (a call with one bad id deletes nothing), then each shard takes its own ids
-uint64_t delete_locked(mi_knn_sharded* t, const uint64_t* ids, uint64_t n) {
-    const std::vector<std::vector<uint64_t>> per = route_list(t, ids, n).per;
-    uint64_t newly = 0;
-    for (uint32_t s = 0; s < t->n(); ++s) {
-        if (per[s].empty()) continue;
-        uint64_t m = 0;
-        const int e = mi_knn_delete(t->shard[s], per[s].data(), per[s].size(), &m);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
-        newly += m;
-    }
-    return newly;
-}
-// t->mu held: the deleted global ids, ascending
-std::vector<uint64_t> deleted_locked(mi_knn_sharded* t) {
-    std::vector<uint64_t> all;
-    for (mi_knn* sh : t->shard) {
-        uint64_t c = 0;
-        if (mi_knn_deleted(sh, nullptr, 0, &c) != MI_OK) fail(MI_ERR_INVALID, "%s", mi_last_error());
-        const size_t at = all.size();
-        all.resize(at + c);
-        if (c && mi_knn_deleted(sh, all.data() + at, c, &c) != MI_OK) fail(MI_ERR_INVALID, "%s", mi_last_error());
-    }
-    std::sort(all.begin(), all.end());
-    return all;
-}
-}  // namespace
-
-extern "C" {
-
-int mi_knn_sharded_delete(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint64_t* newly) {
-    return guarded([&] {
-        if (!t) fail(MI_ERR_INVALID, "null table handle");
-        if (newly) *newly = 0;
-        if (n == 0) return;
-        if (!ids) fail(MI_ERR_INVALID, "ids is null");
-        std::lock_guard<std::mutex> l(t->mu);
-        const uint64_t m = delete_locked(t, ids, n);
-        if (newly) *newly = m;
-    });
-}
-
-int mi_knn_sharded_deleted(mi_knn_sharded* t, uint64_t* ids, uint64_t cap, uint64_t* count) {
-    return guarded([&] {
-        if (!t || !count) fail(MI_ERR_INVALID, "null argument");
-        std::lock_guard<std::mutex> l(t->mu);
-        const std::vector<uint64_t> all = deleted_locked(t);
-        *count = all.size();
-        if (ids) std::copy(all.begin(), all.begin() + std::min<uint64_t>(cap, all.size()), ids);
-    });
-}
-
-}  // extern "C"
-
-// ---- the group column: every shard keeps the column of its own rows (grouped.hip) -------------------------------------
-namespace {
-// t->mu held: every id (nullptr: the first n global rows) checked first, then f(shard, its ids, the positions they came from)
-template <class F>
-void route_ids(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, F&& f) {
-    if (!ids && n > t->rows) fail(MI_ERR_INVALID, "%llu rows asked of a table of %llu", (unsigned long long)n, (unsigned long long)t->rows);
-    std::vector<std::vector<uint64_t>> per(t->n()), at(t->n());
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint64_t id = ids ? ids[i] : i;
-        if (id >= t->rows)
-            fail(MI_ERR_INVALID, "id %llu is not a row of this table (%llu rows)", (unsigned long long)id, (unsigned long long)t->rows);
-        uint32_t s; uint64_t local;
-        sharded_place(t, id, &s, &local);
-        per[s].push_back(id);
-        at[s].push_back(i);
-    }
-    for (uint32_t s = 0; s < t->n(); ++s)
-        if (!per[s].empty()) f(s, per[s], at[s]);
-}
-void set_groups_locked(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, const uint32_t* groups) {
-    const uint64_t bad = grouped_first_bad(groups, n);   // before any shard is written
-    if (bad < n) fail(MI_ERR_INVALID, "group id %u (entry %llu) is neither below 2^24 nor MI_KNN_NO_GROUP", groups[bad], (unsigned long long)bad);
-    route_ids(t, ids, n, [&](uint32_t s, const std::vector<uint64_t>& mine, const std::vector<uint64_t>& at) {
-        std::vector<uint32_t> g(mine.size());
-        for (size_t i = 0; i < mine.size(); ++i) g[i] = groups[at[i]];
-        const int e = mi_knn_set_groups(t->shard[s], mine.data(), mine.size(), g.data());
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
-    });
-}
-void get_groups_locked(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint32_t* groups) {
-    route_ids(t, ids, n, [&](uint32_t s, const std::vector<uint64_t>& mine, const std::vector<uint64_t>& at) {
-        std::vector<uint32_t> g(mine.size());
-        const int e = mi_knn_get_groups(t->shard[s], mine.data(), mine.size(), g.data());
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
-        for (size_t i = 0; i < mine.size(); ++i) groups[at[i]] = g[i];
-    });
-}
-// the attribute columns (where.hip): the same routing.  A column that is null is neither written nor read
-void set_attrs_locked(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, const uint64_t* tags, const int64_t* stamps) {
-    route_ids(t, ids, n, [&](uint32_t s, const std::vector<uint64_t>& mine, const std::vector<uint64_t>& at) {
-        std::vector<uint64_t> tg(tags ? mine.size() : 0);
-        std::vector<int64_t> st(stamps ? mine.size() : 0);
-        for (size_t i = 0; i < mine.size(); ++i) {
-            if (tags) tg[i] = tags[at[i]];
-            if (stamps) st[i] = stamps[at[i]];
-        }
-        const int e = mi_knn_set_attrs(t->shard[s], mine.data(), mine.size(), tags ? tg.data() : nullptr, stamps ? st.data() : nullptr);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
-    });
-}
-void get_attrs_locked(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint64_t* tags, int64_t* stamps) {
-    route_ids(t, ids, n, [&](uint32_t s, const std::vector<uint64_t>& mine, const std::vector<uint64_t>& at) {
-        std::vector<uint64_t> tg(mine.size());
-        std::vector<int64_t> st(mine.size());
-        const int e = mi_knn_get_attrs(t->shard[s], mine.data(), mine.size(), tg.data(), st.data());
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
-        for (size_t i = 0; i < mine.size(); ++i) {
-            if (tags) tags[at[i]] = tg[i];
-            if (stamps) stamps[at[i]] = st[i];
-        }
-    });
-}
-bool has_attrs_locked(mi_knn_sharded* t) {
-    for (mi_knn* sh : t->shard) {
-        std::lock_guard<std::mutex> ls(sh->mu);
-        if (sh->d_tags) return true;
-    }
-    return false;
-}
-void groups_info_locked(mi_knn_sharded* t, uint64_t info[2]) {
-    info[0] = info[1] = 0;
-    for (mi_knn* sh : t->shard) {
-        uint64_t one[2] = {0, 0};
-        const int e = mi_knn_groups_info(sh, one);
-        if (e != MI_OK) fail(e, "%s", mi_last_error());
-        info[0] = std::max(info[0], one[0]);
-        info[1] += one[1];
-    }
-}
-}  // namespace
-
-extern "C" {
-
-int mi_knn_sharded_set_groups(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, const uint32_t* groups) {
-    return guarded([&] {
-        if (!t) fail(MI_ERR_INVALID, "null table handle");
-        if (n == 0) return;
-        if (!groups) fail(MI_ERR_INVALID, "groups is null");
-        std::lock_guard<std::mutex> l(t->mu);
-        set_groups_locked(t, ids, n, groups);
-    });
-}
-
-int mi_knn_sharded_get_groups(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint32_t* groups) {
-    return guarded([&] {
-        if (!t) fail(MI_ERR_INVALID, "null table handle");
-        if (n == 0) return;
-        if (!groups) fail(MI_ERR_INVALID, "groups is null");
-        std::lock_guard<std::mutex> l(t->mu);
-        get_groups_locked(t, ids, n, groups);
-    });
-}
-
-int mi_knn_sharded_set_attrs(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, const uint64_t* tags, const int64_t* stamps) {
-    return guarded([&] {
-        const char* why = "";
-        const int bad = where_check_attrs_args(t, ids, n, &why);
-        if (bad != MI_OK) fail(bad, "%s", why);
-        if (n == 0 || (!tags && !stamps)) return;
-        std::lock_guard<std::mutex> l(t->mu);
-        set_attrs_locked(t, ids, n, tags, stamps);
-    });
-}
-
-int mi_knn_sharded_get_attrs(mi_knn_sharded* t, const uint64_t* ids, uint64_t n, uint64_t* tags, int64_t* stamps) {
-    return guarded([&] {
-        const char* why = "";
-        const int bad = where_check_attrs_args(t, ids, n, &why);
-        if (bad != MI_OK) fail(bad, "%s", why);
-        if (n == 0) return;
-        std::lock_guard<std::mutex> l(t->mu);
-        get_attrs_locked(t, ids, n, tags, stamps);
-    });
-}
-
-int mi_knn_sharded_groups_info(mi_knn_sharded* t, uint64_t info[2]) {
-    return guarded([&] {
-        if (!t || !info) fail(MI_ERR_INVALID, "null argument");
-        std::lock_guard<std::mutex> l(t->mu);
-        groups_info_locked(t, info);
     });
 }
 
@@ -1042,8 +605,7 @@ int mi_knn_sharded_rebalance(mi_knn_sharded* dst, mi_knn_sharded* src) {
         if (dst->rows != 0) fail(MI_ERR_INVALID, "mi_knn_sharded_rebalance needs an empty destination");
         for (uint32_t s = 0; s < dst->n(); ++s) {
             const uint64_t mine = (sharded_rows_of(dst, src->rows, s) + dst->block - 1) / dst->block * dst->block;
-            const int e = mi_knn_reserve(dst->shard[s], mine);  // one allocation per shard, nothing moves during the copy
-            if (e != MI_OK) fail(e, "%s", mi_last_error());
+            call_ok(mi_knn_reserve(dst->shard[s], mine));  // one allocation per shard, nothing moves during the copy
         }
         try {
             for_runs(src, 0, src->rows, [&](uint64_t, uint64_t len, uint32_t s, uint64_t local) {
@@ -1061,21 +623,26 @@ int mi_knn_sharded_rebalance(mi_knn_sharded* dst, mi_knn_sharded* src) {
                 DeviceGuard g(from->device);
                 if (from->stream) HIP_CHECK(hipStreamSynchronize(from->stream));
             }
-            const std::vector<uint64_t> dead = deleted_locked(src);  // global ids: the same rows in the new layout
-            if (!dead.empty()) delete_locked(dst, dead.data(), dead.size());
+            // the columns (sharded_calls.hip), by global id: the same rows in the new layout
+            const std::vector<uint64_t> dead = sharded_deleted(src);
+            if (!dead.empty()) sharded_delete(dst, dead.data(), dead.size());
             uint64_t ginfo[2];
-            groups_info_locked(src, ginfo);
-            if (ginfo[1]) {  // the group column, by global id as the deletions
+            sharded_groups_info(src, ginfo);
+            if (ginfo[1]) {
                 std::vector<uint32_t> col((size_t)src->rows);
-                get_groups_locked(src, nullptr, src->rows, col.data());
-                set_groups_locked(dst, nullptr, src->rows, col.data());
+                sharded_get_groups(src, nullptr, src->rows, col.data());
+                sharded_set_groups(dst, nullptr, src->rows, col.data());
             }
-            if (has_attrs_locked(src) && src->rows) {  // the attribute columns the same way
-                std::vector<uint64_t> ids((size_t)src->rows), tags((size_t)src->rows);
+            bool has_attrs = false;
+            for (mi_knn* sh : src->shard) {
+                std::lock_guard<std::mutex> ls(sh->mu);
+                has_attrs = has_attrs || sh->d_tags;
+            }
+            if (has_attrs && src->rows) {
+                std::vector<uint64_t> tags((size_t)src->rows);
                 std::vector<int64_t> stamps((size_t)src->rows);
-                for (size_t i = 0; i < ids.size(); ++i) ids[i] = i;
-                get_attrs_locked(src, ids.data(), ids.size(), tags.data(), stamps.data());
-                set_attrs_locked(dst, ids.data(), ids.size(), tags.data(), stamps.data());
+                sharded_get_attrs(src, nullptr, src->rows, tags.data(), stamps.data());
+                sharded_set_attrs(dst, nullptr, src->rows, tags.data(), stamps.data());
             }
         } catch (...) {
             dst->rows = 0;
@@ -1101,8 +668,7 @@ int mi_knn_sharded_save(mi_knn_sharded* t, const char* prefix) {
         try {
             for (uint32_t s = 0; s < t->n(); ++s) {
                 if (fail_after >= 0 && (long)s == fail_after) fail(MI_ERR_IO, "injected failure after %u shard files", s);
-                const int e = mi_knn_save(t->shard[s], shard_file(pre, gen, s, t->n()).c_str());
-                if (e != MI_OK) fail(e, "%s", mi_last_error());
+                call_ok(mi_knn_save(t->shard[s], shard_file(pre, gen, s, t->n()).c_str()));
                 ++written;
             }
             const std::string meta = pre + ".shards", tmp = meta + ".tmp";
@@ -1144,8 +710,7 @@ int mi_knn_sharded_load(mi_knn_sharded* t, const char* prefix) {
             if (on == t->n() && ob == t->block) {
                 try {
                     for (uint32_t s = 0; s < t->n(); ++s) {
-                        const int e = mi_knn_load(t->shard[s], file_of(s).c_str());
-                        if (e != MI_OK) fail(e, "%s", mi_last_error());
+                        call_ok(mi_knn_load(t->shard[s], file_of(s).c_str()));
                         t->shard[s]->base = 0;  // ids come from the block-cyclic map, not from the file's base
                         const uint64_t want = sharded_rows_of(t, orows, s);
                         if (t->shard[s]->rows != want)
@@ -1197,12 +762,10 @@ int mi_knn_sharded_load(mi_knn_sharded* t, const char* prefix) {
                 if (fseeko(fs[s], (off_t)(32 + local * t->dim * 4), SEEK_SET) != 0 ||
                     std::fread(buf.data(), 4, (size_t)len * t->dim, fs[s]) != (size_t)len * t->dim)
                     fail(MI_ERR_IO, "%s is truncated", file_of(s).c_str());
-                const int e = mi_knn_sharded_append(t, buf.data(), len, nullptr);
-                if (e != MI_OK) fail(e, "%s", mi_last_error());
+                call_ok(mi_knn_sharded_append(t, buf.data(), len, nullptr));
             }
             if (!dead.empty()) {
-                const int e = mi_knn_sharded_delete(t, dead.data(), dead.size(), nullptr);
-                if (e != MI_OK) fail(e, "%s", mi_last_error());
+                call_ok(mi_knn_sharded_delete(t, dead.data(), dead.size(), nullptr));
             }
         } catch (...) {
             std::lock_guard<std::mutex> l(t->mu);

@@ -1,13 +1,11 @@
 // two_stage.h — host side shared by the calls whose first stage is the 128 x 128 bf16 tile (tile128.h) and whose second
 // stage rescoring decides in the search's arithmetic: the join, the assign, the multi-label assign and the many-query
 // search.  One call's device memory, the table's mirror for the call, the dispatch over the dims the mirror is built for,
-// the scheme that redoes a launch whose candidates overflowed the buffer, and the per-shard fan-out of the sharded calls.
+// and the scheme that redoes a launch whose candidates overflowed the buffer.
 #pragma once
 #include <algorithm>
 #include <string>
-#include <thread>
 #include <type_traits>
-#include <utility>
 #include <vector>
 
 #include "common.h"
@@ -137,53 +135,6 @@ inline unsigned long long read_count(const unsigned long long* d_count, hipStrea
     HIP_CHECK(hipMemcpyAsync(&n, d_count, sizeof n, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     return n;
-}
-
-// f(si, shard) for every shard, each on a host thread of its own (a shard's call reads its candidate counts back between
-// launches); the first shard that failed is reported.  t->mu held.
-template <class F>
-void for_each_shard(mi_knn_sharded* t, F&& f) {
-    const uint32_t n = t->n();
-    std::vector<int> codes(n, MI_OK);
-    std::vector<std::string> msgs(n);
-    std::vector<std::thread> threads;
-    for (uint32_t si = 0; si < n; ++si) {
-        threads.emplace_back([&, si] {
-            try {
-                f(si, t->shard[si]);
-            } catch (const Error& e) {
-                codes[si] = e.code; msgs[si] = e.what();
-            } catch (const std::exception& e) {
-                codes[si] = MI_ERR_INVALID; msgs[si] = e.what();
-            }
-        });
-    }
-    for (std::thread& th : threads) th.join();
-    for (uint32_t si = 0; si < n; ++si)
-        if (codes[si] != MI_OK) fail(codes[si], "shard %u: %s", si, msgs[si].c_str());
-}
-
-// f(row shard, column shard) for every shard pair of one round of between_schedule (join_between_host.h: the pairs of a round
-// share no shard), each on a host thread of its own; the first pair that failed is reported.  t->mu held.
-template <class F>
-void for_each_shard_pair(const std::vector<std::pair<uint32_t, uint32_t>>& round, F&& f) {
-    std::vector<int> codes(round.size(), MI_OK);
-    std::vector<std::string> msgs(round.size());
-    std::vector<std::thread> threads;
-    for (size_t pi = 0; pi < round.size(); ++pi) {
-        threads.emplace_back([&, pi] {
-            try {
-                f(round[pi].first, round[pi].second);
-            } catch (const Error& e) {
-                codes[pi] = e.code; msgs[pi] = e.what();
-            } catch (const std::exception& e) {
-                codes[pi] = MI_ERR_INVALID; msgs[pi] = e.what();
-            }
-        });
-    }
-    for (std::thread& th : threads) th.join();
-    for (size_t pi = 0; pi < round.size(); ++pi)
-        if (codes[pi] != MI_OK) fail(codes[pi], "shards %u x %u: %s", round[pi].first, round[pi].second, msgs[pi].c_str());
 }
 
 }  // namespace mi
