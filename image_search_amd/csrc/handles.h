@@ -337,6 +337,9 @@ struct mi_knn_sharded {
     // mi_knn_sharded_kmeans_stats: {updates run, bytes copied between shards, segments summed in the last update (all shards),
     // merge launches} of the last call
     uint64_t kmeans_stats[4] = {0, 0, 0, 0};
+    // mi_knn_sharded_summarize_stats: {segments summed (all shards), bytes copied between shards, merge launches (sums and
+    // slots), members} of the last call
+    uint64_t summarize_stats[4] = {0, 0, 0, 0};
     std::mutex mu;
     uint32_t n() const { return (uint32_t)shard.size(); }
 };

@@ -20,6 +20,7 @@
 #include "density_sharded_host.h"   // scatter_to_global
 #include "handles.h"
 #include "kmeans_fixed_host.h"
+#include "kmeans_sharded_merge.h"
 #include "kmeans_update.h"
 #include "sharded_call.h"
 #include "two_stage.h"
@@ -28,25 +29,13 @@ using namespace mi;
 
 namespace {
 
-constexpr uint64_t MERGE_CHUNK = 1ull << 21;   // 64-bit sums copied to shard 0's device at a time (16 MB)
-
-// one shard's state for the call; its device memory lives in a.scratch, on the shard's device
-struct KmShard {
-    mi_knn* sh = nullptr;
+// one shard's state for the call; its device memory lives in a.scratch, on the shard's device.  d_vec is a.d_vec and d_S /
+// d_n are u's where the shard has rows
+struct KmShard : KmPart {
     Assign a;
     KmUpdate u;
     IdMap map{0, 0, 0, 0};
     uint32_t n_rows = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t ev = nullptr;        // shard >= 1: its sums are in place; shard 0: the centroids are
-    float* d_vec = nullptr;         // [C][dim]: the centroids (a.d_vec where the shard has rows)
-    long long* d_S = nullptr;       // [C][dim] / [C]: the shard's sums and sizes (u's where it has rows, zeros otherwise)
-    uint32_t* d_n = nullptr;
-    KmShard() = default;
-    KmShard(const KmShard&) = delete;
-    ~KmShard() {
-        if (ev) (void)hipEventDestroy(ev);
-    }
 };
 
 // every shard's stream idle before the call's device memory goes, on every way out
@@ -70,7 +59,6 @@ struct ShardedKmeansOut {
 void update_round(mi_knn_sharded* t, std::vector<std::unique_ptr<KmShard>>& st, uint32_t C, long long* d_in, uint32_t* d_nin,
                   uint64_t* merges) {
     const uint32_t S = t->n(), dim = t->dim;
-    const uint64_t el = (uint64_t)C * dim;
     for (uint32_t si = 0; si < S; ++si) {
         KmShard& x = *st[si];
         std::lock_guard<std::mutex> l(x.sh->mu);
@@ -79,35 +67,9 @@ void update_round(mi_knn_sharded* t, std::vector<std::unique_ptr<KmShard>>& st, 
             dispatch_nch(dim, [&](auto nch) { x.u.template sums_fixed<decltype(nch)::value>(x.sh, x.s, x.a.d_labels, x.a.d_dist, x.n_rows, C); });
         if (si != 0) HIP_CHECK(hipEventRecord(x.ev, x.s));
     }
-    KmShard& z = *st[0];
-    {
-        std::lock_guard<std::mutex> l(z.sh->mu);
-        DeviceGuard g(z.sh->device);
-        const uint32_t max_blocks = (uint32_t)std::max(z.sh->n_cu, 1) * 8u;
-        for (uint32_t si = 1; si < S; ++si) {
-            KmShard& x = *st[si];
-            HIP_CHECK(hipStreamWaitEvent(z.s, x.ev, 0));
-            copy_between(d_nin, z.sh->device, x.d_n, x.sh->device, (size_t)C * sizeof(uint32_t), z.s);
-            for (uint64_t e0 = 0; e0 < el; e0 += MERGE_CHUNK) {
-                const uint64_t n = std::min<uint64_t>(MERGE_CHUNK, el - e0);
-                copy_between(d_in, z.sh->device, x.d_S + e0, x.sh->device, (size_t)n * sizeof(long long), z.s);
-                const uint32_t blocks = (uint32_t)std::min<uint64_t>(max_blocks, (n + 255) / 256);
-                hipLaunchKernelGGL(km_merge_fixed_kernel, dim3(blocks), dim3(256), 0, z.s, z.d_S + e0, (const long long*)d_in, n, z.d_n,
-                                   (const uint32_t*)d_nin, e0 == 0 ? C : 0u);   // (the sizes ride with the first chunk)
-                HIP_CHECK(hipGetLastError());
-                ++*merges;
-            }
-        }
-        KmUpdate::centroids_fixed(z.s, z.d_S, z.d_n, C, dim, z.d_vec);
-        HIP_CHECK(hipEventRecord(z.ev, z.s));
-    }
-    for (uint32_t si = 1; si < S; ++si) {
-        KmShard& x = *st[si];
-        std::lock_guard<std::mutex> l(x.sh->mu);
-        DeviceGuard g(x.sh->device);
-        HIP_CHECK(hipStreamWaitEvent(x.s, z.ev, 0));
-        copy_between(x.d_vec, x.sh->device, z.d_vec, z.sh->device, (size_t)el * sizeof(float), x.s);
-    }
+    std::vector<KmPart*> parts(S);
+    for (uint32_t si = 0; si < S; ++si) parts[si] = st[si].get();
+    km_merge_and_broadcast(parts, C, dim, d_in, d_nin, merges);   // kmeans_sharded_merge.h
 }
 
 // arguments checked; everything lands in `out`, by global row
@@ -164,8 +126,7 @@ void sharded_kmeans_run(ShardedCall& call, const float* centroids, uint32_t C, u
     uint32_t* d_nin = nullptr;
     if (max_iters > 0 && S > 1) {
         DeviceGuard g(st[0]->sh->device);
-        d_in = (long long*)st[0]->a.scratch.get((size_t)std::min<uint64_t>((uint64_t)C * dim, MERGE_CHUNK) * sizeof(long long));
-        d_nin = (uint32_t*)st[0]->a.scratch.get((size_t)C * sizeof(uint32_t));
+        km_merge_staging(st[0]->a.scratch, C, dim, &d_in, &d_nin);
     }
 
     uint64_t dead = 0;

@@ -838,6 +838,23 @@ class ShardedTable {
     }
     // {updates run, bytes copied between shards, segments summed in the last update, merge launches} of the last kmeans
     std::vector<uint64_t> kmeans_stats() const { std::vector<uint64_t> v(4); check(mi_knn_sharded_kmeans_stats(h_, v.data())); return v; }
+    // EmbeddingTable::summarize over all shards (mi_knn_sharded_summarize): labels / dist by global row id, cover / odd global
+    // ids (a tie goes to the lowest global id); bit for bit what one table holding the same rows returns with its option
+    // "kmeans_fixed_sum" = 1.  labels == nullptr: every shard's part of the group column
+    EmbeddingTable::Summary summarize(const std::vector<uint32_t>* labels, uint32_t C) const {
+        const uint64_t n = size();
+        if (labels && labels->size() != n) throw std::invalid_argument("summarize: one label per row");
+        EmbeddingTable::Summary r;
+        r.centroids.resize((size_t)C * dim_); r.cover_dist.resize(C); r.odd_dist.resize(C); r.dist.resize(n + 1);   // (+ 1: never a null pointer)
+        r.count.resize(C); r.cover.resize(C); r.odd.resize(C); r.measured.resize(C); r.spread.resize(C);
+        check(mi_knn_sharded_summarize(h_, labels && n ? labels->data() : nullptr, C, r.centroids.data(), r.count.data(), r.cover.data(),
+                                       r.cover_dist.data(), r.odd.data(), r.odd_dist.data(), r.measured.data(), r.spread.data(),
+                                       r.dist.data(), r.totals));
+        r.dist.resize(n);
+        return r;
+    }
+    // {segments summed, bytes copied between shards, merge launches, members} of the last summarize
+    std::vector<uint64_t> summarize_stats() const { std::vector<uint64_t> v(4); check(mi_knn_sharded_summarize_stats(h_, v.data())); return v; }
     // EmbeddingTable::assign_multi over all shards (mi_knn_sharded_assign_multi): labels / dist [rows * m] by global row id
     std::pair<std::vector<uint32_t>, std::vector<float>> assign_multi(const std::vector<float>& vectors, uint32_t C, uint32_t m,
                                                                       float max_dist = INFINITY) const {

@@ -712,37 +712,42 @@ class EmbeddingTable:
         spread / measured * 2^-30, NaN where nothing was measured; dist [rows] = a member's distance to its centroid with
         assign's bits, NaN for an unusable row of a group, +inf otherwise; totals {"members", "outside", "unusable",
         "groups"}).  cover and odd are ids; every array indexed by row is indexed by local row."""
-        n = len(self)
-        lab = None
-        if labels is not None:
-            lab = np.ascontiguousarray(np.asarray(labels).reshape(-1).astype(np.uint32))
-            if lab.size != n:
-                raise ValueError(f"{lab.size} labels for {n} rows")
-            if n_groups is None:
-                has = lab[lab != NO_LABEL]
-                n_groups = int(has.max()) + 1 if has.size else 1
-        elif n_groups is None:
-            n_groups = max(int(self.groups_info()["n_groups"]), 1)
-        C = int(n_groups)
-        m = max(C, 0)
-        cent = np.empty((m, self.dim), np.float32)
-        count, cover, odd, measured, spread = (np.empty(m, np.uint64) for _ in range(5))
-        cover_dist, odd_dist, dist = np.empty(m, np.float32), np.empty(m, np.float32), np.empty(n, np.float32)
-        totals = np.zeros(4, np.uint64)
-        check(lib().mi_knn_summarize(self._h, lab.ctypes.data if lab is not None and n else None, C, cent.ctypes.data, count.ctypes.data,
-                                     cover.ctypes.data, cover_dist.ctypes.data, odd.ctypes.data, odd_dist.ctypes.data,
-                                     measured.ctypes.data, spread.ctypes.data, dist.ctypes.data if n else None, totals.ctypes.data))
-        with np.errstate(invalid="ignore", divide="ignore"):
-            mean = np.where(measured > 0, spread.astype(np.float64) / measured.astype(np.float64) * 2.0 ** -30, np.nan)
-        return {"centroids": cent, "count": count, "cover": cover, "cover_dist": cover_dist, "odd": odd, "odd_dist": odd_dist,
-                "measured": measured, "spread": spread, "mean_dist": mean, "dist": dist,
-                "totals": dict(zip(("members", "outside", "unusable", "groups"), (int(v) for v in totals)))}
+        return _summarize_call(lib().mi_knn_summarize, self, labels, n_groups)
 
     def summarize_stats(self) -> dict:
         """mi_knn_summarize_stats, of the last summarize on this table"""
         out = (ctypes.c_uint64 * 4)()
         check(lib().mi_knn_summarize_stats(self._h, out))
         return {"segments": out[0], "workgroups": out[1], "rows": out[2]}
+
+
+def _summarize_call(fn, table, labels, n_groups) -> dict:
+    """EmbeddingTable.summarize / ShardedTable.summarize: fn = mi_knn_summarize or mi_knn_sharded_summarize"""
+    n = len(table)
+    lab = None
+    if labels is not None:
+        lab = np.ascontiguousarray(np.asarray(labels).reshape(-1).astype(np.uint32))
+        if lab.size != n:
+            raise ValueError(f"{lab.size} labels for {n} rows")
+        if n_groups is None:
+            has = lab[lab != NO_LABEL]
+            n_groups = int(has.max()) + 1 if has.size else 1
+    elif n_groups is None:
+        n_groups = max(int(table.groups_info()["n_groups"]), 1)
+    C = int(n_groups)
+    m = max(C, 0)
+    cent = np.empty((m, table.dim), np.float32)
+    count, cover, odd, measured, spread = (np.empty(m, np.uint64) for _ in range(5))
+    cover_dist, odd_dist, dist = np.empty(m, np.float32), np.empty(m, np.float32), np.empty(n, np.float32)
+    totals = np.zeros(4, np.uint64)
+    check(fn(table._h, lab.ctypes.data if lab is not None and n else None, C, cent.ctypes.data, count.ctypes.data,
+             cover.ctypes.data, cover_dist.ctypes.data, odd.ctypes.data, odd_dist.ctypes.data, measured.ctypes.data,
+             spread.ctypes.data, dist.ctypes.data if n else None, totals.ctypes.data))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(measured > 0, spread.astype(np.float64) / measured.astype(np.float64) * 2.0 ** -30, np.nan)
+    return {"centroids": cent, "count": count, "cover": cover, "cover_dist": cover_dist, "odd": odd, "odd_dist": odd_dist,
+            "measured": measured, "spread": spread, "mean_dist": mean, "dist": dist,
+            "totals": dict(zip(("members", "outside", "unusable", "groups"), (int(v) for v in totals)))}
 
 
 def dist_keys(dist) -> np.ndarray:
@@ -1222,6 +1227,22 @@ class ShardedTable:
         out = (ctypes.c_uint64 * 4)()
         check(lib().mi_knn_sharded_kmeans_stats(self._h, out))
         return dict(zip(("updates", "bytes_exchanged", "segments", "merge_launches"), (int(v) for v in out)))
+
+    def summarize(self, labels=None, n_groups: Optional[int] = None) -> dict:
+        """EmbeddingTable.summarize over all shards (mi_knn_sharded_summarize): the same dict with labels and dist by global
+        row id and cover / odd as global ids — bit for bit what one table holding the same rows returns with the option
+        "kmeans_fixed_sum" on, whatever the shard count, block size or devices; a tie goes to the lowest global id.
+        labels=None reads every shard's part of the group column where it lies (set_groups); n_groups defaults as there.
+        The step after kmeans / dbscan on a sharded table; typical_order takes the result as it is.  Only sums, counts,
+        centroids and 32 bytes per group cross between the shards."""
+        return _summarize_call(lib().mi_knn_sharded_summarize, self, labels, n_groups)
+
+    def summarize_stats(self) -> dict:
+        """mi_knn_sharded_summarize_stats, of the last summarize: bytes_exchanged = (shards - 1) * C * (8 dim + 4 + 32) inward
+        (sums, counts and the per-group words) + (shards - 1) * 4 * C * dim outward (centroids)"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_sharded_summarize_stats(self._h, out))
+        return dict(zip(("segments", "bytes_exchanged", "merge_launches", "members"), (int(v) for v in out)))
 
     def duplicates(self, max_dist: float, first_new: int = 0, cap: int = 1 << 20) -> list:
         """Groups of near-duplicate rows: near_pairs through pairs_to_groups — lists of global ids chained by distances

@@ -902,7 +902,7 @@ int mi_knn_sharded_stamp_histogram(mi_knn_sharded* t, const float* q, float max_
                                    uint32_t n_edges, uint64_t* hist);
 /* mi_knn_assign over the whole table: every shard labels its own rows on its own stream (concurrently: no exchange is
  * needed), the results land at the rows' global ids.  labels / dist: [rows of the table]; equals the one-table result
- * bit for bit.  (k-means over a sharded table is not offered: its update needs a cross-shard reduction.) */
+ * bit for bit.  (k-means over a sharded table, whose update needs a cross-shard reduction: mi_knn_sharded_kmeans.) */
 int mi_knn_sharded_assign(mi_knn_sharded* t, const float* vectors, uint32_t C, uint32_t* labels, float* dist);
 /* mi_knn_assign_multi over the whole table, as mi_knn_sharded_assign: per shard, results ([rows of the table][m]) at the
  * rows' global ids; equals the one-table result bit for bit */
@@ -963,6 +963,33 @@ int mi_knn_sharded_kmeans(mi_knn_sharded* t, float* centroids, uint32_t C, uint3
 /* of the last mi_knn_sharded_kmeans: {updates run, bytes copied between shards, segments summed in the last update (all
  * shards), merge launches} */
 int mi_knn_sharded_kmeans_stats(mi_knn_sharded* t, uint64_t out[4]);
+/* mi_knn_summarize over the whole table ("describe the themes mi_knn_sharded_kmeans / mi_knn_sharded_dbscan just found"):
+ * every output is mi_knn_summarize's, evaluated over the table the shards form together, and equals, bit for bit, what ONE
+ * mi_knn holding the same rows returns with "kmeans_fixed_sum" = 1 (the shards' option is not consulted) — for any shard
+ * count, block size and devices.  labels: [rows of the table] by global row, as mi_knn_sharded_kmeans' labels are, or NULL:
+ * every shard reads its own part of the group column (mi_knn_sharded_set_groups) on its device; a column that was never set
+ * means every row belongs to nothing.  dist: [rows of the table] by global row; cover / odd are global ids.
+ *   members, dist   as mi_knn_summarize defines them.
+ *   centroid[c]     (float)((double)S * 2^-30 / count[c]), S the int64 sum of the members' components in units of 2^-30
+ *                   (defined at mi_knn_kmeans) over ALL shards; all zeros if empty.
+ *   cover / odd     the smallest / largest (32-bit distance key, id) over the members of the whole table, by the rules of
+ *                   mi_knn_summarize; a tie goes to the lowest GLOBAL id, whichever shard holds it.
+ *   measured, spread, count, totals   integer sums over the shards.
+ * Every shard marks and sums its own rows; the sums S_s [C][dim] int64 and sizes n_s [C] of shards 1 .. S-1 are added into the
+ * first shard's as mi_knn_sharded_kmeans adds them, the centroids go back to every shard, every shard measures its members
+ * against them, turns the rows in its per-group words into global ids and the first shard folds the words together (min,
+ * max, sum, sum).  Bytes that cross between shards: (S - 1) * C * (8 * dim + 4 + 32) inward and (S - 1) * 4 * C * dim
+ * outward, nothing else; a shard without rows takes part with zeros.  Streams are ordered by events; the host waits once
+ * per shard, for the results.
+ * Every output pointer may be NULL.  1 <= C <= 65536 (MI_ERR_UNSUPPORTED above, MI_ERR_INVALID for 0 or a null handle), judged
+ * before the handle is followed; a table without shards: MI_ERR_INVALID; 2^32 or more rows in the table: MI_ERR_UNSUPPORTED;
+ * dim as mi_knn_near_pairs requires.  An error writes nothing.  An empty table succeeds with mi_knn_summarize's padding. */
+int mi_knn_sharded_summarize(mi_knn_sharded* t, const uint32_t* labels /* [rows] by global row, or NULL */, uint32_t C,
+                             float* centroids, uint64_t* count, uint64_t* cover, float* cover_dist, uint64_t* odd, float* odd_dist,
+                             uint64_t* measured, uint64_t* spread, float* dist /* [rows] by global row */, uint64_t totals[4]);
+/* of the last mi_knn_sharded_summarize: {segments summed (all shards), bytes copied between shards, merge launches (sums and
+ * per-group words together), members} */
+int mi_knn_sharded_summarize_stats(mi_knn_sharded* t, uint64_t out[4]);
 /* Change the layout of a LIVE table: every row of `src` into the empty `dst` (another shard count, device set or block
  * size), block by block, device to device — a plain copy where source and destination shard share a GPU,
  * hipMemcpyPeerAsync over xGMI where they do not; nothing passes through the host.  src is unchanged. */
