@@ -87,6 +87,10 @@ SYMBOLS = {
     "mi_knn_density": (ctypes.c_int, [c_vp, ctypes.c_float, c_vp]),
     "mi_knn_dbscan": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mi_knn_dbscan_stats": (ctypes.c_int, [c_vp, c_u64p]),
+    "mi_knn_density_levels": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp]),
+    "mi_knn_dbscan_levels": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mi_dbscan_levels_tree": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, c_vp,
+                                             ctypes.c_uint64, c_u64p]),
     "mi_index_themes": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint32, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_u64p,
                                        c_u64p, c_u64p]),
     "mi_knn_assign": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp, c_vp]),

@@ -272,8 +272,53 @@ class EmbeddingTable {
         for (uint64_t i = 0; i < n; ++i)
             if (r.cluster[i] != MI_KNN_NO_ID) r.labels[i] = (int64_t)(std::lower_bound(names.begin(), names.end(), r.cluster[i]) - names.begin());
     }
+    // neighbor_counts at several distances from one tile pass (mi_knn_density_levels): [levels][rows], slice l =
+    // neighbor_counts(max_dists[l]).  max_dists: strictly ascending, at most MI_KNN_LEVELS_MAX of them
+    std::vector<uint32_t> neighbor_counts_levels(const std::vector<float>& max_dists) const {
+        std::vector<uint32_t> counts(max_dists.size() * size() + 1);   // (+ 1: never a null pointer)
+        check(mi_knn_density_levels(h_, max_dists.data(), (uint32_t)max_dists.size(), counts.data()));
+        counts.resize(max_dists.size() * size());
+        return counts;
+    }
+    // dbscan at several distances from the two tile passes one call runs (mi_knn_dbscan_levels): levels[l] is what
+    // dbscan(max_dists[l], min_pts) returns, to the bit.  tree (mi_dbscan_levels_tree): one edge per cluster of every level below
+    // the top, ascending by (level, child cluster id); parent = the cluster id one level up that holds the child's core rows — a
+    // border row may sit in a cluster that is not its lower cluster's parent
+    struct TreeEdge { uint32_t level; uint64_t child, parent; };
+    struct DbscanLevels {
+        std::vector<Dbscan> levels;
+        std::vector<TreeEdge> tree;
+    };
+    DbscanLevels dbscan_levels(const std::vector<float>& max_dists, uint32_t min_pts = 5) const {
+        const uint64_t n = size(), L = max_dists.size();
+        std::vector<uint64_t> cluster(L * n + 1), via(L * n + 1), summary(L * 4 + 1);
+        std::vector<float> via_dist(L * n + 1);
+        std::vector<uint32_t> counts(L * n + 1);
+        check(mi_knn_dbscan_levels(h_, max_dists.data(), (uint32_t)L, min_pts, cluster.data(), via.data(), via_dist.data(), counts.data(),
+                                   summary.data()));
+        DbscanLevels r;
+        r.levels.resize(L);
+        for (uint64_t l = 0; l < L; ++l) {
+            Dbscan& d = r.levels[l];
+            d.cluster.assign(cluster.begin() + l * n, cluster.begin() + (l + 1) * n);
+            d.via.assign(via.begin() + l * n, via.begin() + (l + 1) * n);
+            d.via_dist.assign(via_dist.begin() + l * n, via_dist.begin() + (l + 1) * n);
+            d.counts.assign(counts.begin() + l * n, counts.begin() + (l + 1) * n);
+            for (int i = 0; i < 4; ++i) d.summary[i] = summary[4 * l + i];
+            dbscan_trim_and_label(d, n);
+        }
+        uint64_t n_edges = 0;
+        check(mi_dbscan_levels_tree(cluster.data(), counts.data(), n, (uint32_t)L, min_pts, nullptr, nullptr, nullptr, 0, &n_edges));
+        std::vector<uint32_t> level(n_edges + 1);
+        std::vector<uint64_t> child(n_edges + 1), parent(n_edges + 1);
+        check(mi_dbscan_levels_tree(cluster.data(), counts.data(), n, (uint32_t)L, min_pts, level.data(), child.data(), parent.data(), n_edges,
+                                    &n_edges));
+        for (uint64_t i = 0; i < n_edges; ++i) r.tree.push_back(TreeEdge{level[i], child[i], parent[i]});
+        return r;
+    }
     // {candidates pass 1, pairs within, tiles pass 1, candidates pass 2, tiles visited pass 2, tiles skipped pass 2, unions that
-    // merged, stage-1 launches} of the last neighbor_counts / dbscan
+    // merged, stage-1 launches} of the last neighbor_counts / dbscan / neighbor_counts_levels / dbscan_levels (after a *_levels
+    // call: pairs within = the top level's, unions = summed over the levels)
     std::vector<uint64_t> dbscan_stats() const { std::vector<uint64_t> v(8); check(mi_knn_dbscan_stats(h_, v.data())); return v; }
     // label every row by the nearest of C vectors (mi_knn_assign): for a live row what a table of the vectors answers to
     // knn(row, 1), id and distance bits; MI_KNN_NO_LABEL / +inf for a deleted row.  vectors: [C * dim]

@@ -426,8 +426,40 @@ class EmbeddingTable:
         return {"labels": dense_labels(cluster), "cluster": cluster, "via": via, "via_dist": via_dist, "counts": counts,
                 "summary": dict(zip(("clusters", "core", "border", "noise"), (int(v) for v in summary)))}
 
+    def neighbor_counts_levels(self, max_dists) -> np.ndarray:
+        """neighbor_counts at several distances from one tile pass (mi_knn_density_levels): counts [L, rows] uint32, row l =
+        neighbor_counts(max_dists[l]).  max_dists: strictly ascending, at most LEVELS_MAX of them."""
+        d = _levels(max_dists)
+        counts = np.empty((d.size, len(self)), np.uint32)
+        check(lib().mi_knn_density_levels(self._h, d.ctypes.data, d.size, counts.ctypes.data))
+        return counts
+
+    def dbscan_levels(self, max_dists, min_pts: int = 5) -> dict:
+        """dbscan at several distances from the two tile passes one call runs (mi_knn_dbscan_levels): "tighter / looser
+        themes".  max_dists: strictly ascending, at most LEVELS_MAX of them.  Every array is [L, rows] and its row l is what
+        dbscan(max_dists[l], min_pts) returns, to the bit: labels (int64, dense per level), cluster, via, via_dist, counts;
+        dense_labels = labels; summary = a list of L dicts {"clusters", "core", "border", "noise"}.
+        tree: for l < L - 1 an int64 array that maps the dense label of a level-l cluster to the dense label of its parent at
+        level l + 1 — the cluster its core rows lie in there (mi_dbscan_levels_tree).  The tree is over clusters through
+        their core rows: a border row may sit in a level-(l + 1) cluster that is not the parent of its level-l cluster."""
+        d = _levels(max_dists)
+        L, n = d.size, len(self)
+        cluster, via = np.empty((L, n), np.uint64), np.empty((L, n), np.uint64)
+        via_dist, counts = np.empty((L, n), np.float32), np.empty((L, n), np.uint32)
+        summary = np.zeros((L, 4), np.uint64)
+        check(lib().mi_knn_dbscan_levels(self._h, d.ctypes.data, L, int(min_pts), cluster.ctypes.data, via.ctypes.data,
+                                         via_dist.ctypes.data, counts.ctypes.data, summary.ctypes.data))
+        labels = np.stack([dense_labels(c) for c in cluster]) if L else np.empty((0, n), np.int64)
+        level, child, parent = dbscan_levels_tree(cluster, counts, min_pts)
+        names = [np.unique(c[c != NO_ID]) for c in cluster]
+        tree = [np.searchsorted(names[l + 1], parent[level == l]).astype(np.int64) for l in range(L - 1)]
+        return {"labels": labels, "dense_labels": labels, "cluster": cluster, "via": via, "via_dist": via_dist, "counts": counts,
+                "summary": [dict(zip(("clusters", "core", "border", "noise"), (int(v) for v in row))) for row in summary],
+                "tree": tree}
+
     def dbscan_stats(self) -> dict:
-        """mi_knn_dbscan_stats, of the last neighbor_counts / dbscan on this table"""
+        """mi_knn_dbscan_stats, of the last neighbor_counts / dbscan / neighbor_counts_levels / dbscan_levels on this table
+        (after a *_levels call: pairs = those of the top level, unions_merged = summed over the levels)"""
         out = (ctypes.c_uint64 * 8)()
         check(lib().mi_knn_dbscan_stats(self._h, out))
         return dict(zip(("candidates_pass1", "pairs", "tiles_pass1", "candidates_pass2", "tiles_visited", "tiles_skipped",
@@ -829,6 +861,34 @@ def dense_labels(cluster) -> np.ndarray:
     has = cluster != NO_ID
     labels[has] = np.searchsorted(np.unique(cluster[has]), cluster[has])
     return labels
+
+
+LEVELS_MAX = 8   # MI_KNN_LEVELS_MAX
+
+
+def _levels(max_dists) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(max_dists, dtype=np.float32).reshape(-1))
+
+
+def dbscan_levels_tree(cluster, counts, min_pts: int):
+    """The tree between the levels of a dbscan_levels result (mi_dbscan_levels_tree, host only): cluster, counts [L, rows] ->
+    (level uint32, child uint64, parent uint64), one entry per cluster of every level l < L - 1, ascending by (level, child
+    cluster id); parent = the cluster id at level l + 1 that holds the child's core rows."""
+    cluster = np.ascontiguousarray(np.asarray(cluster, np.uint64))
+    counts = np.ascontiguousarray(np.asarray(counts, np.uint32))
+    if cluster.ndim != 2 or cluster.shape != counts.shape:
+        raise ValueError(f"cluster {cluster.shape} and counts {counts.shape} must both be [levels, rows]")
+    L, n = cluster.shape
+    pad = np.zeros(1, np.uint64)   # (never a null pointer for an empty table)
+    pc, pd = (cluster.ctypes.data, counts.ctypes.data) if cluster.size else (pad.ctypes.data, pad.ctypes.data)
+    n_edges = ctypes.c_uint64()
+    check(lib().mi_dbscan_levels_tree(pc, pd, n, L, int(min_pts), None, None, None, 0, ctypes.byref(n_edges)))
+    m = n_edges.value
+    level, child, parent = np.empty(m, np.uint32), np.empty(m, np.uint64), np.empty(m, np.uint64)
+    if m:
+        check(lib().mi_dbscan_levels_tree(pc, pd, n, L, int(min_pts), level.ctypes.data, child.ctypes.data, parent.ctypes.data, m,
+                                          ctypes.byref(n_edges)))
+    return level, child, parent
 
 
 def _groups(ids: np.ndarray, starts: np.ndarray) -> list:
@@ -1745,6 +1805,37 @@ class ImageIndex:
         out = set(int(i) for i in ids) | set(int(i) for i in self.table.deleted())
         noise = [r for r in range(n) if r not in out]   # n_noise.value of them
         return [[self.path(int(i), web=web) for i in g] for g in groups], [self.path(r, web=web) for r in noise]
+
+    def theme_tree(self, max_dists, min_pts: int = 5, web: bool = False):
+        """Themes inside themes (EmbeddingTable.dbscan_levels on the index's table): (themes, noise).  themes = the clusters
+        of the loosest distance max_dists[-1], the largest first, equal sizes by their first row; each a dict {"level",
+        "max_dist", "paths" (ordered by row id), "children"}, children = the clusters of the level below whose core rows lie in
+        it, ordered the same way, down to level 0.  noise = the paths of the top level's noise rows.  Removed paths are in
+        neither.  (A child's border path may be missing from its parent's paths: the tree goes through core rows.)"""
+        d = _levels(max_dists)
+        res = self.table.dbscan_levels(d, min_pts)
+        labels, L = res["labels"], d.size
+        paths = {}
+
+        def path(r):
+            if r not in paths:
+                paths[r] = self.path(r, web=web)
+            return paths[r]
+
+        def nodes(l, which):
+            rows = {c: np.flatnonzero(labels[l] == c) for c in which}
+            out = []
+            for c in sorted(which, key=lambda c: (-rows[c].size, int(rows[c][0]))):
+                kids = [int(k) for k in np.flatnonzero(res["tree"][l - 1] == c)] if l > 0 else []
+                out.append({"level": l, "max_dist": float(d[l]), "paths": [path(int(r)) for r in rows[c]],
+                            "children": nodes(l - 1, kids) if l > 0 else []})
+            return out
+
+        top = labels[L - 1]
+        themes = nodes(L - 1, list(range(int(top.max()) + 1 if top.size else 0)))
+        deleted = set(int(r) for r in self.table.deleted())
+        noise = [path(r) for r in range(top.size) if top[r] < 0 and r not in deleted]
+        return themes, noise
 
     def label(self, vectors: np.ndarray, names: Optional[Sequence[str]] = None, web: bool = False) -> dict:
         """"Tag my library" (EmbeddingTable.assign): {path: (label, distance)} for every path that has not been removed;

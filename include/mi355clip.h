@@ -397,11 +397,42 @@ int mi_knn_near_pairs_between_stats(mi_knn* t, uint64_t out[4]);
 int mi_knn_density(mi_knn* t, float max_dist, uint32_t* counts);
 int mi_knn_dbscan(mi_knn* t, float max_dist, uint32_t min_pts, uint64_t* cluster, uint64_t* via, float* via_dist,
                   uint32_t* counts, uint64_t summary[4]);
-/* of the last mi_knn_density / mi_knn_dbscan on this handle: out = {candidate pairs pass 1, pairs within, tiles pass 1,
- * candidate pairs pass 2, tiles visited pass 2, tiles skipped pass 2 (both blocks must hold a row with a neighbour and one a
- * core: exact), unions that merged two trees, stage-1 launches of both passes (re-runs after an overflow included)}.  The tile
- * counts are those of the launches whose candidates were consumed: visited + skipped = the triangle's tiles. */
+/* of the last mi_knn_density / mi_knn_dbscan / mi_knn_density_levels / mi_knn_dbscan_levels on this handle: out = {candidate
+ * pairs pass 1, pairs within, tiles pass 1, candidate pairs pass 2, tiles visited pass 2, tiles skipped pass 2 (both blocks must
+ * hold a row with a neighbour and one a core: exact), unions that merged two trees, stage-1 launches of both passes (re-runs
+ * after an overflow included)}.  The tile counts are those of the launches whose candidates were consumed: visited + skipped =
+ * the triangle's tiles.  After a *_levels call: pairs within = those of the top level, unions merged = summed over the levels. */
 int mi_knn_dbscan_stats(mi_knn* t, uint64_t out[8]);
+/* Themes at several distances in one pass ("tighter / looser themes" on a slider, a theme that contains bursts): what
+ * n_levels calls of mi_knn_density / mi_knn_dbscan with max_dists[0] < max_dists[1] < ... return on the same table, from the
+ * two tile passes ONE such call runs.  Slice l of every output array ([n_levels][rows], level-major, by local row) is exactly
+ * what mi_knn_density(t, max_dists[l], ...) / mi_knn_dbscan(t, max_dists[l], min_pts, ...) writes: ids, distance bits, counts
+ * and summary ([n_levels][4]), under the definitions above (W, deg, core, clusters named by their smallest core row, border by
+ * the minimum of (dist key, core row), noise, a deleted row nothing at all).  n_levels == 1 is mi_knn_dbscan's result.  For one
+ * min_pts the core sets and the core-core edges only grow with the distance, so the clusters of level l nest inside those of
+ * level l + 1 through their core rows (mi_dbscan_levels_tree).
+ * max_dists: strictly ascending, every entry a number >= 0; 1 <= n_levels <= MI_KNN_LEVELS_MAX.  A null handle, max_dists or
+ * required pointer (counts of mi_knn_density_levels; cluster and summary of mi_knn_dbscan_levels), n_levels 0 or above the
+ * maximum, a NaN, a negative entry, two neighbouring entries that do not ascend strictly (equal ones included), min_pts == 0:
+ * MI_ERR_INVALID.  dim, mirror, "join_cap", stream ordering and the step cap's MI_ERR_HIP: as mi_knn_dbscan; there is no new
+ * option.  Device memory: n_levels * 16 + 1 bytes per row beside the join's buffers, plus the result arrays, all freed before
+ * the call returns.  An error writes nothing.  An empty table is valid. */
+#define MI_KNN_LEVELS_MAX 8
+int mi_knn_density_levels(mi_knn* t, const float* max_dists, uint32_t n_levels, uint32_t* counts);
+int mi_knn_dbscan_levels(mi_knn* t, const float* max_dists, uint32_t n_levels, uint32_t min_pts, uint64_t* cluster, uint64_t* via,
+                         float* via_dist, uint32_t* counts, uint64_t* summary);
+/* The tree between the levels of a mi_knn_dbscan_levels result (host only, no device): the edges (l, cluster id at level l,
+ * cluster id at level l + 1) for l < n_levels - 1, ascending by (l, child), into level / child / parent [cap].  cluster and
+ * counts: the call's arrays, [n_levels][rows].  Row r is a core at level l iff cluster[l][r] != MI_KNN_NO_ID and
+ * counts[l][r] + 1 >= min_pts; the parent of a level-l cluster is the level-(l + 1) cluster of its core rows.  All cores of one
+ * cluster must agree, and a core of level l must lie in a cluster at level l + 1: otherwise the input is no result of the call
+ * above and the answer is MI_ERR_INVALID.  *n_edges is the full count even when cap is smaller (the first cap edges are
+ * written), as for the index calls.  The tree is over clusters through their CORE rows: a border row of a level-l cluster may
+ * sit in a level-(l + 1) cluster that is not the parent of its level-l cluster (a row that becomes a core only at the upper
+ * level may be nearer to it than its lower-level core).  Null cluster, counts or n_edges, an output array null with cap > 0,
+ * n_levels 0 or above the maximum, min_pts == 0: MI_ERR_INVALID; rows == 0 is valid (no edges).  An error writes nothing. */
+int mi_dbscan_levels_tree(const uint64_t* cluster, const uint32_t* counts, uint64_t rows, uint32_t n_levels, uint32_t min_pts,
+                          uint32_t* level, uint64_t* child, uint64_t* parent, uint64_t cap, uint64_t* n_edges);
 /* Label every row by its nearest of C vectors ("tag my library" with C text embeddings; the inner step of k-means): the
  * search turned round.  For every row r of the table (rows = mi_knn_size, deleted rows counted):
  *   r live     labels[r], dist[r] = the first entry of mi_knn_search(T_v, q = row r, k = 1) where T_v holds exactly the C
