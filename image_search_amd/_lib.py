@@ -100,6 +100,11 @@ SYMBOLS = {
     "mi_knn_search_many": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_search_many_stats": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_knn_neighbors": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
+    "mi_knn_search_many_where": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_wherep, c_vp, c_vp, c_u64p]),
+    "mi_knn_neighbors_where": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_wherep, c_vp, c_vp]),
+    "mi_knn_propose_groups": (ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32, c_wherep, c_vp, c_vp, c_vp, c_vp,
+                                             c_u64p]),
+    "mi_knn_propose_groups_stats": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_knn_kmeans": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32),
                                      c_u64p, ctypes.POINTER(ctypes.c_double)]),
     "mi_knn_kmeans_seed": (ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, c_vp,
@@ -176,6 +181,7 @@ SYMBOLS = {
     "mi_knn_sharded_assign": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_sharded_assign_multi": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp]),
     "mi_knn_sharded_search_many": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
+    "mi_knn_sharded_search_many_where": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_wherep, c_vp, c_vp, c_u64p]),
     "mi_knn_sharded_place": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32),
                                             c_u64p]),
     "mi_knn_sharded_id": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, c_u64p]),

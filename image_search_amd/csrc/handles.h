@@ -222,6 +222,8 @@ struct mi_knn {
     // the threshold pass over the column tiles (option "many_sample": 0 = chosen by the table's size)
     uint64_t search_many_stats[4] = {0, 0, 0, 0};
     int many_segments = 0, many_sample = 0;
+    // mi_knn_propose_groups (search_many.hip): {candidates, stage-1 launches, tiles, strips} of the last call
+    uint64_t propose_stats[4] = {0, 0, 0, 0};
     // mi_knn_kmeans_seed (kmeans_seed.hip): {candidates, passes run, fallback picks, 0} of the last call
     uint64_t kmeans_seed_stats[4] = {0, 0, 0, 0};
     // the update of mi_knn_kmeans and the centroids of mi_knn_summarize on exact integer sums of 2^-30 instead of the float

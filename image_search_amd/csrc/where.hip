@@ -21,15 +21,6 @@ using namespace mi;
 
 namespace {
 
-WherePred pred_of(const mi_knn_where& w) {
-    WherePred p;
-    p.all_of = w.all_of; p.any_of = w.any_of; p.none_of = w.none_of;
-    p.lo = w.stamp_lo; p.hi = w.stamp_hi;
-    p.group = w.group;
-    p.use_group = (w.flags & MI_KNN_WHERE_GROUP) ? 1u : 0u;
-    return p;
-}
-
 // the count and offsets passes on s, and the wait for their total: the qualifying rows.  Leaves the chunk offsets in
 // t->d_wcounts + 2.  t->mu held, device selected, s ordered behind the handle's writes
 uint64_t where_total(mi_knn* t, const mi_knn_where& w, hipStream_t s) {

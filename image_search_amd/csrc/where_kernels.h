@@ -20,33 +20,13 @@
 
 #include <cstdint>
 
+#include "where_pred.h"   // WherePred, pred_of, where_match: the row test
+
 namespace mi {
 
 constexpr int WHERE_THREADS = 256, WHERE_WAVES = WHERE_THREADS / 64;
 constexpr int WHERE_SCAN_THREADS = 1024;
 constexpr uint32_t WHERE_TILES_MAX = 1024;   // tiles of the largest chunk (65536 rows): the emit pass keeps a ballot per tile in LDS
-
-// the predicate as the kernels take it (mi_knn_where, with the flag decoded); tags / stamps / groups / tomb are nullable:
-// a table without attribute columns holds the defaults (0, 0), one without deletions has no bitmap, and the group word is
-// read only under the flag (the host answers "nothing" itself when the flag is set and there is no column)
-struct WherePred {
-    unsigned long long all_of, any_of, none_of;
-    long long lo, hi;
-    uint32_t group, use_group;
-};
-
-__device__ __forceinline__ bool where_match(const WherePred& p, const unsigned long long* __restrict__ tags,
-                                            const long long* __restrict__ stamps, const uint32_t* __restrict__ groups,
-                                            const unsigned long long* __restrict__ tomb, uint64_t row, uint64_t rows) {
-    if (row >= rows) return false;
-    const unsigned long long tg = tags ? tags[row] : 0ull;
-    const long long st = stamps ? stamps[row] : 0ll;
-    bool ok = (tg & p.all_of) == p.all_of && (p.any_of == 0ull || (tg & p.any_of) != 0ull) && (tg & p.none_of) == 0ull;
-    ok = ok && st >= p.lo && st <= p.hi;
-    if (tomb) ok = ok && ((tomb[row >> 6] >> (row & 63)) & 1ull) == 0ull;   // one word per tile: the same address in all 64 lanes
-    if (p.use_group) ok = ok && groups[row] == p.group;
-    return ok;
-}
 
 // the tiles [first, last) of the chunk's `tiles` that wave `w` owns: a contiguous quarter, the last ones possibly empty
 __device__ __forceinline__ void where_wave_tiles(uint32_t tiles, uint32_t w, uint32_t* first, uint32_t* last) {

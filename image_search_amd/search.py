@@ -189,6 +189,16 @@ def _where_or_null(predicate):
     return ctypes.byref(w), w
 
 
+def _many_where(fn, h, dim, queries, k, predicate):
+    """one mi_*_search_many_where call -> (idx [nq, k], dist [nq, k], matched)"""
+    q = _f32(queries).reshape(-1, dim)
+    idx, dist = np.empty((q.shape[0], int(k)), np.uint64), np.empty((q.shape[0], int(k)), np.float32)
+    matched = ctypes.c_uint64()
+    wp, _w = _where_or_null(predicate)
+    check(fn(h, q.ctypes.data, q.shape[0], int(k), wp, idx.ctypes.data, dist.ctypes.data, ctypes.byref(matched)))
+    return idx, dist, matched.value
+
+
 def _ordered_call(fn, handle, dim, lead, reference, k, max_dist, descending, after, predicate, n_found=False):
     """one mi_*_search_ordered call -> (idx [k], dist [k], stamps [k], counts dict): `lead` = the arguments between the query and
     k (the index's references); after = None or the (stamp, id) of the previous page's last hit"""
@@ -521,6 +531,48 @@ class EmbeddingTable:
         out = (ctypes.c_uint64 * 4)()
         check(lib().mi_knn_search_many_stats(self._h, out))
         return {"candidates": out[0], "hits": out[1], "launches": out[2], "tiles": out[3]}
+
+    def knn_many_where(self, queries: np.ndarray, k: int, **predicate):
+        """knn_many among the rows a predicate keeps (mi_knn_search_many_where): (idx [nq, k], dist [nq, k], matched) — per
+        query what knn_where(query, k, **predicate) answers without the entries whose distance is NaN, ids and distance bits.
+        predicate: make_where's keywords (all_of / any_of / none_of / stamp / group); none = every live row, exactly
+        knn_many.  matched = the qualifying rows."""
+        return _many_where(lib().mi_knn_search_many_where, self._h, self.dim, queries, k, predicate)
+
+    def neighbors_where(self, k: int, first: int = 0, n: Optional[int] = None, **predicate):
+        """neighbors with the candidates narrowed (mi_knn_neighbors_where): every row of the slice asks, whether or not it
+        qualifies itself; only the rows the predicate keeps may answer.  (idx [n, k], dist [n, k])."""
+        if n is None:
+            n = max(int(getattr(self, "_base_id", 0)) + len(self) - int(first), 0)
+        idx, dist = np.empty((int(n), int(k)), np.uint64), np.empty((int(n), int(k)), np.float32)
+        wp, _w = _where_or_null(predicate)
+        check(lib().mi_knn_neighbors_where(self._h, int(first), int(n), int(k), wp, idx.ctypes.data, dist.ctypes.data))
+        return idx, dist
+
+    def propose_groups(self, k: int = 10, max_dist: float = float("inf"), ask_group=None, **voters_predicate) -> dict:
+        """"Where do my unsorted pictures go?" — a k-nearest vote that carries the group column forward
+        (mi_knn_propose_groups).  The askers are the live rows of ask_group (None: the rows without a group); the voters are
+        the live rows of every other group that the predicate keeps (make_where's keywords; none: all of them).  Every asker
+        hears its k <= 16 nearest voters within max_dist; the group with the most of them wins, the nearest among equal
+        counts.  Returns {"group" [rows] uint32 (NO_GROUP: no proposal), "votes" (the winner's count), "heard" (voters
+        heard), "dist" (the winner's nearest voter, +inf: none), "totals": {"askers", "proposed", "voters", "unanimous"}}.
+        The column itself is not written: set_groups applies what the caller accepts."""
+        n = len(self)
+        group, votes, heard = (np.empty(max(n, 1), np.uint32) for _ in range(3))
+        dist = np.empty(max(n, 1), np.float32)
+        totals = (ctypes.c_uint64 * 4)()
+        wp, _w = _where_or_null(voters_predicate)
+        ask = int(NO_GROUP) if ask_group is None else int(ask_group)
+        check(lib().mi_knn_propose_groups(self._h, int(k), float(max_dist), ask, wp, group.ctypes.data, votes.ctypes.data,
+                                          heard.ctypes.data, dist.ctypes.data, totals))
+        return {"group": group[:n], "votes": votes[:n], "heard": heard[:n], "dist": dist[:n],
+                "totals": {"askers": totals[0], "proposed": totals[1], "voters": totals[2], "unanimous": totals[3]}}
+
+    def propose_groups_stats(self):
+        """mi_knn_propose_groups_stats, of the last propose_groups on this table"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_propose_groups_stats(self._h, out))
+        return {"candidates": out[0], "launches": out[1], "tiles": out[2], "strips": out[3]}
 
     def knn_diverse(self, reference: np.ndarray, k: int, min_gap: float, pool: Optional[int] = None, within=None):
         """The k best DISTINCT results (mi_knn_search_diverse): the list knn(reference, pool, within) walked in order, an
@@ -1334,6 +1386,10 @@ class ShardedTable:
         check(lib().mi_knn_sharded_search_many(self._h, q.ctypes.data, q.shape[0], int(k), idx.ctypes.data, dist.ctypes.data))
         return idx, dist
 
+    def knn_many_where(self, queries: np.ndarray, k: int, **predicate):
+        """EmbeddingTable.knn_many_where over all shards (mi_knn_sharded_search_many_where): global ids, matched summed"""
+        return _many_where(lib().mi_knn_sharded_search_many_where, self._h, self.dim, queries, k, predicate)
+
     def neighbors(self, k: int, first: int = 0, n: Optional[int] = None):
         """EmbeddingTable.neighbors over all shards, composed on the host: the rows are read back (rows()), searched with
         k + 1 (knn_many) and lose their own entry (drop_self); deleted rows are padded"""
@@ -1890,6 +1946,47 @@ class ImageIndex:
         idx, dist = self.table.knn_many(vectors, k)
         return {(names[c] if names is not None else c): [(self.path(int(i), web=web), float(d)) for i, d in zip(idx[c], dist[c]) if i != NO_ID]
                 for c in range(idx.shape[0])}
+
+    def best_per_label_where(self, vectors: np.ndarray, names: Optional[Sequence[str]] = None, k: int = 10, web: bool = False,
+                             **predicate) -> dict:
+        """best_per_label among the images a predicate keeps (EmbeddingTable.knn_many_where): "the best k for each of my
+        tags among my favourites, 2019-2021"; with none_of = the hidden flag a hidden picture shows up under no tag."""
+        idx, dist, _matched = self.table.knn_many_where(vectors, k, **predicate)
+        return {(names[c] if names is not None else c): [(self.path(int(i), web=web), float(d)) for i, d in zip(idx[c], dist[c]) if i != NO_ID]
+                for c in range(idx.shape[0])}
+
+    def related_where(self, k: int = 10, web: bool = False, **predicate) -> dict:
+        """related with the answers narrowed (EmbeddingTable.neighbors_where): every image that has not been removed is
+        listed, only the images the predicate keeps stand beside it."""
+        idx, dist = self.table.neighbors_where(k, **predicate)
+        deleted = set(int(r) for r in self.table.deleted())
+        names = {}
+
+        def name(r):
+            if r not in names:
+                names[r] = self.path(r, web=web)
+            return names[r]
+
+        return {name(r): [(name(int(i)), float(d)) for i, d in zip(idx[r], dist[r]) if i != NO_ID]
+                for r in range(idx.shape[0]) if r not in deleted}
+
+    def suggest_folders(self, inbox: str, k: int = 10, max_dist: float = float("inf"), min_votes: int = 1, web: bool = False,
+                        **voters_predicate) -> dict:
+        """"File my inbox" (EmbeddingTable.propose_groups): the images directly in the directory `inbox` ("media/inbox", as
+        group_of takes it) ask, the images of every other folder vote (narrowed by make_where's keywords: hidden pictures do
+        not vote).  {path: (folder name, votes, heard, distance)} for the inbox images whose winning folder got at least
+        min_votes; nothing is moved."""
+        ask = self.group_of(inbox)
+        # the table's group column holds the directories once a call under the group flag has run: one row of the inbox
+        unit = np.zeros(self.dim, np.float32)
+        unit[0] = 1.0
+        self.web_search_where(unit, k=1, group=ask)
+        res = self.table.propose_groups(k, max_dist, ask, **voters_predicate)
+        out = {}
+        for r in np.nonzero((res["group"] != NO_GROUP) & (res["votes"] >= int(min_votes)))[0]:
+            out[self.path(int(r), web=web)] = (self.group_name(int(res["group"][r]), web=web), int(res["votes"][r]),
+                                               int(res["heard"][r]), float(res["dist"][r]))
+        return out
 
     def clusters(self, k: int, max_iters: int = 20, seed: int = 0, web: bool = False, init: str = "uniform",
                  sample: Optional[int] = None) -> list:

@@ -492,6 +492,57 @@ int mi_knn_search_many_stats(mi_knn* t, uint64_t out[4]);
  * copy of the rows, their mirror rows are the table's.  Not offered on a shard borrowed from a sharded table (its ids are
  * not contiguous: MI_ERR_UNSUPPORTED). */
 int mi_knn_neighbors(mi_knn* t, uint64_t first, uint64_t n, uint32_t k, uint64_t* idx, float* dist);
+/* The many-query search narrowed ("the best k pictures for each of my tags among my favourites, 2019-2021"; a picture flagged
+ * hidden under no tag): mi_knn_search_many among the rows that qualify under w (mi_knn_where, declared with mi_knn_search_where
+ * below).  For each query the entries of mi_knn_search_where(t, query, 1, k, w) AFTER removing every entry whose distance is
+ * NaN: same ids, same distance bits, same order; MI_KNN_NO_ID / +inf behind the last hit.  *matched (may be NULL) = the
+ * qualifying rows (mi_knn_count_where).  w == NULL: exactly mi_knn_search_many (same launches, no mask built), *matched = the
+ * live rows.  k, nq, dim, mirror, "join_cap", "many_segments", "many_sample", stream ordering and the empty table: as
+ * mi_knn_search_many; the predicate's errors: as mi_knn_search_where; an argument error writes nothing.  A predicate nothing can
+ * meet gives all padding without a tile launch.
+ * One kernel evaluates the predicate for every row into a call-private bitmap (bit set = the row stays out: deleted or not
+ * qualifying), and stage 1 takes that bitmap in place of the deletion bitmap: a masked column has weight 0, it is never
+ * emitted and never enters a threshold slot, so the thresholds are those of a table that holds the qualifying rows only.
+ * Stage 1 still multiplies every column tile: a narrow predicate saves stage 2's work, not stage 1's.  Known cost: the
+ * thresholds come from m residue slots (row index mod m); where the qualifying rows fall into few residues a slot stays
+ * empty and every qualifying row is emitted for every query (correct, slower).  When qualifying rows x a strip's queries fit
+ * the candidate buffer the threshold pass is skipped and everything is emitted at once.
+ * mi_knn_search_many_stats reports these calls too. */
+struct mi_knn_where;
+int mi_knn_search_many_where(mi_knn* t, const float* q, uint32_t nq, uint32_t k, const struct mi_knn_where* w, uint64_t* idx,
+                             float* dist, uint64_t* matched /* may be NULL */);
+/* mi_knn_neighbors with the candidates narrowed: the queries are the rows first .. first + n - 1 whether or not they qualify
+ * themselves (a deleted row gets padding), the candidates the rows that qualify under w (NULL: every live row, exactly
+ * mi_knn_neighbors).  Per row: mi_knn_search_many_where(q = the row, k + 1, w) with the entry whose id is the row's own removed,
+ * or the last entry removed where that entry is absent (now also: the row does not qualify).  1 <= k <= 15; range errors and
+ * the refusal on a borrowed shard as mi_knn_neighbors. */
+int mi_knn_neighbors_where(mi_knn* t, uint64_t first, uint64_t n, uint32_t k, const struct mi_knn_where* w, uint64_t* idx,
+                           float* dist);
+/* "I sorted 300 pictures into albums by hand, where do the other 40 000 go?" — a k-nearest-neighbour vote that carries the
+ * group column (mi_knn_set_groups) forward.  All arrays are [rows] by local row (rows = mi_knn_size, deleted rows counted).
+ *   asker  a live row whose group is ask_group (MI_KNN_NO_GROUP: the rows without a group; a table whose group column was
+ *          never set: every live row).
+ *   voter  a live row whose group is neither MI_KNN_NO_GROUP nor ask_group and that, with voters != NULL, qualifies under it
+ *          (hidden pictures do not vote).  No row is both.
+ *   L(r)   for an asker r: the voters ordered by (the distance key mi_knn_search(q = row r) reports for them, id) ascending,
+ *          without the entries whose distance is NaN and without those beyond the window dist_to_u32(d) <=
+ *          dist_to_u32(max_dist) (mi_knn_search_page's inclusive window: +INFINITY = no bound, NaN or < 0: MI_ERR_INVALID);
+ *          the first k of what remains.  Distances carry the search's bits.
+ *   tally  n_g = the entries of L(r) whose group is g; the winner is the g with the largest n_g, among equal counts the one
+ *          whose first entry stands earliest in L(r) (the nearest).
+ * group[r] = the winner (MI_KNN_NO_GROUP: L(r) is empty or r is no asker), votes[r] = n_winner, heard[r] = |L(r)|, dist[r] = the
+ * distance of the winner's first entry (+inf: none).  votes, heard, dist and totals may be NULL.  totals = {askers, askers
+ * with a proposal, voters, askers with votes == heard > 0}.
+ * 1 <= k <= 16 (0: MI_ERR_INVALID, above: MI_ERR_UNSUPPORTED); dim as mi_knn_near_pairs; ask_group >= MI_KNN_GROUPS_MAX and not
+ * MI_KNN_NO_GROUP: MI_ERR_INVALID; a shard borrowed from a sharded table: MI_ERR_UNSUPPORTED (it sees only its own voters).
+ * An empty table, no asker or no voter: padding, the counts in totals, MI_OK, no tile launch.  An argument error writes
+ * nothing.  The group column is never written: applying the proposals is the caller's mi_knn_set_groups.  It is the
+ * many-query search with the table's rows as queries, a column mask (not a voter) and a query mask (not an asker), and a
+ * tally behind stage 2.  Runs on the handle's stream behind every write enqueued before it and waits for its results. */
+int mi_knn_propose_groups(mi_knn* t, uint32_t k, float max_dist, uint32_t ask_group, const struct mi_knn_where* voters /* may be NULL */,
+                          uint32_t* group, uint32_t* votes, uint32_t* heard, float* dist, uint64_t totals[4]);
+/* out = {candidates stage 1 handed to stage 2, tile launches, tiles visited, strips} of the last mi_knn_propose_groups */
+int mi_knn_propose_groups_stats(mi_knn* t, uint64_t out[4]);
 /* Spherical k-means (Lloyd's iterations) over the live rows, mi_knn_assign as its inner step:
  *   it = 0
  *   loop: labels = assign(centroids); changed = rows whose label differs from the previous assign (first: the live rows)
@@ -943,6 +994,10 @@ int mi_knn_sharded_assign_multi(mi_knn_sharded* t, const float* vectors, uint32_
  * mi_knn_sharded_assign_multi), the per-shard lists are merged with mi_knn_merge's ordering; equals the one-table result
  * bit for bit */
 int mi_knn_sharded_search_many(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, uint64_t* idx, float* dist);
+/* mi_knn_search_many_where over the whole table: every shard masks and answers locally, the lists meet as
+ * mi_knn_sharded_search_many's do, *matched (may be NULL) = the sum over the shards; equals the one-table result bit for bit */
+int mi_knn_sharded_search_many_where(mi_knn_sharded* t, const float* q, uint32_t nq, uint32_t k, const mi_knn_where* w,
+                                     uint64_t* idx, float* dist, uint64_t* matched /* may be NULL */);
 /* mi_knn_near_pairs over the whole table (the reference's one table in one server, server/src/main.rs, at the size that needs
  * several GPUs): every pair of live rows a < b (global ids) with cosine distance <= max_dist whose larger id is >= first_new,
  * ascending by (a, b) — ids and distance bits are those of mi_knn_near_pairs on ONE table that holds the same rows in id
