@@ -81,6 +81,9 @@ SYMBOLS = {
     "mi_knn_sharded_kmeans": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32),
                                              c_u64p, ctypes.POINTER(ctypes.c_double)]),
     "mi_knn_sharded_kmeans_stats": (ctypes.c_int, [c_vp, c_u64p]),
+    "mi_knn_sharded_kmeans_seed": (ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, c_vp,
+                                                  ctypes.POINTER(ctypes.c_double)]),
+    "mi_knn_sharded_kmeans_seed_stats": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_knn_sharded_summarize": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mi_knn_sharded_summarize_stats": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_index_matches": (ctypes.c_int, [c_vp, c_vp, ctypes.c_float, c_vp, c_vp, c_vp, ctypes.c_uint64, c_u64p]),

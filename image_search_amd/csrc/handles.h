@@ -342,6 +342,8 @@ struct mi_knn_sharded {
     // mi_knn_sharded_summarize_stats: {segments summed (all shards), bytes copied between shards, merge launches (sums and
     // slots), members} of the last call
     uint64_t summarize_stats[4] = {0, 0, 0, 0};
+    // mi_knn_sharded_kmeans_seed_stats: {candidates, passes run, fallback picks, bytes copied between shards} of the last call
+    uint64_t kmeans_seed_stats[4] = {0, 0, 0, 0};
     std::mutex mu;
     uint32_t n() const { return (uint32_t)shard.size(); }
 };

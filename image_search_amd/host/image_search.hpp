@@ -883,6 +883,18 @@ class ShardedTable {
     }
     // {updates run, bytes copied between shards, segments summed in the last update, merge launches} of the last kmeans
     std::vector<uint64_t> kmeans_stats() const { std::vector<uint64_t> v(4); check(mi_knn_sharded_kmeans_stats(h_, v.data())); return v; }
+    // EmbeddingTable::kmeans_seed over all shards (mi_knn_sharded_kmeans_seed): rows are global ids; bit for bit what one table
+    // holding the same rows returns.  centroids [C * dim] are what kmeans() takes as its start
+    EmbeddingTable::Seeds kmeans_seed(uint32_t C, uint64_t seed = 0, const std::vector<uint64_t>* among = nullptr) const {
+        EmbeddingTable::Seeds r;
+        r.rows.resize(C); r.centroids.resize((size_t)C * dim_);
+        static const uint64_t none = 0;   // an empty `among` is an empty set of candidates, not "every row"
+        const uint64_t* ids = among ? (among->empty() ? &none : among->data()) : nullptr;
+        check(mi_knn_sharded_kmeans_seed(h_, C, seed, ids, among ? among->size() : 0, r.rows.data(), r.centroids.data(), &r.potential));
+        return r;
+    }
+    // {candidates, passes run, fallback picks, bytes copied between shards} of the last kmeans_seed
+    std::vector<uint64_t> kmeans_seed_stats() const { std::vector<uint64_t> v(4); check(mi_knn_sharded_kmeans_seed_stats(h_, v.data())); return v; }
     // EmbeddingTable::summarize over all shards (mi_knn_sharded_summarize): labels / dist by global row id, cover / odd global
     // ids (a tie goes to the lowest global id); bit for bit what one table holding the same rows returns with its option
     // "kmeans_fixed_sum" = 1.  labels == nullptr: every shard's part of the group column

@@ -1313,7 +1313,7 @@ class ShardedTable:
         """EmbeddingTable.kmeans over all shards (mi_knn_sharded_kmeans): the same dict, labels / dist by global row id — bit
         for bit what one table holding the same rows returns with fixed_sum=True, whatever the shard count, block size or
         devices.  An int k starts from the rows EmbeddingTable.kmeans(k, seed) picks over the same data.  Only sums, counts
-        and centroids cross between the shards."""
+        and centroids cross between the shards.  (k-means++ seeds: kmeans_seeded.)"""
         if init == "kmeans++":
             raise ValueError('init = "kmeans++" is not offered on a sharded table: the seeding draws every row against the rows '
                              'drawn so far on one device (mi_knn_kmeans_seed) and has no form that runs across shards; seed on '
@@ -1339,6 +1339,42 @@ class ShardedTable:
         out = (ctypes.c_uint64 * 4)()
         check(lib().mi_knn_sharded_kmeans_stats(self._h, out))
         return dict(zip(("updates", "bytes_exchanged", "segments", "merge_launches"), (int(v) for v in out)))
+
+    def kmeans_seed(self, k: int, seed: int = 0, among=None) -> dict:
+        """EmbeddingTable.kmeans_seed over all shards (mi_knn_sharded_kmeans_seed): the same dict, rows as global ids — bit for
+        bit what one table holding the same rows returns, whatever the shard count, block size or devices.  Per seed only
+        per-chunk integer sums, a 16-byte pick word and the chosen row cross between the shards."""
+        k = int(k)
+        rows, cent = np.empty(max(k, 0), np.uint64), np.empty((max(k, 0), self.dim), np.float32)
+        pot = ctypes.c_double()
+        ids, n_ids = None, 0
+        if among is not None:
+            a = _ids(among)
+            n_ids = a.size
+            if a.size == 0:   # an empty set of candidates, not "every row"
+                a = np.zeros(1, np.uint64)
+            ids = a.ctypes.data
+        check(lib().mi_knn_sharded_kmeans_seed(self._h, k, int(seed), ids, n_ids, rows.ctypes.data if k else None,
+                                               cent.ctypes.data if k else None, ctypes.byref(pot)))
+        return {"rows": rows, "centroids": cent, "potential": pot.value}
+
+    def kmeans_seed_stats(self) -> dict:
+        """mi_knn_sharded_kmeans_seed_stats, of the last kmeans_seed: bytes_exchanged = (k + 1) * 8 * (K + shards - 1) +
+        k * (shards - 1) * (32 + 8 dim), K = the chunks (at most 256 candidates of one block) of every shard but the first"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_sharded_kmeans_seed_stats(self._h, out))
+        return dict(zip(("candidates", "passes", "fallbacks", "bytes_exchanged"), (int(v) for v in out)))
+
+    def kmeans_seeded(self, k: int, max_iters: int = 20, seed: int = 0, sample: Optional[int] = None) -> dict:
+        """kmeans from k-means++ seeds: kmeans_seed(k, seed) among all live rows, or, where there are more than `sample` of
+        them (None = max(64 k, 16 384)), among a seeded uniform subset of that size — the rule of
+        EmbeddingTable.kmeans(init="kmeans++") — and then kmeans on those centroids.  Equals, bit for bit, one table's
+        kmeans(k, init="kmeans++", seed=seed, sample=sample, fixed_sum=True) over the same rows."""
+        k = int(k)
+        sample = max(64 * k, 16384) if sample is None else int(sample)
+        live = np.setdiff1d(np.arange(len(self), dtype=np.uint64), self.deleted())
+        among = np.sort(np.random.default_rng(seed).choice(live, size=sample, replace=False)) if live.size > sample else None
+        return self.kmeans(self.kmeans_seed(k, seed, among)["centroids"], max_iters)
 
     def summarize(self, labels=None, n_groups: Optional[int] = None) -> dict:
         """EmbeddingTable.summarize over all shards (mi_knn_sharded_summarize): the same dict with labels and dist by global

@@ -1049,6 +1049,40 @@ int mi_knn_sharded_kmeans(mi_knn_sharded* t, float* centroids, uint32_t C, uint3
 /* of the last mi_knn_sharded_kmeans: {updates run, bytes copied between shards, segments summed in the last update (all
  * shards), merge launches} */
 int mi_knn_sharded_kmeans_stats(mi_knn_sharded* t, uint64_t out[4]);
+/* mi_knn_kmeans_seed over the whole table ("what mi_knn_sharded_kmeans should start from"): every output equals, bit for
+ * bit, what mi_knn_kmeans_seed returns on ONE table holding the same rows under the same ids, with the same deleted rows, C,
+ * seed and among — for any shard count, block size and devices.
+ *   candidates  among == NULL: every live row, ascending by global id.  Otherwise the n_among global ids given, sorted and
+ *               made unique, deleted rows left out; an id that is not a row of the table: MI_ERR_INVALID, nothing runs.
+ *               S = their number, position p = 0 .. S-1 in that order (the GLOBAL position).
+ *   usable, z_j, pick j, weights
+ *               as defined at mi_knn_kmeans_seed: the splitmix64 stream started at `seed`, T = floor(z_j * total / 2^64),
+ *               the smallest global position whose inclusive prefix sum of w exceeds T; total == 0: the lowest GLOBAL
+ *               position not picked before (a fallback pick); z_j is consumed either way;
+ *               w_p = (uint32) floor(min(max(D_p, 0), 2) * 2^30).
+ * rows: [C] = the global id of pick j, in pick order.  centroids: [C, dim] or NULL = those rows' fp32 values (what
+ * mi_knn_sharded_kmeans takes as its initial centroids).  potential (or NULL) = sum of w_p * 2^-30 in double after one more
+ * weight update with the last pick.
+ * How it runs: rows are dealt block-cyclically, so the global candidate order is a fixed interleaving of the shards' local
+ * blocks.  Every shard keeps D, w and the flags of its own candidates and sums w per chunk (at most 256 consecutive positions
+ * of one local block).  Per seed: every shard but the first copies its chunk sums and the lowest global id it has not picked
+ * to the first shard's device; a pick there scans all chunk sums in global order and writes a 16-byte word {owning shard, its
+ * chunk, remainder of T, mode}; the word goes to every shard; the owner finds the position inside its chunk and writes
+ * {id, owner flag, the row} into a slot of 16 + 4 dim bytes; the slots go to the first shard, which appends the flagged one
+ * and sends its 4 dim bytes back as the centre of every shard's next pass.  Sums of uint32 in uint64 are the same in any
+ * order and the distances carry the search's bits, so the picks are the single table's.  Bytes copied between shards
+ * (copies within the first shard not counted), with K = the chunks of shards 1 .. S-1:
+ *     (C + 1) * 8 * (K + S - 1)  +  C * (S - 1) * (32 + 8 * dim).
+ * Streams are ordered by events, nothing is polled, no atomics; everything is enqueued and the host waits once.  A shard
+ * without rows or without candidates takes part with zero chunks.
+ * Checked before the handle is followed: a null handle, a null `rows`, C == 0, among == NULL with n_among != 0:
+ * MI_ERR_INVALID; C > 65536: MI_ERR_UNSUPPORTED.  Then: a table without shards: MI_ERR_INVALID; dim outside {128, 256, 512,
+ * 768, 1024} or 2^32 or more rows: MI_ERR_UNSUPPORTED; an id that is not a row, C > S: MI_ERR_INVALID.  An error writes
+ * nothing, apart from *potential = 0.  Delivers the searches pending on the table first, and waits for its results. */
+int mi_knn_sharded_kmeans_seed(mi_knn_sharded* t, uint32_t C, uint64_t seed, const uint64_t* among, uint64_t n_among, uint64_t* rows,
+                               float* centroids, double* potential);
+/* of the last mi_knn_sharded_kmeans_seed: {candidates S, passes (C + 1), fallback picks, bytes copied between shards} */
+int mi_knn_sharded_kmeans_seed_stats(mi_knn_sharded* t, uint64_t out[4]);
 /* mi_knn_summarize over the whole table ("describe the themes mi_knn_sharded_kmeans / mi_knn_sharded_dbscan just found"):
  * every output is mi_knn_summarize's, evaluated over the table the shards form together, and equals, bit for bit, what ONE
  * mi_knn holding the same rows returns with "kmeans_fixed_sum" = 1 (the shards' option is not consulted) — for any shard
