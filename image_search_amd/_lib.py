@@ -117,7 +117,12 @@ SYMBOLS = {
     "mi_knn_summarize_stats": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_index_folder_overview": (ctypes.c_int, [c_vp, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                 ctypes.POINTER(ctypes.c_uint32)]),
-    "mi_knn_search_diverse": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, ctypes.c_uint64,
+    "mi_knn_representatives": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp, c_vp, c_vp,
+                                              c_vp, c_vp, c_vp, c_vp]),
+    "mi_knn_representatives_stats": (ctypes.c_int, [c_vp, c_u64p]),
+    "mi_index_folder_highlights": (ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp, c_vp,
+                                                  ctypes.POINTER(ctypes.c_uint32)]),
+    "mi_knn_search_diverse":(ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, ctypes.c_uint64,
                                              c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_uint32)]),
     "mi_knn_search_diverse_stats": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_knn_search_compound": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_int, c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32,

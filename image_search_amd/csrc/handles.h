@@ -231,6 +231,9 @@ struct mi_knn {
     int kmeans_fixed_sum = 0;
     // mi_knn_summarize (summary.hip): {segments summed, workgroups of the distance pass, rows read by it, 0} of the last call
     uint64_t summarize_stats[4] = {0, 0, 0, 0};
+    // mi_knn_representatives (representatives.hip): {round launches, segments of the member walk, member rows read by the last
+    // round launched, 0} of the last call
+    uint64_t representatives_stats[4] = {0, 0, 0, 0};
     // mi_knn_search_diverse (diverse.hip): {pool entries P, candidate pairs, conflicting pairs, pool entries hidden} of the last call
     uint64_t diverse_stats[4] = {0, 0, 0, 0};
     // mi_knn_search_compound (compound.hip): {rows or list entries scanned, rows excluded by a negative term, rows with a NaN

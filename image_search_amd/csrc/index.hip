@@ -30,6 +30,7 @@
 #include "grouped_host.h"
 #include "handles.h"
 #include "ordered_host.h"
+#include "representatives_host.h"
 #include "summary_host.h"
 #include "where_host.h"
 
@@ -456,6 +457,38 @@ int mi_index_folder_overview(mi_index* ix, uint32_t cap, uint64_t* count, uint64
         if (odd_dist) std::copy(f32.data() + C, f32.data() + C + n, odd_dist);
         if (measured) std::copy(h_measured, h_measured + n, measured);
         if (spread) std::copy(h_spread, h_spread + n, spread);
+        *n_groups = C;
+    });
+}
+
+// the folders' highlights: the covers of mi_knn_summarize over the column, then mi_knn_representatives started at them; the
+// first min(cap, directories) folders reach the caller
+int mi_index_folder_highlights(mi_index* ix, uint32_t cap, uint32_t m, float min_gap, uint64_t* picks, float* gap, uint32_t* n_picked,
+                               uint32_t* n_groups) {
+    return guarded([&] {
+        if (!ix || !n_groups) fail(MI_ERR_INVALID, "null argument");
+        size_t n_dirs = 0;
+        {
+            std::lock_guard<std::mutex> l(ix->mu);
+            n_dirs = ix->dirs.names.size();
+            const char* why = "";
+            const int bad = rep_check_args(ix, (uint32_t)std::min<size_t>(std::max<size_t>(n_dirs, 1), 0xFFFFFFFFu), m, min_gap, &why);
+            if (bad != MI_OK) fail(bad, "%s (%zu directories, m %u)", why, n_dirs, m);
+            if (n_dirs) sync_groups(ix);
+        }
+        if (n_dirs == 0) { *n_groups = 0; return; }
+        const uint32_t C = (uint32_t)n_dirs;
+        std::vector<uint64_t> cover(C), h_picks((size_t)C * m);
+        std::vector<float> h_gap((size_t)C * m);
+        std::vector<uint32_t> h_n(C);
+        call_ok(mi_knn_summarize(ix->table, nullptr, C, nullptr, nullptr, cover.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr));
+        call_ok(mi_knn_representatives(ix->table, nullptr, C, m, min_gap, cover.data(), h_picks.data(), h_gap.data(), h_n.data(), nullptr,
+                                       nullptr, nullptr, nullptr));
+        const size_t n = std::min<size_t>(cap, C);
+        if (picks) std::copy(h_picks.begin(), h_picks.begin() + n * m, picks);
+        if (gap) std::copy(h_gap.begin(), h_gap.begin() + n * m, gap);
+        if (n_picked) std::copy(h_n.begin(), h_n.begin() + n, n_picked);
         *n_groups = C;
     });
 }

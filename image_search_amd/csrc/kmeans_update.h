@@ -27,6 +27,18 @@ struct KmUpdate {
     // leaves the same values)
     void alloc(Scratch& scratch, uint32_t n, uint32_t C, uint32_t dim, bool fixed_sum = false) {
         fixed = fixed_sum;
+        alloc_buckets(scratch, n, C);
+        if (!fixed) {
+            d_part = (float*)scratch.get((size_t)max_segs * dim * sizeof(float));
+        } else {
+            d_ipart = (long long*)scratch.get((size_t)max_segs * dim * sizeof(long long));
+            d_S = (long long*)scratch.get((size_t)C * dim * sizeof(long long));
+            d_n = (uint32_t*)scratch.get((size_t)C * sizeof(uint32_t));
+        }
+    }
+
+    // what buckets() alone needs (a call that walks the segments without summing them: mi_knn_representatives), and d_inv
+    void alloc_buckets(Scratch& scratch, uint32_t n, uint32_t C) {
         n_waves = std::max<uint32_t>(1u, std::min<uint32_t>({4096u, (1u << 24) / (C + 1), (n + 1023) / 1024}));
         n_waves = (n_waves + 3) / 4 * 4;
         chunk = ((n + n_waves - 1) / n_waves + 63) / 64 * 64;
@@ -37,13 +49,6 @@ struct KmUpdate {
         d_seg = (uint32_t*)scratch.get((size_t)(C + 2) * sizeof(uint32_t));
         d_sorted = (uint32_t*)scratch.get((size_t)n * sizeof(uint32_t));
         d_inv = (float*)scratch.get((size_t)n * sizeof(float));
-        if (!fixed) {
-            d_part = (float*)scratch.get((size_t)max_segs * dim * sizeof(float));
-        } else {
-            d_ipart = (long long*)scratch.get((size_t)max_segs * dim * sizeof(long long));
-            d_S = (long long*)scratch.get((size_t)C * dim * sizeof(long long));
-            d_n = (uint32_t*)scratch.get((size_t)C * sizeof(uint32_t));
-        }
     }
 
     template <int NCH>

@@ -415,6 +415,35 @@ class EmbeddingTable {
     }
     // {segments summed, workgroups of the distance pass, rows read by it, 0} of the last summarize
     std::vector<uint64_t> summarize_stats() const { std::vector<uint64_t> v(4); check(mi_knn_summarize_stats(h_, v.data())); return v; }
+    // m pictures that span every group (mi_knn_representatives): farthest-first picks of every group at once.  labels / C as
+    // summarize; start: nullptr = the member with the lowest id, else one member id per group (summarize's cover, say).
+    // picks / gap [C * m] in pick order (MI_KNN_NO_ID / +inf behind n_picked[c]; gap = a pick's distance to the nearest
+    // earlier one, non-increasing from pick 1 on); reach [C]; rep / rep_dist [rows] = the pick that stands for a row and the
+    // distance to it; totals = {members, groups with a pick, picks, rounds that made a pick}
+    struct Representatives {
+        std::vector<uint64_t> picks;
+        std::vector<float> gap, reach, rep_dist;
+        std::vector<uint32_t> n_picked, rep;
+        uint64_t totals[4] = {0, 0, 0, 0};
+    };
+    Representatives representatives(const std::vector<uint32_t>* labels, uint32_t C, uint32_t m = 9, float min_gap = -INFINITY,
+                                    const std::vector<uint64_t>* start = nullptr) const {
+        uint64_t n = 0;
+        check(mi_knn_size(h_, &n));
+        if (labels && labels->size() != n) throw std::invalid_argument("representatives: one label per row");
+        if (start && start->size() != C) throw std::invalid_argument("representatives: one start id per group");
+        Representatives r;
+        r.picks.resize((size_t)C * m + 1); r.gap.resize((size_t)C * m + 1); r.reach.resize(C + 1); r.n_picked.resize(C + 1);   // (+ 1: never a null pointer)
+        r.rep.resize(n + 1); r.rep_dist.resize(n + 1);
+        check(mi_knn_representatives(h_, labels && n ? labels->data() : nullptr, C, m, min_gap, start ? start->data() : nullptr,
+                                     r.picks.data(), r.gap.data(), r.n_picked.data(), r.reach.data(), r.rep.data(), r.rep_dist.data(),
+                                     r.totals));
+        r.picks.resize((size_t)C * m); r.gap.resize((size_t)C * m); r.reach.resize(C); r.n_picked.resize(C);
+        r.rep.resize(n); r.rep_dist.resize(n);
+        return r;
+    }
+    // {round launches, segments of the member walk, member rows read by the last round launched, 0} of the last representatives
+    std::vector<uint64_t> representatives_stats() const { std::vector<uint64_t> v(4); check(mi_knn_representatives_stats(h_, v.data())); return v; }
     // the k best DISTINCT results (mi_knn_search_diverse): the first `pool` results of knn(query) walked in order, an entry
     // within cosine distance min_gap of an earlier kept one hidden behind it.  idx / dist / hidden [k] (padding MI_KNN_NO_ID /
     // +inf / 0 behind n_kept), rep [pool]: per pool rank its slot, MI_KNN_NO_LABEL when left over.  pool = 0: min(4096, max(4 k, 64))

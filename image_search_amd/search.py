@@ -804,6 +804,76 @@ class EmbeddingTable:
         check(lib().mi_knn_summarize_stats(self._h, out))
         return {"segments": out[0], "workgroups": out[1], "rows": out[2]}
 
+    def representatives(self, labels=None, n_groups: Optional[int] = None, m: int = 9, min_gap: float = float("-inf"),
+                        start="cover") -> dict:
+        """m pictures that span every group (mi_knn_representatives): farthest-first traversal of every group at once —
+        start at one member, then repeatedly take the member farthest from everything taken so far.  labels / n_groups as
+        summarize.  start: "cover" = summarize's cover of every group (one summarize call first), "first" = the member with
+        the lowest id, or an array [n_groups] of ids.  A pick is made only while its distance to the nearest earlier pick
+        is above min_gap.  Returns dict(rows [C, m] = the picked ids in pick order, NO_ID behind the last; gap [C, m] = a
+        pick's distance to the nearest earlier pick, non-increasing from pick 1 on, +inf for pick 0 and the padding;
+        n_picked [C]; reach [C] = every measured member lies within this distance of a pick; rep [rows] = the index of the
+        pick that stands for a row, NO_LABEL for a row that is no member; rep_dist [rows] = its distance to that pick;
+        stands_for [C, m] = how many members a pick stands for (itself included): the "+37 similar" beside a thumbnail;
+        totals {"members", "groups", "picks", "rounds"})."""
+        n = len(self)
+        lab = None
+        if labels is not None:
+            lab = np.ascontiguousarray(np.asarray(labels).reshape(-1).astype(np.uint32))
+            if lab.size != n:
+                raise ValueError(f"{lab.size} labels for {n} rows")
+            if n_groups is None:
+                has = lab[lab != NO_LABEL]
+                n_groups = int(has.max()) + 1 if has.size else 1
+        elif n_groups is None:
+            n_groups = max(int(self.groups_info()["n_groups"]), 1)
+        C, m = int(n_groups), int(m)
+        first = None
+        if isinstance(start, str):
+            if start not in ("cover", "first"):
+                raise ValueError('start is "cover", "first" or an array of ids')
+            if start == "cover" and n and 1 <= C <= 65536:
+                first = np.ascontiguousarray(self.summarize(lab, C)["cover"], np.uint64)
+        else:
+            first = np.ascontiguousarray(np.asarray(start).reshape(-1).astype(np.uint64))
+            if first.size != C:
+                raise ValueError(f"{first.size} start ids for {C} groups")
+        cm = max(C, 0) * max(m, 0)
+        rows, gap = np.empty(cm, np.uint64), np.empty(cm, np.float32)
+        n_picked, reach = np.empty(max(C, 0), np.uint32), np.empty(max(C, 0), np.float32)
+        rep, rep_dist = np.empty(n, np.uint32), np.empty(n, np.float32)
+        totals = np.zeros(4, np.uint64)
+        check(lib().mi_knn_representatives(self._h, lab.ctypes.data if lab is not None and n else None, C, m, float(min_gap),
+                                           first.ctypes.data if first is not None else None, rows.ctypes.data, gap.ctypes.data,
+                                           n_picked.ctypes.data, reach.ctypes.data, rep.ctypes.data if n else None,
+                                           rep_dist.ctypes.data if n else None, totals.ctypes.data))
+        group = lab if lab is not None else (self.groups() if n else np.zeros(0, np.uint32))
+        has = rep != NO_LABEL
+        stands_for = np.bincount(group[has].astype(np.int64) * m + rep[has].astype(np.int64), minlength=C * m)
+        return {"rows": rows.reshape(C, m), "gap": gap.reshape(C, m), "n_picked": n_picked, "reach": reach, "rep": rep,
+                "rep_dist": rep_dist, "stands_for": stands_for.astype(np.uint64).reshape(C, m),
+                "totals": dict(zip(("members", "groups", "picks", "rounds"), (int(v) for v in totals)))}
+
+    def representatives_of(self, ids, m: int = 9, min_gap: float = float("-inf"), start="cover") -> dict:
+        """representatives of ONE group made of the rows `ids` (the highlights of a result list, of a DBSCAN theme, ...):
+        the same dict with one group; start as there (an id, not an array, where it is given)."""
+        ids = np.asarray(ids).reshape(-1).astype(np.uint64)
+        n = len(self)
+        local = ids - np.uint64(getattr(self, "_base_id", 0))
+        if ids.size and (int(ids.min()) < int(getattr(self, "_base_id", 0)) or int(local.max()) >= n):
+            raise ValueError("an id that is not a row of the table")
+        labels = np.full(n, NO_LABEL, np.uint32)
+        labels[local.astype(np.int64)] = 0
+        if not isinstance(start, str):
+            start = [int(start)]
+        return self.representatives(labels, 1, m, min_gap, start)
+
+    def representatives_stats(self) -> dict:
+        """mi_knn_representatives_stats, of the last representatives on this table"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_representatives_stats(self._h, out))
+        return {"rounds": out[0], "segments": out[1], "rows_last_round": out[2]}
+
 
 def _summarize_call(fn, table, labels, n_groups) -> dict:
     """EmbeddingTable.summarize / ShardedTable.summarize: fn = mi_knn_summarize or mi_knn_sharded_summarize"""
@@ -2062,6 +2132,35 @@ class ImageIndex:
         for o in out:
             o["folder"] = o.pop("group")
         return out
+
+    def folder_highlights(self, m: int = 9, min_gap: float = float("-inf"), web: bool = False) -> list:
+        """Up to m pictures that tell what is in each folder (mi_index_folder_highlights: farthest-first picks started at
+        the folder's cover): per directory that holds an image {folder, highlights = paths in pick order, gaps = a pick's
+        distance to the nearest earlier pick (+inf for the cover)}, in directory order.  A pick is made only while that
+        distance is above min_gap; removed paths are never picked."""
+        C, m = self.group_count(), int(m)
+        n = ctypes.c_uint32()
+        picks, gap, n_picked = np.empty(C * max(m, 0), np.uint64), np.empty(C * max(m, 0), np.float32), np.empty(C, np.uint32)
+        check(lib().mi_index_folder_highlights(self._h, C, m, float(min_gap), picks.ctypes.data, gap.ctypes.data, n_picked.ctypes.data,
+                                               ctypes.byref(n)))
+        C = min(C, n.value)
+        picks, gap = picks.reshape(-1, m), gap.reshape(-1, m)
+        out = []
+        for g in range(C):
+            k = int(n_picked[g])
+            if k:
+                out.append({"folder": self.group_name(g, web=web), "highlights": [self.path(int(r), web=web) for r in picks[g, :k]],
+                            "gaps": [float(v) for v in gap[g, :k]]})
+        return out
+
+    def highlights(self, paths: Sequence[str], m: int = 9, min_gap: float = float("-inf"), web: bool = False) -> list:
+        """Up to m of `paths` that span them all (EmbeddingTable.representatives_of over their rows, started at their cover):
+        the highlights of a result list or of a theme, as paths in pick order."""
+        ids = self.rows_of(paths)
+        if not ids:
+            return []
+        res = self.table.representatives_of(ids, m, min_gap)
+        return [self.path(int(r), web=web) for r in res["rows"][0, :int(res["n_picked"][0])]]
 
     def cluster_overview(self, k: int, max_iters: int = 20, seed: int = 0, web: bool = False, init: str = "uniform",
                          sample: Optional[int] = None) -> list:

@@ -635,6 +635,46 @@ int mi_knn_summarize(mi_knn* t, const uint32_t* labels /* [rows] or NULL */, uin
                      float* dist, uint64_t totals[4]);
 /* of the last mi_knn_summarize on this handle: out = {segments summed, workgroups of the distance pass, rows read by it, 0} */
 int mi_knn_summarize_stats(mi_knn* t, uint64_t out[4]);
+/* m pictures that span every group ("show me nine pictures that tell what is in this folder, theme or result list"):
+ * farthest-first traversal, the greedy k-center picks, of every group at once — start at one member, then repeatedly take the
+ * member farthest from everything taken so far.  The nearest members of the centroid all come from a group's largest part;
+ * these picks reach its small parts too, and the gaps say how many thumbnails the group needs.
+ * labels, C, "member of c" (a live usable row with label c < C; a label >= C belongs to nothing) and the id map are exactly
+ * mi_knn_summarize's.
+ *   d(p, r)       the distance mi_knn_search(q = row p) reports for row r, to the bit: the pick is the query, the member the
+ *                 streamed row.  key(d) is the search's 32-bit order: NaN after every number, -0 before +0.
+ *   K_r           per member r, the smallest key(d(p_i, r)) over the picks p_i of its group so far; rep[r] is the lowest i that
+ *                 attains it.
+ *   pick 0        of a non-empty group: start[c] when start is given — an id that is not a member of group c: MI_ERR_INVALID
+ *                 and no round runs; the entry of an empty group is not looked at — else the member with the lowest id.
+ *                 gap[c][0] = +inf.
+ *   pick j >= 1   among the not-yet-picked members whose K_r is a number's key (not NaN's): the largest K_r, the lowest id
+ *                 among equal keys.  It is made only if K_r > key(min_gap); min_gap = -INFINITY means no bound.  gap[c][j] =
+ *                 the distance of that key.  No such member: the group is finished, n_picked[c] = j, the remaining picks are
+ *                 MI_KNN_NO_ID and the remaining gaps +inf.
+ *   consequence   gap[c][1] >= gap[c][2] >= ... in key order, to the bit: K only falls, so the largest K can only fall.
+ *   reach[c]      the distance of the largest number key K_r over ALL members of c after the last pick: every measured member
+ *                 lies within reach[c] of a pick.  +inf for an empty group and for one without a number key.
+ *   rep[r]        the index i of the pick that stands for row r, rep_dist[r] the distance of K_r.  A member whose every d was
+ *                 NaN: MI_KNN_NO_LABEL and NaN.  Every other row that is no member: MI_KNN_NO_LABEL and +inf.
+ *   totals        {members, groups with at least one pick, picks made, rounds that made a pick (the largest n_picked)}.
+ * picks, gap: [C][m]; n_picked, reach: [C]; rep, rep_dist: [rows] by local row; every output pointer may be NULL.
+ * 1 <= C <= 65536, 1 <= m <= 4096 and C * m <= 2^22: MI_ERR_UNSUPPORTED above, MI_ERR_INVALID for a zero C or m, a NaN min_gap
+ * or a null handle.  dim as mi_knn_near_pairs requires.  A shard borrowed from a sharded table: MI_ERR_UNSUPPORTED (a group's
+ * members lie on other shards).  An empty table succeeds with the padding above.  An argument error writes nothing.
+ * The call reads the fp32 rows only: the result does not depend on "prefilter".  Every decision is an integer compare on keys
+ * or a 64-bit integer max, so the same table, labels and start give the same bits on every call.  One read of a group's member
+ * rows per pick it takes (a finished group reads nothing); device memory beside the outputs: 24 bytes per row, the bucket
+ * buffers of the k-means update, 8 bytes per (group, pick) and 28 per group, freed before the call returns.  Runs on the
+ * handle's stream behind every write and search enqueued before it, and waits for its results; between the rounds the host
+ * reads one word every 8 rounds to stop once a round made no pick. */
+int mi_knn_representatives(mi_knn* t, const uint32_t* labels /* [rows] or NULL: the group column */, uint32_t C, uint32_t m,
+                           float min_gap, const uint64_t* start /* [C] ids or NULL */, uint64_t* picks /* [C][m] */,
+                           float* gap /* [C][m] */, uint32_t* n_picked /* [C] */, float* reach /* [C] */, uint32_t* rep /* [rows] */,
+                           float* rep_dist /* [rows] */, uint64_t totals[4]);
+/* of the last mi_knn_representatives on this handle: out = {round launches, segments of the member walk, member rows read by
+ * the last round launched, 0} */
+int mi_knn_representatives_stats(mi_knn* t, uint64_t out[4]);
 /* The k best DISTINCT results of a search ("the grid without the same shot ten times"): the search's own list with
  * near-duplicates collapsed behind the best of them, greedily, and how many look-alikes stand behind each kept result.
  *   pool        L = the result of mi_knn_search(t, q, 1, pool) when among == NULL, else of mi_knn_search_filtered(t, q, 1,
@@ -1323,6 +1363,14 @@ int mi_index_themes(mi_index* ix, float max_dist, uint32_t min_pts, uint64_t* id
  * More than 65536 directories: MI_ERR_UNSUPPORTED.  An index without a row succeeds with *n_groups = 0. */
 int mi_index_folder_overview(mi_index* ix, uint32_t cap, uint64_t* count, uint64_t* cover, float* cover_dist, uint64_t* odd,
                              float* odd_dist, uint64_t* measured, uint64_t* spread, uint32_t* n_groups);
+/* The folders' highlights (mi_knn_representatives over the same directory groups, started at each folder's cover): for
+ * directory g < min(cap, *n_groups) the row ids picks[g][0 .. m-1] (MI_KNN_NO_ID behind the last pick), their gaps gap[g][.]
+ * and n_picked[g], as mi_knn_representatives defines them with labels = NULL, min_gap as given and start = the covers of
+ * mi_index_folder_overview.  picks, gap: [cap][m]; every array may be NULL; *n_groups = the directories seen so far.  m and
+ * the number of directories under mi_knn_representatives' limits, else MI_ERR_UNSUPPORTED; m = 0 or a NaN min_gap:
+ * MI_ERR_INVALID.  An index without a row succeeds with *n_groups = 0. */
+int mi_index_folder_highlights(mi_index* ix, uint32_t cap, uint32_t m, float min_gap, uint64_t* picks, float* gap, uint32_t* n_picked,
+                               uint32_t* n_groups);
 
 /* ------------------------------------------------------------ query refinement */
 
