@@ -33,7 +33,7 @@ inline int dbscan_check_args(const void* t, float max_dist, uint32_t min_pts, co
 }
 
 // act[b]: bit 0 = some row of block b has a neighbour within, bit 1 = some row of it is a core.  Tile (bi, bj) is visited iff
-// both blocks have bit 0 and one of them bit 1 (density_tiles_kernel's test).
+// both blocks have bit 0 and one of them bit 1 (pair_tile's SKIP test, pair_kernels.h).
 inline bool density_tile_visited(uint8_t fa, uint8_t fb) { return (fa & fb & 1u) && ((fa | fb) & 2u); }
 
 // Prefix counts over the blocks, so that the tiles of a rectangle are counted per tile row, not per tile:

@@ -5,14 +5,14 @@
 // the join's two stages (join_kernels.h: a bf16 tile stage that may only err on the side of MORE pairs, under the bound eps2,
 // and the search's fp32 arithmetic deciding), so "within" is the join's decision bit for bit.
 //
-// Pass 1 (degrees).  Stage 1 is join_tiles_kernel itself.  Stage 2, density_count_kernel, is join_rescore_kernel with the
-// compaction replaced by two integer adds: deg[a] += 1, deg[b] += 1.  Integer adds commute: the result is the same in any order.
+// Pass 1 (degrees).  Stage 1 is join_tiles_kernel itself.  Stage 2, density_count_kernel, is join_rescore_kernel (its distance
+// as the function pair_dist of pair_kernels.h) with the compaction replaced by two integer adds: deg[a] += 1, deg[b] += 1.  Integer adds commute: the result is the same in any order.
 //
 // density_blocks_kernel.  Row r is a core iff it is live and deg[r] + 1 >= min_pts.  Per 128-row block one byte: bit 0 = some
 // row has deg > 0, bit 1 = some row is a core.  parent[r] = r, bkey[r] = ~0.
 //
-// Pass 2 (links).  Stage 1, density_tiles_kernel, is the join's tile with one test in front of its first load: the tile
-// (bi, bj) is left at once unless both blocks have bit 0 and one has bit 1.  That skip is exact: a pair of W has both degrees
+// Pass 2 (links).  Stage 1, density_tiles_kernel, is the join's tile (pair_tile) with its SKIP test in front of the first
+// load: the tile (bi, bj) is left at once unless both blocks have bit 0 and one has bit 1.  That skip is exact: a pair of W has both degrees
 // > 0, and pass 2 uses only pairs with a core end.  Stage 2, density_link_kernel, reads the two core flags first; a pair with
 // no core end is dropped without streaming its rows.  Otherwise the join's rescore decides, and a pair within
 //   - with two core ends is a union in a lock-free disjoint-set forest over `parent` (below),
@@ -87,41 +87,19 @@ __device__ __forceinline__ void ds_union(uint32_t* parent, uint32_t x, uint32_t 
     }
 }
 
-// join_rescore_kernel's arithmetic for the pair (pr.x = the query, pr.y = the streamed row): all 16 lanes of a group call it
-template <int NCH>
-__device__ __forceinline__ float density_pair_dist(const float* __restrict__ table, uint2 pr, int i) {
-    constexpr int DIM = NCH * 64;
-    const f32x4* pa = reinterpret_cast<const f32x4*>(table + (uint64_t)pr.x * DIM) + i;
-    const f32x4* pb = reinterpret_cast<const f32x4*>(table + (uint64_t)pr.y * DIM) + i;
-    f32x4 qf[NCH];
-#pragma unroll
-    for (int t = 0; t < NCH; ++t) qf[t] = pa[16 * t];
-    float sq;  // sqrt(q.q), same summation order as a row
-    {
-        RowAcc<NCH> a; a.zero();
-#pragma unroll
-        for (int t = 0; t < NCH; ++t) a.step(qf[t], qf[t]);
-        sq = sqrtf(a.sumsq());
-    }
-    RowAcc<NCH> a; a.zero();
-#pragma unroll
-    for (int t = 0; t < NCH; ++t) a.step(qf[t], __builtin_nontemporal_load(pb + 16 * t));
-    const float d = a.dot(), s = a.sumsq();
-    return 1.0f - d / (sq * sqrtf(s));
-}
-
 // pass 1, stage 2: C candidate pairs (C <= the buffer's capacity) -> deg[a] += 1, deg[b] += 1 for the pairs within
 template <int NCH>
 __global__ __launch_bounds__(256) void density_count_kernel(const float* __restrict__ table, const uint2* __restrict__ cand, uint32_t C,
                                                             float max_dist, uint32_t* __restrict__ deg,
                                                             unsigned long long* __restrict__ words) {
+    constexpr int DIM = NCH * 64;
     const int lane = threadIdx.x & 63, i = lane & 15;
     const uint32_t group = (blockIdx.x * 256 + threadIdx.x) >> 4, n_groups = (gridDim.x * 256) >> 4;
     // (whole waves stay in the loop: row16_sum and the ballot are cross-lane operations)
     for (uint32_t c0 = group; c0 < ((C + n_groups - 1) / n_groups) * n_groups; c0 += n_groups) {
         const bool live = c0 < C;
         const uint2 pr = cand[live ? c0 : 0];
-        const float dist = density_pair_dist<NCH>(table, pr, i);
+        const float dist = pair_dist<NCH>(table + (uint64_t)pr.x * DIM, table + (uint64_t)pr.y * DIM, i);
         const bool keep = live && i == 0 && dist <= max_dist;
         const unsigned long long m = __ballot(keep);
         if (m == 0ull) continue;
@@ -155,65 +133,13 @@ static __global__ __launch_bounds__(TILE) void density_blocks_kernel(const uint3
     if (threadIdx.x == 0) act[blockIdx.x] = (uint8_t)bits;
 }
 
-// pass 2, stage 1: join_tiles_kernel (first_new = 0) behind the activity test.  The tile's kernels differ in their epilogues
-// only; this one has the join's.
+// pass 2, stage 1: join_tiles_kernel (first_new = 0) behind the activity test
 template <int NCH>
 __global__ __launch_bounds__(256) void density_tiles_kernel(const uint16_t* __restrict__ mirror, const float* __restrict__ xx,
                                                              const uint64_t* __restrict__ tomb, const uint8_t* __restrict__ act,
                                                              uint32_t n_rows, uint32_t br0, uint32_t bc0, float c, uint32_t cap,
                                                              uint2* __restrict__ cand, unsigned long long* __restrict__ count) {
-    constexpr int DIM = NCH * 64;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const uint32_t bi = br0 + blockIdx.y, bj = bc0 + blockIdx.x;
-    if (bj < bi) return;
-    {
-        const uint32_t fa = act[bi], fb = act[bj];
-        if (!((fa & fb & 1u) && ((fa | fb) & 2u))) return;   // no pair of W with a core end lies in this tile
-    }
-    const int tid = threadIdx.x;
-    const TileFrag f = tile_frag();
-    const int wr = f.wr, wc = f.wc, l31 = f.l31, lh = f.lh;
-    float* wgt = reinterpret_cast<float*>(smem + TILE_IMGS);   // [0, 128): the tile's rows a, [128, 256): its columns b
-    const uint32_t row0 = bi * TILE, col0 = bj * TILE;
-    const float inf = __uint_as_float(0x7F800000u);
-
-    // a row's weight: sqrt of its stored norm; -inf = marked (a candidate against everything live); NaN = not there
-    {
-        const bool is_col = tid >= TILE;
-        const uint32_t r = (is_col ? col0 : row0) + (uint32_t)(tid & (TILE - 1));
-        wgt[tid] = tile_weight<false>(xx, r, r < n_rows, tomb, r, -inf, __uint_as_float(0x7FC00000u));
-    }
-
-    const uint16_t *ga[4], *gb[4];
-    tile_src<DIM>(ga, mirror, row0, n_rows);
-    tile_src<DIM>(gb, mirror, col0, n_rows);
-    f32x16 acc[2][2];
-    tile_accumulate<NCH>(smem, f, ga, gb, acc);
-
-    // C/D map: register e of lane l is row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31 of its 32 x 32 block
-    const bool diag = bi == bj;
-    unsigned long long hit = 0ull;   // bit (2 ti + tj) * 16 + e
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int ra0 = wr * 64 + ti * 32 + 8 * q + 4 * lh;
-            const f32x4 wa = *reinterpret_cast<const f32x4*>(wgt + ra0);
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) {
-                const int cb = wc * 64 + tj * 32 + l31;
-                const float wb = wgt[TILE + cb];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float p = wa[j] * wb;
-                    bool ok = p == p && (!(acc[ti][tj][4 * q + j] < c * p) || fabsf(p) == inf);
-                    if (diag) ok = ok && cb > ra0 + j;
-                    if (ok) hit |= 1ull << ((2 * ti + tj) * 16 + 4 * q + j);
-                }
-            }
-        }
-    }
-    tile_append(hit, f, row0, col0, cap, cand, count);
+    pair_tile<NCH, true, true>(mirror, xx, tomb, act, n_rows, mirror, xx, tomb, act, n_rows, 0u, 0u, br0, bc0, c, cap, cand, count);
 }
 
 // pass 2, stage 2: C candidate pairs -> unions of core-core pairs within, bkey minima of core-border pairs within.  (The
@@ -223,6 +149,7 @@ __global__ __launch_bounds__(256) void density_link_kernel(const float* __restri
                                                            float max_dist, uint32_t min_pts, const uint32_t* __restrict__ deg,
                                                            uint32_t* parent, unsigned long long* __restrict__ bkey,
                                                            unsigned long long* __restrict__ words) {
+    constexpr int DIM = NCH * 64;
     const int lane = threadIdx.x & 63, i = lane & 15;
     const uint32_t group = (blockIdx.x * 256 + threadIdx.x) >> 4, n_groups = (gridDim.x * 256) >> 4;
     // (whole waves stay in the loop: row16_sum works across the 16 lanes of a group, which take every branch together)
@@ -231,7 +158,7 @@ __global__ __launch_bounds__(256) void density_link_kernel(const float* __restri
         const uint2 pr = cand[live ? c0 : 0];
         const bool core_a = deg[pr.x] >= min_pts - 1u, core_b = deg[pr.y] >= min_pts - 1u;
         if (!live || !(core_a || core_b)) continue;
-        const float dist = density_pair_dist<NCH>(table, pr, i);
+        const float dist = pair_dist<NCH>(table + (uint64_t)pr.x * DIM, table + (uint64_t)pr.y * DIM, i);
         if (i != 0 || !(dist <= max_dist)) continue;
         if (core_a && core_b) ds_union(parent, pr.x, pr.y, words);
         else if (core_a) atomicMin(bkey + pr.y, (unsigned long long)make_key(dist, pr.x));

@@ -1,6 +1,7 @@
 // density_levels.hip — host side of mi_knn_density_levels, mi_knn_dbscan_levels and mi_dbscan_levels_tree.  The kernels and
-// why one pair of tile passes serves every level: density_levels_kernels.h; the host-only rules: density_levels_host.h.  The
-// strips, the overflow scheme and the tile counts are density.hip's (Density::rect, Density::pass), with the top level's bound.
+// why one pair of tile passes serves every level: density_levels_kernels.h; the host-only rules: density_levels_host.h.  Stage 1
+// of both passes, with its overflow scheme and tile counts, is density_call.h's under the top level's bound; the strips are
+// tile_strips (join_between_host.h).
 #include <algorithm>
 #include <cstring>
 
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "density_call.h"
 #include "density_host.h"
 #include "density_levels_host.h"
 #include "density_levels_kernels.h"
@@ -21,82 +23,38 @@ namespace {
 struct LevelsCall {
     mi_knn* t;
     hipStream_t s;
-    const uint16_t* mirror;
-    const float* xx;
-    const uint64_t* tomb;
     uint32_t n_rows, n_blocks;
     DensityLevels lv;
-    float c;                       // stage 1's bound, of the top level
-    uint32_t cand_cap;
-    uint2* d_cand;
     unsigned long long* d_words;   // DWL_* of density_levels_kernels.h
     uint32_t *d_deg, *d_parent;    // [lv.n][n_rows]
     unsigned long long* d_bkey;    // [lv.n][n_rows]
     uint8_t *d_core_from, *d_act;
     DensityBlocks blocks;
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    DensityStage1<true> st1;       // stage 1 of both passes under the top level's bound (density_call.h)
 
-    // Density::rect with this unit's second stages: every pair of the top level's W reaches stage 2 exactly once, also across
-    // overflow halvings (the bins are adds), and only launches whose candidates were consumed count their tiles.
+    // Density::pass with this unit's second stages: every pair of the top level's W reaches stage 2 exactly once, also
+    // across overflow halvings (the bins are adds)
     template <int NCH, int PASS>
-    void rect(uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) {
-        auto stage1 = [&](uint32_t r0, uint32_t r1, uint32_t& c0, uint32_t c1) -> unsigned long long {
-            c0 = std::max(c0, r0);
-            if (c0 >= c1) return 0;
-            uint64_t visited = 0, skipped = 0;
-            if (PASS == 2) {
-                blocks.count(r0, r1, c0, c1, &visited, &skipped);
-                if (visited == 0) { stats[5] += skipped; return 0; }   // every workgroup would leave at once
-            } else {
-                for (uint32_t bi = r0; bi < r1; ++bi) visited += c1 - std::max(c0, bi);
-            }
-            HIP_CHECK(hipMemsetAsync(d_words + DWL_CAND, 0, sizeof(unsigned long long), s));
-            if (PASS == 1) {
-                static DevOnce once;
-                allow_lds_once(once, join_tiles_kernel<NCH>, JOIN_LDS);
-                hipLaunchKernelGGL((join_tiles_kernel<NCH>), dim3(c1 - c0, r1 - r0), dim3(256), JOIN_LDS, s, mirror, xx, tomb, n_rows, 0u,
-                                   r0, c0, c, cand_cap, d_cand, d_words + DWL_CAND);
-            } else {
-                static DevOnce once;
-                allow_lds_once(once, density_tiles_kernel<NCH>, JOIN_LDS);
-                hipLaunchKernelGGL((density_tiles_kernel<NCH>), dim3(c1 - c0, r1 - r0), dim3(256), JOIN_LDS, s, mirror, xx, tomb,
-                                   (const uint8_t*)d_act, n_rows, r0, c0, c, cand_cap, d_cand, d_words + DWL_CAND);
-            }
-            HIP_CHECK(hipGetLastError());
-            ++stats[7];
-            const unsigned long long n = read_count(d_words + DWL_CAND, s);
-            if (n <= cand_cap) {
-                if (PASS == 1) stats[2] += visited;
-                else { stats[4] += visited; stats[5] += skipped; }
-            }
-            return n;
-        };
+    void pass() {
+        auto stage1 = [&](uint32_t r0, uint32_t r1, uint32_t& c0, uint32_t c1) { return st1.template stage1<NCH, PASS>(r0, r1, c0, c1); };
         auto stage2 = [&](uint32_t C) {
             if (PASS == 1) {
                 stats[0] += C;
-                hipLaunchKernelGGL((density_count_levels_kernel<NCH>), dim3(group16_blocks(t, C)), dim3(256), 0, s, t->table, d_cand, C, lv,
-                                   n_rows, d_deg, d_words);
+                hipLaunchKernelGGL((density_count_levels_kernel<NCH>), dim3(group16_blocks(t, C)), dim3(256), 0, s, t->table, st1.d_cand, C,
+                                   lv, n_rows, d_deg, d_words);
             } else {
                 stats[3] += C;
-                hipLaunchKernelGGL((density_link_levels_kernel<NCH>), dim3(group16_blocks(t, C)), dim3(256), 0, s, t->table, d_cand, C, lv,
+                hipLaunchKernelGGL((density_link_levels_kernel<NCH>), dim3(group16_blocks(t, C)), dim3(256), 0, s, t->table, st1.d_cand, C, lv,
                                    n_rows, (const uint8_t*)d_core_from, d_parent, d_bkey, d_words);
             }
             HIP_CHECK(hipGetLastError());
         };
-        rect_stages(br0, br1, bc0, bc1, cand_cap, overflowed, stage1, stage2);
-    }
-
-    // the join's strips (Join::run)
-    template <int NCH, int PASS>
-    void pass() {
-        uint32_t strip = std::max<uint32_t>(1u, std::min<uint32_t>(256u, (1u << 18) / std::max(n_blocks, 1u)));
-        for (uint32_t br = 0; br < n_blocks;) {
-            const uint32_t end = std::min(n_blocks, br + strip);
-            bool overflowed = false;
-            rect<NCH, PASS>(br, end, 0, n_blocks, &overflowed);
-            if (overflowed) strip = std::max(1u, strip / 2);
-            br = end;
-        }
+        tile_strips(0, n_blocks, 0, n_blocks,
+                    [&](uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) {
+                        rect_stages(br0, br1, bc0, bc1, st1.cand_cap, overflowed, stage1, stage2);
+                    },
+                    [] { return false; });
     }
 };
 
@@ -125,10 +83,7 @@ void levels_run(mi_knn* t, const DensityLevels& lv, uint32_t min_pts, bool want_
     d.n_rows = (uint32_t)rows;
     d.n_blocks = (uint32_t)((rows + TILE - 1) / TILE);
     d.lv = lv;
-    d.c = 1.0f - (lv.d[lv.n - 1] + eps2(t->dim));
-    d.cand_cap = std::max<uint32_t>(TILE_CAP_MIN, t->join_cap);
-    d.tomb = t->dead.empty() ? nullptr : t->d_tomb;
-    d.mirror = nullptr; d.xx = nullptr;
+    const uint64_t* tomb = t->dead.empty() ? nullptr : t->d_tomb;
     d.d_deg = (uint32_t*)scratch.get(cells * sizeof(uint32_t));
     d.d_words = (unsigned long long*)scratch.get(DWL_WORDS * sizeof(unsigned long long));
     HIP_CHECK(hipMemsetAsync(d.d_deg, 0, cells * sizeof(uint32_t), s));
@@ -136,8 +91,15 @@ void levels_run(mi_knn* t, const DensityLevels& lv, uint32_t min_pts, bool want_
     const bool pairs_possible = rows >= 2;
     if (pairs_possible) {
         const TableMirror tm = table_mirror(t, s, scratch);
-        d.mirror = tm.mirror; d.xx = tm.xx; d.tomb = tm.tomb;
-        d.d_cand = (uint2*)scratch.get((size_t)d.cand_cap * sizeof(uint2));
+        DensityStage1<true>& st = d.st1;
+        st.s = s;
+        st.a = st.b = DensitySide{tm.mirror, tm.xx, tm.tomb, d.n_rows, nullptr};
+        st.blocks = &d.blocks; st.cross = nullptr;
+        st.c = 1.0f - (lv.d[lv.n - 1] + eps2(t->dim));   // the top level's bound
+        st.cand_cap = std::max<uint32_t>(TILE_CAP_MIN, t->join_cap);
+        st.d_cand = (uint2*)scratch.get((size_t)st.cand_cap * sizeof(uint2));
+        st.d_count = d.d_words + DWL_CAND;
+        st.stats = d.stats;
         dispatch_nch(t->dim, [&](auto nch) { d.template pass<decltype(nch)::value, 1>(); });
     }
 
@@ -148,11 +110,10 @@ void levels_run(mi_knn* t, const DensityLevels& lv, uint32_t min_pts, bool want_
         for (int i = 0; i < 8; ++i) t->dbscan_stats[i] = d.stats[i];
     };
     if (min_pts == 0) {
-        hipLaunchKernelGGL(density_levels_blocks_kernel, dim3(d.n_blocks), dim3(TILE), 0, s, d.d_deg, d.tomb, d.n_rows, lv.n, 0u,
+        hipLaunchKernelGGL(density_levels_blocks_kernel, dim3(d.n_blocks), dim3(TILE), 0, s, d.d_deg, tomb, d.n_rows, lv.n, 0u,
                            (uint32_t*)nullptr, (unsigned long long*)nullptr, (uint8_t*)nullptr, (uint8_t*)nullptr);
         HIP_CHECK(hipGetLastError());
-        out->counts.resize(cells);
-        HIP_CHECK(hipMemcpyAsync(out->counts.data(), d.d_deg, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        read_back(&out->counts, d.d_deg, cells, s);
         HIP_CHECK(hipMemcpyAsync(words, d.d_words, sizeof words, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         finish_stats();
@@ -163,7 +124,7 @@ void levels_run(mi_knn* t, const DensityLevels& lv, uint32_t min_pts, bool want_
     d.d_bkey = (unsigned long long*)scratch.get(cells * sizeof(unsigned long long));
     d.d_core_from = (uint8_t*)scratch.get(rows);
     d.d_act = (uint8_t*)scratch.get(d.n_blocks);
-    hipLaunchKernelGGL(density_levels_blocks_kernel, dim3(d.n_blocks), dim3(TILE), 0, s, d.d_deg, d.tomb, d.n_rows, lv.n, min_pts, d.d_parent,
+    hipLaunchKernelGGL(density_levels_blocks_kernel, dim3(d.n_blocks), dim3(TILE), 0, s, d.d_deg, tomb, d.n_rows, lv.n, min_pts, d.d_parent,
                        d.d_bkey, d.d_core_from, d.d_act);
     HIP_CHECK(hipGetLastError());
     if (pairs_possible) {
@@ -172,6 +133,7 @@ void levels_run(mi_knn* t, const DensityLevels& lv, uint32_t min_pts, bool want_
         HIP_CHECK(hipMemcpyAsync(d.blocks.act.data(), d.d_act, d.n_blocks, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         d.blocks.index();
+        d.st1.a.act = d.st1.b.act = d.d_act;
         dispatch_nch(t->dim, [&](auto nch) { d.template pass<decltype(nch)::value, 2>(); });
     }
 
@@ -180,36 +142,21 @@ void levels_run(mi_knn* t, const DensityLevels& lv, uint32_t min_pts, bool want_
     float* d_via_dist = want_via_dist ? (float*)scratch.get(cells * sizeof(float)) : nullptr;
     const IdMap map = knn_id_map(t);
     hipLaunchKernelGGL(density_levels_finish_kernel, dim3((d.n_rows + 255) / 256, lv.n), dim3(256), 0, s, d.d_parent, d.d_bkey,
-                       (const uint8_t*)d.d_core_from, d.tomb, d.n_rows, map, d_cluster, d_via, d_via_dist, d.d_words);
+                       (const uint8_t*)d.d_core_from, tomb, d.n_rows, map, d_cluster, d_via, d_via_dist, d.d_words);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(words, d.d_words, sizeof words, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     if (words[DWL_ERROR] != 0)
         fail(MI_ERR_HIP, "internal error: a step cap of the disjoint-set forest expired (%llu times); nothing was written",
              (unsigned long long)words[DWL_ERROR]);
-    out->cluster.resize(cells);
-    HIP_CHECK(hipMemcpyAsync(out->cluster.data(), d_cluster, cells * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    if (want_via) {
-        out->via.resize(cells);
-        HIP_CHECK(hipMemcpyAsync(out->via.data(), d_via, cells * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    }
-    if (want_via_dist) {
-        out->via_dist.resize(cells);
-        HIP_CHECK(hipMemcpyAsync(out->via_dist.data(), d_via_dist, cells * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
-    if (want_counts) {
-        out->counts.resize(cells);
-        HIP_CHECK(hipMemcpyAsync(out->counts.data(), d.d_deg, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    }
+    read_back(&out->cluster, d_cluster, cells, s);
+    if (want_via) read_back(&out->via, d_via, cells, s);
+    if (want_via_dist) read_back(&out->via_dist, d_via_dist, cells, s);
+    if (want_counts) read_back(&out->counts, d.d_deg, cells, s);
     HIP_CHECK(hipStreamSynchronize(s));
     for (uint32_t m = 0; m < lv.n; ++m)
         for (int i = 0; i < 4; ++i) out->summary[m][i] = words[DWL_SUMMARY + 4 * m + i];
     finish_stats();
-}
-
-template <class T>
-void copy_out(const std::vector<T>& v, T* p) {
-    if (p && !v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(T));
 }
 
 }  // namespace

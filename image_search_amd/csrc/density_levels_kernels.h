@@ -1,10 +1,10 @@
 // density_levels_kernels.h — device code of mi_knn_density_levels and mi_knn_dbscan_levels (density_levels.hip): what L calls
 // of mi_knn_density / mi_knn_dbscan at ascending distances d[0] < ... < d[L - 1] return, from the two tile passes one call runs.
-// The tiles, the rescore arithmetic and the forest are density_kernels.h's and join_kernels.h's, unedited.
+// The tiles and the pair distance are pair_kernels.h's (pair_tile, pair_dist), the forest is density_kernels.h's, unedited.
 //
 // Why one pass serves every level.  Let W_l be the pairs mi_knn_near_pairs(d[l]) reports.  Stage 1 (join_tiles_kernel under
 // c = 1 - (d[L - 1] + eps2)) passes a superset of W_{L-1}, and W_l is a subset of W_{L-1} for every l, since dist <= d[l]
-// implies dist <= d[L - 1].  Stage 2 computes density_pair_dist, the single call's fp32 bits, which do not depend on the
+// implies dist <= d[L - 1].  Stage 2 computes pair_dist (pair_kernels.h), the single call's fp32 bits, which do not depend on the
 // threshold; lv = the number of levels with !(dist <= d[l]) is, the thresholds ascending, the first level with dist <= d[lv]:
 // the same float compare the single call makes, so the pair is in W_m exactly for m >= lv (a NaN: lv = L, in no level).
 //
@@ -49,6 +49,7 @@ constexpr int DWL_WITHIN = 8;    // [MI_KNN_LEVELS_MAX]: pairs whose first level
 constexpr int DWL_SUMMARY = 16;  // [MI_KNN_LEVELS_MAX][4]: clusters, core rows, border rows, noise rows
 constexpr int DWL_WORDS = DWL_SUMMARY + 4 * MI_KNN_LEVELS_MAX;
 static_assert(DWL_MERGED == DW_MERGED && DWL_ERROR == DW_ERROR, "ds_find / ds_union write DW_MERGED and DW_ERROR of the words they are given");
+static_assert(DWL_CAND == DW_CAND, "DensityStage1 (density_call.h) is handed the word; both layouts keep it first");
 static_assert(DWL_CAND != DWL_MERGED && DWL_CAND != DWL_ERROR && DWL_WITHIN > DWL_ERROR, "the words must not overlap");
 
 // density_level_of_host on the device: the levels that fail the single call's compare
@@ -65,13 +66,14 @@ template <int NCH>
 __global__ __launch_bounds__(256) void density_count_levels_kernel(const float* __restrict__ table, const uint2* __restrict__ cand,
                                                                    uint32_t C, DensityLevels lv, uint32_t n_rows,
                                                                    uint32_t* __restrict__ degbin, unsigned long long* __restrict__ words) {
+    constexpr int DIM = NCH * 64;
     const int lane = threadIdx.x & 63, i = lane & 15;
     const uint32_t group = (blockIdx.x * 256 + threadIdx.x) >> 4, n_groups = (gridDim.x * 256) >> 4;
     // (whole waves stay in the loop: row16_sum and the ballots are cross-lane operations)
     for (uint32_t c0 = group; c0 < ((C + n_groups - 1) / n_groups) * n_groups; c0 += n_groups) {
         const bool live = c0 < C;
         const uint2 pr = cand[live ? c0 : 0];
-        const float dist = density_pair_dist<NCH>(table, pr, i);
+        const float dist = pair_dist<NCH>(table + (uint64_t)pr.x * DIM, table + (uint64_t)pr.y * DIM, i);
         const uint32_t l = density_level_of(lv, dist);
         const bool keep = live && i == 0 && l < lv.n;
         if (__ballot(keep) == 0ull) continue;
@@ -133,6 +135,7 @@ __global__ __launch_bounds__(256) void density_link_levels_kernel(const float* _
                                                                   DensityLevels lv, uint32_t n_rows, const uint8_t* __restrict__ core_from,
                                                                   uint32_t* parent, unsigned long long* __restrict__ bkey,
                                                                   unsigned long long* __restrict__ words) {
+    constexpr int DIM = NCH * 64;
     const int lane = threadIdx.x & 63, i = lane & 15;
     const uint32_t group = (blockIdx.x * 256 + threadIdx.x) >> 4, n_groups = (gridDim.x * 256) >> 4;
     // (whole waves stay in the loop: row16_sum works across the 16 lanes of a group, which take every branch together)
@@ -142,7 +145,7 @@ __global__ __launch_bounds__(256) void density_link_levels_kernel(const float* _
         const uint32_t fa = core_from[pr.x], fb = core_from[pr.y];
         const uint32_t lo = fa < fb ? fa : fb, hi = fa < fb ? fb : fa;   // one end is a core from lo on, both from hi on
         if (!live || lo >= lv.n) continue;
-        const float dist = density_pair_dist<NCH>(table, pr, i);
+        const float dist = pair_dist<NCH>(table + (uint64_t)pr.x * DIM, table + (uint64_t)pr.y * DIM, i);
         const uint32_t l0 = density_level_of(lv, dist);
         if (i != 0 || l0 >= lv.n) continue;
         // below hi the end that turns core later is the border row

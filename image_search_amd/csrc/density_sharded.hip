@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.h"
+#include "density_call.h"
 #include "density_sharded_host.h"
 #include "density_sharded_kernels.h"
 #include "handles.h"
@@ -26,6 +27,83 @@
 #include "two_stage.h"
 
 using namespace mi;
+
+namespace mi {
+
+// ---- the small kernels between the pieces --------------------------------------------------------------------------------
+static __global__ __launch_bounds__(256) void density_forest_init_kernel(uint32_t* __restrict__ parent, uint32_t n) {
+    for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < n; g += gridDim.x * 256) parent[g] = g;
+}
+// a staged chunk's degrees / border keys into the column shard's own, on its device (the shard is idle meanwhile)
+static __global__ __launch_bounds__(256) void density_add_kernel(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, uint32_t n) {
+    for (uint32_t r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) dst[r] += src[r];
+}
+static __global__ __launch_bounds__(256) void density_min_kernel(unsigned long long* __restrict__ dst, const unsigned long long* __restrict__ src,
+                                                          uint32_t n) {
+    for (uint32_t r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) dst[r] = min(dst[r], src[r]);
+}
+
+// other[i] = the parent of global row g0 + i in another shard's forest, copied here: where that is no root, a union in `parent`
+static __global__ __launch_bounds__(256) void density_forest_merge_kernel(uint32_t* parent, const uint32_t* __restrict__ other, uint32_t g0,
+                                                                   uint32_t n, unsigned long long* __restrict__ words) {
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const uint32_t g = g0 + i, p = other[i];
+        if (p != g) ds_union(parent, g, p, words);
+    }
+}
+
+// root[g] = the root of g (parent is final: the walk reads, nothing writes any more; parent[x] < x off a root)
+static __global__ __launch_bounds__(256) void density_roots_kernel(const uint32_t* __restrict__ parent, uint32_t* __restrict__ root, uint32_t n) {
+    for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < n; g += gridDim.x * 256) {
+        uint32_t x = g;
+        for (uint32_t p = parent[x]; p != x; p = parent[x]) x = p;
+        root[g] = x;
+    }
+}
+
+// per local row of one shard what the contract names; `from` is a global row, root [G] the flattened forest.  via /
+// via_dist may be null.  The summary: a cluster is counted by the shard that holds its root.
+static __global__ __launch_bounds__(256) void density_finish_sharded_kernel(const uint32_t* __restrict__ deg,
+                                                                     const unsigned long long* __restrict__ bkey,
+                                                                     const uint64_t* __restrict__ tomb, const uint32_t* __restrict__ root,
+                                                                     uint32_t n_rows, uint32_t min_pts, IdMap map,
+                                                                     uint64_t* __restrict__ cluster, uint64_t* __restrict__ via,
+                                                                     float* __restrict__ via_dist, unsigned long long* __restrict__ words) {
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int kind = -1;   // 0 a cluster's root, 1 another core, 2 border, 3 noise
+    if (r < n_rows) {
+        uint64_t cl = MI_KNN_NO_ID, v = MI_KNN_NO_ID;
+        float vd = __uint_as_float(0x7F800000u);
+        if (!tile_dead(tomb, r)) {
+            const uint32_t g = (uint32_t)id_of_local(map, r);
+            const unsigned long long key = bkey[r];
+            if (deg[r] >= min_pts - 1u) {
+                const uint32_t x = root[g];
+                cl = x; v = g; vd = 0.0f;
+                kind = x == g ? 0 : 1;
+            } else if (key != KEY_MAX) {
+                const uint32_t from = (uint32_t)key;
+                cl = root[from]; v = from; vd = u32_to_dist((uint32_t)(key >> 32));
+                kind = 2;
+            } else {
+                kind = 3;
+            }
+        }
+        cluster[r] = cl;
+        if (via) via[r] = v;
+        if (via_dist) via_dist[r] = vd;
+    }
+    // clusters, core rows, border rows, noise rows: lane j < 4 adds word j, one atomic instruction per wave
+    const unsigned long long m0 = __ballot(kind == 0), m1 = __ballot(kind == 0 || kind == 1), m2 = __ballot(kind == 2),
+                             m3 = __ballot(kind == 3);
+    if (lane < 4) {
+        const unsigned long long m = lane == 0 ? m0 : lane == 1 ? m1 : lane == 2 ? m2 : m3;
+        if (m != 0ull) atomicAdd(words + DW_SUMMARY + lane, (unsigned long long)__popcll(m));
+    }
+}
+
+}  // namespace mi
 
 namespace {
 
@@ -58,15 +136,12 @@ struct Params {
     uint32_t G;
 };
 
-// One piece of one pass: the row-side shard A with itself (self) or with the column chunk `col` of another shard.  The stages
-// for rect_stages (two_stage.h): it hands a candidate buffer to stage 2 only when the launch that filled it fitted and redoes
-// the ground of one that did not in halves without consuming anything, so every pair reaches stage 2 exactly once (the adds
-// of pass 1 rely on that) and only the launches whose candidates were consumed count their tiles.
+// One piece of one pass: the row-side shard A with itself (SELF) or with the column chunk `col` of another shard.  Stage 1 is
+// density_call.h's (DensityStage1: the overflow scheme and the tile counts live there); stage 2 is this unit's.
 struct Piece {
     ShardState* A;
     hipStream_t s;
     Params p;
-    bool self;
     // the column side (self: A's own arrays)
     ColChunk col;
     IdMap map_b;
@@ -75,62 +150,21 @@ struct Piece {
     const uint8_t* d_act_col;    // the chunk's activity bytes on A's device
     CrossBlocks cross;           // ... and their prefix counts on the host
 
-    template <int NCH, int PASS>
+    template <int NCH, int PASS, bool SELF>
     void rect(uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) {
         mi_knn* a = A->sh;
         uint64_t* stats = A->stats;
         unsigned long long* words = A->d_words;
-        auto stage1 = [&](uint32_t r0, uint32_t r1, uint32_t& c0, uint32_t c1) -> unsigned long long {
-            if (self) c0 = std::max(c0, r0);   // tiles on or above the diagonal
-            if (c0 >= c1) return 0;
-            uint64_t visited = 0, skipped = 0;
-            if (PASS == 2) {
-                if (self) A->blocks.count(r0, r1, c0, c1, &visited, &skipped);
-                else cross.count(A->blocks.act.data(), r0, r1, c0, c1, &visited, &skipped);
-                if (visited == 0) { stats[5] += skipped; return 0; }   // every workgroup would leave at once
-            } else if (self) {
-                for (uint32_t bi = r0; bi < r1; ++bi) visited += c1 - std::max(c0, bi);
-            } else {
-                visited = (uint64_t)(r1 - r0) * (c1 - c0);
-            }
-            HIP_CHECK(hipMemsetAsync(words + DW_CAND, 0, sizeof(unsigned long long), s));
-            const dim3 grid(c1 - c0, r1 - r0);
-            if (self && PASS == 1) {
-                static DevOnce once;
-                allow_lds_once(once, join_tiles_kernel<NCH>, JOIN_LDS);
-                hipLaunchKernelGGL((join_tiles_kernel<NCH>), grid, dim3(256), JOIN_LDS, s, A->tm.mirror, A->tm.xx, A->tm.tomb, A->n_rows, 0u,
-                                   r0, c0, p.c, A->cand_cap, A->d_cand, words + DW_CAND);
-            } else if (self) {
-                static DevOnce once;
-                allow_lds_once(once, density_tiles_kernel<NCH>, JOIN_LDS);
-                hipLaunchKernelGGL((density_tiles_kernel<NCH>), grid, dim3(256), JOIN_LDS, s, A->tm.mirror, A->tm.xx, A->tm.tomb,
-                                   (const uint8_t*)A->d_act, A->n_rows, r0, c0, p.c, A->cand_cap, A->d_cand, words + DW_CAND);
-            } else if (PASS == 1) {
-                static DevOnce once;
-                allow_lds_once(once, cross_tiles_kernel<NCH>, JOIN_LDS);
-                hipLaunchKernelGGL((cross_tiles_kernel<NCH>), grid, dim3(256), JOIN_LDS, s, A->tm.mirror, A->tm.xx, A->tm.tomb, A->n_rows,
-                                   col.mirror, col.xx, col.tomb, col.n, 0u, 0u, r0, c0, p.c, A->cand_cap, A->d_cand, words + DW_CAND);
-            } else {
-                static DevOnce once;
-                allow_lds_once(once, density_cross_tiles_kernel<NCH>, JOIN_LDS);
-                hipLaunchKernelGGL((density_cross_tiles_kernel<NCH>), grid, dim3(256), JOIN_LDS, s, A->tm.mirror, A->tm.xx, A->tm.tomb,
-                                   (const uint8_t*)A->d_act, A->n_rows, col.mirror, col.xx, col.tomb, d_act_col, col.n, r0, c0, p.c,
-                                   A->cand_cap, A->d_cand, words + DW_CAND);
-            }
-            HIP_CHECK(hipGetLastError());
-            ++stats[7];
-            const unsigned long long n = read_count(words + DW_CAND, s);
-            if (n <= A->cand_cap) {
-                if (PASS == 1) stats[2] += visited;
-                else { stats[4] += visited; stats[5] += skipped; }
-            }
-            return n;
-        };
+        DensityStage1<SELF> st1{s,
+                                DensitySide{A->tm.mirror, A->tm.xx, A->tm.tomb, A->n_rows, A->d_act},
+                                DensitySide{col.mirror, col.xx, col.tomb, col.n, d_act_col},
+                                &A->blocks, &cross, p.c, A->cand_cap, A->d_cand, words + DW_CAND, stats};
+        auto stage1 = [&](uint32_t r0, uint32_t r1, uint32_t& c0, uint32_t c1) { return st1.template stage1<NCH, PASS>(r0, r1, c0, c1); };
         auto stage2 = [&](uint32_t C) {
             const dim3 grid(group16_blocks(a, C));
             if (PASS == 1) {
                 stats[0] += C;
-                if (self)
+                if (SELF)
                     hipLaunchKernelGGL((density_count_kernel<NCH>), grid, dim3(256), 0, s, a->table, A->d_cand, C, p.max_dist, A->d_deg, words);
                 else
                     hipLaunchKernelGGL((density_count_between_kernel<NCH>), grid, dim3(256), 0, s, a->table, col.rows, A->map, map_b, col.off,
@@ -146,24 +180,18 @@ struct Piece {
         rect_stages(br0, br1, bc0, bc1, A->cand_cap, overflowed, stage1, stage2);
     }
 
-    // a shard with itself: the join's strips (density.hip)
+    // a shard with itself: the join's triangle in the join's strips
     template <int NCH, int PASS>
     void run_self() {
-        const uint32_t nb = A->n_blocks;
-        uint32_t strip = std::max<uint32_t>(1u, std::min<uint32_t>(256u, (1u << 18) / std::max(nb, 1u)));
-        for (uint32_t br = 0; br < nb;) {
-            const uint32_t end = std::min(nb, br + strip);
-            bool overflowed = false;
-            rect<NCH, PASS>(br, end, 0, nb, &overflowed);
-            if (overflowed) strip = std::max(1u, strip / 2);
-            br = end;
-        }
+        tile_strips(0, A->n_blocks, 0, A->n_blocks,
+                    [&](uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) { rect<NCH, PASS, true>(br0, br1, bc0, bc1, overflowed); },
+                    [] { return false; });
     }
     // the chunk in `col` against all of A
     template <int NCH, int PASS>
     void run_chunk() {
         between_strips(A->n_rows, col.n, 0u, 0u,
-                       [&](uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) { rect<NCH, PASS>(br0, br1, bc0, bc1, overflowed); },
+                       [&](uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) { rect<NCH, PASS, false>(br0, br1, bc0, bc1, overflowed); },
                        [] { return false; });
     }
 };
@@ -173,7 +201,7 @@ template <int PASS>
 void self_piece(ShardState& x, const Params& p, hipStream_t s) {
     if (x.n_rows < 2) return;
     Piece pc;
-    pc.A = &x; pc.s = s; pc.p = p; pc.self = true;
+    pc.A = &x; pc.s = s; pc.p = p;
     pc.col = ColChunk{x.tm.mirror, x.tm.xx, x.tm.tomb, x.sh->table, x.n_rows, 0u, 0u};
     pc.map_b = x.map;
     pc.deg_col = x.d_deg; pc.bkey_col = x.d_bkey;
@@ -198,7 +226,7 @@ void cross_piece(ShardState& A, ShardState& B, const Params& p) {
     b->reads.begin(s);
     ColumnWalk walk(a, b, s, scratch, &B.tm);
     Piece pc;
-    pc.A = &A; pc.s = s; pc.p = p; pc.self = false;
+    pc.A = &A; pc.s = s; pc.p = p;
     pc.map_b = B.map;
     uint32_t* st_deg = nullptr;
     unsigned long long* st_bkey = nullptr;
@@ -434,11 +462,6 @@ void sharded_density_run(ShardedCall& call, float max_dist, uint32_t min_pts, bo
         fail(MI_ERR_HIP, "internal error: a step cap of the disjoint-set forest expired (%llu times); nothing was written", errors);
     for (int i = 0; i < 8; ++i) t->dbscan_stats[i] = stats[i];
     *out = std::move(res);
-}
-
-template <class T>
-void copy_out(const std::vector<T>& v, T* p) {
-    if (p && !v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(T));
 }
 
 }  // namespace

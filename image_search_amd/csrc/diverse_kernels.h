@@ -133,6 +133,7 @@ __global__ __launch_bounds__(256) void diverse_rescore_kernel(const float* __res
         const uint2 pr = cand[live ? c0 : 0];
         const f32x4* pa = reinterpret_cast<const f32x4*>(table + (uint64_t)pr.x * DIM) + i;
         const f32x4* pb = reinterpret_cast<const f32x4*>(table + (uint64_t)pr.y * DIM) + i;
+        // (pair_dist of pair_kernels.h, written out: as a call it compiles to another register allocation here at NCH >= 8)
         f32x4 qf[NCH];
 #pragma unroll
         for (int t = 0; t < NCH; ++t) qf[t] = pa[16 * t];

@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "handles.h"
+#include "join_between_host.h"
 #include "join_kernels.h"
 #include "two_stage.h"
 
@@ -79,18 +80,10 @@ struct Join {
 
     template <int NCH>
     void run() {
-        const uint32_t fnb = first_new / TILE;   // column blocks below hold no b >= first_new
-        const uint32_t n_cols = n_blocks - fnb;
-        // strips of tile rows: enough tiles per launch to fill the device a few times over, few enough that an ordinary
-        // corpus never meets the candidate buffer's end
-        uint32_t strip = std::max<uint32_t>(1u, std::min<uint32_t>(256u, (1u << 18) / std::max(n_cols, 1u)));
-        for (uint32_t br = 0; br < n_blocks && !over;) {
-            const uint32_t end = std::min(n_blocks, br + strip);
-            bool overflowed = false;
-            rect<NCH>(br, end, fnb, n_blocks, &overflowed);
-            if (overflowed) strip = std::max(1u, strip / 2);
-            br = end;
-        }
+        // column blocks below first_new / TILE hold no b >= first_new
+        tile_strips(0, n_blocks, first_new / TILE, n_blocks,
+                    [&](uint32_t br0, uint32_t br1, uint32_t bc0, uint32_t bc1, bool* overflowed) { rect<NCH>(br0, br1, bc0, bc1, overflowed); },
+                    [&] { return over; });
     }
 };
 

@@ -60,6 +60,23 @@ inline uint32_t between_chunk_bound(uint64_t fn_b, uint64_t c0, uint64_t c1) { r
 // times over, few enough that an ordinary corpus never meets the candidate buffer's end
 inline uint32_t between_strip(uint32_t n_cols) { return std::max<uint32_t>(1u, std::min<uint32_t>(256u, (1u << 18) / std::max(n_cols, 1u))); }
 
+// The tile rows [r0, r1) against the tile columns [c0, c1), in strips of between_strip(c1 - c0) tile rows: the one strip walk
+// of the self-join, the join of two row sets and the density passes.  rect(br0, br1, c0, c1, &overflowed) runs one strip
+// (rect_stages with the caller's two stages) and reports whether its candidates overflowed the buffer: the strips after it
+// are half as tall, never below one tile row.  stop() ends the walk between strips.
+template <class Rect, class Stop>
+void tile_strips(uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1, Rect&& rect, Stop&& stop) {
+    if (c0 >= c1) return;
+    uint32_t strip = between_strip(c1 - c0);
+    for (uint32_t br = r0; br < r1 && !stop();) {
+        const uint32_t end = std::min(r1, br + strip);
+        bool overflowed = false;
+        rect(br, end, c0, c1, &overflowed);
+        if (overflowed) strip = std::max(1u, strip / 2);
+        br = end;
+    }
+}
+
 // ---- the tiles to launch -------------------------------------------------------------------------------------------------
 // Element (ra, cb) of n_a x n_b rows qualifies iff ra >= fn_a or cb >= fn_b (fn_a <= n_a, fn_b <= n_b; 0, 0: everything).
 // A tile is launched iff it holds a qualifying element: tile row bi has one by its rows iff bi >= ta, tile column bj by its

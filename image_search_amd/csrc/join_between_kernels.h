@@ -1,7 +1,7 @@
 // join_between_kernels.h — device code of the threshold join of TWO row sets (mi_knn_near_pairs_between: "which pictures of
 // that other library do I already have?"; mi_knn_sharded_near_pairs: the pairs whose rows live in different shards).  The
 // kernels of join_kernels.h with a row operand (A, where the work runs) and a column operand (B) that come from different
-// tables; the tile core (tile128.h) already keeps the two apart.
+// tables: pair_tile and pair_dist (pair_kernels.h) keep the two apart, the self-join passes one table as both.
 //
 // Stage 1 (cross_tiles_kernel).  S = M_a M_b^T over the two bf16 mirrors, every tile of the rectangle the host launches:
 // there is no diagonal, every element of a tile may be a pair.  The bound eps2 (join_kernels.h) is a bound on two
@@ -38,56 +38,8 @@ __global__ __launch_bounds__(256) void cross_tiles_kernel(const uint16_t* __rest
                                                            const uint64_t* __restrict__ tomb_b, uint32_t n_b, uint32_t fn_a,
                                                            uint32_t fn_b, uint32_t br0, uint32_t bc0, float c, uint32_t cap,
                                                            uint2* __restrict__ cand, unsigned long long* __restrict__ count) {
-    constexpr int DIM = NCH * 64;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const uint32_t bi = br0 + blockIdx.y, bj = bc0 + blockIdx.x;
-    const int tid = threadIdx.x;
-    const TileFrag f = tile_frag();
-    const int wr = f.wr, wc = f.wc, l31 = f.l31, lh = f.lh;
-    float* wgt = reinterpret_cast<float*>(smem + TILE_IMGS);   // [0, 128): the tile's rows of A, [128, 256): its rows of B
-    const uint32_t row0 = bi * TILE, col0 = bj * TILE;
-    const float inf = __uint_as_float(0x7F800000u);
-
-    {
-        const bool is_col = tid >= TILE;
-        const uint32_t r = (is_col ? col0 : row0) + (uint32_t)(tid & (TILE - 1));
-        wgt[tid] = tile_weight<false>(is_col ? xx_b : xx_a, r, r < (is_col ? n_b : n_a), is_col ? tomb_b : tomb_a, r, -inf,
-                                      __uint_as_float(0x7FC00000u));
-    }
-
-    const uint16_t *ga[4], *gb[4];
-    tile_src<DIM>(ga, mirror_a, row0, n_a);
-    tile_src<DIM>(gb, mirror_b, col0, n_b);
-    f32x16 acc[2][2];
-    tile_accumulate<NCH>(smem, f, ga, gb, acc);
-
-    // C/D map: register e of lane l is row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31 of its 32 x 32 block.
-    // A tile that straddles a bound: rows below fn_a pair only with columns >= fn_b.  `rlo` = the tile rows below fn_a
-    // (0 when the whole tile qualifies by its rows or by its columns: then the test below never fires).
-    const uint32_t rlo = (col0 >= fn_b || row0 >= fn_a) ? 0u : min(fn_a - row0, (uint32_t)TILE);
-    unsigned long long hit = 0ull;   // bit (2 ti + tj) * 16 + e
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int ra0 = wr * 64 + ti * 32 + 8 * q + 4 * lh;
-            const f32x4 wa = *reinterpret_cast<const f32x4*>(wgt + ra0);
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) {
-                const int cb = wc * 64 + tj * 32 + l31;
-                const float wb = wgt[TILE + cb];
-                const bool col_new = col0 + (uint32_t)cb >= fn_b;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float p = wa[j] * wb;
-                    bool ok = p == p && (!(acc[ti][tj][4 * q + j] < c * p) || fabsf(p) == inf);
-                    ok = ok && (col_new || (uint32_t)(ra0 + j) >= rlo);
-                    if (ok) hit |= 1ull << ((2 * ti + tj) * 16 + 4 * q + j);
-                }
-            }
-        }
-    }
-    tile_append(hit, f, row0, col0, cap, cand, count);
+    pair_tile<NCH, false, false>(mirror_a, xx_a, tomb_a, nullptr, n_a, mirror_b, xx_b, tomb_b, nullptr, n_b, fn_a, fn_b, br0, bc0, c, cap,
+                                 cand, count);
 }
 
 // stage 2: C candidates (ra, cb) (C <= the buffer's capacity: checked by the host before this runs) -> the pairs with exact
@@ -112,6 +64,7 @@ __global__ __launch_bounds__(256) void cross_rescore_kernel(const float* __restr
         const bool b_asks = by_id && id_of_local(map_b, (uint64_t)col_off + pr.y) < id_of_local(map_a, pr.x);
         const f32x4* pq = reinterpret_cast<const f32x4*>(b_asks ? rb : ra) + i;   // the query
         const f32x4* px = reinterpret_cast<const f32x4*>(b_asks ? ra : rb) + i;   // the row streamed against it
+        // (pair_dist of pair_kernels.h, written out: as a call it compiles to another register allocation here at NCH >= 8)
         f32x4 qf[NCH];
 #pragma unroll
         for (int t = 0; t < NCH; ++t) qf[t] = pq[16 * t];

@@ -6,7 +6,7 @@
 // lives there ("direct"), or a staged copy — the fp32 rows of chunk [c0, c1) copied into the call's scratch (device to
 // device, or peer to peer from another GPU), mirrored there with knn_mirror_kernel, its deletion words built from B's host
 // list.  Inside a chunk the rectangles a pair of bounds leaves (between_rects) are walked in strips of tile rows
-// (between_strip), halved after an overflow; what a strip does is the consumer's (rect_stages with its two stages).
+// (tile_strips), halved after an overflow; what a strip does is the consumer's (rect_stages with its two stages).
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -101,17 +101,8 @@ template <class Rect, class Stop>
 void between_strips(uint32_t n_a, uint32_t n_b, uint32_t fn_a, uint32_t fn_b, Rect&& rect, Stop&& stop) {
     TileRect rects[2];
     const uint32_t n_rects = between_rects(n_a, n_b, fn_a, fn_b, rects);
-    for (uint32_t i = 0; i < n_rects && !stop(); ++i) {
-        const TileRect& r = rects[i];
-        uint32_t strip = between_strip(r.c1 - r.c0);
-        for (uint32_t br = r.r0; br < r.r1 && !stop();) {
-            const uint32_t end = std::min(r.r1, br + strip);
-            bool overflowed = false;
-            rect(br, end, r.c0, r.c1, &overflowed);
-            if (overflowed) strip = std::max(1u, strip / 2);
-            br = end;
-        }
-    }
+    for (uint32_t i = 0; i < n_rects && !stop(); ++i)
+        tile_strips(rects[i].r0, rects[i].r1, rects[i].c0, rects[i].c1, rect, stop);
 }
 
 }  // namespace mi

@@ -4,7 +4,7 @@
 // Two stages, the contract of the two-stage search (knn_kernels.h "bf16 mirror as prefilter"): a cheap first stage that may
 // only err on the side of MORE pairs, and the fp32 arithmetic of knn_scan_kernel deciding.
 //
-// Stage 1 (join_tiles_kernel), the matrix pipe.  S = M M^T over the bf16 mirror M (knn_mirror_kernel: rows rounded to
+// Stage 1 (join_tiles_kernel: pair_tile of pair_kernels.h as the self-join calls it), the matrix pipe.  S = M M^T over the bf16 mirror M (knn_mirror_kernel: rows rounded to
 // nearest even, stored fp32 squared norms, -1 = marked), in tiles of 128 x 128 rows, only tiles on or above the diagonal.
 // A workgroup of four waves owns one tile, a wave a 64 x 64 quadrant as 2 x 2 accumulators of v_mfma_f32_32x32x16_bf16;
 // K runs in steps of 64 elements through a double-buffered LDS image (2 x 2 x 16 KiB).  The epilogue compares every
@@ -26,18 +26,19 @@
 //
 // Stage 2 (join_rescore_kernel): one 16-lane group per candidate pair.  Row a is the query — its sqrt(q.q) from RowAcc as
 // in knn_scan_kernel / knn_rescore_kernel — row b is streamed, dist = 1 - dot / (sq * sqrt(xx)): the value mi_knn_search
-// with q = row a reports for row b, bit for bit.  Pairs with dist <= max_dist (never a NaN) are compacted as (a, b, dist).
+// with q = row a reports for row b, bit for bit.  That is pair_dist (pair_kernels.h), which the density kernels call; the three
+// kernels that compact or mark pairs (this one, cross_rescore_kernel, diverse_rescore_kernel) keep it written out.  Pairs with dist <= max_dist (never a NaN) are compacted as (a, b, dist).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "common.h"
+#include "pair_kernels.h"
 #include "tile128.h"
 
 namespace mi {
 
-constexpr int JOIN_LDS = TILE_IMGS + 2 * TILE * 4;                   // the tile's images + the rows' weights
 constexpr uint32_t JOIN_CAP_DEFAULT = PREF_CAP;
 
 // grid (column blocks, row blocks): workgroup (x, y) takes tile (bi = br0 + y, bj = bc0 + x) and leaves at once when
@@ -48,54 +49,8 @@ __global__ __launch_bounds__(256) void join_tiles_kernel(const uint16_t* __restr
                                                           const uint64_t* __restrict__ tomb, uint32_t n_rows, uint32_t first_new,
                                                           uint32_t br0, uint32_t bc0, float c, uint32_t cap,
                                                           uint2* __restrict__ cand, unsigned long long* __restrict__ count) {
-    constexpr int DIM = NCH * 64;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const uint32_t bi = br0 + blockIdx.y, bj = bc0 + blockIdx.x;
-    if (bj < bi) return;
-    const int tid = threadIdx.x;
-    const TileFrag f = tile_frag();
-    const int wr = f.wr, wc = f.wc, l31 = f.l31, lh = f.lh;
-    float* wgt = reinterpret_cast<float*>(smem + TILE_IMGS);   // [0, 128): the tile's rows a, [128, 256): its columns b
-    const uint32_t row0 = bi * TILE, col0 = bj * TILE;
-    const float inf = __uint_as_float(0x7F800000u);
-
-    // a row's weight: sqrt of its stored norm; -inf = marked (a candidate against everything live); NaN = not there
-    {
-        const bool is_col = tid >= TILE;
-        const uint32_t r = (is_col ? col0 : row0) + (uint32_t)(tid & (TILE - 1));
-        wgt[tid] = tile_weight<false>(xx, r, r < n_rows && !(is_col && r < first_new), tomb, r, -inf, __uint_as_float(0x7FC00000u));
-    }
-
-    const uint16_t *ga[4], *gb[4];
-    tile_src<DIM>(ga, mirror, row0, n_rows);
-    tile_src<DIM>(gb, mirror, col0, n_rows);
-    f32x16 acc[2][2];
-    tile_accumulate<NCH>(smem, f, ga, gb, acc);
-
-    // C/D map: register e of lane l is row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31 of its 32 x 32 block
-    const bool diag = bi == bj;
-    unsigned long long hit = 0ull;   // bit (2 ti + tj) * 16 + e
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int ra0 = wr * 64 + ti * 32 + 8 * q + 4 * lh;
-            const f32x4 wa = *reinterpret_cast<const f32x4*>(wgt + ra0);
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) {
-                const int cb = wc * 64 + tj * 32 + l31;
-                const float wb = wgt[TILE + cb];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float p = wa[j] * wb;
-                    bool ok = p == p && (!(acc[ti][tj][4 * q + j] < c * p) || fabsf(p) == inf);
-                    if (diag) ok = ok && cb > ra0 + j;
-                    if (ok) hit |= 1ull << ((2 * ti + tj) * 16 + 4 * q + j);
-                }
-            }
-        }
-    }
-    tile_append(hit, f, row0, col0, cap, cand, count);
+    pair_tile<NCH, true, false>(mirror, xx, tomb, nullptr, n_rows, mirror, xx, tomb, nullptr, n_rows, 0u, first_new, br0, bc0, c, cap, cand,
+                                count);
 }
 
 // stage 2: C candidate pairs (C <= the buffer's capacity: checked by the host before this runs) -> the pairs with exact
@@ -113,6 +68,7 @@ __global__ __launch_bounds__(256) void join_rescore_kernel(const float* __restri
         const uint2 pr = cand[live ? c0 : 0];
         const f32x4* pa = reinterpret_cast<const f32x4*>(table + (uint64_t)pr.x * DIM) + i;
         const f32x4* pb = reinterpret_cast<const f32x4*>(table + (uint64_t)pr.y * DIM) + i;
+        // (pair_dist of pair_kernels.h, written out: as a call it compiles to another register allocation here at NCH >= 8)
         f32x4 qf[NCH];
 #pragma unroll
         for (int t = 0; t < NCH; ++t) qf[t] = pa[16 * t];

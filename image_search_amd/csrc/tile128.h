@@ -1,5 +1,6 @@
-// tile128.h — the 128 x 128 bf16 tile that stage 1 of the join, the assign, the multi-label assign and the many-query search
-// share (join_kernels.h has the bound eps2 that makes such a first stage exact; each kernel's header has its own superset
+// tile128.h — the 128 x 128 bf16 tile that stage 1 of the threshold-pair calls (the join, the join of two row sets, the
+// density passes: pair_kernels.h), the assign, the multi-label assign and the many-query search share (join_kernels.h has
+// the bound eps2 that makes such a first stage exact; each kernel's header has its own superset
 // argument).  S = A B^T over two bf16 mirrors (knn_mirror_kernel: rows rounded to nearest even, stored fp32 squared norms,
 // -1 = marked).  A workgroup of four waves owns one tile, a wave a 64 x 64 quadrant as 2 x 2 accumulators of
 // v_mfma_f32_32x32x16_bf16; K runs in steps of 64 elements through a double-buffered LDS image (2 x 2 x 16 KiB, at the
@@ -9,6 +10,8 @@
 //     tile_accumulate         the K loop,
 //     tile_weight             a row's weight from its stored norm,
 //     tile_append             the `hit` mask -> the candidate buffer, one atomic per wave that has any.
+// pair_tile (pair_kernels.h) puts the four together with the threshold test as its epilogue: the whole stage 1 of the
+// threshold-pair calls.
 #pragma once
 #include <hip/hip_runtime.h>
 

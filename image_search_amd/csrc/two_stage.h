@@ -4,6 +4,7 @@
 // and the scheme that redoes a launch whose candidates overflowed the buffer.
 #pragma once
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -28,6 +29,18 @@ struct Scratch {
         for (void* q : p) (void)hipFree(q);
     }
 };
+
+// n elements of a call's device array into a host vector, enqueued on s (the caller waits for the stream)
+template <class T>
+void read_back(std::vector<T>* v, const T* d, size_t n, hipStream_t s) {
+    v->resize(n);
+    HIP_CHECK(hipMemcpyAsync(v->data(), d, n * sizeof(T), hipMemcpyDeviceToHost, s));
+}
+// a call's result into the caller's array, which may be null, once the call's frame has left
+template <class T>
+void copy_out(const std::vector<T>& v, T* p) {
+    if (p && !v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(T));
+}
 
 // The bound of a first stage with BOTH operands rounded to bf16 (derived in join_kernels.h):
 // |coarse - exact| <= eps2 on the cosine of every pair the mirror does not mark.

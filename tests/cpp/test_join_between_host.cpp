@@ -1,6 +1,6 @@
 // The host-only pieces of the join of two row sets (image_search_amd/csrc/join_between_host.h) as a stand-alone program: the
 // argument rules, the round-robin schedule of the shard pairs, the rectangles of tiles a pair of bounds leaves against a
-// brute-force walk, a shard's local first_new against an enumeration of the ids, and the column chunks.  Built with
+// brute-force walk, a shard's local first_new against an enumeration of the ids, the column chunks, and the strip walk.  Built with
 // -fsanitize=address,undefined (tests/test_join_between_host.py).
 #include <cmath>
 #include <cstdio>
@@ -156,12 +156,79 @@ static void chunks() {
     EXPECT(between_strip(1) == 256 && between_strip(1u << 12) == 64 && between_strip(1u << 20) == 1 && between_strip(0) == 256);
 }
 
+// the one strip walk: the rectangles it hands out, the halving after an overflow, stop(), the empty grounds
+static void strips() {
+    struct Call { uint32_t r0, r1, c0, c1; };
+    const auto never = [] { return false; };
+    // the rectangles tile [r0, r1) x [c0, c1) exactly once, whole column ranges, in ascending strips of between_strip(c1 - c0) rows
+    const uint32_t grounds[][4] = {{0, 1, 0, 1}, {0, 3, 0, 3}, {5, 700, 2, 9}, {0, 1000, 0, 2048}, {3, 40, 7, 7 + (1u << 17)}, {0, 5, 0, 1u << 20}};
+    for (const auto& g : grounds) {
+        std::vector<Call> calls;
+        tile_strips(g[0], g[1], g[2], g[3], [&](uint32_t a, uint32_t b, uint32_t c, uint32_t d, bool*) { calls.push_back(Call{a, b, c, d}); }, never);
+        uint32_t at = g[0];
+        for (size_t i = 0; i < calls.size(); ++i) {
+            const Call& k = calls[i];
+            EXPECT(k.r0 == at && k.r1 > k.r0 && k.c0 == g[2] && k.c1 == g[3]);
+            EXPECT(k.r1 - k.r0 == between_strip(g[3] - g[2]) || (i + 1 == calls.size() && k.r1 - k.r0 < between_strip(g[3] - g[2])));
+            at = k.r1;
+        }
+        EXPECT(at == g[1]);
+    }
+    // *overflowed is false on entry; a reported overflow halves the strips that follow, never below one tile row, and the
+    // walk still covers every row once
+    {
+        std::vector<Call> calls;
+        uint32_t n = 0;
+        tile_strips(0, 1000, 0, 4096, [&](uint32_t a, uint32_t b, uint32_t, uint32_t, bool* over) {
+            EXPECT(!*over);
+            calls.push_back(Call{a, b, 0, 0});
+            if (n++ < 9) *over = true;   // nine overflows from a strip of 64: 64, 32, 16, 8, 4, 2, 1, 1, 1, then 1 for good
+        }, never);
+        const uint32_t want[] = {64, 32, 16, 8, 4, 2, 1, 1, 1, 1, 1};
+        EXPECT(calls.size() > 11);
+        uint32_t at = 0;
+        for (size_t i = 0; i < calls.size(); ++i) {
+            EXPECT(calls[i].r0 == at && calls[i].r1 - calls[i].r0 == (i < 11 ? want[i] : 1u));
+            at = calls[i].r1;
+        }
+        EXPECT(at == 1000);
+    }
+    {   // an overflow in the middle only: the strips before it keep their height, those after it have half
+        std::vector<uint32_t> heights;
+        tile_strips(0, 1024, 0, 1024, [&](uint32_t a, uint32_t b, uint32_t, uint32_t, bool* over) {
+            heights.push_back(b - a);
+            if (heights.size() == 2) *over = true;
+        }, never);
+        EXPECT(heights.size() == 6 && heights[0] == 256 && heights[1] == 256 && heights[2] == 128 && heights[5] == 128);
+    }
+    // stop() is asked before every strip and ends the walk between strips
+    {
+        uint32_t n = 0, asked = 0;
+        tile_strips(0, 1000, 0, 4096, [&](uint32_t, uint32_t, uint32_t, uint32_t, bool*) { ++n; }, [&] { ++asked; return n == 3; });
+        EXPECT(n == 3 && asked == 4);
+        n = 0;
+        tile_strips(0, 1000, 0, 4096, [&](uint32_t, uint32_t, uint32_t, uint32_t, bool*) { ++n; }, [] { return true; });
+        EXPECT(n == 0);
+    }
+    // an empty ground calls nothing
+    {
+        uint32_t n = 0;
+        const auto count = [&](uint32_t, uint32_t, uint32_t, uint32_t, bool*) { ++n; };
+        tile_strips(7, 7, 0, 10, count, never);
+        tile_strips(0, 10, 4, 4, count, never);
+        tile_strips(9, 3, 0, 10, count, never);
+        tile_strips(0, 10, 8, 2, count, never);
+        EXPECT(n == 0);
+    }
+}
+
 int main() {
     args();
     schedule();
     rects();
     first_new();
     chunks();
+    strips();
     if (failures) { std::printf("%d failures\n", failures); return 1; }
     std::printf("ok\n");
     return 0;
