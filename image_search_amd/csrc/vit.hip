@@ -562,7 +562,7 @@ void attention(mi_clip* m, const void* qkv, void* ctx, size_t n, hipStream_t s, 
     }
             if (m->S <= 80) MI_ATTNF(80)          // the text tower's 77 positions; ViT-B/32
             else if (m->S <= 208) MI_ATTNF(208)   // ViT-B/16 @224
-            else MI_ATTNF(272)                    // ViT-L/14, ViT-H/14 @224
+            else MI_ATTNF(272)                    // ViT-L/14 @224 (ViT-H/14 has 80-wide heads: refused at load)
 #undef MI_ATTNF
         } else {
             const int qb = first_tile_only ? 1 : (m->S + 63) / 64;
@@ -586,7 +586,7 @@ void attention(mi_clip* m, const void* qkv, void* ctx, size_t n, hipStream_t s, 
             if (m->attn_nt) MI_ATTN32_L(SP, SC, false, 2) else MI_ATTN32_L(SP, SC, false, 0)                           \
         }                                                                                                              \
     }
-        if (m->S == 257) MI_ATTN32(288, 257)       // ViT-L/14, ViT-H/14 @224
+        if (m->S == 257) MI_ATTN32(288, 257)       // ViT-L/14 @224 (ViT-H/14 has 80-wide heads: refused at load)
         else if (m->S == 197) MI_ATTN32(224, 197)  // ViT-B/16 @224
         else if (m->S <= 128) MI_ATTN32(128, 0)
         else if (m->S <= 224) MI_ATTN32(224, 0)
@@ -603,7 +603,7 @@ void attention(mi_clip* m, const void* qkv, void* ctx, size_t n, hipStream_t s, 
         allow_lds_once(once, attn_bf16_kernel<SP, SC>, SP * 256);                                                    \
         hipLaunchKernelGGL((attn_bf16_kernel<SP, SC>), dim3(blocks), dim3(256), SP * 256, s, (const bf16_t*)qkv, (bf16_t*)ctx, m->S, m->D, m->H, first_tile_only ? 1 : 0, m->text ? 1 : 0); \
     }
-        if (m->S == 257) MI_ATTN(288, 257)       // ViT-L/14, ViT-H/14 @224
+        if (m->S == 257) MI_ATTN(288, 257)       // ViT-L/14 @224 (ViT-H/14 has 80-wide heads: refused at load)
         else if (m->S == 197) MI_ATTN(224, 197)  // ViT-B/16 @224
         else if (m->S == 50) MI_ATTN(64, 50)     // ViT-B/32 @224
         else if (sp <= 32) MI_ATTN(32, 0)

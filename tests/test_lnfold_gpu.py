@@ -62,12 +62,15 @@ def block_sums(x):
 
 
 def stats_of(part, d, eps):
-    """ln_stats_kernel's order: lane j of 16 adds blocks 2j and 2j + 1, the 16 lanes add as a balanced tree."""
+    """ln_stats_kernel's order: lane j of 16 adds blocks 2j and 2j + 1 of each group of 32 blocks, the groups in order
+    (hidden 1280 and 1536 have 40 and 48 blocks: a second trip), then the 16 lanes add as a balanced tree."""
     m, nb, _ = part.shape
-    assert nb <= 32
+    assert nb % 2 == 0
     lanes = np.zeros((m, 16, 2), F32)
     pair = (part[:, 0::2, :] + part[:, 1::2, :]).astype(F32)
-    lanes[:, :nb // 2] = pair
+    for g in range(0, nb // 2, 16):
+        grp = pair[:, g:g + 16]
+        lanes[:, :grp.shape[1]] = (lanes[:, :grp.shape[1]] + grp).astype(F32)
     while lanes.shape[1] > 1:
         lanes = (lanes[:, 0::2] + lanes[:, 1::2]).astype(F32)
     s, q = lanes[:, 0, 0], lanes[:, 0, 1]
@@ -171,6 +174,64 @@ def test_lnf_epilogue_exact_on_integers(built, monkeypatch, grid):
         ref = st[:, :1] * (x @ w.T) + st[:, 1:] * c + b
         assert np.abs(ref).max() <= 256
         assert np.array_equal(ops.linear_lnf(x, w, b, c, st, ops.EPI_LNF), ref), (grid, m, n, k)
+
+
+# ---- the persistent GEMM at the column counts and K depths of the other hidden sizes -----------------------------------
+
+# q/k/v, fc1 and fc2 of a 768-wide tower (9 and 12 column tiles, 48 K tiles), of a 1280-wide one (15 and 20 column tiles: tile
+# order 4 does not divide 15 and falls back to row-major, 20 gives five groups; 80 K tiles), out_proj of 1536 and 1280
+WIDE_SHAPES = [(700, 2304, 768), (700, 3072, 768), (700, 768, 3072), (700, 3840, 1280), (700, 5120, 1280), (700, 1280, 5120),
+               (700, 1536, 1536), (520, 1280, 1280)]
+HIDDEN_SIZES = (128, 256, 384, 512, 768, 1024, 1280, 1536, 1664)
+_wide_cases = {}
+
+
+def _wide_case(shape):
+    """Integer operands and the exact results of the three epilogues, made once per shape.  w is sparse (5 % of {-1, 0, 1}) so
+    that |x W^T| stays far below 256 at K = 5120 and every output is a small integer: exactly representable in bf16."""
+    if shape not in _wide_cases:
+        m, n, k = shape
+        rng = np.random.default_rng(31)
+        x = rng.integers(-2, 3, (m, k)).astype(F32)
+        w = (rng.integers(-1, 2, (n, k)) * (rng.random((n, k)) < 0.05)).astype(F32)
+        b = rng.integers(-3, 4, n).astype(F32)
+        c = rng.integers(-2, 3, n).astype(F32)
+        st = np.stack([rng.integers(1, 3, m), rng.integers(-2, 3, m)], -1).astype(F32)   # {a, b}: small integers
+        res = (rng.integers(-4000, 4001, (m, n)) / 16).astype(F32)                        # 12 bits + 4 fraction bits
+        acc = x @ w.T                                                                     # integers below 2^24: exact in fp32
+        _wide_cases[shape] = dict(x=x, w=w, b=b, c=c, st=st, res=res, bias=acc + b, lnf=st[:, :1] * acc + st[:, 1:] * c + b)
+    return _wide_cases[shape]
+
+
+@pytest.mark.parametrize("order", [0, 4])
+@pytest.mark.parametrize("grid", ["3", "8", "256"])
+@pytest.mark.parametrize("shape", WIDE_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_persistent_gemm_exact_on_integers_at_the_other_widths(built, monkeypatch, shape, grid, order):
+    """EPI_BIAS, EPI_LNF and (where N is a hidden size) EPI_RESID24 at the shapes the 768-, 1280- and 1536-wide towers give
+    the persistent kernel: every output bit against numpy, with several tiles per workgroup (3, 8) and one round (256), in
+    row-major tile order and in the tower's default.  N = 1280 and 1536 give ln_stats_kernel 40 and 48 sum blocks per row."""
+    monkeypatch.setenv("MI_OP_GRID", grid)
+    monkeypatch.setenv("MI_OP_GEMM_ORDER", str(order))
+    m, n, k = shape
+    t = _wide_case(shape)
+    ref = t["bias"]
+    assert np.abs(ref).max() <= 256  # exactly representable in bf16
+    assert np.array_equal(ops.linear(t["x"], t["w"], t["b"], ops.EPI_BIAS, PRECISION_BF16), ref), ("EPI_BIAS", shape, grid, order)
+    ref = t["lnf"]
+    assert np.abs(ref).max() <= 256
+    assert np.array_equal(ops.linear_lnf(t["x"], t["w"], t["b"], t["c"], t["st"], ops.EPI_LNF), ref), ("EPI_LNF", shape, grid, order)
+    if n not in HIDDEN_SIZES:
+        return
+    delta = t["bias"]
+    assert np.abs(delta).max() <= 256
+    want = (t["res"] + delta).astype(F32)
+    got, hi, part, stats = ops.linear_resid24(t["x"], t["w"], t["b"], t["res"])
+    hi_w, lo_w = enc24(want)
+    assert np.array_equal(got.view(np.uint32), dec24(hi_w, lo_w).view(np.uint32)), ("EPI_RESID24", shape, grid, order)
+    assert np.array_equal(hi.view(np.uint32), hi_as_float(hi_w).view(np.uint32))
+    pw = block_sums(want)
+    assert np.array_equal(part.view(np.uint32), pw.view(np.uint32))
+    assert np.allclose(stats, stats_of(pw, n, 1e-5), rtol=2e-6, atol=0)
 
 
 @pytest.mark.parametrize("epi", [ops.EPI_LNF, ops.EPI_LNF_QGELU])

@@ -81,6 +81,25 @@ def test_linear_epilogues(built, prec, tol, shape):
     assert np.abs(ops.linear(x, w, b, ops.EPI_BIAS_QGELU, prec) - ref / (1 + np.exp(-1.702 * ref))).max() <= tol * scale
 
 
+@pytest.mark.parametrize("prec,tol", [(PRECISION_F32, 2e-6), (PRECISION_BF16, 1.2e-2)])
+@pytest.mark.parametrize("shape", [(257, 2304, 768), (300, 1280, 5120), (64, 512, 2048)])
+def test_linear_epilogues_at_the_other_widths(built, prec, tol, shape):
+    """test_linear_epilogues at the q/k/v shape of a 768-wide tower (nine column tiles), the fc2 shape of a 1280-wide one
+    (K = 5120) and the fc2 shape of a 512-wide one on 64 rows — same operands' recipe, same tolerances."""
+    m, n, k = shape
+    rng = np.random.default_rng(1)
+    x = rng.standard_normal((m, k)).astype(np.float32)
+    w = (rng.standard_normal((n, k)) * k ** -0.5).astype(np.float32)
+    b = rng.standard_normal(n).astype(np.float32)
+    res = rng.standard_normal((m, n)).astype(np.float32)
+    xr, wr = (bf16_round(x), bf16_round(w)) if prec else (x, w)
+    ref = xr.astype(np.float64) @ wr.astype(np.float64).T + b
+    scale = float(np.abs(ref).max())
+    assert np.abs(ops.linear(x, w, b, ops.EPI_BIAS, prec) - ref).max() <= tol * scale
+    assert np.abs(ops.linear(x, w, b, ops.EPI_BIAS_RESID, prec, out=res) - (ref + res)).max() <= 3e-6 * scale
+    assert np.abs(ops.linear(x, w, b, ops.EPI_BIAS_QGELU, prec) - ref / (1 + np.exp(-1.702 * ref))).max() <= tol * scale
+
+
 @pytest.mark.parametrize("grid", ["8", "3", "64"])
 def test_persistent_gemm_rounds_and_split_tail(built, monkeypatch, grid):
     """bf16 persistent 256x256 kernel: several tiles per workgroup, the counted store/LDS-DMA
@@ -183,6 +202,23 @@ def test_attention32_one_hot_and_exponent_window(built, S, beta, gamma, why):
             assert np.abs(got - want).max() <= 2e-3, (why, S, b, h, np.abs(got - want).max())
 
 
+@pytest.mark.parametrize("S", [50, 77, 100, 197, 224, 288])
+def test_old_bf16_attention_kernel_one_hot(built, monkeypatch, S):
+    """The 16-query-tile kernel (attn_ver 1, MI_OP_ATTN=1) at its other instantiations — <64,50>, <96,0>, <224,0> below and at
+    its last key tile, <224,197>, <288,0>: every query returns exactly its key's V row, so a wrong key, column or tile mapping
+    shows as another row."""
+    monkeypatch.setenv("MI_OP_ATTN", "1")
+    n, H = 2, 2
+    D = 64 * H
+    qkv, pi = _peaked_qkv(S, n, H, 4.0, 0.0, 11 + S)
+    out = ops.attention(qkv, H, PRECISION_BF16)
+    for b in range(n):
+        for h in range(H):
+            want = qkv[b, pi[b, h], 2 * D + h * 64:2 * D + (h + 1) * 64]
+            got = out[b, :, h * 64:(h + 1) * 64]
+            assert np.abs(got - want).max() <= 2e-3, (S, b, h, np.abs(got - want).max())
+
+
 def test_attention32_forced_shift_and_old_kernel_agree(built, monkeypatch):
     rng = np.random.default_rng(5)
     n, H, S = 3, 2, 257
@@ -229,17 +265,32 @@ def test_attention32_row_pitch_and_pair_order_do_not_change_a_bit(built, monkeyp
     assert np.array_equal(ops.attention(qkv, H, PRECISION_BF16).view(np.uint32), base.view(np.uint32)), "rows, default cache policy"
 
 
-@pytest.mark.parametrize("prec,tol", [(PRECISION_F32, 2e-6), (PRECISION_BF16, 5e-3)])
-@pytest.mark.parametrize("D", [128, 768, 1024])
-def test_layernorm(built, prec, tol, D):
+def _layernorm_against_fp64(prec, tol, D, rows):
     rng = np.random.default_rng(3)
-    x = (rng.standard_normal((37, D)) * 3 + 1).astype(np.float32)
+    x = (rng.standard_normal((rows, D)) * 3 + 1).astype(np.float32)
     w = rng.standard_normal(D).astype(np.float32)
     b = rng.standard_normal(D).astype(np.float32)
     xd = x.astype(np.float64)
     d = xd - xd.mean(-1, keepdims=True)
     ref = d / np.sqrt((d * d).mean(-1, keepdims=True) + 1e-5) * w + b
-    assert np.abs(ops.layernorm(x, w, b, 1e-5, prec) - ref).max() <= tol * np.abs(ref).max()
+    got = ops.layernorm(x, w, b, 1e-5, prec)
+    assert got.shape == ref.shape
+    assert np.abs(got - ref).max() <= tol * np.abs(ref).max()
+
+
+@pytest.mark.parametrize("prec,tol", [(PRECISION_F32, 2e-6), (PRECISION_BF16, 5e-3)])
+@pytest.mark.parametrize("D", [128, 256, 384, 512, 768, 1024, 1280, 1536, 1664])
+def test_layernorm(built, prec, tol, D):
+    """Every width of the LayerNorm dispatch (D = 64 * VEC * NT): 37 rows are nine full workgroups of four and one row."""
+    _layernorm_against_fp64(prec, tol, D, 37)
+
+
+@pytest.mark.parametrize("prec,tol", [(PRECISION_F32, 2e-6), (PRECISION_BF16, 5e-3)])
+@pytest.mark.parametrize("rows", [1, 5])
+@pytest.mark.parametrize("D", [384, 1664])
+def test_layernorm_ragged_last_workgroup_at_the_two_lane_pair_widths(built, prec, tol, D, rows):
+    """VEC = 2 with NT = 3 and 13: one row alone in its workgroup, and a full workgroup followed by one row."""
+    _layernorm_against_fp64(prec, tol, D, rows)
 
 
 # ---- whole model ----------------------------------------------------------------------

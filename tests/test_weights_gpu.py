@@ -154,6 +154,8 @@ def _vision_cases():
         "hidden 192": of(synth.VitConfig(hidden=192, layers=1, heads=3, ff=256, patch=14, image=28, proj=64)),
         "hidden 896, 14 heads": of(synth.VitConfig(hidden=896, layers=1, heads=14, ff=128, patch=2, image=4, proj=8)),
         "ff 200": of(synth.VitConfig(hidden=128, layers=2, heads=2, ff=200, patch=14, image=56, proj=64)),
+        # ViT-H/14's attention: 1280 is a width the LayerNorms are built for, but its 16 heads are 80 wide
+        "hidden 1280, 16 heads": of(synth.VitConfig(hidden=1280, layers=1, heads=16, ff=128, patch=2, image=4, proj=8)),
         "11 positions": edited("embeddings.position_embedding.weight", z(11, D)),     # not G * G + 1 (10 is: a 3 x 3 grid)
         "1 position": edited("embeddings.position_embedding.weight", z(1, D)),
         "patch 14 x 16": edited("embeddings.patch_embedding.weight", z(D, 3, 14, 16)),
@@ -185,6 +187,8 @@ def test_what_cannot_run_is_refused_at_load(vision, tmp_path):
             msg = _refused(lib().mi_clip_load, path, precision, codes, name)
         if name.startswith("hidden 640"):
             assert "640" in msg and "LayerNorm" in msg, msg
+        if name.startswith("hidden 1280"):
+            assert "1280" in msg and "16 heads" in msg and "head_dim 64" in msg, msg
     # 10 positions are the class token and a 3 x 3 grid: a geometry the library runs, so it loads (42 x 42 pixels)
     synth.save_safetensors({**wr, "vision_model.embeddings.position_embedding.weight": np.zeros((10, cfg.hidden), np.float32)}, path,
                            {"num_attention_heads": cfg.heads}, dtype="F16")
