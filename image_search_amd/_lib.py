@@ -96,6 +96,15 @@ SYMBOLS = {
                                              ctypes.c_uint64, c_u64p]),
     "mi_index_themes": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint32, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_u64p,
                                        c_u64p, c_u64p]),
+    "mi_knn_near_pairs_window": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp, c_vp, ctypes.c_uint64,
+                                                c_u64p]),
+    "mi_knn_density_window": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint64, c_vp]),
+    "mi_knn_dbscan_window": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mi_knn_window_stats": (ctypes.c_int, [c_vp, c_u64p]),
+    "mi_index_bursts": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, c_vp, ctypes.c_uint64,
+                                       c_vp, ctypes.c_uint64, c_u64p, c_u64p]),
+    "mi_index_events": (ctypes.c_int, [c_vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32, c_vp, ctypes.c_uint64, c_vp,
+                                       ctypes.c_uint64, c_u64p, c_u64p, c_u64p]),
     "mi_knn_assign": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_assign_stats": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_knn_assign_multi": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp]),

@@ -1,4 +1,6 @@
-// density.hip — host side of mi_knn_density, mi_knn_dbscan, mi_knn_dbscan_stats and mi_index_themes.  The kernels, the
+// density.hip — host side of mi_knn_density, mi_knn_dbscan, mi_knn_dbscan_stats and mi_index_themes, and of their windowed
+// forms (mi_knn_density_window, mi_knn_dbscan_window, mi_index_events: the same passes with window.hip's stage 1, i.e. over
+// W_win in place of W).  The kernels, the
 // exactness of the tile skip and the disjoint-set forest: density_kernels.h; the host-only rules: density_host.h; stage 1 of
 // the passes, shared with the levels and the sharded passes: density_call.h.
 #include <algorithm>
@@ -14,6 +16,7 @@
 #include "density_kernels.h"
 #include "handles.h"
 #include "two_stage.h"
+#include "window_call.h"
 
 using namespace mi;
 
@@ -31,11 +34,14 @@ struct Density {
     DensityBlocks blocks;
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     DensityStage1<true> st1;       // the table's mirror, the candidate buffer and stage 1 of both passes (density_call.h)
+    WindowCall* win = nullptr;     // the windowed passes: stage 1 is window.hip's (it keeps the tile and launch counts)
 
     // one pass over the join's triangle in the join's strips: stage 1 is st1's, stage 2 this unit's
     template <int NCH, int PASS>
     void pass() {
-        auto stage1 = [&](uint32_t r0, uint32_t r1, uint32_t& c0, uint32_t c1) { return st1.template stage1<NCH, PASS>(r0, r1, c0, c1); };
+        auto stage1 = [&](uint32_t r0, uint32_t r1, uint32_t& c0, uint32_t c1) {
+            return win ? window_stage1(*win, PASS, r0, r1, c0, c1) : st1.template stage1<NCH, PASS>(r0, r1, c0, c1);
+        };
         auto stage2 = [&](uint32_t C) {
             if (PASS == 1) {
                 stats[0] += C;
@@ -64,10 +70,12 @@ struct DensityOut {
 };
 
 // min_pts == 0: the degrees only (mi_knn_density).  want_*: which optional arrays to fetch.  Everything lands in `out`; the
-// caller's arrays are written by the caller once this has returned.
-void density_run(mi_knn* t, float max_dist, uint32_t min_pts, bool want_via, bool want_via_dist, bool want_counts, DensityOut* out) {
+// caller's arrays are written by the caller once this has returned.  window (nullable): the passes run over W_win, the pairs
+// whose stamps lie within *window of each other; the call's figures then go to t->window_stats and t->dbscan_stats stays as it is.
+void density_run(mi_knn* t, float max_dist, uint32_t min_pts, bool want_via, bool want_via_dist, bool want_counts, DensityOut* out,
+                 const uint64_t* window = nullptr) {
     std::lock_guard<std::mutex> l(t->mu);
-    for (uint64_t& v : t->dbscan_stats) v = 0;
+    for (uint64_t& v : window ? t->window_stats : t->dbscan_stats) v = 0;
     check_mirror_dim(t->dim, "the density pass's");
     const uint64_t rows = t->rows;
     if (rows >= (1ull << 32)) fail(MI_ERR_UNSUPPORTED, "at most 2^32 - 1 rows (got %llu)", (unsigned long long)rows);
@@ -87,6 +95,16 @@ void density_run(mi_knn* t, float max_dist, uint32_t min_pts, bool want_via, boo
     HIP_CHECK(hipMemsetAsync(d.d_deg, 0, rows * sizeof(uint32_t), s));
     HIP_CHECK(hipMemsetAsync(d.d_words, 0, DW_WORDS * sizeof(unsigned long long), s));
     const bool pairs_possible = rows >= 2;
+    WindowCall w;
+    // the call's figures: mi_knn_dbscan_stats' words, or mi_knn_window_stats' (the tile and launch words are window_stage1's)
+    auto keep_stats = [&] {
+        if (!window) {
+            for (int i = 0; i < 8; ++i) t->dbscan_stats[i] = d.stats[i];
+            return;
+        }
+        w.stats[WS_CAND1] = d.stats[0]; w.stats[WS_WITHIN] = d.stats[1]; w.stats[WS_CAND2] = d.stats[3];
+        for (int i = 0; i < WS_WORDS; ++i) t->window_stats[i] = w.stats[i];
+    };
     if (pairs_possible) {
         const TableMirror tm = table_mirror(t, s, scratch);
         DensityStage1<true>& st = d.st1;
@@ -98,6 +116,13 @@ void density_run(mi_knn* t, float max_dist, uint32_t min_pts, bool want_via, boo
         st.d_cand = (uint2*)scratch.get((size_t)st.cand_cap * sizeof(uint2));
         st.d_count = d.d_words + DW_CAND;
         st.stats = d.stats;
+        if (window) {
+            w.s = s; w.dim = t->dim; w.n_rows = n_rows; w.first_new = 0;
+            w.mirror = tm.mirror; w.xx = tm.xx; w.tomb = tm.tomb;
+            w.c = st.c; w.cand_cap = st.cand_cap; w.d_cand = st.d_cand; w.d_count = st.d_count;
+            window_ranges(t, s, scratch, *window, &w);
+            d.win = &w;
+        }
         dispatch_nch(t->dim, [&](auto nch) { d.template pass<decltype(nch)::value, 1>(); });
     }
 
@@ -107,7 +132,7 @@ void density_run(mi_knn* t, float max_dist, uint32_t min_pts, bool want_via, boo
         HIP_CHECK(hipMemcpyAsync(words, d.d_words, sizeof words, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         d.stats[1] = words[DW_WITHIN];
-        for (int i = 0; i < 8; ++i) t->dbscan_stats[i] = d.stats[i];
+        keep_stats();
         return;
     }
 
@@ -123,6 +148,7 @@ void density_run(mi_knn* t, float max_dist, uint32_t min_pts, bool want_via, boo
         HIP_CHECK(hipStreamSynchronize(s));
         d.blocks.index();
         d.st1.a.act = d.st1.b.act = d.d_act;
+        if (window) { w.blocks.act = d.blocks.act; w.d_act = d.d_act; }
         dispatch_nch(t->dim, [&](auto nch) { d.template pass<decltype(nch)::value, 2>(); });
     }
 
@@ -146,32 +172,29 @@ void density_run(mi_knn* t, float max_dist, uint32_t min_pts, bool want_via, boo
     for (int i = 0; i < 4; ++i) out->summary[i] = words[DW_SUMMARY + i];
     d.stats[1] = words[DW_WITHIN];
     d.stats[6] = words[DW_MERGED];
-    for (int i = 0; i < 8; ++i) t->dbscan_stats[i] = d.stats[i];
+    keep_stats();
 }
 
-}  // namespace
-
-extern "C" {
-
-int mi_knn_density(mi_knn* t, float max_dist, uint32_t* counts) {
+// the public calls, each once for its plain and its windowed form (window null: the plain one)
+int density_call(mi_knn* t, float max_dist, const uint64_t* window, uint32_t* counts) {
     return guarded([&] {
         const char* why = "";
         const int bad = density_check_args(t, max_dist, counts, &why);
         if (bad != MI_OK) fail(bad, "%s", why);
         DensityOut out;
-        density_run(t, max_dist, 0, false, false, true, &out);
+        density_run(t, max_dist, 0, false, false, true, &out, window);
         copy_out(out.counts, counts);
     });
 }
 
-int mi_knn_dbscan(mi_knn* t, float max_dist, uint32_t min_pts, uint64_t* cluster, uint64_t* via, float* via_dist, uint32_t* counts,
-                  uint64_t summary[4]) {
+int dbscan_call(mi_knn* t, float max_dist, const uint64_t* window, uint32_t min_pts, uint64_t* cluster, uint64_t* via, float* via_dist,
+                uint32_t* counts, uint64_t summary[4]) {
     return guarded([&] {
         const char* why = "";
         const int bad = dbscan_check_args(t, max_dist, min_pts, cluster, summary, &why);
         if (bad != MI_OK) fail(bad, "%s", why);
         DensityOut out;
-        density_run(t, max_dist, min_pts, via != nullptr, via_dist != nullptr, counts != nullptr, &out);
+        density_run(t, max_dist, min_pts, via != nullptr, via_dist != nullptr, counts != nullptr, &out, window);
         copy_out(out.cluster, cluster);
         copy_out(out.via, via);
         copy_out(out.via_dist, via_dist);
@@ -180,16 +203,8 @@ int mi_knn_dbscan(mi_knn* t, float max_dist, uint32_t min_pts, uint64_t* cluster
     });
 }
 
-int mi_knn_dbscan_stats(mi_knn* t, uint64_t out[8]) {
-    return guarded([&] {
-        if (!t || !out) fail(MI_ERR_INVALID, "null argument");
-        std::lock_guard<std::mutex> l(t->mu);
-        for (int i = 0; i < 8; ++i) out[i] = t->dbscan_stats[i];
-    });
-}
-
-int mi_index_themes(mi_index* ix, float max_dist, uint32_t min_pts, uint64_t* ids, uint64_t cap_ids, uint64_t* group_start,
-                    uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups, uint64_t* n_noise) {
+int themes_call(mi_index* ix, float max_dist, const uint64_t* window, uint32_t min_pts, uint64_t* ids, uint64_t cap_ids,
+                uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups, uint64_t* n_noise) {
     return guarded([&] {
         if (!ix) fail(MI_ERR_INVALID, "null index handle");
         if (!(max_dist >= 0.0f)) fail(MI_ERR_INVALID, "max_dist must be a number >= 0 (got %g)", (double)max_dist);
@@ -200,7 +215,7 @@ int mi_index_themes(mi_index* ix, float max_dist, uint32_t min_pts, uint64_t* id
         if (!t) fail(MI_ERR_INVALID, "the index has no table");
         // (a removed path's rows are deleted rows of the table: they are in no cluster and are not noise)
         DensityOut out;
-        density_run(t, max_dist, min_pts, false, false, false, &out);
+        density_run(t, max_dist, min_pts, false, false, false, &out, window);
         IdMap map;
         {
             std::lock_guard<std::mutex> l(t->mu);
@@ -218,4 +233,41 @@ int mi_index_themes(mi_index* ix, float max_dist, uint32_t min_pts, uint64_t* id
     });
 }
 
+}  // namespace
+
+extern "C" {
+
+int mi_knn_density(mi_knn* t, float max_dist, uint32_t* counts) { return density_call(t, max_dist, nullptr, counts); }
+
+int mi_knn_density_window(mi_knn* t, float max_dist, uint64_t window, uint32_t* counts) { return density_call(t, max_dist, &window, counts); }
+
+int mi_knn_dbscan(mi_knn* t, float max_dist, uint32_t min_pts, uint64_t* cluster, uint64_t* via, float* via_dist, uint32_t* counts,
+                  uint64_t summary[4]) {
+    return dbscan_call(t, max_dist, nullptr, min_pts, cluster, via, via_dist, counts, summary);
+}
+
+int mi_knn_dbscan_window(mi_knn* t, float max_dist, uint64_t window, uint32_t min_pts, uint64_t* cluster, uint64_t* via, float* via_dist,
+                         uint32_t* counts, uint64_t summary[4]) {
+    return dbscan_call(t, max_dist, &window, min_pts, cluster, via, via_dist, counts, summary);
+}
+
+int mi_knn_dbscan_stats(mi_knn* t, uint64_t out[8]) {
+    return guarded([&] {
+        if (!t || !out) fail(MI_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> l(t->mu);
+        for (int i = 0; i < 8; ++i) out[i] = t->dbscan_stats[i];
+    });
+}
+
+int mi_index_themes(mi_index* ix, float max_dist, uint32_t min_pts, uint64_t* ids, uint64_t cap_ids, uint64_t* group_start,
+                    uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups, uint64_t* n_noise) {
+    return themes_call(ix, max_dist, nullptr, min_pts, ids, cap_ids, group_start, cap_groups, n_ids, n_groups, n_noise);
+}
+
+int mi_index_events(mi_index* ix, float max_dist, uint64_t window, uint32_t min_pts, uint64_t* ids, uint64_t cap_ids,
+                    uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups, uint64_t* n_noise) {
+    return themes_call(ix, max_dist, &window, min_pts, ids, cap_ids, group_start, cap_groups, n_ids, n_groups, n_noise);
+}
+
 }  // extern "C"
+

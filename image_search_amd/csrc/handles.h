@@ -213,6 +213,10 @@ struct mi_knn {
     // mi_knn_density / mi_knn_dbscan (density.hip): {candidates pass 1, pairs within, tiles pass 1, candidates pass 2, tiles
     // visited pass 2, tiles skipped pass 2, unions that merged, stage-1 launches} of the last call
     uint64_t dbscan_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // mi_knn_near_pairs_window / mi_knn_density_window / mi_knn_dbscan_window (window.hip; window_call.h: WS_*): {candidates pass
+    // 1, pairs within, tiles computed pass 1, tiles skipped by the stamp ranges pass 1, candidates pass 2, tiles computed pass 2,
+    // tiles skipped pass 2, stage-1 launches} of the last windowed call; the unwindowed calls' words above are not touched by it
+    uint64_t window_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // mi_knn_assign (assign.hip): {candidates, live rows labelled, stage-1 launches, tiles} of the last assign
     uint64_t assign_stats[4] = {0, 0, 0, 0};
     // mi_knn_assign_multi (assign_multi.hip): {candidates, (row, label) hits written, stage-1 launches, tiles} of the last call

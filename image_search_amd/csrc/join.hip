@@ -1,4 +1,5 @@
-// join.hip — host side of the threshold self-join (mi_knn_near_pairs, mi_pairs_to_groups, mi_index_duplicates).
+// join.hip — host side of the threshold self-join (mi_knn_near_pairs, mi_pairs_to_groups, mi_index_duplicates) and of its
+// windowed form (mi_knn_near_pairs_window, mi_index_bursts: the same call with window.hip's stage 1).
 // The kernels and the bound that makes the bf16 first stage exact: join_kernels.h.
 #include <algorithm>
 #include <cmath>
@@ -12,6 +13,7 @@
 #include "join_between_host.h"
 #include "join_kernels.h"
 #include "two_stage.h"
+#include "window_call.h"
 
 using namespace mi;
 
@@ -35,6 +37,7 @@ struct Join {
     std::vector<JoinPair> out;
     uint64_t stats[4] = {0, 0, 0, 0};
     bool over = false;
+    WindowCall* win = nullptr;     // the windowed join: stage 1 is window.hip's (it keeps the tile and launch counts)
 
     // The join's stages for rect_stages (two_stage.h).  Its tiles lie on or above the diagonal: bc0 is raised to br0, the
     // grid is two-dimensional and the tiles counted are the triangle's; once more than user_cap pairs qualify nothing more
@@ -44,6 +47,7 @@ struct Join {
         auto stage1 = [&](uint32_t r0, uint32_t r1, uint32_t& c0, uint32_t c1) -> unsigned long long {
             c0 = std::max(c0, r0);
             if (over || c0 >= c1) return 0;
+            if (win) return window_stage1(*win, 1, r0, r1, c0, c1);
             static DevOnce once;
             allow_lds_once(once, join_tiles_kernel<NCH>, JOIN_LDS);
             HIP_CHECK(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), s));
@@ -107,12 +111,15 @@ uint32_t local_first_new(const mi_knn* t, uint64_t first_new) {
 // the join itself: pairs as local rows, ascending by (a, b); *over = more than user_cap pairs qualify (out is then partial).
 // first_new_id: an id (local_first_new), or with first_new_is_local the local row itself (what a shard of the sharded join is
 // handed: the number of its rows below the global bound)
+// window (nullable): only the pairs whose stamps lie within *window of each other (W_win); the call's figures then go to
+// t->window_stats and t->join_stats stays as it is
 void near_pairs(mi_knn* t, float max_dist, uint64_t first_new_id, uint64_t user_cap, std::vector<JoinPair>* out, bool* over,
-                bool first_new_is_local = false) {
+                bool first_new_is_local = false, const uint64_t* window = nullptr) {
     out->clear();
     *over = false;
     std::lock_guard<std::mutex> l(t->mu);
-    for (uint64_t& v : t->join_stats) v = 0;
+    if (window) std::fill(std::begin(t->window_stats), std::end(t->window_stats), 0);
+    else std::fill(std::begin(t->join_stats), std::end(t->join_stats), 0);
     const uint32_t fn = first_new_is_local ? (uint32_t)std::min<uint64_t>(first_new_id, t->rows) : local_first_new(t, first_new_id);
     check_mirror_dim(t->dim, "the join's");
     if (t->rows < 2 || fn >= t->rows) return;
@@ -133,9 +140,22 @@ void near_pairs(mi_knn* t, float max_dist, uint64_t first_new_id, uint64_t user_
     j.d_pairs = (uint2*)scratch.get((size_t)j.cand_cap * sizeof(uint2));
     j.d_dist = (float*)scratch.get((size_t)j.cand_cap * sizeof(float));
     j.d_count = (unsigned long long*)scratch.get(2 * sizeof(unsigned long long));
+    WindowCall w;
+    if (window) {
+        w.s = s; w.dim = t->dim; w.n_rows = j.n_rows; w.first_new = fn;
+        w.mirror = tm.mirror; w.xx = tm.xx; w.tomb = tm.tomb;
+        w.c = j.c; w.cand_cap = j.cand_cap; w.d_cand = j.d_cand; w.d_count = j.d_count; w.count_words = 2;
+        window_ranges(t, s, scratch, *window, &w);
+        j.win = &w;
+    }
 
     dispatch_nch(t->dim, [&](auto nch) { j.template run<decltype(nch)::value>(); });
-    for (int i = 0; i < 4; ++i) t->join_stats[i] = j.stats[i];
+    if (window) {
+        w.stats[WS_CAND1] = j.stats[0]; w.stats[WS_WITHIN] = j.stats[1];
+        for (int i = 0; i < WS_WORDS; ++i) t->window_stats[i] = w.stats[i];
+    } else {
+        for (int i = 0; i < 4; ++i) t->join_stats[i] = j.stats[i];
+    }
     *over = j.over;
     if (j.over) return;
     std::sort(j.out.begin(), j.out.end(), [](const JoinPair& x, const JoinPair& y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
@@ -198,8 +218,9 @@ void knn_near_pairs_local(mi_knn* t, float max_dist, uint64_t first_new_local, u
 
 extern "C" {
 
-int mi_knn_near_pairs(mi_knn* t, float max_dist, uint64_t first_new, uint64_t* a, uint64_t* b, float* dist, uint64_t cap,
-                      uint64_t* count) {
+// mi_knn_near_pairs (window null) and mi_knn_near_pairs_window: one contract, W or W_win
+static int near_pairs_call(mi_knn* t, float max_dist, const uint64_t* window, uint64_t first_new, uint64_t* a, uint64_t* b, float* dist,
+                           uint64_t cap, uint64_t* count) {
     return guarded([&] {
         if (count) *count = 0;
         check_join_args(t, max_dist);
@@ -207,7 +228,7 @@ int mi_knn_near_pairs(mi_knn* t, float max_dist, uint64_t first_new, uint64_t* a
         if (cap && (!a || !b || !dist)) fail(MI_ERR_INVALID, "a, b or dist is null with cap %llu", (unsigned long long)cap);
         std::vector<JoinPair> pairs;
         bool over = false;
-        near_pairs(t, max_dist, first_new, cap, &pairs, &over);
+        near_pairs(t, max_dist, first_new, cap, &pairs, &over, false, window);
         if (over) {
             *count = cap + 1;
             fail(MI_ERR_UNSUPPORTED, "more than %llu pairs lie within %g: lower max_dist or raise cap", (unsigned long long)cap,
@@ -221,6 +242,16 @@ int mi_knn_near_pairs(mi_knn* t, float max_dist, uint64_t first_new, uint64_t* a
         }
         *count = pairs.size();
     });
+}
+
+int mi_knn_near_pairs(mi_knn* t, float max_dist, uint64_t first_new, uint64_t* a, uint64_t* b, float* dist, uint64_t cap,
+                      uint64_t* count) {
+    return near_pairs_call(t, max_dist, nullptr, first_new, a, b, dist, cap, count);
+}
+
+int mi_knn_near_pairs_window(mi_knn* t, float max_dist, uint64_t window, uint64_t first_new, uint64_t* a, uint64_t* b, float* dist,
+                             uint64_t cap, uint64_t* count) {
+    return near_pairs_call(t, max_dist, &window, first_new, a, b, dist, cap, count);
 }
 
 int mi_knn_near_pairs_stats(mi_knn* t, uint64_t out[4]) {
@@ -245,8 +276,9 @@ int mi_pairs_to_groups(const uint64_t* a, const uint64_t* b, uint64_t n_pairs, u
     });
 }
 
-int mi_index_duplicates(mi_index* ix, float max_dist, uint64_t first_new, uint64_t max_pairs, uint64_t* ids, uint64_t cap_ids,
-                        uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups) {
+// mi_index_duplicates (window null) and mi_index_bursts: the components of W or of W_win
+static int duplicates_call(mi_index* ix, float max_dist, const uint64_t* window, uint64_t first_new, uint64_t max_pairs, uint64_t* ids,
+                           uint64_t cap_ids, uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups) {
     return guarded([&] {
         if (n_ids) *n_ids = 0;
         if (n_groups) *n_groups = 0;
@@ -258,7 +290,7 @@ int mi_index_duplicates(mi_index* ix, float max_dist, uint64_t first_new, uint64
         std::vector<JoinPair> pairs;
         bool over = false;
         // (a removed path's rows are deleted rows of the table: the join never reports them)
-        near_pairs(t, max_dist, first_new, max_pairs, &pairs, &over);
+        near_pairs(t, max_dist, first_new, max_pairs, &pairs, &over, false, window);
         if (over)
             fail(MI_ERR_UNSUPPORTED, "more than %llu pairs lie within %g: lower max_dist or raise max_pairs",
                  (unsigned long long)max_pairs, (double)max_dist);
@@ -269,6 +301,16 @@ int mi_index_duplicates(mi_index* ix, float max_dist, uint64_t first_new, uint64
         groups_of(pa.data(), pb.data(), pairs.size(), &gids, &starts);
         write_groups(gids, starts, ids, cap_ids, group_start, cap_groups, n_ids, n_groups);
     });
+}
+
+int mi_index_duplicates(mi_index* ix, float max_dist, uint64_t first_new, uint64_t max_pairs, uint64_t* ids, uint64_t cap_ids,
+                        uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups) {
+    return duplicates_call(ix, max_dist, nullptr, first_new, max_pairs, ids, cap_ids, group_start, cap_groups, n_ids, n_groups);
+}
+
+int mi_index_bursts(mi_index* ix, float max_dist, uint64_t window, uint64_t first_new, uint64_t max_pairs, uint64_t* ids,
+                    uint64_t cap_ids, uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups) {
+    return duplicates_call(ix, max_dist, &window, first_new, max_pairs, ids, cap_ids, group_start, cap_groups, n_ids, n_groups);
 }
 
 }  // extern "C"

@@ -10,10 +10,20 @@
 
 #include "common.h"
 #include "tile128.h"
+#include "window_host.h"
 
 namespace mi {
 
 constexpr int JOIN_LDS = TILE_IMGS + 2 * TILE * 4;                   // the tile's images + the rows' weights
+constexpr int PAIR_WINDOW_LDS = 2 * TILE * 8;                        // WIN: the rows' stamps behind them
+
+// WIN: what the windowed calls add (window_kernels.h).  stamps: one per row, null = every stamp is 0; range: one per 128-row
+// block (stamp_ranges_kernel).  Both sides of a tile read the same two arrays: the windowed calls are self passes.
+struct PairWindow {
+    const int64_t* stamps;
+    const StampRange* range;
+    uint64_t window;
+};
 
 // Tile (bi = br0 + blockIdx.y, bj = bc0 + blockIdx.x) of the rows of A against the rows of B; all 256 threads of the
 // workgroup call it with JOIN_LDS bytes of dynamic LDS.  c = 1 - (max_dist + eps2): element (ra, cb) is a candidate when
@@ -28,18 +38,26 @@ constexpr int JOIN_LDS = TILE_IMGS + 2 * TILE * 4;                   // the tile
 //   SKIP: the density passes' test in front of the first load.  act_a[bi], act_b[bj]: bit 0 = some row of the block has a
 //         neighbour within, bit 1 = some row is a core; the tile is left at once unless both blocks have bit 0 and one has
 //         bit 1.  Without SKIP the two arrays are not read.
-template <int NCH, bool SELF, bool SKIP>
+//   WIN:  the stamp test of the windowed calls, with PAIR_WINDOW_LDS more bytes of LDS.  The tile is left at once when the gap
+//         between the two blocks' stamp ranges exceeds win.window, and an element is a candidate only if its two stamps lie
+//         within win.window of each other (window_host.h: stamp_within; a marked row takes the test like any other).
+//         Without WIN `win` is not read and the tile is what it was before the parameter existed.
+template <int NCH, bool SELF, bool SKIP, bool WIN = false>
 __device__ __forceinline__ void pair_tile(const uint16_t* __restrict__ mirror_a, const float* __restrict__ xx_a,
                                           const uint64_t* __restrict__ tomb_a, const uint8_t* __restrict__ act_a, uint32_t n_a,
                                           const uint16_t* __restrict__ mirror_b, const float* __restrict__ xx_b,
                                           const uint64_t* __restrict__ tomb_b, const uint8_t* __restrict__ act_b, uint32_t n_b,
                                           uint32_t fn_a, uint32_t fn_b, uint32_t br0, uint32_t bc0, float c, uint32_t cap,
-                                          uint2* __restrict__ cand, unsigned long long* __restrict__ count) {
+                                          uint2* __restrict__ cand, unsigned long long* __restrict__ count,
+                                          PairWindow win = PairWindow{nullptr, nullptr, 0}) {
     constexpr int DIM = NCH * 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t bi = br0 + blockIdx.y, bj = bc0 + blockIdx.x;
     if constexpr (SELF) {
         if (bj < bi) return;
+    }
+    if constexpr (WIN) {
+        if (!window_tile_live(win.range[bi], win.range[bj], win.window)) return;   // no pair within the window lies in this tile
     }
     if constexpr (SKIP) {
         const uint32_t fa = act_a[bi], fb = act_b[bj];
@@ -59,6 +77,10 @@ __device__ __forceinline__ void pair_tile(const uint16_t* __restrict__ mirror_a,
         bool there = r < (is_col ? n_b : n_a);
         if constexpr (SELF) there = there && !(is_col && r < fn_b);
         wgt[tid] = tile_weight<false>(is_col ? xx_b : xx_a, r, there, is_col ? tomb_b : tomb_a, r, -inf, __uint_as_float(0x7FC00000u));
+        if constexpr (WIN) {
+            int64_t* stamp = reinterpret_cast<int64_t*>(smem + JOIN_LDS);   // [0, 128): the rows' stamps, [128, 256): the columns'
+            stamp[tid] = (win.stamps && r < (is_col ? n_b : n_a)) ? win.stamps[r] : 0;
+        }
     }
 
     const uint16_t *ga[4], *gb[4];
@@ -96,6 +118,17 @@ __device__ __forceinline__ void pair_tile(const uint16_t* __restrict__ mirror_a,
                     if (ok) hit |= 1ull << ((2 * ti + tj) * 16 + 4 * q + j);
                 }
             }
+        }
+    }
+    if constexpr (WIN) {
+        // candidates are rare: the stamp test walks the set bits (tile_append's decoding of them), not the accumulators
+        const int64_t* stamp = reinterpret_cast<const int64_t*>(smem + JOIN_LDS);
+        for (unsigned long long h = hit; h;) {
+            const int bit = __ffsll((long long)h) - 1;
+            h &= h - 1ull;
+            const int e = bit & 15, ti = bit >> 5, tj = (bit >> 4) & 1;
+            const int ra = wr * 64 + ti * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh, cb = wc * 64 + tj * 32 + l31;
+            if (!stamp_within(stamp[ra], stamp[TILE + cb], win.window)) hit &= ~(1ull << bit);
         }
     }
     tile_append(hit, f, row0, col0, cap, cand, count);

@@ -222,6 +222,19 @@ class EmbeddingTable {
     }
     // {candidate pairs, pairs accepted, strips run, tiles visited} of the last near_pairs
     std::vector<uint64_t> near_pairs_stats() const { std::vector<uint64_t> v(4); check(mi_knn_near_pairs_stats(h_, v.data())); return v; }
+    // bursts (mi_knn_near_pairs_window): the pairs of near_pairs whose stamps (set_attrs) lie within `window` of each other,
+    // |stamp_a - stamp_b| <= window taken exactly; 0: equal stamps, UINT64_MAX: every pair.  Same ids, order and distance bits
+    NearPairs near_pairs_window(float max_dist, uint64_t window, uint64_t first_new = 0, uint64_t cap = 1ull << 20) const {
+        NearPairs r;
+        r.a.resize(cap); r.b.resize(cap); r.dist.resize(cap);
+        uint64_t n = 0;
+        check(mi_knn_near_pairs_window(h_, max_dist, window, first_new, r.a.data(), r.b.data(), r.dist.data(), cap, &n));
+        r.a.resize(n); r.b.resize(n); r.dist.resize(n);
+        return r;
+    }
+    // {candidates pass 1, pairs within, tiles computed pass 1, tiles skipped by the stamp ranges pass 1, candidates pass 2, tiles
+    // computed pass 2, tiles skipped pass 2, stage-1 launches} of the last near_pairs_window / neighbor_counts_window / dbscan_window
+    std::vector<uint64_t> window_stats() const { std::vector<uint64_t> v(8); check(mi_knn_window_stats(h_, v.data())); return v; }
     // the join with another table (mi_knn_near_pairs_between): every pair of a live row of this table (a, the query) and a live
     // row of `other` (b) with cosine distance <= max_dist, ascending by (a, b); neither table changes
     NearPairs near_pairs_with(const EmbeddingTable& other, float max_dist, uint64_t cap = 1ull << 20) const {
@@ -258,6 +271,23 @@ class EmbeddingTable {
         const uint64_t n = size();
         r.cluster.resize(n + 1); r.via.resize(n + 1); r.via_dist.resize(n + 1); r.counts.resize(n + 1);   // (+ 1: never a null pointer)
         check(mi_knn_dbscan(h_, max_dist, min_pts, r.cluster.data(), r.via.data(), r.via_dist.data(), r.counts.data(), r.summary));
+        dbscan_trim_and_label(r, n);
+        return r;
+    }
+    // neighbor_counts and dbscan over the pairs of near_pairs_window (mi_knn_density_window, mi_knn_dbscan_window): the
+    // neighbourhood is "within max_dist and within `window` in time" — a theme shot in two far-apart periods is two clusters
+    std::vector<uint32_t> neighbor_counts_window(float max_dist, uint64_t window) const {
+        std::vector<uint32_t> counts(size());
+        uint32_t none = 0;
+        check(mi_knn_density_window(h_, max_dist, window, counts.empty() ? &none : counts.data()));
+        return counts;
+    }
+    Dbscan dbscan_window(float max_dist, uint64_t window, uint32_t min_pts = 5) const {
+        Dbscan r;
+        const uint64_t n = size();
+        r.cluster.resize(n + 1); r.via.resize(n + 1); r.via_dist.resize(n + 1); r.counts.resize(n + 1);   // (+ 1: never a null pointer)
+        check(mi_knn_dbscan_window(h_, max_dist, window, min_pts, r.cluster.data(), r.via.data(), r.via_dist.data(), r.counts.data(),
+                                   r.summary));
         dbscan_trim_and_label(r, n);
         return r;
     }
@@ -778,6 +808,19 @@ class ImageIndex {
         }
         return out;
     }
+    // bursts (mi_index_bursts): duplicates' groups over the pairs that look alike and were taken within `window` of each other
+    std::vector<std::vector<std::string>> bursts(float max_dist, uint64_t window, bool web = false, uint64_t max_pairs = 1ull << 20) const {
+        uint64_t n_ids = 0, n_groups = 0;
+        check(mi_index_bursts(h_, max_dist, window, 0, max_pairs, nullptr, 0, nullptr, 0, &n_ids, &n_groups));
+        std::vector<uint64_t> ids(n_ids), start(n_groups + 1);
+        check(mi_index_bursts(h_, max_dist, window, 0, max_pairs, ids.data(), ids.size(), start.data(), start.size(), &n_ids, &n_groups));
+        std::vector<std::vector<std::string>> out;
+        for (const auto& g : groups_from(ids, start)) {
+            out.emplace_back();
+            for (uint64_t id : g) out.back().push_back(path(id, web));
+        }
+        return out;
+    }
     // "skip what I already have" (mi_index_matches): (path here, path in `other`, distance) of every pair of images within
     // max_dist, ordered by this index's row, then the other's; removed paths never appear
     struct Match { std::string mine, theirs; float dist; };
@@ -796,6 +839,23 @@ class ImageIndex {
         uint64_t n_ids = 0, n_groups = 0, noise = 0;
         std::vector<uint64_t> ids(size() + 1), start(size() + 1);   // every row in a theme of its own still fits: one call, not two
         check(mi_index_themes(h_, max_dist, min_pts, ids.data(), ids.size(), start.data(), start.size(), &n_ids, &n_groups, &noise));
+        ids.resize(n_ids); start.resize(n_groups + 1);
+        if (n_noise) *n_noise = noise;
+        auto groups = groups_from(ids, start);
+        std::stable_sort(groups.begin(), groups.end(), [](const auto& x, const auto& y) { return x.size() > y.size(); });
+        std::vector<std::vector<std::string>> out;
+        for (const auto& g : groups) {
+            out.emplace_back();
+            for (uint64_t id : g) out.back().push_back(path(id, web));
+        }
+        return out;
+    }
+    // events (mi_index_events): themes() with the neighbourhood "within max_dist and within `window` in time"; same output shape
+    std::vector<std::vector<std::string>> events(float max_dist, uint64_t window, uint32_t min_pts = 5, bool web = false,
+                                                 uint64_t* n_noise = nullptr) const {
+        uint64_t n_ids = 0, n_groups = 0, noise = 0;
+        std::vector<uint64_t> ids(size() + 1), start(size() + 1);
+        check(mi_index_events(h_, max_dist, window, min_pts, ids.data(), ids.size(), start.data(), start.size(), &n_ids, &n_groups, &noise));
         ids.resize(n_ids); start.resize(n_groups + 1);
         if (n_noise) *n_noise = noise;
         auto groups = groups_from(ids, start);

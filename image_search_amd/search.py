@@ -253,6 +253,16 @@ def _pairs_call(fn, lead, cap: int):
     return a[:n.value].copy(), b[:n.value].copy(), dist[:n.value].copy()
 
 
+def _dbscan_call(fn, lead, n: int) -> dict:
+    """fn(*lead, cluster, via, via_dist, counts, summary) of the dbscan calls over n rows -> EmbeddingTable.dbscan's dict"""
+    cluster, via = np.empty(n, np.uint64), np.empty(n, np.uint64)
+    via_dist, counts = np.empty(n, np.float32), np.empty(n, np.uint32)
+    summary = np.zeros(4, np.uint64)
+    check(fn(*lead, cluster.ctypes.data, via.ctypes.data, via_dist.ctypes.data, counts.ctypes.data, summary.ctypes.data))
+    return {"labels": dense_labels(cluster), "cluster": cluster, "via": via, "via_dist": via_dist, "counts": counts,
+            "summary": dict(zip(("clusters", "core", "border", "noise"), (int(v) for v in summary)))}
+
+
 def _ptrs(vecs):
     arr = (c_f * len(vecs))()
     for i, v in enumerate(vecs):
@@ -427,14 +437,33 @@ class EmbeddingTable:
         neighbours within), summary {"clusters", "core", "border", "noise"}.
         labels.astype(np.uint32) fits set_groups (-1 becomes NO_GROUP: a row of its own), so knn_grouped then answers "the best
         picture of each theme"."""
-        n = len(self)
-        cluster, via = np.empty(n, np.uint64), np.empty(n, np.uint64)
-        via_dist, counts = np.empty(n, np.float32), np.empty(n, np.uint32)
-        summary = np.zeros(4, np.uint64)
-        check(lib().mi_knn_dbscan(self._h, float(max_dist), int(min_pts), cluster.ctypes.data, via.ctypes.data, via_dist.ctypes.data,
-                                  counts.ctypes.data, summary.ctypes.data))
-        return {"labels": dense_labels(cluster), "cluster": cluster, "via": via, "via_dist": via_dist, "counts": counts,
-                "summary": dict(zip(("clusters", "core", "border", "noise"), (int(v) for v in summary)))}
+        return _dbscan_call(lib().mi_knn_dbscan, (self._h, float(max_dist), int(min_pts)), len(self))
+
+    def near_pairs_window(self, max_dist: float, window: int, first_new: int = 0, cap: int = 1 << 20):
+        """Bursts (mi_knn_near_pairs_window): the pairs of near_pairs(max_dist, first_new) whose stamps (set_attrs) lie within
+        `window` of each other — |stamp_a - stamp_b| <= window, taken exactly over the whole int64 range; window 0: equal stamps,
+        2**64 - 1: every pair.  Same ids, order and distance bits; a table without stamps: near_pairs itself."""
+        return _pairs_call(lib().mi_knn_near_pairs_window, (self._h, float(max_dist), int(window), int(first_new)), cap)
+
+    def neighbor_counts_window(self, max_dist: float, window: int) -> np.ndarray:
+        """neighbor_counts over the pairs of near_pairs_window(max_dist, window) (mi_knn_density_window)"""
+        counts = np.empty(len(self), np.uint32)
+        check(lib().mi_knn_density_window(self._h, float(max_dist), int(window), counts.ctypes.data))
+        return counts
+
+    def dbscan_window(self, max_dist: float, window: int, min_pts: int = 5) -> dict:
+        """Events (mi_knn_dbscan_window): dbscan whose neighbourhood is "within max_dist and within `window` in time" (ST-DBSCAN)
+        — dbscan's contract and dict over the pairs of near_pairs_window(max_dist, window): "beach 2019" and "beach 2023" come
+        out as two clusters."""
+        return _dbscan_call(lib().mi_knn_dbscan_window, (self._h, float(max_dist), int(window), int(min_pts)), len(self))
+
+    def window_stats(self) -> dict:
+        """mi_knn_window_stats, of the last near_pairs_window / neighbor_counts_window / dbscan_window on this table; per pass
+        tiles + tiles_skipped = the triangle's tiles"""
+        out = (ctypes.c_uint64 * 8)()
+        check(lib().mi_knn_window_stats(self._h, out))
+        return dict(zip(("candidates_pass1", "pairs", "tiles_pass1", "tiles_skipped_pass1", "candidates_pass2", "tiles_pass2",
+                         "tiles_skipped_pass2", "launches"), (int(v) for v in out)))
 
     def neighbor_counts_levels(self, max_dists) -> np.ndarray:
         """neighbor_counts at several distances from one tile pass (mi_knn_density_levels): counts [L, rows] uint32, row l =
@@ -1939,13 +1968,22 @@ class ImageIndex:
         """Groups of near-duplicate images (mi_index_duplicates): lists of paths whose embeddings are chained by cosine
         distances <= max_dist, ordered by row id inside a group and by their first row between groups; removed paths
         never appear.  first_new: only what the rows from that id on duplicate.  web: names as sent to the client."""
+        return self._pair_groups(lib().mi_index_duplicates, (self._h, float(max_dist), int(first_new), max_pairs), web)
+
+    def _pair_groups(self, fn, lead, web: bool) -> list:
+        """fn(*lead, ids, cap_ids, group_start, cap_groups, &n_ids, &n_groups) of duplicates / bursts -> lists of paths"""
         n_ids, n_groups = ctypes.c_uint64(), ctypes.c_uint64()
-        check(lib().mi_index_duplicates(self._h, float(max_dist), int(first_new), max_pairs, None, 0, None, 0,
-                                        ctypes.byref(n_ids), ctypes.byref(n_groups)))
+        check(fn(*lead, None, 0, None, 0, ctypes.byref(n_ids), ctypes.byref(n_groups)))
         ids, starts = np.empty(n_ids.value, np.uint64), np.empty(n_groups.value + 1, np.uint64)
-        check(lib().mi_index_duplicates(self._h, float(max_dist), int(first_new), max_pairs, ids.ctypes.data if ids.size else None,
-                                        ids.size, starts.ctypes.data, starts.size, ctypes.byref(n_ids), ctypes.byref(n_groups)))
+        check(fn(*lead, ids.ctypes.data if ids.size else None, ids.size, starts.ctypes.data, starts.size, ctypes.byref(n_ids),
+                 ctypes.byref(n_groups)))
         return [[self.path(int(i), web=web) for i in g] for g in _groups(ids, starts)]
+
+    def bursts(self, max_dist: float, window: int, web: bool = False, max_pairs: int = 1 << 20) -> list:
+        """Bursts (mi_index_bursts): duplicates' groups over the pairs that look alike AND were taken within `window` of each
+        other (the stamps set_attrs set; EmbeddingTable.near_pairs_window through pairs_to_groups) — "the twelve shots of that
+        jump", not every beach picture of ten years."""
+        return self._pair_groups(lib().mi_index_bursts, (self._h, float(max_dist), int(window), 0, max_pairs), web)
 
     def matches(self, other: "ImageIndex", max_dist: float, web: bool = False, max_pairs: int = 1 << 20) -> list:
         """"Skip what I already have" (mi_index_matches): (path here, path in `other`, distance) for every pair of images
@@ -1957,11 +1995,21 @@ class ImageIndex:
         """The events / themes that are really there, however many, and the odd pictures (mi_index_themes: EmbeddingTable.dbscan
         on the index's table): (lists of paths, the largest cluster first, equal sizes by their first row, paths ordered by
         row id inside a list; the paths of the noise rows).  Removed paths are in neither."""
+        return self._clusters(lib().mi_index_themes, (self._h, float(max_dist), int(min_pts)), web)
+
+    def events(self, max_dist: float, window: int, min_pts: int = 5, web: bool = False):
+        """Events (mi_index_events): themes() whose neighbourhood is "within max_dist and within `window` in time"
+        (EmbeddingTable.dbscan_window on the index's table): a theme photographed in two far-apart periods is two events.
+        Same output shape as themes()."""
+        return self._clusters(lib().mi_index_events, (self._h, float(max_dist), int(window), int(min_pts)), web)
+
+    def _clusters(self, fn, lead, web: bool):
+        """fn(*lead, ids, cap_ids, group_start, cap_groups, &n_ids, &n_groups, &n_noise) of themes / events -> (lists, noise)"""
         n_ids, n_groups, n_noise = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         n = len(self.table)
         ids, starts = np.empty(n, np.uint64), np.empty(n + 1, np.uint64)
-        check(lib().mi_index_themes(self._h, float(max_dist), int(min_pts), ids.ctypes.data if n else None, n, starts.ctypes.data,
-                                    starts.size, ctypes.byref(n_ids), ctypes.byref(n_groups), ctypes.byref(n_noise)))
+        check(fn(*lead, ids.ctypes.data if n else None, n, starts.ctypes.data, starts.size, ctypes.byref(n_ids), ctypes.byref(n_groups),
+                 ctypes.byref(n_noise)))
         ids, starts = ids[:n_ids.value], starts[:n_groups.value + 1]
         groups = sorted(_groups(ids, starts), key=lambda g: (-len(g), int(g[0])))
         out = set(int(i) for i in ids) | set(int(i) for i in self.table.deleted())

@@ -352,6 +352,18 @@ int mi_knn_near_pairs(mi_knn* t, float max_dist, uint64_t first_new, uint64_t* a
 /* of the last mi_knn_near_pairs on this handle: out = {candidate pairs stage 1 passed to stage 2, pairs accepted,
  * strips run (re-runs after an overflow included), tiles visited} */
 int mi_knn_near_pairs_stats(mi_knn* t, uint64_t out[4]);
+/* Bursts ("which shots were taken within a few seconds of each other and look alike?"): mi_knn_near_pairs restricted to the
+ * pairs whose capture times lie within a window.  The stamp test: rows a and b pass when |stamp_a - stamp_b| <= window, stamp
+ * being the column mi_knn_set_attrs sets.  The difference is taken exactly — max - min in uint64 arithmetic, right for every
+ * pair of int64 values: INT64_MIN against INT64_MAX is 2^64 - 1 — so window == UINT64_MAX restricts nothing and window == 0
+ * means equal stamps only.  A table that never set attributes behaves as if every stamp were 0: every pair passes.
+ * W_win = the pairs of mi_knn_near_pairs(t, max_dist, first_new) whose two rows pass the stamp test; ids, order (ascending by
+ * (a, b)) and distance bits are those of W.  The cap protocol, the errors, dim, mirror, "join_cap" and the stream ordering
+ * are mi_knn_near_pairs'.  The test runs inside stage 1, so pairs that look alike but lie apart in time never reach the
+ * candidate buffer, and tiles whose two blocks' stamp ranges lie further apart than the window are not computed at all: on a
+ * table appended in capture order only a band along the diagonal is. */
+int mi_knn_near_pairs_window(mi_knn* t, float max_dist, uint64_t window, uint64_t first_new, uint64_t* a, uint64_t* b,
+                             float* dist, uint64_t cap, uint64_t* count);
 /* The join of TWO tables ("which pictures on this card, or in that other library, do I already have?" — the reference has one
  * table in one server, server/src/main.rs, and could only answer this by inserting the other rows first): every pair of a
  * live row of `t` and a live row of `other` with cosine distance <= max_dist.  a[i]: an id of t; b[i]: an id of other (the two
@@ -403,6 +415,22 @@ int mi_knn_dbscan(mi_knn* t, float max_dist, uint32_t min_pts, uint64_t* cluster
  * after an overflow included)}.  The tile counts are those of the launches whose candidates were consumed: visited + skipped =
  * the triangle's tiles.  After a *_levels call: pairs within = those of the top level, unions merged = summed over the levels. */
 int mi_knn_dbscan_stats(mi_knn* t, uint64_t out[8]);
+/* Events ("beach 2019" and "beach 2023" as two clusters): density and DBSCAN whose neighbourhood is "within max_dist AND
+ * within a time window" — ST-DBSCAN (Birant & Kut, 2007).  Exactly the contract of mi_knn_density / mi_knn_dbscan above with
+ * W_win (mi_knn_near_pairs_window at first_new = 0) in place of W: deg, core, clusters named by their smallest core row, border
+ * by the minimum of (distance key, core row) over the core neighbours in W_win, noise, a deleted row nothing at all.  The
+ * arguments, errors (an error writes nothing), dim, mirror, "join_cap" and stream ordering are the unwindowed calls'. */
+int mi_knn_density_window(mi_knn* t, float max_dist, uint64_t window, uint32_t* counts);
+int mi_knn_dbscan_window(mi_knn* t, float max_dist, uint64_t window, uint32_t min_pts, uint64_t* cluster, uint64_t* via,
+                         float* via_dist, uint32_t* counts, uint64_t summary[4]);
+/* of the last mi_knn_near_pairs_window / mi_knn_density_window / mi_knn_dbscan_window (mi_index_bursts / mi_index_events
+ * included) on this handle: out = {candidate pairs pass 1, pairs within, tiles computed pass 1, tiles skipped by the blocks' stamp
+ * ranges pass 1, candidate pairs pass 2, tiles computed pass 2, tiles skipped pass 2 (by the stamp ranges or by the activity
+ * bytes of mi_knn_dbscan_stats), stage-1 launches (re-runs after an overflow included)}.  The pass-2 words are 0 after
+ * mi_knn_near_pairs_window and mi_knn_density_window.  Per pass, computed + skipped = the tiles of the triangle the pass covers
+ * (the launches whose candidates were consumed are counted).  The windowed calls keep these words to themselves: they leave
+ * mi_knn_near_pairs_stats and mi_knn_dbscan_stats as they were, and the unwindowed calls leave these. */
+int mi_knn_window_stats(mi_knn* t, uint64_t out[8]);
 /* Themes at several distances in one pass ("tighter / looser themes" on a slider, a theme that contains bursts): what
  * n_levels calls of mi_knn_density / mi_knn_dbscan with max_dists[0] < max_dists[1] < ... return on the same table, from the
  * two tile passes ONE such call runs.  Slice l of every output array ([n_levels][rows], level-major, by local row) is exactly
@@ -1347,6 +1375,10 @@ int mi_index_live_paths(mi_index* ix, char* buf, size_t cap, size_t* needed);
  * max_pairs bounds the join (MI_ERR_UNSUPPORTED beyond it). */
 int mi_index_duplicates(mi_index* ix, float max_dist, uint64_t first_new, uint64_t max_pairs, uint64_t* ids,
                         uint64_t cap_ids, uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups);
+/* bursts of table `image`: mi_index_duplicates over mi_knn_near_pairs_window — the connected components of W_win, i.e. groups
+ * chained by pairs that look alike AND were taken within `window` of each other (the stamps mi_index_set_attrs set). */
+int mi_index_bursts(mi_index* ix, float max_dist, uint64_t window, uint64_t first_new, uint64_t max_pairs, uint64_t* ids,
+                    uint64_t cap_ids, uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups);
 /* "skip what I already have" at import: mi_knn_near_pairs_between on the two indexes' tables (the reference, one table in one
  * server — server/src/main.rs — can only compare paths).  a[i]: a row id of ix, b[i]: a row id of other (mi_index_path names
  * them), ascending by (a, b); removed paths are deleted rows and never reported. */
@@ -1356,6 +1388,10 @@ int mi_index_matches(mi_index* ix, mi_index* other, float max_dist, uint64_t* a,
  * their smallest id, ids ascending inside; noise is not listed, *n_noise counts it; removed paths are in neither. */
 int mi_index_themes(mi_index* ix, float max_dist, uint32_t min_pts, uint64_t* ids, uint64_t cap_ids, uint64_t* group_start,
                     uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups, uint64_t* n_noise);
+/* events of table `image`: mi_index_themes over mi_knn_dbscan_window — a theme photographed in two far-apart periods comes out
+ * as two clusters. */
+int mi_index_events(mi_index* ix, float max_dist, uint64_t window, uint32_t min_pts, uint64_t* ids, uint64_t cap_ids,
+                    uint64_t* group_start, uint64_t cap_groups, uint64_t* n_ids, uint64_t* n_groups, uint64_t* n_noise);
 /* The folders at a glance (mi_knn_summarize over the directory groups of mi_index_search_grouped): for directory g <
  * min(cap, *n_groups) its number of images count[g], its cover and odd one out (row ids: mi_index_path names them) with their
  * distances to the folder's centroid, measured[g] and spread[g] as mi_knn_summarize defines them.  Removed paths are deleted
