@@ -65,6 +65,8 @@ SYMBOLS = {
     "mi_knn_load": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
     "mi_knn_delete": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_u64p]),
     "mi_knn_deleted": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_u64p]),
+    "mi_knn_compact": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_u64p]),
+    "mi_knn_compact_stats": (ctypes.c_int, [c_vp, c_u64p]),
     "mi_knn_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, c_vp]),
     "mi_knn_search_batched_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, c_vp]),
@@ -170,6 +172,7 @@ SYMBOLS = {
     "mi_knn_sharded_search_async": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
     "mi_knn_sharded_sync": (ctypes.c_int, [c_vp]),
     "mi_knn_sharded_rebalance": (ctypes.c_int, [c_vp, c_vp]),
+    "mi_knn_sharded_compact_into": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, c_u64p]),
     "mi_knn_sharded_append_synthetic": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]),
     "mi_knn_sharded_get_rows": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp]),
     "mi_knn_sharded_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
@@ -212,6 +215,7 @@ SYMBOLS = {
     "mi_index_adopt": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t]),
     "mi_index_live_paths": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "mi_index_remove": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, c_u64p]),
+    "mi_index_compact": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_u64p]),
     "mi_index_rows_of": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, c_vp, ctypes.c_size_t,
                                         ctypes.POINTER(ctypes.c_size_t)]),
     "mi_index_path": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,

@@ -17,7 +17,7 @@ SOURCES = ["core.hip", "knn.hip", "vit.hip", "preprocess.hip", "pipeline.hip", "
            "assign_multi.hip", "search_many.hip", "kmeans_seed.hip", "diverse.hip", "compound.hip", "page.hip",
            "grouped.hip", "where.hip", "ordered.hip", "density.hip", "join_between.hip", "summary.hip", "density_sharded.hip",
            "kmeans_sharded.hip", "summary_sharded.hip", "density_levels.hip", "kmeans_seed_sharded.hip",
-           "representatives.hip", "window.hip"]
+           "representatives.hip", "window.hip", "compact.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-ffp-contract=off",
          "-Wall", "-Wno-unused-function", "-Wno-unused-const-variable"]
 

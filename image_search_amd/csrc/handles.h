@@ -281,6 +281,10 @@ struct mi_knn {
     size_t wcounts_cap = 0;
     uint64_t* h_wtotal = nullptr;
     int where_chunk = 0;
+    // mi_knn_compact (compact.hip): destination rows of one chunk of the in-place move (option "compact_chunk_rows": 0 = what a
+    // 64 MiB staging buffer holds), and {rows removed, rows moved, chunks gathered in place, chunks staged} of the last call
+    int compact_chunk_rows = 0;
+    uint64_t compact_stats[4] = {0, 0, 0, 0};
     std::mutex mu;
 };
 

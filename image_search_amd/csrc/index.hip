@@ -709,4 +709,40 @@ int mi_index_remove(mi_index* ix, const char* const* paths, size_t n, uint64_t* 
     });
 }
 
+// mi_knn_compact on the table, then the path column by the same map: the rows the table dropped leave `paths` and `row_dir`,
+// the lookups are rebuilt over the new ids (the directory dictionary keeps its group ids: the table's group column travelled
+// with the rows, and the next grouped search uploads it again because the table's groups_epoch has moved on)
+int mi_index_compact(mi_index* ix, uint64_t* new_ids, uint64_t cap, uint64_t* removed) {
+    return guarded([&] {
+        if (!ix) fail(MI_ERR_INVALID, "null index handle");
+        std::lock_guard<std::mutex> l(ix->mu);
+        uint64_t rows = 0;
+        (void)mi_knn_size(ix->table, &rows);
+        if (new_ids && cap < rows) fail(MI_ERR_INVALID, "new_ids holds %llu entries, the table %llu rows", (unsigned long long)cap, (unsigned long long)rows);
+        std::vector<uint64_t> map((size_t)rows);
+        uint64_t gone = 0;
+        call_ok(mi_knn_compact(ix->table, map.data(), map.size(), &gone));   // the rows first: a failure changes nothing
+        if (gone) {
+            std::vector<std::string> old;
+            old.swap(ix->paths);
+            std::vector<uint32_t> old_dir;
+            old_dir.swap(ix->row_dir);
+            ix->removed.clear();
+            ix->rows_of.clear();
+            ix->live.clear();
+            for (size_t o = 0; o < old.size(); ++o) {
+                if (o < map.size() && map[o] == MI_KNN_NO_ID) continue;
+                ix->rows_of[old[o]].push_back(ix->paths.size());
+                ix->live.insert(old[o]);
+                ix->paths.push_back(std::move(old[o]));
+                ix->removed.push_back(0);
+                ix->row_dir.push_back(old_dir[o]);
+            }
+            ix->groups_uploaded = 0;
+        }
+        if (new_ids) std::copy(map.begin(), map.end(), new_ids);
+        if (removed) *removed = gone;
+    });
+}
+
 }  // extern "C"

@@ -1188,8 +1188,13 @@ int mi_knn_set_option(mi_knn* t, const char* key, int value) {
             // multiple of 64 up to 65536.  Same answers whatever the value.
             if (!where_chunk_ok(value)) fail(MI_ERR_INVALID, "where_chunk must be 0 or a multiple of 64 up to 65536 (got %d)", value);
             t->where_chunk = value;
+        } else if (k == "compact_chunk_rows") {
+            // mi_knn_compact: destination rows of one chunk of its in-place move (and of its staging buffer).  0 (default): what
+            // 64 MiB hold of rows of this dim (21 845 at dim 768).  Same table afterwards whatever the value.
+            if (value < 0) fail(MI_ERR_INVALID, "compact_chunk_rows must be >= 0 (got %d)", value);
+            t->compact_chunk_rows = value;
         } else {
-            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, join_stage, join_stage_rows, many_segments, many_sample, kmeans_fixed_sum, compound_blocks, page_blocks, group_blocks, group_lds_max, where_chunk)", key);
+            fail(MI_ERR_INVALID, "unknown option '%s' (known: prefilter, prefilter_adaptive, prefilter_sample, batch_stage1, join_cap, join_stage, join_stage_rows, many_segments, many_sample, kmeans_fixed_sum, compound_blocks, page_blocks, group_blocks, group_lds_max, where_chunk, compact_chunk_rows)", key);
         }
     });
 }

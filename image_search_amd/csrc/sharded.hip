@@ -594,6 +594,89 @@ int mi_knn_sharded_sync(mi_knn_sharded* t) {
     });
 }
 
+}  // extern "C"
+
+namespace {
+// Both tables' locks held, dst empty: the rows of src into dst in global order — all of them with the deleted ones marked in dst
+// too (drop_dead false: mi_knn_sharded_rebalance), or the live ones only (true: mi_knn_sharded_compact_into; `dead` = src's
+// deleted global rows, ascending).  The columns follow by the row's global id in dst.  A failure leaves dst empty.
+void redeal(mi_knn_sharded* dst, mi_knn_sharded* src, const std::vector<uint64_t>& dead, bool drop_dead) {
+    const uint64_t total = drop_dead ? src->rows - dead.size() : src->rows;
+    for (uint32_t s = 0; s < dst->n(); ++s) {
+        const uint64_t mine = (sharded_rows_of(dst, total, s) + dst->block - 1) / dst->block * dst->block;
+        call_ok(mi_knn_reserve(dst->shard[s], mine));  // one allocation per shard, nothing moves during the copy
+    }
+    // src's global rows [a, a + n): each run that is contiguous inside one shard is routed by append_device_locked
+    auto copy_rows = [&](uint64_t a, uint64_t n) {
+        for_runs(src, a, n, [&](uint64_t, uint64_t len, uint32_t s, uint64_t local) {
+            mi_knn* from = src->shard[s];
+            hipStream_t st;
+            {
+                std::lock_guard<std::mutex> ls(from->mu);
+                DeviceGuard g(from->device);
+                st = knn_own_stream(from);
+                from->writes.begin(st);  // the rows being read have landed
+            }
+            append_device_locked(dst, from->table + local * src->dim, len, from->device, st);
+        });
+    };
+    // a column by src's global row -> by dst's: the deleted rows' entries leave when the rows did
+    auto by_dst_row = [&](auto& col) {
+        if (!drop_dead) return;
+        size_t c = 0, w = 0;
+        for (size_t o = 0; o < col.size(); ++o) {
+            if (c < dead.size() && dead[c] == o) { ++c; continue; }
+            col[w++] = col[o];
+        }
+        col.resize(w);
+    };
+    try {
+        if (!drop_dead) copy_rows(0, src->rows);
+        else {   // the live runs: the gaps between consecutive deleted rows
+            uint64_t a = 0;
+            for (size_t c = 0; c <= dead.size(); ++c) {
+                const uint64_t b = c < dead.size() ? dead[c] : src->rows;
+                if (b > a) copy_rows(a, b - a);
+                a = b + 1;
+            }
+        }
+        for (mi_knn* from : src->shard) {  // the source may be freed as soon as this returns
+            DeviceGuard g(from->device);
+            if (from->stream) HIP_CHECK(hipStreamSynchronize(from->stream));
+        }
+        // the columns (sharded_calls.hip), by global id: the same rows in the new layout
+        if (!drop_dead && !dead.empty()) sharded_delete(dst, dead.data(), dead.size());
+        uint64_t ginfo[2];
+        sharded_groups_info(src, ginfo);
+        if (ginfo[1]) {
+            std::vector<uint32_t> col((size_t)src->rows);
+            sharded_get_groups(src, nullptr, src->rows, col.data());
+            by_dst_row(col);
+            if (!col.empty()) sharded_set_groups(dst, nullptr, col.size(), col.data());
+        }
+        bool has_attrs = false;
+        for (mi_knn* sh : src->shard) {
+            std::lock_guard<std::mutex> ls(sh->mu);
+            has_attrs = has_attrs || sh->d_tags;
+        }
+        if (has_attrs && src->rows) {
+            std::vector<uint64_t> tags((size_t)src->rows);
+            std::vector<int64_t> stamps((size_t)src->rows);
+            sharded_get_attrs(src, nullptr, src->rows, tags.data(), stamps.data());
+            by_dst_row(tags);
+            by_dst_row(stamps);
+            if (!tags.empty()) sharded_set_attrs(dst, nullptr, tags.size(), tags.data(), stamps.data());
+        }
+    } catch (...) {
+        dst->rows = 0;
+        roll_back(dst);
+        throw;
+    }
+}
+}  // namespace
+
+extern "C" {
+
 // Every row of `src` into the EMPTY `dst` (another shard count, device set or block size) without leaving the devices:
 // src's blocks are walked in global order and each contiguous run is routed by append_device_locked — a device-to-device
 // copy when source and destination shard share a GPU, hipMemcpyPeerAsync over xGMI otherwise.  src is unchanged.
@@ -603,52 +686,29 @@ int mi_knn_sharded_rebalance(mi_knn_sharded* dst, mi_knn_sharded* src) {
         if (dst->dim != src->dim) fail(MI_ERR_INVALID, "dim %u into dim %u", src->dim, dst->dim);
         std::scoped_lock l(dst->mu, src->mu);
         if (dst->rows != 0) fail(MI_ERR_INVALID, "mi_knn_sharded_rebalance needs an empty destination");
-        for (uint32_t s = 0; s < dst->n(); ++s) {
-            const uint64_t mine = (sharded_rows_of(dst, src->rows, s) + dst->block - 1) / dst->block * dst->block;
-            call_ok(mi_knn_reserve(dst->shard[s], mine));  // one allocation per shard, nothing moves during the copy
+        redeal(dst, src, sharded_deleted(src), false);
+    });
+}
+
+// mi_knn_sharded_rebalance that leaves the deleted rows behind: src's live global runs in order, the columns by compacted
+// global id.  new_ids comes from the sorted list of deleted global rows, on the host.
+int mi_knn_sharded_compact_into(mi_knn_sharded* dst, mi_knn_sharded* src, uint64_t* new_ids, uint64_t cap, uint64_t* removed) {
+    return guarded([&] {
+        if (!dst || !src || dst == src) fail(MI_ERR_INVALID, "two distinct table handles are needed");
+        if (dst->dim != src->dim) fail(MI_ERR_INVALID, "dim %u into dim %u", src->dim, dst->dim);
+        std::scoped_lock l(dst->mu, src->mu);
+        if (dst->rows != 0) fail(MI_ERR_INVALID, "mi_knn_sharded_compact_into needs an empty destination");
+        if (new_ids && cap < src->rows) fail(MI_ERR_INVALID, "new_ids holds %llu entries, the table %llu rows", (unsigned long long)cap, (unsigned long long)src->rows);
+        const std::vector<uint64_t> dead = sharded_deleted(src);
+        redeal(dst, src, dead, true);
+        if (new_ids) {
+            size_t c = 0;
+            for (uint64_t o = 0; o < src->rows; ++o) {
+                if (c < dead.size() && dead[c] == o) { new_ids[o] = MI_KNN_NO_ID; ++c; }
+                else new_ids[o] = o - c;
+            }
         }
-        try {
-            for_runs(src, 0, src->rows, [&](uint64_t, uint64_t len, uint32_t s, uint64_t local) {
-                mi_knn* from = src->shard[s];
-                hipStream_t st;
-                {
-                    std::lock_guard<std::mutex> ls(from->mu);
-                    DeviceGuard g(from->device);
-                    st = knn_own_stream(from);
-                    from->writes.begin(st);  // the rows being read have landed
-                }
-                append_device_locked(dst, from->table + local * src->dim, len, from->device, st);
-            });
-            for (mi_knn* from : src->shard) {  // the source may be freed as soon as this returns
-                DeviceGuard g(from->device);
-                if (from->stream) HIP_CHECK(hipStreamSynchronize(from->stream));
-            }
-            // the columns (sharded_calls.hip), by global id: the same rows in the new layout
-            const std::vector<uint64_t> dead = sharded_deleted(src);
-            if (!dead.empty()) sharded_delete(dst, dead.data(), dead.size());
-            uint64_t ginfo[2];
-            sharded_groups_info(src, ginfo);
-            if (ginfo[1]) {
-                std::vector<uint32_t> col((size_t)src->rows);
-                sharded_get_groups(src, nullptr, src->rows, col.data());
-                sharded_set_groups(dst, nullptr, src->rows, col.data());
-            }
-            bool has_attrs = false;
-            for (mi_knn* sh : src->shard) {
-                std::lock_guard<std::mutex> ls(sh->mu);
-                has_attrs = has_attrs || sh->d_tags;
-            }
-            if (has_attrs && src->rows) {
-                std::vector<uint64_t> tags((size_t)src->rows);
-                std::vector<int64_t> stamps((size_t)src->rows);
-                sharded_get_attrs(src, nullptr, src->rows, tags.data(), stamps.data());
-                sharded_set_attrs(dst, nullptr, src->rows, tags.data(), stamps.data());
-            }
-        } catch (...) {
-            dst->rows = 0;
-            roll_back(dst);
-            throw;
-        }
+        if (removed) *removed = dead.size();
     });
 }
 

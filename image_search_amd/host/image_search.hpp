@@ -198,6 +198,15 @@ class EmbeddingTable {
         if (n) check(mi_knn_deleted(h_, v.data(), n, &n));
         return v;
     }
+    // the deleted rows leave the table physically (mi_knn_compact); returns the old-to-new id map, [rows before the call],
+    // MI_KNN_NO_ID for a deleted row: every id held outside the table (labels, cursors) must go through it
+    std::vector<uint64_t> compact(uint64_t* removed = nullptr) {
+        std::vector<uint64_t> new_ids(size());
+        check(mi_knn_compact(h_, new_ids.data(), new_ids.size(), removed));
+        return new_ids;
+    }
+    // {rows removed, rows moved, chunks gathered in place, chunks staged} of the last compact
+    std::vector<uint64_t> compact_stats() const { std::vector<uint64_t> v(4); check(mi_knn_compact_stats(h_, v.data())); return v; }
     // what the database's storage did for the reference: one file per shard
     void save(const std::string& path) const { check(mi_knn_save(h_, path.c_str())); }
     void load(const std::string& path) { check(mi_knn_load(h_, path.c_str())); }

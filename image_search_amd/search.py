@@ -367,6 +367,20 @@ class EmbeddingTable:
         """ids of the deleted rows, ascending (mi_knn_deleted)"""
         return _deleted(lib().mi_knn_deleted, self._h)
 
+    def compact(self) -> dict:
+        """The deleted rows leave the table physically (mi_knn_compact): the survivors close up in order and take new ids,
+        their groups, tags and stamps travel with them, and every search runs the code of a table without deletions
+        again.  Returns {"removed": rows reclaimed, "new_ids": [rows before the call] uint64, the new id of every old
+        row, NO_ID for a deleted one}.  Ids held outside the table (label arrays, page / ordered cursors) must be mapped
+        through new_ids."""
+        return _compact(lib().mi_knn_compact, self._h, len(self))
+
+    def compact_stats(self) -> dict:
+        """mi_knn_compact_stats, of the last compact on this table"""
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().mi_knn_compact_stats(self._h, out))
+        return {"removed": out[0], "moved": out[1], "straight": out[2], "staged": out[3]}
+
     def knn(self, reference: np.ndarray, k: int = K_REFERENCE, within=None):
         """`WHERE embedding <|k|> $reference` (search.rs:70-77): (ids, cosine distances),
         ascending distance then id.  reference: [dim] or [nq,dim].
@@ -1081,6 +1095,13 @@ def _deleted(fn, h) -> np.ndarray:
     return out
 
 
+def _compact(fn, h, rows: int) -> dict:
+    new_ids = np.empty(rows, dtype=np.uint64)
+    removed = ctypes.c_uint64()
+    check(fn(h, new_ids.ctypes.data if rows else None, rows, ctypes.byref(removed)))
+    return {"removed": removed.value, "new_ids": new_ids}
+
+
 class PinnedBuffer:
     """Page-locked host memory (mi_host_alloc) viewed as a numpy array: upload buffers of the
     fused pipeline (asynchronous H2D needs pinned memory)."""
@@ -1270,6 +1291,16 @@ class ShardedTable:
     def rebalance_from(self, src: "ShardedTable"):
         """every row of `src` into this empty table, device to device (mi_knn_sharded_rebalance)"""
         check(lib().mi_knn_sharded_rebalance(self._h, src._h))
+
+    def compact_into(self, dst: "ShardedTable") -> dict:
+        """every LIVE row of this table into the empty `dst`, in global order, with its group, tags and stamp
+        (mi_knn_sharded_compact_into): the compaction of a sharded table.  This table is unchanged.  Returns {"removed",
+        "new_ids"} as EmbeddingTable.compact, new_ids by this table's global row."""
+        rows = len(self)
+        new_ids = np.empty(rows, dtype=np.uint64)
+        removed = ctypes.c_uint64()
+        check(lib().mi_knn_sharded_compact_into(dst._h, self._h, new_ids.ctypes.data if rows else None, rows, ctypes.byref(removed)))
+        return {"removed": removed.value, "new_ids": new_ids}
 
     def knn(self, reference: np.ndarray, k: int = K_REFERENCE, within=None):
         """EmbeddingTable.knn over all shards; within: global ids (mi_knn_sharded_search_filtered)"""
@@ -1746,6 +1777,11 @@ class ImageIndex:
         n = ctypes.c_uint64()
         check(lib().mi_index_remove(self._h, _cstrs(paths), len(paths), ctypes.byref(n)))
         return n.value
+
+    def compact(self) -> dict:
+        """The removed rows leave the table and the path column (mi_index_compact); every lookup and search names the same
+        paths as before, row ids change.  Returns {"removed", "new_ids"} as EmbeddingTable.compact."""
+        return _compact(lib().mi_index_compact, self._h, len(self.table))
 
     def live_paths(self) -> set:
         """the image_path of every row that has not been removed (mi_index_live_paths: one call)"""
@@ -2310,14 +2346,16 @@ def prune_missing_images(index, media_dir: str, found=None) -> int:
 
 
 def embed_all_images_in_dir(model, index: ImageIndex, media_dir: str, image_chunk_size: int = 500, decode=None,
-                            shuffle_seed=None, prune: bool = False) -> int:
+                            shuffle_seed=None, prune: bool = False, compact_above: Optional[float] = None) -> int:
     """clip.rs:42-151: walk `media_dir` (following links), keep the allow-listed extensions, shuffle,
     and per chunk: skip paths that already have a row, decode, embed (resize + normalise + tower on
     the device: Model.forward_images), insert.  A crash loses at most one chunk; a rerun resumes.
     `decode(path) -> RGB8 [H,W,3]` defaults to Pillow; files that fail to decode are logged and
     skipped TOGETHER WITH their path (the reference zips the unfiltered path list with the
     surviving embeddings, clip.rs:125-134, which shifts paths after a failure).  prune=True first removes the rows of
-    files that are gone from media_dir (prune_missing_images; the reference only ever adds).  Returns rows added."""
+    files that are gone from media_dir (prune_missing_images; the reference only ever adds); compact_above: after such a
+    prune, when deleted rows / rows exceeds this fraction the index is compacted (ImageIndex.compact: row ids change,
+    paths do not); None = never.  Returns rows added."""
     import logging
     import random
     if decode is None:
@@ -2329,6 +2367,10 @@ def embed_all_images_in_dir(model, index: ImageIndex, media_dir: str, image_chun
             logging.getLogger(__name__).error("walk of %s incomplete (%s): rows not pruned", media_dir, errors[0])
         else:
             prune_missing_images(index, media_dir, paths)
+            if compact_above is not None:
+                rows = len(index.table)
+                if rows and len(index.table.deleted()) / rows > compact_above:
+                    index.compact()
     random.Random(shuffle_seed).shuffle(paths)
     added = 0
     for c0 in range(0, len(paths), image_chunk_size):

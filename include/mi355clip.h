@@ -300,6 +300,30 @@ int mi_knn_load(mi_knn* t, const char* path);
 int mi_knn_delete(mi_knn* t, const uint64_t* ids, uint64_t n, uint64_t* newly);
 /* *count = deleted rows; the first min(cap, count) of their ids, ascending, into ids (may be NULL) */
 int mi_knn_deleted(mi_knn* t, uint64_t* ids, uint64_t cap, uint64_t* count);
+/* Remove the deleted rows physically ("vacuum": a long-lived library gets the space of its deletions back).  Survivors keep
+ * their relative order; the survivor at old local row o moves to local row o - (number of deleted rows below o) and its id
+ * becomes base + that.  new_ids (may be NULL): [rows before the call], new_ids[o] = the new id, MI_KNN_NO_ID for a deleted
+ * row; cap = its length (cap < rows before: MI_ERR_INVALID, nothing changes).  *removed (may be NULL) = rows reclaimed.
+ * With L = rows - deleted, afterwards: mi_knn_size = L, mi_knn_deleted is empty, mi_knn_get_rows(0, L) returns the survivors'
+ * fp32 rows in their old order bit for bit, and each survivor's group, tags and stamp have travelled with it (mi_knn_groups_info's
+ * group count stays the high-water mark it was).  The freed rows [L, old rows) hold the defaults (no group, tags 0, stamp 0)
+ * and the next append reuses them.  Every call of the library returns on the compacted table what it returns on a fresh
+ * table of the same dim, base and options that was given the survivors by mi_knn_append and their columns by
+ * mi_knn_set_groups / mi_knn_set_attrs — in particular every search runs the code of a table without deletions again, and
+ * mi_knn_save writes the MIKNNv01 file of L rows.  What does NOT survive: every id the caller holds (label arrays, the
+ * cursors of mi_knn_search_page / mi_knn_search_ordered): map them through new_ids.  The "prefilter" mirrors of the moved
+ * rows are rebuilt by the next search.
+ * The rows move in place on the device, in ascending chunks of option "compact_chunk_rows" destination rows (0 = default:
+ * what 64 MiB hold, 21 845 rows at dim 768), each either gathered straight into place or through a staging buffer of one
+ * chunk; rows below the first deleted row are not touched.  Extra device memory while the call runs: that buffer, 4 bytes
+ * per deleted row and 12 per moved row; never a second table.  The allocation itself does not shrink.  The call waits for
+ * everything enqueued on the table (as a reallocation does), checks every argument and allocates every buffer before the
+ * first row moves, and has finished when it returns.  A table without deletions: *removed = 0, new_ids = the ids as they
+ * are, nothing is launched.  Every row deleted: the table becomes empty.  A shard borrowed from a sharded table:
+ * MI_ERR_UNSUPPORTED (its ids are not its own to renumber: mi_knn_sharded_compact_into).  A null handle: MI_ERR_INVALID. */
+int mi_knn_compact(mi_knn* t, uint64_t* new_ids, uint64_t cap, uint64_t* removed);
+/* {rows removed, rows moved, chunks gathered in place, chunks staged} of the last mi_knn_compact on this handle */
+int mi_knn_compact_stats(mi_knn* t, uint64_t out[4]);
 
 /* Replaces `SELECT id, image_path, vector::distance::knn() FROM image WHERE
  * embedding <|K|> $reference` (server/src/search.rs:70-86; K = 1000 there).
@@ -1182,6 +1206,14 @@ int mi_knn_sharded_summarize_stats(mi_knn_sharded* t, uint64_t out[4]);
  * size), block by block, device to device — a plain copy where source and destination shard share a GPU,
  * hipMemcpyPeerAsync over xGMI where they do not; nothing passes through the host.  src is unchanged. */
 int mi_knn_sharded_rebalance(mi_knn_sharded* dst, mi_knn_sharded* src);
+/* The compaction of a sharded table: every LIVE row of src into the empty dst (same dim; any shard count, device set or
+ * block size), in global order — mi_knn_sharded_rebalance that leaves the deleted rows behind.  Groups, tags and stamps
+ * travel by compacted global id; dst equals a fresh sharded table given the survivors in order.  src is unchanged.  new_ids
+ * (may be NULL): [src's rows] by src's global row, the row's id in dst, MI_KNN_NO_ID for a deleted row; cap = its length
+ * (cap < rows: MI_ERR_INVALID, nothing changes); *removed (may be NULL) = rows left behind.  A failure leaves dst empty.  (A
+ * sharded table is not compacted in place: survivors change shard under the block-cyclic deal, so that would be this
+ * redistribution anyway.) */
+int mi_knn_sharded_compact_into(mi_knn_sharded* dst, mi_knn_sharded* src, uint64_t* new_ids, uint64_t cap, uint64_t* removed);
 /* the placement arithmetic by itself (host-only): global row <-> (shard, local row) */
 int mi_knn_sharded_place(uint32_t block_rows, uint32_t n_shards, uint64_t row, uint32_t* shard, uint64_t* local);
 int mi_knn_sharded_id(uint32_t block_rows, uint32_t n_shards, uint32_t shard, uint64_t local, uint64_t* row);
@@ -1367,6 +1399,11 @@ int mi_index_load(mi_index* ix, const char* dir); /* into an empty index */
  * such a row fails with MI_ERR_INVALID.  Paths without rows are ignored.  *removed_rows (may be NULL) = rows deleted.
  * The removal is saved with the embedding file (MIKNNv02); the path file is unchanged. */
 int mi_index_remove(mi_index* ix, const char* const* paths, size_t n, uint64_t* removed_rows);
+/* mi_knn_compact on mi_index_table, and the path column with it: the removed rows leave, the others close up and take new
+ * ids (new_ids, cap, *removed: as mi_knn_compact).  Every lookup and search names the same paths as before the call (the
+ * server's responses carry paths, never row ids: clients notice nothing); mi_index_save then writes the MIKNNv01 file
+ * (32 + L x dim x 4 bytes) and a path file of L entries. */
+int mi_index_compact(mi_index* ix, uint64_t* new_ids, uint64_t cap, uint64_t* removed);
 /* every image_path that has a row that was not removed, once each, as consecutive NUL-terminated strings; *needed = bytes
  * of the whole list, whole paths up to `cap` bytes are written (buf may be NULL) — what a scan's prune compares with the
  * files it found (search.py prune_missing_images) */
