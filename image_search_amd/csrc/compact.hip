@@ -22,20 +22,6 @@ using namespace mi;
 
 namespace {
 
-// device memory of this call alone, freed on every way out
-struct Scratch {
-    std::vector<void*> p;
-    void* get(size_t bytes) {
-        void* q = nullptr;
-        HIP_CHECK(hipMalloc(&q, std::max<size_t>(bytes, 16)));
-        p.push_back(q);
-        return q;
-    }
-    ~Scratch() {
-        for (void* q : p) (void)hipFree(q);
-    }
-};
-
 uint32_t compact_grid(const mi_knn* t, uint64_t work) {
     const uint64_t blocks = (work + COMPACT_THREADS - 1) / COMPACT_THREADS;
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)std::max(t->n_cu, 1) * 16));
@@ -49,18 +35,19 @@ void launch_move(const mi_knn* t, const float* src, float* dst, const uint32_t* 
     HIP_CHECK(hipGetLastError());
 }
 
-// col[first .. first + n) = col[rows[..]] through tmp, then the freed tail [first + n, old_rows) = `fill` bytes
+// the device half of a column (one that exists): col[first .. first + n) = col[rows[..]] through tmp, then the freed tail
+// [first + n, old_rows) = the default
 template <class T>
-void compact_device_column(const mi_knn* t, T* col, size_t col_cap, const uint32_t* d_src, uint64_t first, uint64_t n, uint64_t old_rows,
-                           int fill, void* tmp, hipStream_t s) {
-    if (!col) return;
+void compact_device_column(const mi_knn* t, RowColumn<T>& col, const uint32_t* d_src, uint64_t first, uint64_t n, uint64_t old_rows, void* tmp,
+                           hipStream_t s) {
+    if (!col.p) return;
     if (n) {
-        hipLaunchKernelGGL(compact_gather_kernel<T>, dim3(compact_grid(t, n)), dim3(COMPACT_THREADS), 0, s, (const T*)col, d_src, (uint32_t)n, (T*)tmp);
+        hipLaunchKernelGGL(compact_gather_kernel<T>, dim3(compact_grid(t, n)), dim3(COMPACT_THREADS), 0, s, (const T*)col.p, d_src, (uint32_t)n, (T*)tmp);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(col + first, tmp, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(col.p + first, tmp, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, s));
     }
-    const uint64_t end = std::min<uint64_t>(old_rows, col_cap);
-    if (end > first + n) HIP_CHECK(hipMemsetAsync(col + first + n, fill, (size_t)(end - first - n) * sizeof(T), s));
+    const uint64_t end = std::min<uint64_t>(old_rows, col.cap);
+    if (end > first + n) HIP_CHECK(hipMemsetAsync(col.p + first + n, col.fill, (size_t)(end - first - n) * sizeof(T), s));
 }
 
 }  // namespace
@@ -85,9 +72,9 @@ int mi_knn_compact(mi_knn* t, uint64_t* new_ids, uint64_t cap, uint64_t* removed
         const uint64_t n_dead = dead.size(), n_move = plan.live - plan.first;
         const size_t row_elems = t->dim;
         // the host columns as they will be, built aside: nothing of the handle changes before the device work has run
-        std::vector<uint32_t> h_groups = t->h_groups;
-        std::vector<uint64_t> h_tags = t->h_tags;
-        std::vector<int64_t> h_stamps = t->h_stamps;
+        std::vector<uint32_t> h_groups = t->d_groups.host;
+        std::vector<uint64_t> h_tags = t->d_tags.host;
+        std::vector<int64_t> h_stamps = t->d_stamps.host;
         compact_column(h_groups, dead);
         compact_column(h_tags, dead);
         compact_column(h_stamps, dead);
@@ -126,10 +113,10 @@ int mi_knn_compact(mi_knn* t, uint64_t* new_ids, uint64_t cap, uint64_t* removed
             }
         }
         // the columns by the same list, out of place; then their freed tails hold the defaults (knn_truncate's guarantee)
-        compact_device_column(t, t->d_groups, t->groups_cap, d_src, plan.first, n_move, rows, 0xFF, d_col, s);
-        compact_device_column(t, t->d_tags, t->attrs_cap, d_src, plan.first, n_move, rows, 0, d_col, s);
-        compact_device_column(t, t->d_stamps, t->attrs_cap, d_src, plan.first, n_move, rows, 0, d_col, s);
-        if (t->d_tomb) HIP_CHECK(hipMemsetAsync(t->d_tomb, 0, t->tomb_words * sizeof(uint64_t), s));
+        compact_device_column(t, t->d_groups, d_src, plan.first, n_move, rows, d_col, s);
+        compact_device_column(t, t->d_tags, d_src, plan.first, n_move, rows, d_col, s);
+        compact_device_column(t, t->d_stamps, d_src, plan.first, n_move, rows, d_col, s);
+        if (t->d_tomb) HIP_CHECK(hipMemsetAsync(t->d_tomb, 0, t->d_tomb.cap * sizeof(uint64_t), s));
         const hipError_t done = hipStreamSynchronize(s);
         if (done != hipSuccess) fail(MI_ERR_HIP, "the compaction failed on the device (%s): the table's rows are partly moved", hipGetErrorString(done));
 
@@ -140,16 +127,16 @@ int mi_knn_compact(mi_knn* t, uint64_t* new_ids, uint64_t cap, uint64_t* removed
         t->compact_stats[2] = plan.n_straight; t->compact_stats[3] = plan.n_staged;
         t->rows = plan.live;
         t->mirror_rows = std::min(t->mirror_rows, plan.first);   // the next search mirrors the moved rows again
-        t->h_groups.swap(h_groups);
-        t->h_tags.swap(h_tags);
-        t->h_stamps.swap(h_stamps);
+        t->d_groups.host.swap(h_groups);
+        t->d_tags.host.swap(h_tags);
+        t->d_stamps.host.swap(h_stamps);
         t->n_grouped = n_grouped;
         ++t->groups_epoch;
         t->gslots_valid = false;
         t->n_flist = 0;
         t->last_prefiltered = false;
         t->dead.clear();
-        if (t->d_dead) { (void)hipFree(t->d_dead); t->d_dead = nullptr; t->dead_cap = 0; }
+        t->d_dead.release();
     });
 }
 

@@ -1,5 +1,5 @@
 // compact_host.h — the host-only rules of mi_knn_compact (compact.hip): where every surviving row comes from, the old-to-new id
-// map, the plan of chunks with its straight / staged decision, and the compaction of the columns' host copies.  No HIP in
+// map and the plan of chunks with its straight / staged decision (the columns' host copies: columns_host.h).  No HIP in
 // here: tests/cpp/test_compact_host.cpp compiles this header alone and runs it under the sanitizers.
 //
 // `dead` is always the table's list of deleted local rows: ascending, once each, every one below `rows`.
@@ -8,6 +8,8 @@
 #include <cstddef>
 #include <cstdint>
 #include <vector>
+
+#include "columns_host.h"   // compact_column: the same for a column's host copy
 
 namespace mi {
 
@@ -72,19 +74,6 @@ inline CompactPlan compact_plan(const std::vector<uint32_t>& dead, uint64_t rows
         j0 = j1;
     }
     return p;
-}
-
-// a column's host copy (it may be shorter than the table: the rows it was never told about hold the default): the entries of
-// deleted rows leave, the others close up in order.  Returns the entries that left.
-template <class T>
-inline size_t compact_column(std::vector<T>& col, const std::vector<uint32_t>& dead) {
-    size_t c = 0, w = 0;
-    for (size_t o = 0; o < col.size(); ++o) {
-        if (c < dead.size() && dead[c] == o) { ++c; continue; }
-        col[w++] = col[o];
-    }
-    col.resize(w);
-    return c;
 }
 
 }  // namespace mi

@@ -52,10 +52,10 @@ void knn_search_grouped(mi_knn* t, const float* q, uint32_t k, float max_dist, c
     const uint32_t blocks = grouped_grid(n, t->n_cu, t->group_blocks);
     unsigned char* d_rec = scan_record(t, rec.bytes);
     uint32_t* keys32 = scan_keys32(t, n);
-    if (G) knn_reserve(t, (void**)&t->d_gslots, &t->gslots_cap, (size_t)G * 3, sizeof(uint32_t));
+    if (G) t->d_gslots.reserve(t->reads, (size_t)G * 3);
 
     unsigned long long* d_totals = reinterpret_cast<unsigned long long*>(d_rec + rec.totals);
-    unsigned long long* d_best = reinterpret_cast<unsigned long long*>(t->d_gslots);   // [G] u64, then [G] u32
+    unsigned long long* d_best = reinterpret_cast<unsigned long long*>(t->d_gslots.p);   // [G] u64, then [G] u32
     uint32_t* d_cnt = t->d_gslots ? t->d_gslots + (size_t)G * 2 : nullptr;
     HIP_CHECK(hipMemcpyAsync(t->d_q, q, (size_t)t->dim * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemsetAsync(d_totals, 0, 4 * sizeof(uint64_t), s));
@@ -104,7 +104,7 @@ void knn_grouped_members(mi_knn* t, const uint32_t* group, uint32_t k, uint32_t*
     if (!t->gslots_valid || k == 0) return;
     TableCall call(t);
     hipStream_t s = call.s;
-    knn_reserve(t, (void**)&t->d_gwin, &t->gwin_cap, (size_t)2 * PAGE_K_MAX, sizeof(uint32_t));
+    t->d_gwin.reserve(t->reads, (size_t)2 * PAGE_K_MAX);
     const uint32_t G = t->gslots_groups;
     HIP_CHECK(hipMemcpyAsync(t->d_gwin, group, (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(group_gather_kernel, dim3((k + 255) / 256), dim3(256), 0, s, t->d_gwin, k, t->d_gslots + (size_t)G * 2, G,
@@ -129,14 +129,13 @@ int mi_knn_set_groups(mi_knn* t, const uint64_t* ids, uint64_t n, const uint32_t
         const std::vector<uint32_t> rows = knn_local_rows(t, ids, n);   // every id checked before anything is written
         TableCall call(t);
         knn_groups_fit(t);
-        if (t->h_groups.size() < t->rows) t->h_groups.resize((size_t)t->rows, MI_KNN_NO_GROUP);
         for (uint64_t i = 0; i < n; ++i) {
-            uint32_t& slot = t->h_groups[rows[(size_t)i]];
+            uint32_t& slot = t->d_groups.slot((size_t)t->rows, rows[(size_t)i]);
             t->n_grouped += (groups[i] != MI_KNN_NO_GROUP) - (slot != MI_KNN_NO_GROUP);
             slot = groups[i];
             if (groups[i] != MI_KNN_NO_GROUP) t->n_groups = std::max(t->n_groups, groups[i] + 1);
         }
-        upload_span(call, rows, {{t->d_groups, t->h_groups.data(), sizeof(uint32_t)}});
+        upload_span(call, rows, {{t->d_groups.p, t->d_groups.host.data(), sizeof(uint32_t)}});
         ++t->groups_epoch;
     });
 }
@@ -148,8 +147,7 @@ int mi_knn_get_groups(mi_knn* t, const uint64_t* ids, uint64_t n, uint32_t* grou
         if (!groups) fail(MI_ERR_INVALID, "groups is null");
         std::lock_guard<std::mutex> l(t->mu);
         const std::vector<uint32_t> rows = knn_local_rows(t, ids, n);
-        for (uint64_t i = 0; i < n; ++i)   // rows appended since the last set hold no group
-            groups[i] = rows[(size_t)i] < t->h_groups.size() ? t->h_groups[rows[(size_t)i]] : MI_KNN_NO_GROUP;
+        for (uint64_t i = 0; i < n; ++i) groups[i] = t->d_groups.get(rows[(size_t)i]);   // rows appended since the last set hold no group
     });
 }
 

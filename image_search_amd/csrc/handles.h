@@ -5,7 +5,9 @@
 #include <mutex>
 #include <vector>
 
+#include "columns.h"
 #include "common.h"
+#include "device_mem.h"
 #include "ids.h"
 
 namespace mi {
@@ -124,50 +126,46 @@ struct mi_knn {
     uint64_t base = 0, rows = 0, cap = 0;
     // a shard of a block-cyclic table (mi_knn_sharded): ids = base + ((local / block) * n + rank) * block + local % block
     uint32_t cyc_block = 0, cyc_n = 0, cyc_rank = 0;
-    float* table = nullptr;
+    mi::DevArray<float> table;   // [cap][dim] (`cap` counts rows, table.cap elements)
     hipStream_t stream = nullptr;
     int n_cu = 0;
     // search workspace
-    float* d_q = nullptr;        // [16][dim]
-    uint64_t* d_cand = nullptr;  // per-wave lists
-    uint64_t* d_tmp = nullptr;   // merge level output
-    uint64_t* d_keys = nullptr;  // final keys (k rounded up to 1024 multiples)
-    uint64_t* d_idx = nullptr;
-    float* d_dist = nullptr;
-    size_t cand_keys = 0, tmp_keys = 0, keys_cap = 0, idx_cap = 0, dist_cap = 0;
+    mi::DevArray<float> d_q;        // [16][dim]
+    mi::DevArray<uint64_t> d_cand;  // per-wave lists
+    mi::DevArray<uint64_t> d_tmp;   // merge level output
+    mi::DevArray<uint64_t> d_keys;  // final keys (k rounded up to 1024 multiples)
+    mi::DevArray<uint64_t> d_idx;
+    mi::DevArray<float> d_dist;
     bool select_path = true;       // 64 < k <= 4096 by radix select over all keys (MI_KNN_SELECT=0: the per-wave LDS lists)
-    uint32_t* d_keys32 = nullptr;  // one distance key per row (selection path, 64 < k <= 4096)
-    uint32_t* d_sel = nullptr;     // 6 x 2048 histogram bins + the collect counter
-    size_t keys32_cap = 0, sel_cap = 0;
+    mi::DevArray<uint32_t> d_keys32;  // one distance key per row (selection path, 64 < k <= 4096)
+    mi::DevArray<uint32_t> d_sel;     // 6 x 2048 histogram bins + the collect counter
     // two-stage exact search (mi_knn_set_option "prefilter"): a bf16 copy of the rows + their squared norms, kept up to
     // `mirror_rows` and caught up by the next search; candidate rows / keys of stage 2
     int prefilter = 0;              // 0 off, 1 bf16 mirror, 2 byte mirror
     int coarse_ring = 8;            // rows in flight + 1 per lane group in the byte stage-1 scan (MI_KNN_RING: A/B)
     bool last_prefiltered = false;  // the most recent single-query search went through the two stages
-    uint16_t* d_mirror = nullptr;   // bf16 rows (prefilter 1) or byte rows (prefilter 2: dim bytes per row)
-    float* d_scale8 = nullptr;      // prefilter 2: per-row scale, per-row bound factor, rho of the query in flight
-    float* d_cfac8 = nullptr;
-    float* d_rho8 = nullptr;
-    float* d_g8 = nullptr;          // prefilter 2: per-dimension scale [dim] (+ [dim] accumulators), fixed once the first rows are mirrored
+    // bf16 rows (prefilter 1) or byte rows (prefilter 2: dim bytes per row).  Sized in 16-bit units for both: the byte
+    // mirror of cap rows takes (cap * dim + 1) / 2 of them
+    mi::DevArray<uint16_t> d_mirror;
+    mi::DevArray<float> d_scale8;   // prefilter 2: per-row scale, per-row bound factor, rho of the query in flight
+    mi::DevArray<float> d_cfac8;
+    mi::DevArray<float> d_rho8;
+    mi::DevArray<float> d_g8;       // prefilter 2: per-dimension scale [dim] (+ [dim] accumulators), fixed once the first rows are mirrored
     bool g8_ready = false;
-    size_t scale8_cap = 0, cfac8_cap = 0, rho8_cap = 0, g8_cap = 0;
-    float* d_xx = nullptr;
+    mi::DevArray<float> d_xx;
     bool batch_stage1_mfma = true;  // the shared stage 1 of a group of queries on the matrix pipe (option "batch_stage1")
-    int8_t* d_digits = nullptr;     // [KNN_GROUP_MAX = 16][3][dim]: the queries of a group as three signed 7-bit digits
-    float* d_qs = nullptr;          // [KNN_GROUP_MAX][4]: {digit scale S, |q|, rho, -}
-    size_t digits_cap = 0, qs_cap = 0;
+    mi::DevArray<int8_t> d_digits;  // [KNN_GROUP_MAX = 16][3][dim]: the queries of a group as three signed 7-bit digits
+    mi::DevArray<float> d_qs;       // [KNN_GROUP_MAX][4]: {digit scale S, |q|, rho, -}
     int pref_sample = 1;            // k <= 64 over the byte mirror: the collect threshold from a sample of the stage-1 keys — 1: for groups of queries, 2: for single queries too, 0: never (option "prefilter_sample")
-    uint32_t* d_skeys = nullptr;    // [queries of a group][sample rows]: the keys of every 8th tile, compact
-    size_t skeys_cap = 0;
+    mi::DevArray<uint32_t> d_skeys; // [queries of a group][sample rows]: the keys of every 8th tile, compact
     uint64_t mirror_rows = 0;
-    size_t mirror_cap = 0, xx_cap = 0;
     uint64_t g8_rows = 0;              // rows the table held when the channel scales were taken (refreshed at 4x)
     // Feedback of the two-stage search, read back asynchronously (a query or two late, never a host block): after two
     // consecutive fallbacks stage 1 is skipped for the next PREF_SKIP single-query searches and then probed again — a corpus the mirror cannot thin out pays the single
     // pass, not stage 1 on top of it ("prefilter_adaptive" = 0 turns this off).
     static constexpr int PREF_RING = 8, PREF_SKIP = 64;
     bool pref_adaptive = true;
-    uint32_t* h_pref_ring = nullptr;   // pinned [PREF_RING][2]: {candidates, fell back}
+    mi::PinnedBuf h_pref_ring;         // uint32_t [PREF_RING][2]: {candidates, fell back}
     hipEvent_t pref_ev[PREF_RING] = {};
     bool pref_ev_pending[PREF_RING] = {};
     uint32_t pref_consec = 0, pref_skip_left = 0;
@@ -176,10 +174,9 @@ struct mi_knn {
     bool pref_probing = false;
     uint32_t pref_probes_left = 0, pref_reports_due = 0;
     uint64_t pref_seq = 0, pref_skipped = 0;
-    uint32_t* d_pref_rows = nullptr;   // [2 * PREF_CAP]: candidate rows, then their exact distance keys
-    uint64_t* d_pref_keys = nullptr;   // [4096]: the k best keys of stage 2
-    uint32_t* d_pref_flag = nullptr;   // {candidate count, fallback, go}
-    size_t pref_rows_cap = 0, pref_keys_cap = 0, pref_flag_cap = 0;
+    mi::DevArray<uint32_t> d_pref_rows;   // [2 * PREF_CAP]: candidate rows, then their exact distance keys
+    mi::DevArray<uint64_t> d_pref_keys;   // [4096]: the k best keys of stage 2
+    mi::DevArray<uint32_t> d_pref_flag;   // {candidate count, fallback, go}
     // Order across caller streams.  `writes`: the last append (a search must see every row counted in
     // `rows`).  `reads`: the last search (searches share the workspace above, and a reallocation of the
     // table must wait for them).  An append only ever writes rows beyond `rows`, so it does not wait
@@ -190,16 +187,14 @@ struct mi_knn {
     // d_dead = the same rows on the device in deletion order (what a two-stage search walks after stage 1).  With `dead`
     // empty every search runs the code that ran before deletions existed.
     std::vector<uint32_t> dead;
-    uint64_t* d_tomb = nullptr;
-    uint32_t* d_dead = nullptr;
-    size_t tomb_words = 0, dead_cap = 0;
+    mi::DevArray<uint64_t> d_tomb;
+    mi::DevArray<uint32_t> d_dead;
     // Filtered search (mi_knn_search_filtered): the filter's live local rows, ascending — n_flist of them in pinned host
     // memory, what the upload reads (kept until the next filtered search: every filtered entry point waits for its results),
     // and the device copy.
-    uint32_t* h_flist = nullptr;
-    size_t n_flist = 0, h_flist_cap = 0;
-    uint32_t* d_flist = nullptr;
-    size_t flist_cap = 0;
+    mi::PinnedBuf h_flist{hipHostMallocPortable};   // uint32_t rows
+    size_t n_flist = 0;
+    mi::DevArray<uint32_t> d_flist;
     // Threshold self-join (mi_knn_near_pairs, join.hip): candidate pairs one strip of stage 1 may hand to stage 2 (option
     // "join_cap"; its buffers live for the call only), and {candidates, pairs, strips, tiles} of the last call.
     uint32_t join_cap = 1u << 22;
@@ -247,39 +242,32 @@ struct mi_knn {
     // mi_knn_search_page (page.hip): workgroups of its scan (option "page_blocks": 0 = the single pass's grid)
     int page_blocks = 0;
     // The group column (grouped.hip): one group id per row of capacity, MI_KNN_NO_GROUP = none.  d_groups exists from the first
-    // mi_knn_set_groups on (sized by `cap`, carried over by grow(), the rows it gains hold no group); h_groups = the same on the
+    // mi_knn_set_groups on (sized by `cap`, carried over by grow(), the rows it gains hold no group); d_groups.host = the same on the
     // host for the rows it has been told about (what get_groups, groups_info and a rebalance read).  n_groups = 1 + the largest
     // group id ever set, n_grouped = rows that hold one; groups_epoch counts the set calls (the index tells from it whether the
     // column still holds what it uploaded).
-    uint32_t* d_groups = nullptr;
-    size_t groups_cap = 0;
-    std::vector<uint32_t> h_groups;
+    mi::RowColumn<uint32_t> d_groups{0xFF};
     uint32_t n_groups = 0;
     uint64_t n_grouped = 0, groups_epoch = 0;
-    // mi_knn_search_grouped: the slot arrays best [n_groups] u64 | cnt [n_groups] u32 (gslots_cap in 32-bit words) — after a
+    // mi_knn_search_grouped: the slot arrays best [n_groups] u64 | cnt [n_groups] u32 (d_gslots in 32-bit words) — after a
     // search they hold that search's values (gslots_valid; gslots_groups = its n_groups) for knn_grouped_members; d_gwin = the
     // groups asked there and their counts; workgroups of the reduce and mark passes (option "group_blocks": 0 = four per CU)
     // and the largest n_groups that takes the block-private LDS form of the reduce (option "group_lds_max")
-    uint32_t* d_gslots = nullptr;
-    uint32_t* d_gwin = nullptr;
-    size_t gslots_cap = 0, gwin_cap = 0;
+    mi::DevArray<uint32_t> d_gslots;
+    mi::DevArray<uint32_t> d_gwin;
     bool gslots_valid = false;
     uint32_t gslots_groups = 0;
     int group_blocks = 0, group_lds_max = 4096;
     // The attribute columns (where.hip): 64 flags (`tags`) and one ordered value (`stamp`) per row of capacity, both 0 by
     // default.  They exist from the first mi_knn_set_attrs on (sized by `cap`, carried over by grow(), the rows they gain hold
-    // the defaults); h_tags / h_stamps = the same on the host for the rows they have been told about (what get_attrs and a
+    // the defaults); their .host = the same on the host for the rows they have been told about (what get_attrs and a
     // rebalance read).  A table that never set attributes allocates nothing and matches as if every row held the defaults.
-    uint64_t* d_tags = nullptr;
-    int64_t* d_stamps = nullptr;
-    size_t attrs_cap = 0;
-    std::vector<uint64_t> h_tags;
-    std::vector<int64_t> h_stamps;
+    mi::RowColumn<uint64_t> d_tags{0};
+    mi::RowColumn<int64_t> d_stamps{0};
     // mi_knn_search_where and its kin: [0, 2) the total (one 64-bit word), [2, 2 + chunks) the chunk counts, then offsets, of
     // the predicate passes; the pinned word the total is copied to; rows per workgroup (option "where_chunk": 0 = 4096)
-    uint32_t* d_wcounts = nullptr;
-    size_t wcounts_cap = 0;
-    uint64_t* h_wtotal = nullptr;
+    mi::DevArray<uint32_t> d_wcounts;
+    mi::PinnedBuf h_wtotal;
     int where_chunk = 0;
     // mi_knn_compact (compact.hip): destination rows of one chunk of the in-place move (option "compact_chunk_rows": 0 = what a
     // 64 MiB staging buffer holds), and {rows removed, rows moved, chunks gathered in place, chunks staged} of the last call
@@ -304,17 +292,6 @@ struct DevBuf {
         cap = b;
     }
 };
-struct PinnedBuf2 {
-    void* p = nullptr;
-    size_t cap = 0;
-    void reserve(size_t b) {
-        if (b <= cap) return;
-        if (p) HIP_CHECK(hipHostFree(p));
-        p = nullptr; cap = 0;
-        HIP_CHECK(hipHostMalloc(&p, b, hipHostMallocPortable));  // read and written by streams of several devices
-        cap = b;
-    }
-};
 // one search in flight on a sharded table: per-shard query / result buffers, the gathered lists and the merged result
 // on the first shard's device, pinned copies for the host, and where the caller wants them
 struct ShardedSlot {
@@ -322,7 +299,7 @@ struct ShardedSlot {
     std::vector<DevBuf> d_q, d_rec;           // [shard]
     std::vector<DevBuf> g_rec;                // [shard] (RCCL receive side: n records) or [0] only (copy transport)
     DevBuf m_rec;                             // merged record, on shard 0's device
-    PinnedBuf2 h_q, h_rec;
+    PinnedBuf h_q{hipHostMallocPortable}, h_rec{hipHostMallocPortable};   // read and written by streams of several devices
     std::vector<hipEvent_t> ev;               // [shard]: list of shard s is in place
     hipEvent_t done = nullptr;
     uint32_t nq = 0, k = 0;
@@ -378,7 +355,6 @@ void knn_truncate(mi_knn* t, uint64_t rows);        // forget the rows behind `r
 void knn_search_filtered_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, const uint64_t* ids, uint64_t n_ids,
                               uint64_t* d_idx, float* d_dist, hipStream_t s);   // t->mu held, device selected
 // for the calls that run a scan of their own through the search's selection (compound.hip); t->mu held, device selected
-void knn_reserve(mi_knn* t, void** p, size_t* have, size_t want, size_t elem);   // a workspace buffer of the handle holds `want` elements (may wait for searches in flight)
 void knn_filter_rows(mi_knn* t, const uint64_t* ids, uint64_t n_ids);            // ids -> t->h_flist / n_flist: live local rows, ascending, once each; MI_ERR_INVALID for an id that is not a row
 void knn_filter_upload(mi_knn* t, hipStream_t s);                                // ... -> t->d_flist
 // nq queries (contiguous at d_q) over the list in t->d_flist / n_flist (knn_filter_upload's or knn_filter_where's), on s

@@ -8,8 +8,10 @@
 #include <unistd.h>
 
 #include <iterator>
+#include <memory>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "common.h"
@@ -23,27 +25,6 @@ namespace {
 
 constexpr int MAX_BATCH_Q = 8;
 
-void ensure(mi_knn* t, void** p, size_t* have, size_t want, size_t elem) {
-    if (*have >= want) return;
-    t->reads.sync();  // a search still in flight uses the buffer freed here
-    if (*p) HIP_CHECK(hipFree(*p));
-    *p = nullptr; *have = 0;
-    HIP_CHECK(hipMalloc(p, want * elem));
-    *have = want;
-}
-
-// as ensure(), keeping the first `keep` elements (a mirror that grows with the table must not be rebuilt from the fp32 rows)
-void ensure_keep(mi_knn* t, void** p, size_t* have, size_t want, size_t elem, size_t keep) {
-    if (*have >= want) return;
-    t->reads.sync();
-    void* np_ = nullptr;
-    HIP_CHECK(hipMalloc(&np_, want * elem));
-    if (*p && keep) HIP_CHECK(hipMemcpy(np_, *p, std::min(keep, *have) * elem, hipMemcpyDeviceToDevice));
-    if (*p) HIP_CHECK(hipFree(*p));
-    *p = np_;
-    *have = want;
-}
-
 // the handle's own stream, created on first use (an idle stream still takes one of the four
 // hardware queues HIP multiplexes streams onto)
 hipStream_t own_stream(mi_knn* t) {
@@ -55,24 +36,28 @@ hipStream_t own_stream(mi_knn* t) {
 // the bitmap the kernels consult, or nullptr: a table without deletions runs the kernels it ran before they existed
 const uint64_t* tomb_of(const mi_knn* t) { return t->dead.empty() ? nullptr : t->d_tomb; }
 
-// the bitmap covers `cap` rows (the words it gains are zero); nothing in flight may use the old one
-void tomb_fit(mi_knn* t) {
-    const size_t want = (size_t)((t->cap + 63) / 64);
-    if (t->tomb_words >= want && t->d_tomb) return;
+// Arrays that keep one element (or bit) per row of capacity cover n elements: the elements they gain hold the byte `fill`, the
+// old contents are carried over.  Nothing in flight may use the old arrays.  Every new array is allocated before an old one
+// is replaced, so a failed allocation (MI_ERR_OOM) leaves the handle as it was.
+template <class... T>
+void fit(mi_knn* t, size_t n, int fill, DevArray<T>&... a) {
+    if (((a.p && a.cap >= n) && ...)) return;
     t->writes.sync();
     t->reads.sync();
-    uint64_t* nb = nullptr;
-    HIP_CHECK(hipMalloc((void**)&nb, std::max<size_t>(want, 1) * sizeof(uint64_t)));
-    // the fill and the carry-over copy on the handle's own stream, and waited for (groups_fit: the bits set on that stream
-    // next must not be overtaken by a fill on the null stream)
-    hipStream_t s = own_stream(t);
-    HIP_CHECK(hipMemsetAsync(nb, 0, std::max<size_t>(want, 1) * sizeof(uint64_t), s));
-    if (t->d_tomb) HIP_CHECK(hipMemcpyAsync(nb, t->d_tomb, t->tomb_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (t->d_tomb) HIP_CHECK(hipFree(t->d_tomb));
-    t->d_tomb = nb;
-    t->tomb_words = std::max<size_t>(want, 1);
+    std::tuple<DevArray<T>...> grown;
+    std::apply([&](auto&... g) {
+        (g.alloc(n), ...);
+        // the fills and the carry-over copies on the handle's own stream, and waited for: that stream does not order itself
+        // behind the null stream, and what is enqueued on it next (an upload, the bits of a deletion) must not be overtaken
+        hipStream_t s = own_stream(t);
+        (HIP_CHECK(hipMemsetAsync(g.p, fill, n * sizeof(*g.p), s)), ...);
+        ((a.p ? HIP_CHECK(hipMemcpyAsync(g.p, a.p, a.cap * sizeof(*g.p), hipMemcpyDeviceToDevice, s)) : (void)0), ...);
+        HIP_CHECK(hipStreamSynchronize(s));
+        (a.swap(g), ...);
+    }, grown);
 }
+// the deletion bitmap: one bit per row of capacity, the words it gains are zero
+void tomb_fit(mi_knn* t) { fit(t, std::max<size_t>((size_t)((t->cap + 63) / 64), 1), 0, t->d_tomb); }
 
 // `rows` (sorted, none deleted yet) join the deleted rows: device list and bitmap on `s`, then the host list
 void tomb_add(mi_knn* t, const std::vector<uint32_t>& rows, hipStream_t s) {
@@ -81,11 +66,11 @@ void tomb_add(mi_knn* t, const std::vector<uint32_t>& rows, hipStream_t s) {
     const size_t have = t->dead.size();
     // (grown geometrically: a caller that deletes one row per call must not copy the whole list each time)
     const size_t want = have + rows.size();
-    ensure_keep(t, (void**)&t->d_dead, &t->dead_cap, want > t->dead_cap ? std::max(want, 2 * t->dead_cap) : want, sizeof(uint32_t), have);
+    t->d_dead.reserve_keep(t->reads, want > t->d_dead.cap ? std::max(want, 2 * t->d_dead.cap) : want, have);
     HIP_CHECK(hipMemcpyAsync(t->d_dead + have, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     const uint32_t n = (uint32_t)rows.size();
     hipLaunchKernelGGL(knn_tomb_set_kernel, dim3(std::max(1u, std::min<uint32_t>((n + 255) / 256, (uint32_t)t->n_cu * 4))), dim3(256), 0, s,
-                       t->d_dead + have, n, (unsigned long long*)t->d_tomb);
+                       t->d_dead + have, n, (unsigned long long*)t->d_tomb.p);
     HIP_CHECK(hipGetLastError());
     std::vector<uint32_t> merged(have + rows.size());
     std::merge(t->dead.begin(), t->dead.end(), rows.begin(), rows.end(), merged.begin());
@@ -98,60 +83,11 @@ void tomb_rebuild(mi_knn* t) {
     tomb_fit(t);
     t->writes.sync();
     t->reads.sync();
-    HIP_CHECK(hipMemsetAsync(t->d_tomb, 0, t->tomb_words * sizeof(uint64_t), own_stream(t)));   // (the stream the bits are set on)
+    HIP_CHECK(hipMemsetAsync(t->d_tomb, 0, t->d_tomb.cap * sizeof(uint64_t), own_stream(t)));   // (the stream the bits are set on)
     std::vector<uint32_t> rows;
     rows.swap(t->dead);
     tomb_add(t, rows, own_stream(t));
     HIP_CHECK(hipStreamSynchronize(t->stream));
-}
-
-// ---- the group column (handles.h: d_groups; grouped.hip) ---------------------------------------------------------
-// one id per row of capacity, the rows it gains hold MI_KNN_NO_GROUP (all ones); nothing in flight may use the old one
-void groups_fit(mi_knn* t) {
-    const size_t want = std::max<size_t>((size_t)t->cap, 64);
-    if (t->groups_cap >= want && t->d_groups) return;
-    t->writes.sync();
-    t->reads.sync();
-    uint32_t* nb = nullptr;
-    HIP_CHECK(hipMalloc((void**)&nb, want * sizeof(uint32_t)));
-    // on the handle's own stream, and waited for: that stream does not order itself behind the null stream, and an upload
-    // enqueued on it next must not be overtaken by this fill
-    hipStream_t s = own_stream(t);
-    HIP_CHECK(hipMemsetAsync(nb, 0xFF, want * sizeof(uint32_t), s));
-    if (t->d_groups) HIP_CHECK(hipMemcpyAsync(nb, t->d_groups, t->groups_cap * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (t->d_groups) HIP_CHECK(hipFree(t->d_groups));
-    t->d_groups = nb;
-    t->groups_cap = want;
-}
-
-// ---- the attribute columns (handles.h: d_tags, d_stamps; where.hip) -----------------------------------------------
-// 64 flags and one ordered value per row of capacity, the rows they gain hold 0 / 0; nothing in flight may use the old ones
-void attrs_fit(mi_knn* t) {
-    const size_t want = std::max<size_t>((size_t)t->cap, 64);
-    if (t->attrs_cap >= want && t->d_tags && t->d_stamps) return;
-    t->writes.sync();
-    t->reads.sync();
-    uint64_t* nt = nullptr;
-    int64_t* ns = nullptr;
-    HIP_CHECK(hipMalloc((void**)&nt, want * sizeof(uint64_t)));
-    if (hipMalloc((void**)&ns, want * sizeof(int64_t)) != hipSuccess) {
-        (void)hipFree(nt);
-        fail(MI_ERR_OOM, "no device memory for the attribute columns of %zu rows", want);
-    }
-    // fills and carry-over copies on the handle's own stream, and waited for (groups_fit: an upload enqueued on that stream
-    // next must not be overtaken by a fill on the null stream)
-    hipStream_t s = own_stream(t);
-    HIP_CHECK(hipMemsetAsync(nt, 0, want * sizeof(uint64_t), s));
-    HIP_CHECK(hipMemsetAsync(ns, 0, want * sizeof(int64_t), s));
-    if (t->d_tags) HIP_CHECK(hipMemcpyAsync(nt, t->d_tags, t->attrs_cap * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-    if (t->d_stamps) HIP_CHECK(hipMemcpyAsync(ns, t->d_stamps, t->attrs_cap * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (t->d_tags) HIP_CHECK(hipFree(t->d_tags));
-    if (t->d_stamps) HIP_CHECK(hipFree(t->d_stamps));
-    t->d_tags = nt;
-    t->d_stamps = ns;
-    t->attrs_cap = want;
 }
 
 void grow(mi_knn* t, uint64_t want_rows) {
@@ -163,18 +99,19 @@ void grow(mi_knn* t, uint64_t want_rows) {
     // the table moves: everything enqueued against the old allocation must have finished
     t->writes.sync();
     t->reads.sync();
-    float* nt = nullptr;
-    HIP_CHECK(hipMalloc((void**)&nt, ncap * t->dim * sizeof(float)));
-    if (t->rows) {
-        HIP_CHECK(hipMemcpyAsync(nt, t->table, t->rows * t->dim * sizeof(float), hipMemcpyDeviceToDevice, own_stream(t)));
-        HIP_CHECK(hipStreamSynchronize(t->stream));
+    {
+        DevArray<float> nt;
+        nt.alloc(ncap * t->dim);
+        if (t->rows) {
+            HIP_CHECK(hipMemcpyAsync(nt, t->table, t->rows * t->dim * sizeof(float), hipMemcpyDeviceToDevice, own_stream(t)));
+            HIP_CHECK(hipStreamSynchronize(t->stream));
+        }
+        t->table.swap(nt);   // the old rows are freed here, before the columns grow
     }
-    if (t->table) HIP_CHECK(hipFree(t->table));
-    t->table = nt;
     t->cap = ncap;
     if (t->d_tomb) tomb_fit(t);  // the deletion bitmap keeps one bit per row of capacity
-    if (t->d_groups) groups_fit(t);  // the group column one id
-    if (t->d_tags) attrs_fit(t);     // the attribute columns one word each
+    if (t->d_groups) knn_groups_fit(t);  // the group column one id
+    if (t->d_tags) knn_attrs_fit(t);     // the attribute columns one word each
 }
 
 template <class K>
@@ -236,7 +173,7 @@ void one_pass(mi_knn* t, const float* d_q, uint32_t kp, const uint64_t* lo, uint
     uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)t->n_cu * bpc, (n_tiles + 3) / 4);
     blocks = std::max(blocks, 1u);
     const uint32_t lists = blocks * 4;
-    ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)lists * kp * gy, sizeof(uint64_t));
+    t->d_cand.reserve(t->reads, (size_t)lists * kp * gy);
     qg.lists = (uint64_t)lists * kp;
     launch_scan<Top>(t, d_q, kp, lo, t->d_cand, blocks, s, run_if, gy, qg);
     reduce_wave_lists<Top>(t, lists, kp, keys_out, s, run_if, gy, qg);
@@ -249,7 +186,7 @@ void reduce_wave_lists(mi_knn* t, uint32_t lists, uint32_t kp, uint64_t* keys_ou
     if constexpr (Top::LDS_KEYS != 0) {
         // k > 64: block-cooperative tree, 16 lists per block per level, ping-pong between d_tmp halves
         constexpr uint32_t LPB = 16;
-        ensure(t, (void**)&t->d_tmp, &t->tmp_keys, (size_t)2 * ((lists + LPB - 1) / LPB) * kp, sizeof(uint64_t));
+        t->d_tmp.reserve(t->reads, (size_t)2 * ((lists + LPB - 1) / LPB) * kp);
         const uint64_t* in = t->d_cand;
         uint32_t n = lists, lvl = 0;
         while (true) {
@@ -267,7 +204,7 @@ void reduce_wave_lists(mi_knn* t, uint32_t lists, uint32_t kp, uint64_t* keys_ou
         launch_merge<Top>(t->d_cand, lists, kp, lists, keys_out, gy, qg.lists, qg.out, s, run_if, qg.flags);
     } else {
         const uint32_t lpb = 32, mid = (lists + lpb - 1) / lpb;
-        ensure(t, (void**)&t->d_tmp, &t->tmp_keys, (size_t)mid * kp * gy, sizeof(uint64_t));
+        t->d_tmp.reserve(t->reads, (size_t)mid * kp * gy);
         launch_merge<Top>(t->d_cand, lists, kp, lpb, t->d_tmp, gy, qg.lists, (size_t)mid * kp, s, run_if, qg.flags);
         launch_merge<Top>(t->d_tmp, mid, kp, mid, keys_out, gy, (size_t)mid * kp, qg.out, s, run_if, qg.flags);
     }
@@ -342,12 +279,12 @@ QGroup group_of(const mi_knn* t, uint32_t gy) {
 uint32_t* prefilter_pass(mi_knn* t, const float* d_q, uint32_t k, hipStream_t s, uint32_t nq_batch = 0) {
     const uint32_t gy = std::max(1u, nq_batch);
     const QGroup qg = group_of(t, gy);
-    ensure(t, (void**)&t->d_keys32, &t->keys32_cap, (size_t)t->cap * gy, sizeof(uint32_t));
-    ensure(t, (void**)&t->d_sel, &t->sel_cap, (size_t)SEL_WORDS * gy, sizeof(uint32_t));
-    ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)4096 * gy, sizeof(uint64_t));
-    ensure(t, (void**)&t->d_pref_rows, &t->pref_rows_cap, (size_t)2 * PREF_CAP * gy, sizeof(uint32_t));  // rows, then their exact keys
-    ensure(t, (void**)&t->d_pref_keys, &t->pref_keys_cap, (size_t)4096 * gy, sizeof(uint64_t));
-    ensure(t, (void**)&t->d_pref_flag, &t->pref_flag_cap, (size_t)4 * gy, sizeof(uint32_t));
+    t->d_keys32.reserve(t->reads, (size_t)t->cap * gy);
+    t->d_sel.reserve(t->reads, (size_t)SEL_WORDS * gy);
+    t->d_cand.reserve(t->reads, (size_t)4096 * gy);
+    t->d_pref_rows.reserve(t->reads, (size_t)2 * PREF_CAP * gy);  // rows, then their exact keys
+    t->d_pref_keys.reserve(t->reads, (size_t)4096 * gy);
+    t->d_pref_flag.reserve(t->reads, (size_t)4 * gy);
     const bool bytes = t->prefilter == 2;
     // The threshold from a SAMPLE of the keys (byte mirror, k <= 64): stage 1 also writes the keys of every 8th tile compactly,
     // the three histogram passes read that eighth, and the collect pass filters ALL keys against the sample's k-th smallest
@@ -364,7 +301,7 @@ uint32_t* prefilter_pass(mi_knn* t, const float* d_q, uint32_t k, hipStream_t s,
     // sized by the table's CAPACITY, not its rows: a table that grows by a chunk per step (the pipeline) must not reallocate
     // the sample — and wait for the searches in flight — every other query
     const uint64_t sample_stride = sample_shift ? ((((t->cap + tile_rows - 1) / tile_rows + (1u << sample_shift) - 1) >> sample_shift) * tile_rows + 63) / 64 * 64 : 0;
-    if (sample_shift) ensure(t, (void**)&t->d_skeys, &t->skeys_cap, (size_t)sample_stride * gy, sizeof(uint32_t));
+    if (sample_shift) t->d_skeys.reserve(t->reads, (size_t)sample_stride * gy);
     const size_t mirror_elems = bytes ? ((size_t)t->cap * t->dim + 1) / 2 : (size_t)t->cap * t->dim;  // in uint16 units
     t->mirror_rows = std::min(t->mirror_rows, t->rows);
     if (bytes && t->g8_ready && t->rows >= 4 * std::max<uint64_t>(t->g8_rows, 1)) t->g8_ready = false;  // the table has grown 4x since the
@@ -372,15 +309,15 @@ uint32_t* prefilter_pass(mi_knn* t, const float* d_q, uint32_t k, hipStream_t s,
     if (bytes && !t->g8_ready) t->mirror_rows = 0;  // new scales: every byte row changes
     // the table grew past the mirror's allocation: the rows mirrored so far move over, only the new ones are converted
     const size_t keep_m = bytes ? ((size_t)t->mirror_rows * t->dim + 1) / 2 : (size_t)t->mirror_rows * t->dim;
-    ensure_keep(t, (void**)&t->d_mirror, &t->mirror_cap, mirror_elems, sizeof(uint16_t), keep_m);
-    ensure_keep(t, (void**)&t->d_xx, &t->xx_cap, (size_t)t->cap, sizeof(float), (size_t)t->mirror_rows);
+    t->d_mirror.reserve_keep(t->reads, mirror_elems, keep_m);
+    t->d_xx.reserve_keep(t->reads, (size_t)t->cap, (size_t)t->mirror_rows);
     if (bytes) {
-        ensure_keep(t, (void**)&t->d_scale8, &t->scale8_cap, (size_t)t->cap, sizeof(float), (size_t)t->mirror_rows);
-        ensure_keep(t, (void**)&t->d_cfac8, &t->cfac8_cap, (size_t)t->cap, sizeof(float), (size_t)t->mirror_rows);
-        ensure(t, (void**)&t->d_rho8, &t->rho8_cap, (size_t)KNN_GROUP_MAX, sizeof(float));
-        ensure(t, (void**)&t->d_digits, &t->digits_cap, (size_t)KNN_GROUP_MAX * 3 * t->dim + 64, sizeof(int8_t));   // a group's queries as int8 digits
-        ensure(t, (void**)&t->d_qs, &t->qs_cap, (size_t)KNN_GROUP_MAX * 4, sizeof(float));
-        ensure(t, (void**)&t->d_g8, &t->g8_cap, (size_t)2 * t->dim, sizeof(float));
+        t->d_scale8.reserve_keep(t->reads, (size_t)t->cap, (size_t)t->mirror_rows);
+        t->d_cfac8.reserve_keep(t->reads, (size_t)t->cap, (size_t)t->mirror_rows);
+        t->d_rho8.reserve(t->reads, (size_t)KNN_GROUP_MAX);
+        t->d_digits.reserve(t->reads, (size_t)KNN_GROUP_MAX * 3 * t->dim + 64);   // a group's queries as int8 digits
+        t->d_qs.reserve(t->reads, (size_t)KNN_GROUP_MAX * 4);
+        t->d_g8.reserve(t->reads, (size_t)2 * t->dim);
         if (!t->g8_ready) {  // the channel scales: RMS per dimension over a sample spread over the table (any positive values are correct)
             const uint64_t sample = std::min<uint64_t>(t->rows, 1u << 16), stride = t->rows / sample;
             HIP_CHECK(hipMemsetAsync(t->d_g8 + t->dim, 0, t->dim * sizeof(float), s));
@@ -417,7 +354,7 @@ uint32_t* prefilter_pass(mi_knn* t, const float* d_q, uint32_t k, hipStream_t s,
                            sample_stride, sample_shift, tile_rows);
     };
     if (bytes) {
-        uint8_t* m8 = reinterpret_cast<uint8_t*>(t->d_mirror);
+        uint8_t* m8 = reinterpret_cast<uint8_t*>(t->d_mirror.p);
         const uint32_t* keys_q = t->d_keys32;   // query y: + y * cap (QGroup)
         // what the histogram passes read: every key, or the sample (its own stride between the queries of a group)
         const uint32_t* keys_h = sample_shift ? t->d_skeys : keys_q;
@@ -504,9 +441,9 @@ void select_pass(mi_knn* t, const float* d_q, uint32_t k, uint64_t* keys_out, hi
     const uint64_t n_tiles = (t->rows + 63) / 64;
     uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)t->n_cu * 4, (n_tiles + 3) / 4);
     blocks = std::max(blocks, 1u);
-    ensure(t, (void**)&t->d_keys32, &t->keys32_cap, (size_t)t->cap * gy, sizeof(uint32_t));
-    ensure(t, (void**)&t->d_sel, &t->sel_cap, (size_t)SEL_WORDS * gy, sizeof(uint32_t));
-    ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)4096 * gy, sizeof(uint64_t));
+    t->d_keys32.reserve(t->reads, (size_t)t->cap * gy);
+    t->d_sel.reserve(t->reads, (size_t)SEL_WORDS * gy);
+    t->d_cand.reserve(t->reads, (size_t)4096 * gy);
     HIP_CHECK(hipMemsetAsync(t->d_sel, 0, (size_t)SEL_WORDS * gy * sizeof(uint32_t), s));
     const uint64_t* tomb = tomb_of(t);
     const uint64_t n_dead = t->dead.size();
@@ -568,19 +505,19 @@ void pref_poll(mi_knn* t) {
         if (!t->pref_ev_pending[i]) continue;
         if (hipEventQuery(t->pref_ev[i]) != hipSuccess) { (void)hipGetLastError(); break; }  // keep the order: stop at the first one still in flight
         t->pref_ev_pending[i] = false;
-        pref_fold(t, t->h_pref_ring[2 * i], t->h_pref_ring[2 * i + 1]);
+        pref_fold(t, t->h_pref_ring.as<uint32_t>()[2 * i], t->h_pref_ring.as<uint32_t>()[2 * i + 1]);
     }
 }
 // behind a two-stage search on `s`: {candidates, fell back} -> pinned memory, an event to say when
 void pref_record(mi_knn* t, hipStream_t s) {
-    if (!t->h_pref_ring) HIP_CHECK(hipHostMalloc((void**)&t->h_pref_ring, (size_t)mi_knn::PREF_RING * 2 * sizeof(uint32_t), hipHostMallocDefault));
+    t->h_pref_ring.reserve((size_t)mi_knn::PREF_RING * 2 * sizeof(uint32_t));
     const int i = (int)(t->pref_seq % mi_knn::PREF_RING);
     if (t->pref_ev_pending[i]) {  // eight readbacks still in flight: this query goes unreported rather than waited for
         if (t->pref_probing && t->pref_reports_due && --t->pref_reports_due == 0) t->pref_probing = false;
         return;
     }
     if (!t->pref_ev[i]) HIP_CHECK(hipEventCreateWithFlags(&t->pref_ev[i], hipEventDisableTiming));
-    HIP_CHECK(hipMemcpyAsync(t->h_pref_ring + 2 * i, t->d_pref_flag, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(t->h_pref_ring.as<uint32_t>() + 2 * i, t->d_pref_flag, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipEventRecord(t->pref_ev[i], s));
     t->pref_ev_pending[i] = true;
     ++t->pref_seq;
@@ -607,11 +544,11 @@ void two_stage(mi_knn* t, const float* d_q, uint32_t k, uint64_t* d_idx, float* 
     const uint32_t gy = std::max(1u, nq_batch);
     const QGroup qg = group_of(t, gy);
     // every workspace of this search at its final size BEFORE the first launch: growing one later would free a buffer
-    // that kernels already queued on `s` still use (ensure() only waits for EARLIER searches)
+    // that kernels already queued on `s` still use (reserve() only waits for EARLIER searches)
     if (k <= 64) {
         const uint32_t lists = reg_pass_lists(t);
-        ensure(t, (void**)&t->d_cand, &t->cand_keys, std::max<size_t>((size_t)4096 * gy, (size_t)lists * k * gy), sizeof(uint64_t));
-        if (lists > 64) ensure(t, (void**)&t->d_tmp, &t->tmp_keys, (size_t)((lists + 31) / 32) * k * gy, sizeof(uint64_t));
+        t->d_cand.reserve(t->reads, std::max<size_t>((size_t)4096 * gy, (size_t)lists * k * gy));
+        if (lists > 64) t->d_tmp.reserve(t->reads, (size_t)((lists + 31) / 32) * k * gy);
     }
     const uint32_t* fallback = prefilter_pass(t, d_q, k, s, nq_batch);
     // the single pass, every kernel of it returning at once unless the query's fallback word is set
@@ -647,7 +584,7 @@ bool batched_two_stage_applies(mi_knn* t, uint32_t k) {
     return true;
 }
 void search_batched_two_stage(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
-    ensure(t, (void**)&t->d_keys, &t->keys_cap, (size_t)4096 * nq, sizeof(uint64_t));
+    t->d_keys.reserve(t->reads, (size_t)4096 * nq);
     t->last_prefiltered = true;
     two_stage(t, d_q, k, d_idx, d_dist, s, nq);
     if (t->pref_adaptive) pref_record(t, s);   // the group's first query speaks for it (d_pref_flag[0..1])
@@ -661,7 +598,7 @@ void search_one(mi_knn* t, const float* d_q, uint32_t k, uint64_t* d_idx, float*
         return;
     }
     const uint32_t passes = (k + 1023) / 1024;
-    ensure(t, (void**)&t->d_keys, &t->keys_cap, (size_t)std::max<uint32_t>(passes * 1024, 4096), sizeof(uint64_t));
+    t->d_keys.reserve(t->reads, (size_t)std::max<uint32_t>(passes * 1024, 4096));
     t->last_prefiltered = prefilter_applies(t, k);
     if (t->last_prefiltered && t->pref_adaptive) {
         pref_poll(t);
@@ -724,8 +661,8 @@ void search_batched(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint64
     uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)t->n_cu * 2, (n_tiles + 3) / 4);
     blocks = std::max(blocks, 1u);
     const uint32_t lists = blocks * 4;
-    ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)nq * lists * k, sizeof(uint64_t));
-    ensure(t, (void**)&t->d_keys, &t->keys_cap, (size_t)std::max<uint32_t>(1024, nq * k), sizeof(uint64_t));
+    t->d_cand.reserve(t->reads, (size_t)nq * lists * k);
+    t->d_keys.reserve(t->reads, (size_t)std::max<uint32_t>(1024, nq * k));
     if (nq == 2) launch_batched<2>(t, d_q, k, t->d_cand, blocks, s);
     else if (nq == 4) launch_batched<4>(t, d_q, k, t->d_cand, blocks, s);
     else launch_batched<8>(t, d_q, k, t->d_cand, blocks, s);
@@ -734,7 +671,7 @@ void search_batched(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint64
         launch_merge<WaveTopReg>(t->d_cand, lists, k, lists, t->d_keys, nq, cstride, k, s);
     } else {
         const uint32_t lpb = 32, mid = (lists + lpb - 1) / lpb;
-        ensure(t, (void**)&t->d_tmp, &t->tmp_keys, (size_t)nq * mid * k, sizeof(uint64_t));
+        t->d_tmp.reserve(t->reads, (size_t)nq * mid * k);
         launch_merge<WaveTopReg>(t->d_cand, lists, k, lpb, t->d_tmp, nq, cstride, (size_t)mid * k, s);
         launch_merge<WaveTopReg>(t->d_tmp, mid, k, mid, t->d_keys, nq, (size_t)mid * k, k, s);
     }
@@ -775,15 +712,8 @@ constexpr uint32_t FILTER_K_MAX = 4096;
 // room for `want` rows in the pinned host list (its old contents are not kept; nothing in flight reads it: every filtered
 // entry point has waited for its results before it returned)
 uint32_t* flist_reserve(mi_knn* t, size_t want) {
-    if (want > t->h_flist_cap) {
-        if (t->h_flist) HIP_CHECK(hipHostFree(t->h_flist));
-        t->h_flist = nullptr;
-        t->h_flist_cap = 0;
-        const size_t cap = std::max(want, (size_t)4096);
-        HIP_CHECK(hipHostMalloc((void**)&t->h_flist, cap * sizeof(uint32_t), hipHostMallocPortable));
-        t->h_flist_cap = cap;
-    }
-    return t->h_flist;
+    t->h_flist.reserve(std::max(want, (size_t)4096) * sizeof(uint32_t));
+    return t->h_flist.as<uint32_t>();
 }
 
 // ids -> t->h_flist [0, n_flist): the local rows they name, ascending, once each, deleted rows left out; MI_ERR_INVALID (and
@@ -822,7 +752,7 @@ uint32_t gather_blocks(const mi_knn* t, uint32_t n, uint32_t bpc) {
 template <class Top>
 void gather_lists(mi_knn* t, const float* d_q, uint32_t n, uint32_t kp, uint64_t* keys_out, hipStream_t s) {
     const uint32_t blocks = gather_blocks(t, n, Top::LDS_KEYS == 0 ? 4 : (Top::KP <= 256 ? 4 : 2)), lists = blocks * 4;
-    ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)lists * kp, sizeof(uint64_t));
+    t->d_cand.reserve(t->reads, (size_t)lists * kp);
     const size_t lds = (size_t)4 * Top::LDS_KEYS * sizeof(uint64_t);
     switch (t->dim / 64) {
 #define MI_CASE(NCH)                                                                                                    \
@@ -858,9 +788,9 @@ void select_keys32(mi_knn* t, uint64_t n, uint32_t k, uint64_t* keys_out, const 
 // the k <= 4096 smallest keys of the n entries, ascending, into keys_out: one distance key per entry, the radix select over
 // (key, position), then positions back to rows
 void gather_select(mi_knn* t, const float* d_q, uint32_t n, uint32_t k, uint64_t* keys_out, hipStream_t s) {
-    ensure(t, (void**)&t->d_keys32, &t->keys32_cap, (size_t)n, sizeof(uint32_t));
-    ensure(t, (void**)&t->d_sel, &t->sel_cap, (size_t)SEL_WORDS, sizeof(uint32_t));
-    ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)4096, sizeof(uint64_t));
+    t->d_keys32.reserve(t->reads, (size_t)n);
+    t->d_sel.reserve(t->reads, (size_t)SEL_WORDS);
+    t->d_cand.reserve(t->reads, (size_t)4096);
     HIP_CHECK(hipMemsetAsync(t->d_sel, 0, (size_t)SEL_WORDS * sizeof(uint32_t), s));
     const uint32_t blocks = gather_blocks(t, n, 4);
     switch (t->dim / 64) {
@@ -899,7 +829,7 @@ void filtered_one(mi_knn* t, const float* d_q, uint32_t n, uint32_t k, uint64_t*
         HIP_CHECK(hipGetLastError());
         return;
     }
-    ensure(t, (void**)&t->d_keys, &t->keys_cap, (size_t)FILTER_K_MAX, sizeof(uint64_t));
+    t->d_keys.reserve(t->reads, (size_t)FILTER_K_MAX);
     if (!filter_takes_lists(t, n, k)) gather_select(t, d_q, n, k, t->d_keys, s);
     else if (k <= 64) gather_lists<WaveTopReg>(t, d_q, n, k, t->d_keys, s);
     else gather_lists<WaveTopLds<1024>>(t, d_q, n, k, t->d_keys, s);
@@ -911,8 +841,8 @@ void filtered_one(mi_knn* t, const float* d_q, uint32_t n, uint32_t k, uint64_t*
 // nq in {2, 4, 8} queries over one filter, k <= 64, dim 768: one gathered pass (knn_scan_gather_batched_kernel)
 void filtered_batched(mi_knn* t, const float* d_q, uint32_t nq, uint32_t n, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
     const uint32_t blocks = gather_blocks(t, n, 2), lists = blocks * 4;
-    ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)nq * lists * k, sizeof(uint64_t));
-    ensure(t, (void**)&t->d_keys, &t->keys_cap, (size_t)std::max<uint32_t>(FILTER_K_MAX, nq * k), sizeof(uint64_t));
+    t->d_cand.reserve(t->reads, (size_t)nq * lists * k);
+    t->d_keys.reserve(t->reads, (size_t)std::max<uint32_t>(FILTER_K_MAX, nq * k));
     if (nq == 2)
         hipLaunchKernelGGL((knn_scan_gather_batched_kernel<12, 2>), dim3(blocks), dim3(256), 0, s, t->table, t->d_flist, n, d_q, k, t->d_cand);
     else if (nq == 4)
@@ -925,7 +855,7 @@ void filtered_batched(mi_knn* t, const float* d_q, uint32_t nq, uint32_t n, uint
         launch_merge<WaveTopReg>(t->d_cand, lists, k, lists, t->d_keys, nq, cstride, k, s);
     } else {
         const uint32_t lpb = 32, mid = (lists + lpb - 1) / lpb;
-        ensure(t, (void**)&t->d_tmp, &t->tmp_keys, (size_t)nq * mid * k, sizeof(uint64_t));
+        t->d_tmp.reserve(t->reads, (size_t)nq * mid * k);
         launch_merge<WaveTopReg>(t->d_cand, lists, k, lpb, t->d_tmp, nq, cstride, (size_t)mid * k, s);
         launch_merge<WaveTopReg>(t->d_tmp, mid, k, mid, t->d_keys, nq, (size_t)mid * k, k, s);
     }
@@ -938,8 +868,8 @@ void filtered_batched(mi_knn* t, const float* d_q, uint32_t nq, uint32_t n, uint
 void upload_filter(mi_knn* t, hipStream_t s) {
     const size_t n = t->n_flist;
     if (n == 0) return;
-    ensure(t, (void**)&t->d_flist, &t->flist_cap, n, sizeof(uint32_t));
-    HIP_CHECK(hipMemcpyAsync(t->d_flist, t->h_flist, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    t->d_flist.reserve(t->reads, n);
+    HIP_CHECK(hipMemcpyAsync(t->d_flist, t->h_flist.p, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
 }
 
 // nq queries (contiguous at d_q) over the uploaded filter, in groups of 8 / 4 / 2 (k <= 64, dim 768) or one by one
@@ -978,7 +908,6 @@ std::vector<uint32_t> knn_local_rows(const mi_knn* t, const uint64_t* ids, uint6
     return rows;
 }
 hipStream_t knn_own_stream(mi_knn* t) { return own_stream(t); }
-void knn_reserve(mi_knn* t, void** p, size_t* have, size_t want, size_t elem) { ensure(t, p, have, want, elem); }
 void knn_filter_rows(mi_knn* t, const uint64_t* ids, uint64_t n_ids) { filter_rows(t, ids, n_ids); }
 void knn_filter_upload(mi_knn* t, hipStream_t s) { upload_filter(t, s); }
 void knn_filtered_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
@@ -990,8 +919,8 @@ void knn_reduce_lists64(mi_knn* t, uint32_t lists, uint32_t k, uint64_t* keys_ou
     reduce_wave_lists<WaveTopReg>(t, lists, k, keys_out, s, nullptr, 1, qg);
 }
 void knn_select_keys32(mi_knn* t, uint64_t n, uint32_t k, uint64_t* keys_out, const uint32_t* list, hipStream_t s) {
-    ensure(t, (void**)&t->d_sel, &t->sel_cap, (size_t)SEL_WORDS, sizeof(uint32_t));
-    ensure(t, (void**)&t->d_cand, &t->cand_keys, (size_t)4096, sizeof(uint64_t));
+    t->d_sel.reserve(t->reads, (size_t)SEL_WORDS);
+    t->d_cand.reserve(t->reads, (size_t)4096);
     HIP_CHECK(hipMemsetAsync(t->d_sel, 0, (size_t)SEL_WORDS * sizeof(uint32_t), s));
     select_keys32(t, n, k, keys_out, list, s);
 }
@@ -999,8 +928,10 @@ void knn_search_many(mi_knn* t, const float* d_q, uint32_t nq, uint32_t k, uint6
     search_many(t, d_q, nq, k, d_idx, d_dist, s);
 }
 void knn_grow(mi_knn* t, uint64_t want_rows) { grow(t, want_rows); }
-void knn_groups_fit(mi_knn* t) { groups_fit(t); }
-void knn_attrs_fit(mi_knn* t) { attrs_fit(t); }
+// the group column (grouped.hip): one id per row of capacity, the rows it gains hold MI_KNN_NO_GROUP (all ones)
+void knn_groups_fit(mi_knn* t) { fit(t, std::max<size_t>((size_t)t->cap, 64), t->d_groups.fill, t->d_groups); }
+// the attribute columns (where.hip): 64 flags and one ordered value per row of capacity, the rows they gain hold 0 / 0
+void knn_attrs_fit(mi_knn* t) { fit(t, std::max<size_t>((size_t)t->cap, 64), t->d_tags.fill, t->d_tags, t->d_stamps); }
 void knn_search_one(mi_knn* t, const float* d_q, uint32_t k, uint64_t* d_idx, float* d_dist, hipStream_t s) {
     search_one(t, d_q, k, d_idx, d_dist, s);
 }
@@ -1009,27 +940,20 @@ void knn_truncate(mi_knn* t, uint64_t rows) {
     if (rows >= t->rows) return;
     t->rows = rows;
     t->mirror_rows = std::min(t->mirror_rows, rows);
-    // ... and their groups (a later append reuses those rows, without a group)
-    if (t->d_groups && rows < t->groups_cap) {
+    // ... and what their columns held (a later append reuses those rows, without a group and with the default attributes)
+    if (t->d_groups || t->d_tags) {
         DeviceGuard g(t->device);
         t->writes.sync();
         t->reads.sync();
-        HIP_CHECK(hipMemsetAsync(t->d_groups + rows, 0xFF, (t->groups_cap - (size_t)rows) * sizeof(uint32_t), own_stream(t)));
-        HIP_CHECK(hipStreamSynchronize(t->stream));
-        for (size_t r = (size_t)rows; r < t->h_groups.size(); ++r) t->n_grouped -= t->h_groups[r] != MI_KNN_NO_GROUP;
-        if (t->h_groups.size() > rows) t->h_groups.resize((size_t)rows);
-        ++t->groups_epoch;
-    }
-    // ... and their attributes (a later append reuses those rows, with the defaults)
-    if (t->d_tags && rows < t->attrs_cap) {
-        DeviceGuard g(t->device);
-        t->writes.sync();
-        t->reads.sync();
-        HIP_CHECK(hipMemsetAsync(t->d_tags + rows, 0, (t->attrs_cap - (size_t)rows) * sizeof(uint64_t), own_stream(t)));
-        HIP_CHECK(hipMemsetAsync(t->d_stamps + rows, 0, (t->attrs_cap - (size_t)rows) * sizeof(int64_t), t->stream));
-        HIP_CHECK(hipStreamSynchronize(t->stream));
-        if (t->h_tags.size() > rows) t->h_tags.resize((size_t)rows);
-        if (t->h_stamps.size() > rows) t->h_stamps.resize((size_t)rows);
+        if (t->d_groups) {
+            for (size_t r = (size_t)rows; r < t->d_groups.host.size(); ++r) t->n_grouped -= t->d_groups.host[r] != MI_KNN_NO_GROUP;
+            ++t->groups_epoch;
+        }
+        hipStream_t s = own_stream(t);
+        t->d_groups.truncate((size_t)rows, s);
+        t->d_tags.truncate((size_t)rows, s);
+        t->d_stamps.truncate((size_t)rows, s);
+        HIP_CHECK(hipStreamSynchronize(s));
     }
     // the rows beyond are forgotten, their tombstones with them (a later append reuses those rows, live)
     const auto cut = std::lower_bound(t->dead.begin(), t->dead.end(), (uint32_t)std::min<uint64_t>(rows, 0xFFFFFFFFull));
@@ -1059,16 +983,16 @@ int mi_knn_create(uint32_t dim, int device, mi_knn** out) {
         *out = nullptr;
         if (dim == 0 || dim % 64 != 0) fail(MI_ERR_UNSUPPORTED, "dim must be a positive multiple of 64 (got %u)", dim);
         DeviceGuard g(device);
-        auto t = new mi_knn();
+        std::unique_ptr<mi_knn> t(new mi_knn());   // whatever fails below, what it owns by then goes with it
         t->device = device; t->dim = dim;
         hipDeviceProp_t prop;
         HIP_CHECK(hipGetDeviceProperties(&prop, device));
         t->n_cu = prop.multiProcessorCount;
-        HIP_CHECK(hipMalloc((void**)&t->d_q, (size_t)16 * dim * sizeof(float)));
+        t->d_q.alloc((size_t)16 * dim);
         if (const char* e = std::getenv("MI_KNN_SELECT")) t->select_path = std::atoi(e) != 0;  // A/B hook, read at creation
         if (const char* e = std::getenv("MI_KNN_RING")) t->coarse_ring = std::atoi(e) == 8 ? 8 : 4;
         if (const char* e = std::getenv("MI_KNN_BATCH_STAGE1")) t->batch_stage1_mfma = std::atoi(e) != 0;  // A/B hook, read at creation
-        *out = t;
+        *out = t.release();
     });
 }
 
@@ -1079,19 +1003,9 @@ void mi_knn_free(mi_knn* t) {
     t->writes.destroy();
     t->reads.destroy();
     if (t->stream) { (void)hipStreamSynchronize(t->stream); (void)hipStreamDestroy(t->stream); }
-    for (void* p : {(void*)t->table, (void*)t->d_q, (void*)t->d_cand, (void*)t->d_tmp, (void*)t->d_keys,
-                    (void*)t->d_idx, (void*)t->d_dist, (void*)t->d_keys32, (void*)t->d_sel, (void*)t->d_mirror,
-                    (void*)t->d_xx, (void*)t->d_pref_rows, (void*)t->d_pref_keys, (void*)t->d_pref_flag, (void*)t->d_scale8,
-                    (void*)t->d_cfac8, (void*)t->d_rho8, (void*)t->d_g8, (void*)t->d_digits, (void*)t->d_qs, (void*)t->d_skeys, (void*)t->d_tomb, (void*)t->d_dead,
-                    (void*)t->d_flist, (void*)t->d_groups, (void*)t->d_gslots, (void*)t->d_gwin, (void*)t->d_tags, (void*)t->d_stamps,
-                    (void*)t->d_wcounts})
-        if (p) (void)hipFree(p);
     for (hipEvent_t e : t->pref_ev)
         if (e) (void)hipEventDestroy(e);
-    if (t->h_pref_ring) (void)hipHostFree(t->h_pref_ring);
-    if (t->h_flist) (void)hipHostFree(t->h_flist);
-    if (t->h_wtotal) (void)hipHostFree(t->h_wtotal);
-    delete t;
+    delete t;   // the workspace, the columns and the pinned buffers go with their owners
 }
 
 int mi_knn_set_option(mi_knn* t, const char* key, int value) {
@@ -1106,9 +1020,10 @@ int mi_knn_set_option(mi_knn* t, const char* key, int value) {
             if (value != t->prefilter && t->d_mirror) {  // another form (or none): the mirror goes, the next search rebuilds
                 DeviceGuard g(t->device);
                 t->reads.sync();
-                for (void** p : {(void**)&t->d_mirror, (void**)&t->d_xx, (void**)&t->d_scale8, (void**)&t->d_cfac8})
-                    if (*p) { HIP_CHECK(hipFree(*p)); *p = nullptr; }
-                t->mirror_cap = t->xx_cap = t->scale8_cap = t->cfac8_cap = 0;
+                t->d_mirror.release();
+                t->d_xx.release();
+                t->d_scale8.release();
+                t->d_cfac8.release();
                 t->mirror_rows = 0;
                 t->g8_ready = false;
             }
@@ -1378,11 +1293,6 @@ namespace {
 struct KnnFileHeader { char magic[8]; uint32_t dim, reserved; uint64_t rows, base; };
 static_assert(sizeof(KnnFileHeader) == 32, "header layout");
 constexpr size_t IO_CHUNK = 64u << 20;
-struct PinnedBuf {
-    void* p = nullptr;
-    explicit PinnedBuf(size_t b) { HIP_CHECK(hipHostMalloc(&p, b, hipHostMallocDefault)); }
-    ~PinnedBuf() { (void)hipHostFree(p); }
-};
 struct File {
     FILE* f;
     File(const char* path, const char* mode) : f(std::fopen(path, mode)) {}
@@ -1409,11 +1319,11 @@ int mi_knn_save(mi_knn* t, const char* path) {
             if (std::fwrite(&h, sizeof h, 1, f.f) != 1) fail(MI_ERR_IO, "write to %s failed", tmp.c_str());
             const size_t total = (size_t)t->rows * t->dim * sizeof(float);
             if (total) {
-                PinnedBuf buf(std::min(total, IO_CHUNK));
+                PinnedBuf buf(std::min(total, IO_CHUNK), hipHostMallocDefault);
                 t->writes.begin(t->stream);
                 for (size_t off = 0; off < total; off += IO_CHUNK) {
                     const size_t n = std::min(IO_CHUNK, total - off);
-                    HIP_CHECK(hipMemcpyAsync(buf.p, (const char*)t->table + off, n, hipMemcpyDeviceToHost, t->stream));
+                    HIP_CHECK(hipMemcpyAsync(buf.p, (const char*)t->table.p + off, n, hipMemcpyDeviceToHost, t->stream));
                     HIP_CHECK(hipStreamSynchronize(t->stream));
                     if (std::fwrite(buf.p, 1, n, f.f) != n) fail(MI_ERR_IO, "write to %s failed (disk full?)", tmp.c_str());
                 }
@@ -1461,7 +1371,7 @@ int mi_knn_load(mi_knn* t, const char* path) {
         if (total == 0) return;
         if (t->rows + h.rows > 0xFFFFFFFFull) fail(MI_ERR_UNSUPPORTED, "a shard holds at most 2^32-1 rows");
         grow(t, t->rows + h.rows);
-        PinnedBuf buf(std::min(total, IO_CHUNK));
+        PinnedBuf buf(std::min(total, IO_CHUNK), hipHostMallocDefault);
         char* dst = (char*)(t->table + t->rows * t->dim);
         for (size_t off = 0; off < total; off += IO_CHUNK) {
             const size_t n = std::min(IO_CHUNK, total - off);
@@ -1543,8 +1453,8 @@ int mi_knn_search(mi_knn* t, const float* q, uint32_t nq, uint32_t k, uint64_t* 
         // groups of up to 16 queries: one upload, table passes of 8 / 4 / 2 queries where the register
         // path applies (k <= 64; same arithmetic per query as the single-query pass), one readback
         constexpr uint32_t GROUP = 16;
-        ensure(t, (void**)&t->d_idx, &t->idx_cap, (size_t)GROUP * k, sizeof(uint64_t));
-        ensure(t, (void**)&t->d_dist, &t->dist_cap, (size_t)GROUP * k, sizeof(float));
+        t->d_idx.reserve(t->reads, (size_t)GROUP * k);
+        t->d_dist.reserve(t->reads, (size_t)GROUP * k);
         t->writes.begin(t->stream);
         t->reads.begin(t->stream);
         for (uint32_t u0 = 0; u0 < nq; u0 += GROUP) {
@@ -1589,8 +1499,8 @@ int mi_knn_search_filtered(mi_knn* t, const float* q, uint32_t nq, uint32_t k, c
         DeviceGuard g(t->device);
         own_stream(t);
         constexpr uint32_t GROUP = 16;
-        ensure(t, (void**)&t->d_idx, &t->idx_cap, (size_t)GROUP * k, sizeof(uint64_t));
-        ensure(t, (void**)&t->d_dist, &t->dist_cap, (size_t)GROUP * k, sizeof(float));
+        t->d_idx.reserve(t->reads, (size_t)GROUP * k);
+        t->d_dist.reserve(t->reads, (size_t)GROUP * k);
         t->writes.begin(t->stream);
         t->reads.begin(t->stream);
         upload_filter(t, t->stream);

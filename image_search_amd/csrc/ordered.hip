@@ -64,9 +64,9 @@ void knn_search_ordered(mi_knn* t, const float* q, uint32_t k, float max_dist, c
     hipStream_t s = call.s;
     const OrderedRecord rec = ordered_record(k);
     unsigned char* d_rec = scan_record(t, rec.bytes);
-    knn_reserve(t, (void**)&t->d_keys, &t->keys_cap, (size_t)ORDERED_K_MAX * 2, sizeof(uint64_t));   // sorted: hi [4096] | lo [4096]
-    knn_reserve(t, (void**)&t->d_cand, &t->cand_keys, (size_t)ORDERED_K_MAX * 2, sizeof(uint64_t));  // collected: the same
-    knn_reserve(t, (void**)&t->d_sel, &t->sel_cap, ORD_SEL_WORDS, sizeof(uint32_t));
+    t->d_keys.reserve(t->reads, (size_t)ORDERED_K_MAX * 2);   // sorted: hi [4096] | lo [4096]
+    t->d_cand.reserve(t->reads, (size_t)ORDERED_K_MAX * 2);  // collected: the same
+    t->d_sel.reserve(t->reads, ORD_SEL_WORDS);
     uint32_t* keys32 = scan_keys32(t, t->rows);
 
     unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(d_rec + rec.counts);
@@ -85,7 +85,7 @@ void knn_search_ordered(mi_knn* t, const float* q, uint32_t k, float max_dist, c
     uint32_t* c_lo = reinterpret_cast<uint32_t*>(t->d_cand + ORDERED_K_MAX);
     uint64_t* s_hi = t->d_keys;
     uint32_t* s_lo = reinterpret_cast<uint32_t*>(t->d_keys + ORDERED_K_MAX);
-    const long long* d_stamps = reinterpret_cast<const long long*>(t->d_stamps);
+    const long long* d_stamps = reinterpret_cast<const long long*>(t->d_stamps.p);
     // one entry per thread and round; the grid rule (and the option) of the scan in front
     const uint32_t blocks = scan_grid(n, t->n_cu, t->page_blocks, PAGE_BLOCKS_PER_CU);
     for (int p = 0; p < ORD_PASSES; ++p) {
@@ -118,7 +118,7 @@ void knn_stamp_histogram(mi_knn* t, const float* q, float max_dist, const mi_knn
     TableCall call(t);
     hipStream_t s = call.s;
     unsigned char* d_rec = scan_record(t, (bins + 4) * sizeof(uint64_t));                             // hist [bins] | the scan's counts [4]
-    knn_reserve(t, (void**)&t->d_keys, &t->keys_cap, (size_t)ORDERED_K_MAX * 2, sizeof(uint64_t));   // the edges
+    t->d_keys.reserve(t->reads, (size_t)ORDERED_K_MAX * 2);   // the edges
     uint32_t* keys32 = scan_keys32(t, t->rows);
 
     unsigned long long* d_hist = reinterpret_cast<unsigned long long*>(d_rec);
@@ -131,7 +131,7 @@ void knn_stamp_histogram(mi_knn* t, const float* q, float max_dist, const mi_knn
     HIP_CHECK(hipMemcpyAsync(t->d_keys, edges, (size_t)n_edges * sizeof(int64_t), hipMemcpyHostToDevice, s));
     const uint32_t blocks = scan_grid(c.n, t->n_cu, t->page_blocks, PAGE_BLOCKS_PER_CU);
     hipLaunchKernelGGL(ordered_stamp_hist_kernel, dim3(blocks), dim3(256), 0, s, keys32, c.n, c.list,
-                       reinterpret_cast<const long long*>(t->d_stamps), reinterpret_cast<const long long*>(t->d_keys), n_edges, d_hist);
+                       reinterpret_cast<const long long*>(t->d_stamps.p), reinterpret_cast<const long long*>(t->d_keys.p), n_edges, d_hist);
     HIP_CHECK(hipGetLastError());
     // hist is written only on success: the bins come to the host first
     std::memcpy(hist, scan_record_fetch(d_rec, bins * sizeof(uint64_t), s).data(), bins * sizeof(uint64_t));

@@ -4,19 +4,12 @@
 #include <vector>
 
 #include "common.h"
+#include "device_mem.h"
 #include "preprocess_kernels.h"
 
 using namespace mi;
 
 namespace {
-struct DevBuf {
-    void* p = nullptr;
-    explicit DevBuf(size_t bytes) { HIP_CHECK(hipMalloc(&p, bytes ? bytes : 16)); }
-    ~DevBuf() { (void)hipFree(p); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-};
-
 template <bool TO_CHW>
 void run(int device, const uint8_t* src, uint32_t w, uint32_t h, uint32_t nw, uint32_t nh, void* dst) {
     if (!src || !dst) fail(MI_ERR_INVALID, "null buffer");
@@ -24,15 +17,16 @@ void run(int device, const uint8_t* src, uint32_t w, uint32_t h, uint32_t nw, ui
     if (!resize_supported(w, h, nw, nh, &why)) fail(MI_ERR_UNSUPPORTED, "resize %ux%u -> %ux%u: %s", w, h, nw, nh, why);
     DeviceGuard g(device);
     const size_t in_b = (size_t)w * h * 3, out_n = (size_t)nw * nh * 3;
-    DevBuf d_src(in_b), d_tmp((size_t)nh * w * 3 * 4), d_out(out_n * (TO_CHW ? 4 : 1));
+    Scratch scratch;
+    void *d_src = scratch.get(in_b), *d_tmp = scratch.get((size_t)nh * w * 3 * 4), *d_out = scratch.get(out_n * (TO_CHW ? 4 : 1));
     hipStream_t s = nullptr;
     HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
-    HIP_CHECK(hipMemcpyAsync(d_src.p, src, in_b, hipMemcpyHostToDevice, s));
-    resize_catmullrom_launch<TO_CHW>((const uint8_t*)d_src.p, w, h, nw, nh, (float*)d_tmp.p, TO_CHW ? nullptr : (uint8_t*)d_out.p,
-                                     TO_CHW ? (float*)d_out.p : nullptr, s);
+    HIP_CHECK(hipMemcpyAsync(d_src, src, in_b, hipMemcpyHostToDevice, s));
+    resize_catmullrom_launch<TO_CHW>((const uint8_t*)d_src, w, h, nw, nh, (float*)d_tmp, TO_CHW ? nullptr : (uint8_t*)d_out,
+                                     TO_CHW ? (float*)d_out : nullptr, s);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(dst, d_out.p, out_n * (TO_CHW ? 4 : 1), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(dst, d_out, out_n * (TO_CHW ? 4 : 1), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
 }
 }  // namespace

@@ -52,8 +52,8 @@ struct Settle {
 // of the call alone (Scratch) is declared BEFORE the frame, so that it is freed after the stream has gone idle (hipFree finds
 // the memory's device by itself, whichever is selected by then).
 //
-// The handle's workspace is reserved AFTER the frame opens (knn_reserve, knn_select_keys32, knn_filter_where all do).  That is
-// the same as reserving in front of it: knn_reserve touches the order words only when it must grow a buffer, and then waits
+// The handle's workspace is reserved AFTER the frame opens (DevArray::reserve on t->reads; knn_select_keys32 and knn_filter_where do the same).  That is
+// the same as reserving in front of it: reserve touches the order words only when it must grow a buffer, and then waits
 // on the host for the searches in flight (reads.sync) before it frees — the wait the stream has just been given (reads.begin)
 // is then a wait for an event that has fired, and reads.pending is false either way.  Writes never use the workspace.
 struct TableCall {
@@ -107,8 +107,8 @@ inline ScanSet scan_set(mi_knn* t, hipStream_t s, ScanFrom from) {
 // the radix select's half alone: room for one 32-bit key per row or list entry (what knn_select_keys32 reads) and for the k
 // best in t->d_keys
 inline uint32_t* scan_keys32(mi_knn* t, uint64_t n) {
-    knn_reserve(t, (void**)&t->d_keys, &t->keys_cap, (size_t)SCAN_K_MAX, sizeof(uint64_t));
-    knn_reserve(t, (void**)&t->d_keys32, &t->keys32_cap, (size_t)std::max<uint64_t>(n, t->cap), sizeof(uint32_t));
+    t->d_keys.reserve(t->reads, (size_t)SCAN_K_MAX);
+    t->d_keys32.reserve(t->reads, (size_t)std::max<uint64_t>(n, t->cap));
     return t->d_keys32;
 }
 // k <= 64: the scan's waves keep lists of k keys (cand, `lists` of them), reduced by the search's merge tree; above: the scan
@@ -121,8 +121,8 @@ struct ScanSelect {
 };
 inline ScanSelect scan_select_reserve(mi_knn* t, uint64_t n, uint32_t k, uint32_t lists) {
     if (k > 64) return ScanSelect{n, k, lists, nullptr, scan_keys32(t, n)};
-    knn_reserve(t, (void**)&t->d_keys, &t->keys_cap, (size_t)SCAN_K_MAX, sizeof(uint64_t));
-    knn_reserve(t, (void**)&t->d_cand, &t->cand_keys, (size_t)lists * k, sizeof(uint64_t));
+    t->d_keys.reserve(t->reads, (size_t)SCAN_K_MAX);
+    t->d_cand.reserve(t->reads, (size_t)lists * k);
     return ScanSelect{n, k, lists, t->d_cand, nullptr};
 }
 inline void scan_select(mi_knn* t, const ScanSelect& sel, const uint32_t* list, hipStream_t s) {
@@ -132,8 +132,8 @@ inline void scan_select(mi_knn* t, const ScanSelect& sel, const uint32_t* list, 
 
 // ---- the one record a call leaves on the device (in t->d_idx) and copies back in one piece -------------------------------
 inline unsigned char* scan_record(mi_knn* t, size_t bytes) {
-    knn_reserve(t, (void**)&t->d_idx, &t->idx_cap, (bytes + 7) / 8, sizeof(uint64_t));
-    return reinterpret_cast<unsigned char*>(t->d_idx);
+    t->d_idx.reserve(t->reads, (bytes + 7) / 8);
+    return reinterpret_cast<unsigned char*>(t->d_idx.p);
 }
 // its first `bytes` on the host, once everything enqueued on s has run
 inline std::vector<unsigned char> scan_record_fetch(const unsigned char* d_rec, size_t bytes, hipStream_t s) {

@@ -216,8 +216,8 @@ struct SearchMany {
         const uint64_t words = (t->rows + 63) / 64;
         uint64_t* mask = (uint64_t*)scratch.get((size_t)words * sizeof(uint64_t));
         hipLaunchKernelGGL(many_mask_kernel, dim3((uint32_t)((words + 3) / 4)), dim3(256), 0, s, p,
-                           reinterpret_cast<const unsigned long long*>(t->d_tags), reinterpret_cast<const long long*>(t->d_stamps),
-                           t->d_groups, t->dead.empty() ? nullptr : reinterpret_cast<const unsigned long long*>(t->d_tomb), t->rows,
+                           reinterpret_cast<const unsigned long long*>(t->d_tags.p), reinterpret_cast<const long long*>(t->d_stamps.p),
+                           t->d_groups, t->dead.empty() ? nullptr : reinterpret_cast<const unsigned long long*>(t->d_tomb.p), t->rows,
                            rule, x, mask, d_clear);
         HIP_CHECK(hipGetLastError());
         return mask;

@@ -98,8 +98,6 @@ void free_sharded(mi_knn_sharded* t) {
         if (!t->devices.empty()) (void)hipSetDevice(t->devices[0]);
         for (DevBuf* b : {&sl.m_rec})
             if (b->p) (void)hipFree(b->p);
-        for (PinnedBuf2* b : {&sl.h_q, &sl.h_rec})
-            if (b->p) (void)hipHostFree(b->p);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
     for (hipEvent_t e : t->ev_src)
@@ -622,13 +620,7 @@ void redeal(mi_knn_sharded* dst, mi_knn_sharded* src, const std::vector<uint64_t
     };
     // a column by src's global row -> by dst's: the deleted rows' entries leave when the rows did
     auto by_dst_row = [&](auto& col) {
-        if (!drop_dead) return;
-        size_t c = 0, w = 0;
-        for (size_t o = 0; o < col.size(); ++o) {
-            if (c < dead.size() && dead[c] == o) { ++c; continue; }
-            col[w++] = col[o];
-        }
-        col.resize(w);
+        if (drop_dead) compact_column(col, dead);
     };
     try {
         if (!drop_dead) copy_rows(0, src->rows);

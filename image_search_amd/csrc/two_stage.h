@@ -1,6 +1,6 @@
 // two_stage.h — host side shared by the calls whose first stage is the 128 x 128 bf16 tile (tile128.h) and whose second
 // stage rescoring decides in the search's arithmetic: the join, the assign, the multi-label assign and the many-query
-// search.  One call's device memory, the table's mirror for the call, the dispatch over the dims the mirror is built for,
+// search.  The table's mirror for the call, the dispatch over the dims the mirror is built for,
 // and the scheme that redoes a launch whose candidates overflowed the buffer.
 #pragma once
 #include <algorithm>
@@ -15,20 +15,6 @@
 #include "scan_call.h"   // Settle, the frame of a call (TableCall), the dim rule
 
 namespace mi {
-
-// device memory of one call, freed on every way out
-struct Scratch {
-    std::vector<void*> p;
-    void* get(size_t bytes) {
-        void* q = nullptr;
-        HIP_CHECK(hipMalloc(&q, std::max<size_t>(bytes, 16)));
-        p.push_back(q);
-        return q;
-    }
-    ~Scratch() {
-        for (void* q : p) (void)hipFree(q);
-    }
-};
 
 // n elements of a call's device array into a host vector, enqueued on s (the caller waits for the stream)
 template <class T>
@@ -75,18 +61,6 @@ inline void mirror_rows(mi_knn* t, hipStream_t s, const float* rows, uint64_t fr
     HIP_CHECK(hipGetLastError());
 }
 
-// the table's own mirror grows with its capacity, keeping the rows mirrored so far (what the two-stage search does)
-inline void grow_keep(mi_knn* t, void** p, size_t* have, size_t want, size_t elem, size_t keep) {
-    if (*have >= want) return;
-    t->reads.sync();
-    void* np_ = nullptr;
-    HIP_CHECK(hipMalloc(&np_, want * elem));
-    if (*p && keep) HIP_CHECK(hipMemcpy(np_, *p, std::min(keep, *have) * elem, hipMemcpyDeviceToDevice));
-    if (*p) HIP_CHECK(hipFree(*p));
-    *p = np_;
-    *have = want;
-}
-
 // The table's mirror for this call: the table's own when "prefilter" = 1 keeps one (caught up here as a search would), else
 // one built for the call in `scratch`.  tomb: the deleted rows' bits, null when there are none.  t->mu held, t not empty.
 struct TableMirror {
@@ -100,8 +74,9 @@ inline TableMirror table_mirror(mi_knn* t, hipStream_t s, Scratch& scratch) {
     uint64_t from = 0;
     if (t->prefilter == 1) {
         t->mirror_rows = std::min(t->mirror_rows, t->rows);
-        grow_keep(t, (void**)&t->d_mirror, &t->mirror_cap, (size_t)t->cap * t->dim, sizeof(uint16_t), (size_t)t->mirror_rows * t->dim);
-        grow_keep(t, (void**)&t->d_xx, &t->xx_cap, (size_t)t->cap, sizeof(float), (size_t)t->mirror_rows);
+        // the table's own mirror grows with its capacity, keeping the rows mirrored so far (what the two-stage search does)
+        t->d_mirror.reserve_keep(t->reads, (size_t)t->cap * t->dim, (size_t)t->mirror_rows * t->dim);
+        t->d_xx.reserve_keep(t->reads, (size_t)t->cap, (size_t)t->mirror_rows);
         m = t->d_mirror; x = t->d_xx; from = t->mirror_rows;
     } else {
         m = (uint16_t*)scratch.get((size_t)t->rows * t->dim * sizeof(uint16_t));

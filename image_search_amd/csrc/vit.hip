@@ -1433,9 +1433,9 @@ int mi_clip_embed_images(mi_clip* m, const uint8_t* const* rgb8, const uint32_t*
 // ---- op-level entry points (include/mi355clip_ops.h): host buffers in fp32, the op runs
 // on the device in `precision`; used by the per-op parity tests.
 namespace {
-struct Scratch {
+struct OpScratch {
     std::vector<void*> p;
-    ~Scratch() { for (void* q : p) (void)hipFree(q); }
+    ~OpScratch() { for (void* q : p) (void)hipFree(q); }
     void* bytes(size_t b) { void* q = nullptr; HIP_CHECK(hipMalloc(&q, std::max<size_t>(b, 16))); HIP_CHECK(hipMemset(q, 0, std::max<size_t>(b, 16))); p.push_back(q); return q; }
     // host f32 [rows][cols] -> device T [rows_pad][cols]
     void* up(int precision, const float* h, size_t rows, size_t cols, size_t rows_pad) {
@@ -1468,7 +1468,7 @@ void op_linear_x3(int device, int epilogue, const float* x, const float* w, cons
     if (!pp_shape_ok(mp, n, k, pair ? 2 * n : n, 4, pair ? 2 : 4))
         fail(MI_ERR_UNSUPPORTED, "MI_PRECISION_BF16X3: shape [%zu x %d x %d] is not one of the persistent GEMM's", m_rows, n, k);
     DeviceGuard g(device);
-    Scratch sc;
+    OpScratch sc;
     const std::vector<uint16_t> xs = split_rows_x3(x, m_rows, (size_t)k, mp), ws = split_rows_x3(w, (size_t)n, (size_t)k, (size_t)n);
     void* dx = sc.bytes(xs.size() * 2);
     void* dw = sc.bytes(ws.size() * 2);
@@ -1515,7 +1515,7 @@ int mi_op_linear(int device, int precision, int epilogue, const float* x, const 
         if (epilogue != EPI_STORE_F32 && !bias) fail(MI_ERR_INVALID, "bias is null");
         if (precision == MI_PRECISION_BF16X3) { op_linear_x3(device, epilogue, x, w, bias, out, m_rows, n, k); return; }
         DeviceGuard g(device);
-        Scratch sc;
+        OpScratch sc;
         const size_t mp = pad256(m_rows);
         void* dx = sc.up(precision, x, m_rows, k, mp);
         void* dw = sc.up(precision, w, n, k, n);
@@ -1566,7 +1566,7 @@ int mi_op_linear_lnf(int device, int epilogue, const float* x, const float* w, c
         const size_t mp = pad256(m_rows);
         if (!pp_shape_ok(mp, n, k, n)) fail(MI_ERR_UNSUPPORTED, "shape [%zu x %d x %d] is not one of the persistent GEMM's", m_rows, n, k);
         DeviceGuard g(device);
-        Scratch sc;
+        OpScratch sc;
         void* dx = sc.up(MI_PRECISION_BF16, x, m_rows, k, mp);
         void* dw = sc.up(MI_PRECISION_BF16, w, n, k, n);
         float* db = (float*)sc.up(MI_PRECISION_F32, bias, 1, n, 1);
@@ -1591,7 +1591,7 @@ int mi_op_linear_resid24(int device, const float* x, const float* w, const float
         if (!pp_shape_ok(mp, n, k, n) || mp * (size_t)(n / 32) * 8 >= (1ull << 32))
             fail(MI_ERR_UNSUPPORTED, "shape [%zu x %d x %d] is not one of the persistent GEMM's", m_rows, n, k);
         DeviceGuard g(device);
-        Scratch sc;
+        OpScratch sc;
         void* dx = sc.up(MI_PRECISION_BF16, x, m_rows, k, mp);
         void* dw = sc.up(MI_PRECISION_BF16, w, n, k, n);
         float* db = (float*)sc.up(MI_PRECISION_F32, bias, 1, n, 1);
@@ -1639,7 +1639,7 @@ int mi_op_attention(int device, int precision, const float* qkv, float* ctx, siz
         if (d != heads * 64) fail(MI_ERR_UNSUPPORTED, "head_dim must be 64");
         if (precision == MI_PRECISION_BF16X3) fail(MI_ERR_UNSUPPORTED, "no attention op for MI_PRECISION_BF16X3 (the tower's is the fp32 kernel)");
         DeviceGuard g(device);
-        Scratch sc;
+        OpScratch sc;
         mi_clip m;
         m.precision = precision; m.S = s_tok; m.D = d; m.H = heads;
         if (const char* e = std::getenv("MI_OP_ATTN")) m.attn_ver = std::atoi(e) == 1 ? 1 : 2;   // test hook: which bf16 kernel
@@ -1703,7 +1703,7 @@ int mi_op_layernorm(int device, int precision, const float* x, const float* w, c
         if (!x || !w || !b || !y) fail(MI_ERR_INVALID, "null buffer");
         if (precision == MI_PRECISION_BF16X3) fail(MI_ERR_UNSUPPORTED, "no LayerNorm op for MI_PRECISION_BF16X3");
         DeviceGuard g(device);
-        Scratch sc;
+        OpScratch sc;
         mi_clip m;
         m.precision = precision; m.D = d; m.eps = eps;
         float* dx = (float*)sc.up(MI_PRECISION_F32, x, rows, d, rows);

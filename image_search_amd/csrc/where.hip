@@ -26,19 +26,19 @@ namespace {
 uint64_t where_total(mi_knn* t, const mi_knn_where& w, hipStream_t s) {
     if (t->rows == 0 || where_never(w, t->d_groups != nullptr)) return 0;
     const uint32_t chunk = where_chunk_rows(t->where_chunk), chunks = where_chunks(t->rows, chunk);
-    knn_reserve(t, (void**)&t->d_wcounts, &t->wcounts_cap, (size_t)chunks + 2, sizeof(uint32_t));
-    if (!t->h_wtotal) HIP_CHECK(hipHostMalloc((void**)&t->h_wtotal, sizeof(uint64_t), hipHostMallocDefault));
-    const unsigned long long* tomb = t->dead.empty() ? nullptr : reinterpret_cast<const unsigned long long*>(t->d_tomb);
+    t->d_wcounts.reserve(t->reads, (size_t)chunks + 2);
+    t->h_wtotal.reserve(sizeof(uint64_t));
+    const unsigned long long* tomb = t->dead.empty() ? nullptr : reinterpret_cast<const unsigned long long*>(t->d_tomb.p);
     hipLaunchKernelGGL(where_count_kernel, dim3(chunks), dim3(WHERE_THREADS), 0, s, pred_of(w),
-                       reinterpret_cast<const unsigned long long*>(t->d_tags), reinterpret_cast<const long long*>(t->d_stamps),
+                       reinterpret_cast<const unsigned long long*>(t->d_tags.p), reinterpret_cast<const long long*>(t->d_stamps.p),
                        t->d_groups, tomb, t->rows, chunk, t->d_wcounts + 2);
     HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(where_offsets_kernel, dim3(1), dim3(WHERE_SCAN_THREADS), 0, s, t->d_wcounts + 2, chunks,
-                       reinterpret_cast<unsigned long long*>(t->d_wcounts));
+                       reinterpret_cast<unsigned long long*>(t->d_wcounts.p));
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(t->h_wtotal, t->d_wcounts, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(t->h_wtotal.p, t->d_wcounts, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    return *t->h_wtotal;
+    return *t->h_wtotal.as<uint64_t>();
 }
 
 // ... and the emit pass: the rows into t->d_flist (room made first: the total is known), n_flist = their number
@@ -46,11 +46,11 @@ void where_list(mi_knn* t, const mi_knn_where& w, hipStream_t s) {
     const uint64_t total = where_total(t, w, s);
     t->n_flist = (size_t)total;
     if (total == 0) return;
-    knn_reserve(t, (void**)&t->d_flist, &t->flist_cap, (size_t)total, sizeof(uint32_t));
+    t->d_flist.reserve(t->reads, (size_t)total);
     const uint32_t chunk = where_chunk_rows(t->where_chunk), chunks = where_chunks(t->rows, chunk);
-    const unsigned long long* tomb = t->dead.empty() ? nullptr : reinterpret_cast<const unsigned long long*>(t->d_tomb);
+    const unsigned long long* tomb = t->dead.empty() ? nullptr : reinterpret_cast<const unsigned long long*>(t->d_tomb.p);
     hipLaunchKernelGGL(where_emit_kernel, dim3(chunks), dim3(WHERE_THREADS), 0, s, pred_of(w),
-                       reinterpret_cast<const unsigned long long*>(t->d_tags), reinterpret_cast<const long long*>(t->d_stamps),
+                       reinterpret_cast<const unsigned long long*>(t->d_tags.p), reinterpret_cast<const long long*>(t->d_stamps.p),
                        t->d_groups, tomb, t->rows, chunk, t->d_wcounts + 2, t->d_flist);
     HIP_CHECK(hipGetLastError());
 }
@@ -75,15 +75,13 @@ int mi_knn_set_attrs(mi_knn* t, const uint64_t* ids, uint64_t n, const uint64_t*
         const std::vector<uint32_t> rows = knn_local_rows(t, ids, n);   // every id checked before anything is written
         TableCall call(t);
         knn_attrs_fit(t);
-        if (t->h_tags.size() < t->rows) t->h_tags.resize((size_t)t->rows, 0);
-        if (t->h_stamps.size() < t->rows) t->h_stamps.resize((size_t)t->rows, 0);
         for (uint64_t i = 0; i < n; ++i) {
             const uint32_t r = rows[(size_t)i];
-            if (tags) t->h_tags[r] = tags[i];
-            if (stamps) t->h_stamps[r] = stamps[i];
+            if (tags) t->d_tags.slot((size_t)t->rows, r) = tags[i];
+            if (stamps) t->d_stamps.slot((size_t)t->rows, r) = stamps[i];
         }
-        upload_span(call, rows, {{tags ? t->d_tags : nullptr, t->h_tags.data(), sizeof(uint64_t)},
-                                 {stamps ? t->d_stamps : nullptr, t->h_stamps.data(), sizeof(int64_t)}});
+        upload_span(call, rows, {{tags ? t->d_tags.p : nullptr, t->d_tags.host.data(), sizeof(uint64_t)},
+                                 {stamps ? t->d_stamps.p : nullptr, t->d_stamps.host.data(), sizeof(int64_t)}});
     });
 }
 
@@ -97,8 +95,8 @@ int mi_knn_get_attrs(mi_knn* t, const uint64_t* ids, uint64_t n, uint64_t* tags,
         const std::vector<uint32_t> rows = knn_local_rows(t, ids, n);
         for (uint64_t i = 0; i < n; ++i) {   // rows appended since the last set hold the defaults
             const uint32_t r = rows[(size_t)i];
-            if (tags) tags[i] = r < t->h_tags.size() ? t->h_tags[r] : 0;
-            if (stamps) stamps[i] = r < t->h_stamps.size() ? t->h_stamps[r] : 0;
+            if (tags) tags[i] = t->d_tags.get(r);
+            if (stamps) stamps[i] = t->d_stamps.get(r);
         }
     });
 }
@@ -146,8 +144,8 @@ int mi_knn_search_where(mi_knn* t, const float* q, uint32_t nq, uint32_t k, cons
         TableCall call(t);
         hipStream_t s = call.s;
         constexpr uint32_t GROUP = 16;
-        knn_reserve(t, (void**)&t->d_idx, &t->idx_cap, (size_t)GROUP * k, sizeof(uint64_t));
-        knn_reserve(t, (void**)&t->d_dist, &t->dist_cap, (size_t)GROUP * k, sizeof(float));
+        t->d_idx.reserve(t->reads, (size_t)GROUP * k);
+        t->d_dist.reserve(t->reads, (size_t)GROUP * k);
         where_list(t, *w, s);
         if (matched) *matched = t->n_flist;
         for (uint32_t u0 = 0; u0 < nq; u0 += GROUP) {
