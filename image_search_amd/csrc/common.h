@@ -78,30 +78,4 @@ inline void allow_lds_once(DevOnce& once, K kernel, int bytes) {
     once.mask.fetch_or(bit, std::memory_order_release);
 }
 
-// Order of the work of ONE handle across streams.  Every entry point that enqueues work which touches
-// the handle's buffers calls begin(s) first (s waits for whatever the handle enqueued last, on any
-// stream) and end(s) last.  Work on a handle therefore runs in call order whichever streams the
-// callers pass; the host never blocks.  sync() is for the few places that free or move buffers.
-struct WorkOrder {
-    hipEvent_t ev = nullptr;
-    bool pending = false;
-    void begin(hipStream_t s) {
-        if (pending) HIP_CHECK(hipStreamWaitEvent(s, ev, 0));
-    }
-    void end(hipStream_t s) {
-        if (!ev) HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        HIP_CHECK(hipEventRecord(ev, s));
-        pending = true;
-    }
-    void sync() {
-        if (pending) HIP_CHECK(hipEventSynchronize(ev));
-        pending = false;
-    }
-    void destroy() {
-        if (ev) (void)hipEventDestroy(ev);
-        ev = nullptr;
-        pending = false;
-    }
-};
-
 }  // namespace mi

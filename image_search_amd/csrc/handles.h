@@ -30,14 +30,14 @@ struct mi_clip {
     int device = 0, precision = 0;
     int image = 0, patch = 0, grid = 0, S = 0, D = 0, L = 0, H = 0, FF = 0, E = 0, Kp = 0;
     float eps = 1e-5f;
-    std::vector<void*> allocs;
+    mi::Scratch allocs;   // the weights, as uploaded at load
     float *cls = nullptr, *pos = nullptr, *pre_w = nullptr, *pre_b = nullptr, *post_w = nullptr, *post_b = nullptr,
           *proj = nullptr;
     void* wpatch = nullptr;  // T [D][Kp]
     std::vector<mi::Layer> layers;
-    // workspace for `cap` images
+    // workspace for `cap` images (text tower: `text_cap` sequences); the pointers below and in `act` are views into it
     size_t cap = 0;
-    std::vector<void*> ws;
+    mi::Scratch ws;
     float *d_in = nullptr, *d_in2 = nullptr, *d_out = nullptr, *d_out2 = nullptr;
     // activations: set 0 serves a whole chunk; set 1 exists so that two half-chunks can run as two
     // independent streams (see forward()).
@@ -54,12 +54,12 @@ struct mi_clip {
         float *part = nullptr, *stats = nullptr;
         float* c_stats = nullptr;   // ... of the CLS rows (last layer: the query columns are computed for those rows only)
     } act[4];
-    hipStream_t aux[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
+    mi::Stream aux[3];
+    mi::Event ev_fork, ev_join[3];
     // a forward's front (patch gather + patch GEMM) may run on a stream of its own, under the PREVIOUS forward's layers
     // (forward(..., front)): ev_embed[p] = the last embed_ln of activation set p has read `patch` (the next front may
     // overwrite col / patch), ev_front[p] = the front of set p has written `patch` (embed_ln may read it)
-    hipEvent_t ev_embed[4] = {nullptr, nullptr, nullptr, nullptr}, ev_front[4] = {nullptr, nullptr, nullptr, nullptr};
+    mi::Event ev_embed[4], ev_front[4];
     bool ev_embed_set[4] = {false, false, false, false};
     bool x24 = true;          // bf16 image tower: the residual stream as 24-bit floats in two planes (3 bytes per element instead of 4; option "x24", MI_CLIP_X24)
     bool ln_fold = true;      // bf16 image tower without LayerNorm kernels in the layer loop where the geometry allows (option "ln_fold", MI_CLIP_LN_FOLD; forward() in vit.hip)
@@ -80,20 +80,30 @@ struct mi_clip {
     float* tok = nullptr;
     int *d_ids = nullptr, *d_rows = nullptr;
     size_t text_cap = 0;
+    mi::PinnedBuf h_ids_pin, h_out_pin;   // pinned staging of one query's ids / its embedding: the graph copies from / to them
     // one text query as a captured hipGraph (forward_text_one is ~90 short kernels; launched one by one the host's launch
-    // calls cost more than the kernels): 0 = not yet run, 1 = ran once eagerly (function attributes are set), 2 = captured
-    int* h_ids_pin = nullptr;      // pinned staging of one query's ids / its embedding: the graph copies from / to them
-    float* h_out_pin = nullptr;
-    int text_graph_state = 0;
-    hipGraph_t text_graph = nullptr;
-    hipGraphExec_t text_graph_exec = nullptr;
-    // mi_clip_embed_images: two upload buffers for decoded images, the resize intermediate, a copy stream
-    uint8_t* d_img_src[2] = {nullptr, nullptr};
-    float* d_img_tmp = nullptr;
-    size_t img_src_cap = 0, img_tmp_cap = 0;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_used[2] = {nullptr, nullptr};
-    hipStream_t stream = nullptr;
+    // calls cost more than the kernels).  state: 0 = not yet run, 1 = ran once eagerly (function attributes are set), 2 = captured
+    struct TextGraph {
+        int state = 0;
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        TextGraph() = default;
+        TextGraph(const TextGraph&) = delete;
+        TextGraph& operator=(const TextGraph&) = delete;
+        ~TextGraph() { drop(); }
+        void drop() {   // the caller has waited for the handle's work: a replay in flight reads the exec
+            if (exec) (void)hipGraphExecDestroy(exec);
+            if (graph) (void)hipGraphDestroy(graph);
+            exec = nullptr; graph = nullptr;
+            state = 0;
+        }
+    } text_graph;
+    // mi_clip_embed_images: two upload buffers for decoded images (they grow together), the resize intermediate, a copy stream
+    mi::DevArray<uint8_t> d_img_src[2];
+    mi::DevArray<float> d_img_tmp;    // [image][widest source][3]
+    mi::Stream copy_stream;
+    mi::Event ev_up[2], ev_used[2];
+    mi::Stream stream;
     size_t max_batch = 256;
     // options (mi_clip_set_option; the MI_CLIP_* / MI_GEMM_* environment variables only seed them at load)
     bool split_ln = false;    // MI_PRECISION_BF16_SPLIT: LayerNorm outputs as hi + lo bf16 pairs, q/k/v and fc1 run over K = 2D
@@ -127,7 +137,7 @@ struct mi_knn {
     // a shard of a block-cyclic table (mi_knn_sharded): ids = base + ((local / block) * n + rank) * block + local % block
     uint32_t cyc_block = 0, cyc_n = 0, cyc_rank = 0;
     mi::DevArray<float> table;   // [cap][dim] (`cap` counts rows, table.cap elements)
-    hipStream_t stream = nullptr;
+    mi::Stream stream;
     int n_cu = 0;
     // search workspace
     mi::DevArray<float> d_q;        // [16][dim]
@@ -166,7 +176,7 @@ struct mi_knn {
     static constexpr int PREF_RING = 8, PREF_SKIP = 64;
     bool pref_adaptive = true;
     mi::PinnedBuf h_pref_ring;         // uint32_t [PREF_RING][2]: {candidates, fell back}
-    hipEvent_t pref_ev[PREF_RING] = {};
+    mi::Event pref_ev[PREF_RING];
     bool pref_ev_pending[PREF_RING] = {};
     uint32_t pref_consec = 0, pref_skip_left = 0;
     // behind a skip window exactly two probes go out; until both have reported, later queries keep to the single pass
@@ -281,27 +291,16 @@ struct mi_knn {
 // on shard b % n at local block b / n; every shard is an ordinary mi_knn whose kernels emit global ids (IdMap).
 typedef struct ncclComm* ncclComm_t;
 namespace mi {
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    void reserve(size_t b) {  // caller has the device selected and nothing in flight that uses the old buffer
-        if (b <= cap) return;
-        if (p) HIP_CHECK(hipFree(p));
-        p = nullptr; cap = 0;
-        HIP_CHECK(hipMalloc(&p, b));
-        cap = b;
-    }
-};
 // one search in flight on a sharded table: per-shard query / result buffers, the gathered lists and the merged result
 // on the first shard's device, pinned copies for the host, and where the caller wants them
 struct ShardedSlot {
     // a shard's answer is one packed record [nq*k x u64 id | nq*k x f32 distance] (padded to 16 bytes)
-    std::vector<DevBuf> d_q, d_rec;           // [shard]
-    std::vector<DevBuf> g_rec;                // [shard] (RCCL receive side: n records) or [0] only (copy transport)
-    DevBuf m_rec;                             // merged record, on shard 0's device
+    std::vector<DevArray<unsigned char>> d_q, d_rec;   // [shard], sized in bytes
+    std::vector<DevArray<unsigned char>> g_rec;        // [shard] (RCCL receive side: n records) or [0] only (copy transport)
+    DevArray<unsigned char> m_rec;                     // merged record, on shard 0's device
     PinnedBuf h_q{hipHostMallocPortable}, h_rec{hipHostMallocPortable};   // read and written by streams of several devices
-    std::vector<hipEvent_t> ev;               // [shard]: list of shard s is in place
-    hipEvent_t done = nullptr;
+    std::vector<Event> ev;                    // [shard]: list of shard s is in place
+    Event done;
     uint32_t nq = 0, k = 0;
     uint64_t* user_idx = nullptr;
     float* user_dist = nullptr;
@@ -321,7 +320,7 @@ struct mi_knn_sharded {
     bool use_rccl = false;
     struct { uint64_t searches = 0, collectives = 0, copies = 0, merges = 0; } stats;   // mi_knn_sharded_stats
     uint64_t generation = 0;                  // of the files last saved or loaded (mi_knn_sharded_save)
-    std::vector<hipEvent_t> ev_src;           // [device ordinal]: the peer copies of the last append_device from that device
+    std::vector<mi::Event> ev_src;            // [device ordinal]: the peer copies of the last append_device from that device
     uint64_t join_stats[4] = {0, 0, 0, 0};    // mi_knn_sharded_near_pairs_stats: summed over every shard and shard pair of the last call
     uint64_t dbscan_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // mi_knn_sharded_dbscan_stats: mi_knn::dbscan_stats summed the same way, plus the forest merge
     // mi_knn_sharded_kmeans_stats: {updates run, bytes copied between shards, segments summed in the last update (all shards),

@@ -33,7 +33,7 @@ struct SeedShard {
     Scratch scratch;
     mi_knn* sh = nullptr;
     hipStream_t s = nullptr;
-    hipEvent_t ev = nullptr;              // shard >= 1: its words / its slot are in place; shard 0: the pick word / the centre is
+    Event ev;                             // shard >= 1: its words / its slot are in place; shard 0: the pick word / the centre is
     IdMap map{0, 0, 0, 0};
     uint32_t n_list = 0, n_chunks = 0;
     uint32_t* d_list = nullptr;
@@ -44,11 +44,6 @@ struct SeedShard {
     unsigned long long* d_slot = nullptr;    // [kmpp_slot_words]
     KmppPick* d_pick = nullptr;
     float* d_centre = nullptr;               // [dim]
-    SeedShard() = default;
-    SeedShard(const SeedShard&) = delete;
-    ~SeedShard() {
-        if (ev) (void)hipEventDestroy(ev);
-    }
 };
 
 // every shard's stream idle before the call's device memory goes, and its order word saying so (what TableCall leaves
@@ -150,7 +145,7 @@ void sharded_seed_run(ShardedCall& call, const KmppPlan& plan, uint32_t C, uint6
         x.s = knn_own_stream(sh);
         sh->writes.begin(x.s);
         sh->reads.begin(x.s);
-        HIP_CHECK(hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+        x.ev.get(hipEventDisableTiming);
         if (si == 0) {
             d_all = (unsigned long long*)x.scratch.get((size_t)n_words * sizeof(unsigned long long));
             d_slots = (unsigned long long*)x.scratch.get((size_t)S * slot_bytes);

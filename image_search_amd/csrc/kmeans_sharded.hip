@@ -98,7 +98,7 @@ void sharded_kmeans_run(ShardedCall& call, const float* centroids, uint32_t C, u
         if (x.n_rows == 0) {   // it takes part in the exchange with zeros
             DeviceGuard g(sh->device);
             x.s = knn_own_stream(sh);
-            HIP_CHECK(hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+            x.ev.get(hipEventDisableTiming);
             x.d_vec = (float*)x.a.scratch.get(cbytes);
             x.d_S = (long long*)x.a.scratch.get((size_t)C * dim * sizeof(long long));
             x.d_n = (uint32_t*)x.a.scratch.get((size_t)C * sizeof(uint32_t));
@@ -109,7 +109,7 @@ void sharded_kmeans_run(ShardedCall& call, const float* centroids, uint32_t C, u
         }
         TableCall call(sh);
         x.s = call.s;
-        HIP_CHECK(hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+        x.ev.get(hipEventDisableTiming);
         x.a.setup(call, C);
         x.d_vec = x.a.d_vec;
         HIP_CHECK(hipMemcpyAsync(x.d_vec, centroids, cbytes, hipMemcpyHostToDevice, x.s));

@@ -22,15 +22,10 @@ constexpr uint64_t KM_MERGE_CHUNK = 1ull << 21;   // 64-bit sums copied to shard
 struct KmPart {
     mi_knn* sh = nullptr;
     hipStream_t s = nullptr;
-    hipEvent_t ev = nullptr;        // shard >= 1: its sums are in place; shard 0: the centroids are
+    Event ev;                       // shard >= 1: its sums are in place; shard 0: the centroids are
     float* d_vec = nullptr;         // [C][dim]: the centroids
     long long* d_S = nullptr;       // [C][dim] / [C]: the shard's sums and sizes (zeros where it has no rows)
     uint32_t* d_n = nullptr;
-    KmPart() = default;
-    KmPart(const KmPart&) = delete;
-    ~KmPart() {
-        if (ev) (void)hipEventDestroy(ev);
-    }
 };
 
 // where shard 0 stages another shard's sums and sizes; shard 0's device selected

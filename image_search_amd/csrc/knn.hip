@@ -28,8 +28,7 @@ constexpr int MAX_BATCH_Q = 8;
 // the handle's own stream, created on first use (an idle stream still takes one of the four
 // hardware queues HIP multiplexes streams onto)
 hipStream_t own_stream(mi_knn* t) {
-    if (!t->stream) HIP_CHECK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    return t->stream;
+    return t->stream.get(hipStreamNonBlocking);
 }
 
 // ---- deleted rows (handles.h: dead, d_tomb, d_dead) -------------------------------------------------------------
@@ -516,7 +515,7 @@ void pref_record(mi_knn* t, hipStream_t s) {
         if (t->pref_probing && t->pref_reports_due && --t->pref_reports_due == 0) t->pref_probing = false;
         return;
     }
-    if (!t->pref_ev[i]) HIP_CHECK(hipEventCreateWithFlags(&t->pref_ev[i], hipEventDisableTiming));
+    t->pref_ev[i].get(hipEventDisableTiming);
     HIP_CHECK(hipMemcpyAsync(t->h_pref_ring.as<uint32_t>() + 2 * i, t->d_pref_flag, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipEventRecord(t->pref_ev[i], s));
     t->pref_ev_pending[i] = true;
@@ -1000,12 +999,9 @@ void mi_knn_free(mi_knn* t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
     (void)hipDeviceSynchronize();
-    t->writes.destroy();
-    t->reads.destroy();
-    if (t->stream) { (void)hipStreamSynchronize(t->stream); (void)hipStreamDestroy(t->stream); }
-    for (hipEvent_t e : t->pref_ev)
-        if (e) (void)hipEventDestroy(e);
-    delete t;   // the workspace, the columns and the pinned buffers go with their owners
+    if (t->stream) (void)hipStreamSynchronize(t->stream);
+    t->stream.reset();
+    delete t;   // the workspace, the columns, the pinned buffers and the events go with their owners
 }
 
 int mi_knn_set_option(mi_knn* t, const char* key, int value) {

@@ -33,26 +33,26 @@ namespace {
 constexpr int N_SLOTS = 16;
 constexpr int N_SPANS = 32;
 struct QuerySlot {
-    float* h_q = nullptr;        // pinned staging of the query
-    float* d_q = nullptr;
-    uint64_t *d_idx = nullptr, *h_idx = nullptr;
-    float *d_dist = nullptr, *h_dist = nullptr;
+    PinnedBuf h_q;               // pinned staging of the query
+    DevArray<float> d_q;
+    DevArray<uint64_t> d_idx;    // results for cap_k entries: on the device and their pinned copies
+    DevArray<float> d_dist;
+    PinnedBuf h_idx, h_dist;
     uint32_t cap_k = 0, k = 0;
     uint64_t* user_idx = nullptr;
     float* user_dist = nullptr;
-    hipEvent_t done = nullptr;
+    Event done;
     bool busy = false;
 };
-struct Span { hipEvent_t a = nullptr, b = nullptr; bool used = false; };
+struct Span { Event a, b; bool used = false; };
 // one tower replica feeding one shard, both on `device`
 struct Lane {
     mi_clip* m = nullptr;
     mi_knn* t = nullptr;
     int device = 0;
-    hipStream_t ingest = nullptr, copy = nullptr;
-    hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_used[2] = {nullptr, nullptr};
-    float* d_in[2] = {nullptr, nullptr};
-    size_t in_cap = 0;   // images per upload buffer
+    Stream ingest, copy;
+    Event ev_up[2], ev_used[2];
+    DevArray<float> d_in[2];   // the upload buffers: they grow together
     uint64_t seq = 0;    // chunks enqueued on this lane
     Span fwd[N_SPANS];
     uint64_t n_fwd = 0;
@@ -63,7 +63,7 @@ struct mi_pipeline {
     std::vector<Lane> lanes;
     mi_knn_sharded* st = nullptr;   // sharded form: lane s feeds st->shard[s]; null: one lane, lanes[0].t is the table
     int device = 0;                 // of the search stream (one-GPU form)
-    hipStream_t search = nullptr;
+    Stream search;
     QuerySlot slots[N_SLOTS];
     int next_slot = 0;
     // device time of the forwards / scans, from timing events on their own streams (mi_pipeline_stats)
@@ -81,26 +81,23 @@ void deliver(QuerySlot& s) {
     if (!s.busy) return;
     HIP_CHECK(hipEventSynchronize(s.done));
     if (s.user_idx) {  // a query whose results stay on the device (mi_pipeline_query_device) has nothing to hand over
-        std::memcpy(s.user_idx, s.h_idx, (size_t)s.k * sizeof(uint64_t));
-        std::memcpy(s.user_dist, s.h_dist, (size_t)s.k * sizeof(float));
+        std::memcpy(s.user_idx, s.h_idx.p, (size_t)s.k * sizeof(uint64_t));
+        std::memcpy(s.user_dist, s.h_dist.p, (size_t)s.k * sizeof(float));
     }
     s.busy = false;
 }
 
+// the slot has been delivered: nothing in flight uses what it holds
 void slot_reserve(QuerySlot& s, uint32_t dim, uint32_t k) {
-    if (!s.done) HIP_CHECK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    if (!s.h_q) {
-        HIP_CHECK(hipHostMalloc((void**)&s.h_q, (size_t)dim * 4, hipHostMallocDefault));
-        HIP_CHECK(hipMalloc((void**)&s.d_q, (size_t)dim * 4));
-    }
+    s.done.get(hipEventDisableTiming);
+    s.h_q.reserve((size_t)dim * 4);
+    s.d_q.reserve(dim);
     if (k <= s.cap_k) return;
-    if (s.d_idx) { HIP_CHECK(hipFree(s.d_idx)); HIP_CHECK(hipFree(s.d_dist)); HIP_CHECK(hipHostFree(s.h_idx)); HIP_CHECK(hipHostFree(s.h_dist)); }
-    s.d_idx = nullptr; s.d_dist = nullptr; s.h_idx = nullptr; s.h_dist = nullptr; s.cap_k = 0;
     const uint32_t cap = (k + 63) / 64 * 64;
-    HIP_CHECK(hipMalloc((void**)&s.d_idx, (size_t)cap * 8));
-    HIP_CHECK(hipMalloc((void**)&s.d_dist, (size_t)cap * 4));
-    HIP_CHECK(hipHostMalloc((void**)&s.h_idx, (size_t)cap * 8, hipHostMallocDefault));
-    HIP_CHECK(hipHostMalloc((void**)&s.h_dist, (size_t)cap * 4, hipHostMallocDefault));
+    s.d_idx.reserve(cap);
+    s.d_dist.reserve(cap);
+    s.h_idx.reserve((size_t)cap * 8);
+    s.h_dist.reserve((size_t)cap * 4);
     s.cap_k = cap;
 }
 
@@ -118,7 +115,8 @@ void collect(mi_pipeline* p, Span& sp, int kind) {
 Span& span_begin(mi_pipeline* p, Span* ring, uint64_t* count, int kind, hipStream_t s) {
     Span& sp = ring[(*count)++ % N_SPANS];
     collect(p, sp, kind);  // ring full: the oldest span finished long ago
-    if (!sp.a) { HIP_CHECK(hipEventCreate(&sp.a)); HIP_CHECK(hipEventCreate(&sp.b)); }
+    sp.a.get(hipEventDefault);   // timing events
+    sp.b.get(hipEventDefault);
     HIP_CHECK(hipEventRecord(sp.a, s));
     return sp;
 }
@@ -128,46 +126,23 @@ void span_end(Span& sp, hipStream_t s) {
     sp.used = true;
 }
 
-void free_spans(Span* ring) {
-    for (int i = 0; i < N_SPANS; ++i) {
-        if (ring[i].a) (void)hipEventDestroy(ring[i].a);
-        if (ring[i].b) (void)hipEventDestroy(ring[i].b);
-    }
-}
-
 void free_pipeline(mi_pipeline* p) {
     if (!p) return;
     for (Lane& ln : p->lanes) {
         (void)hipSetDevice(ln.device);
-        for (hipStream_t s : {ln.ingest, ln.copy})
+        for (hipStream_t s : {ln.ingest.s, ln.copy.s})
             if (s) (void)hipStreamSynchronize(s);
     }
     if (p->st) (void)mi_knn_sharded_sync(p->st);
     (void)hipSetDevice(p->device);
     if (p->search) (void)hipStreamSynchronize(p->search);
-    free_spans(p->scan);
-    for (auto& s : p->slots) {
-        if (s.done) (void)hipEventDestroy(s.done);
-        if (s.h_q) (void)hipHostFree(s.h_q);
-        if (s.d_q) (void)hipFree(s.d_q);
-        if (s.d_idx) (void)hipFree(s.d_idx);
-        if (s.d_dist) (void)hipFree(s.d_dist);
-        if (s.h_idx) (void)hipHostFree(s.h_idx);
-        if (s.h_dist) (void)hipHostFree(s.h_dist);
-    }
-    if (p->search) (void)hipStreamDestroy(p->search);
-    for (Lane& ln : p->lanes) {
+    p->search.reset();
+    for (Lane& ln : p->lanes) {   // every stream goes with its own device selected
         (void)hipSetDevice(ln.device);
-        free_spans(ln.fwd);
-        for (int b = 0; b < 2; ++b) {
-            if (ln.ev_up[b]) (void)hipEventDestroy(ln.ev_up[b]);
-            if (ln.ev_used[b]) (void)hipEventDestroy(ln.ev_used[b]);
-            if (ln.d_in[b]) (void)hipFree(ln.d_in[b]);
-        }
-        for (hipStream_t s : {ln.ingest, ln.copy})
-            if (s) (void)hipStreamDestroy(s);
+        ln.ingest.reset();
+        ln.copy.reset();
     }
-    delete p;
+    delete p;   // the slots, the spans and the lanes' buffers and events go with their owners
 }
 
 void lane_init(Lane& ln, mi_clip* model, mi_knn* table) {
@@ -180,11 +155,11 @@ void lane_init(Lane& ln, mi_clip* model, mi_knn* table) {
         fail(MI_ERR_INVALID, "the model embeds into %d dimensions, the table holds %u", model->E, table->dim);
     ln.m = model; ln.t = table; ln.device = model->device;
     DeviceGuard g(ln.device);
-    HIP_CHECK(hipStreamCreateWithFlags(&ln.ingest, hipStreamNonBlocking));
-    HIP_CHECK(hipStreamCreateWithFlags(&ln.copy, hipStreamNonBlocking));
+    ln.ingest.get(hipStreamNonBlocking);
+    ln.copy.get(hipStreamNonBlocking);
     for (int b = 0; b < 2; ++b) {
-        HIP_CHECK(hipEventCreateWithFlags(&ln.ev_up[b], hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&ln.ev_used[b], hipEventDisableTiming));
+        ln.ev_up[b].get(hipEventDisableTiming);
+        ln.ev_used[b].get(hipEventDisableTiming);
     }
 }
 
@@ -198,14 +173,9 @@ void lane_ingest(mi_pipeline* p, int li, const float* nchw, size_t n) {
     const size_t px = (size_t)m->image * m->image * 3;
     const size_t chunk = std::min(n, m->max_batch);
     clip_ensure_workspace(m, chunk);
-    if (chunk > ln.in_cap) {
-        for (hipStream_t s : {ln.ingest, ln.copy}) HIP_CHECK(hipStreamSynchronize(s));
-        for (int b = 0; b < 2; ++b) {
-            if (ln.d_in[b]) HIP_CHECK(hipFree(ln.d_in[b]));
-            ln.d_in[b] = nullptr;
-            HIP_CHECK(hipMalloc((void**)&ln.d_in[b], chunk * px * 4));
-        }
-        ln.in_cap = chunk;
+    if (chunk * px > std::min(ln.d_in[0].cap, ln.d_in[1].cap)) {
+        for (hipStream_t s : {ln.ingest.s, ln.copy.s}) HIP_CHECK(hipStreamSynchronize(s));
+        for (auto& d : ln.d_in) d.reserve(chunk * px);
     }
     knn_grow(t, t->rows + n);  // a reallocation waits for everything in flight (reserve ahead to avoid it)
     for (size_t i = 0; i < n; i += chunk) {
@@ -247,7 +217,7 @@ int mi_pipeline_create(mi_clip* model, mi_knn* table, mi_pipeline** out) {
         lane_init(p->lanes[0], model, table);
         p->device = model->device;
         DeviceGuard g(p->device);
-        HIP_CHECK(hipStreamCreateWithFlags(&p->search, hipStreamNonBlocking));
+        p->search.get(hipStreamNonBlocking);
         *out = p;
     });
     if (rc != MI_OK && p) free_pipeline(p);
@@ -337,17 +307,17 @@ int mi_pipeline_query(mi_pipeline* p, const float* q, uint32_t k, uint64_t* idx,
         p->next_slot = (p->next_slot + 1) % N_SLOTS;
         deliver(s);  // the ring is full only when 16 queries are pending: finish the oldest
         slot_reserve(s, t->dim, k);
-        std::memcpy(s.h_q, q, (size_t)t->dim * 4);
+        std::memcpy(s.h_q.p, q, (size_t)t->dim * 4);
         s.k = k; s.user_idx = idx; s.user_dist = dist;
-        HIP_CHECK(hipMemcpyAsync(s.d_q, s.h_q, (size_t)t->dim * 4, hipMemcpyHostToDevice, p->search));
+        HIP_CHECK(hipMemcpyAsync(s.d_q, s.h_q.p, (size_t)t->dim * 4, hipMemcpyHostToDevice, p->search));
         t->writes.begin(p->search);  // every row counted in t->rows has landed before the scan reads it
         t->reads.begin(p->search);   // searches share the candidate workspace
         auto& sp = span_begin(p, p->scan, &p->n_scan, 1, p->search);
         knn_search_one(t, s.d_q, k, s.d_idx, s.d_dist, p->search);
         span_end(sp, p->search);
         t->reads.end(p->search);
-        HIP_CHECK(hipMemcpyAsync(s.h_idx, s.d_idx, (size_t)k * 8, hipMemcpyDeviceToHost, p->search));
-        HIP_CHECK(hipMemcpyAsync(s.h_dist, s.d_dist, (size_t)k * 4, hipMemcpyDeviceToHost, p->search));
+        HIP_CHECK(hipMemcpyAsync(s.h_idx.p, s.d_idx, (size_t)k * 8, hipMemcpyDeviceToHost, p->search));
+        HIP_CHECK(hipMemcpyAsync(s.h_dist.p, s.d_dist, (size_t)k * 4, hipMemcpyDeviceToHost, p->search));
         HIP_CHECK(hipEventRecord(s.done, p->search));
         s.busy = true;
     });
@@ -369,9 +339,9 @@ int mi_pipeline_query_device(mi_pipeline* p, const float* q, uint32_t k, uint64_
         p->next_slot = (p->next_slot + 1) % N_SLOTS;
         deliver(s);
         slot_reserve(s, t->dim, 0);  // only the query's staging buffers
-        std::memcpy(s.h_q, q, (size_t)t->dim * 4);
+        std::memcpy(s.h_q.p, q, (size_t)t->dim * 4);
         s.k = k; s.user_idx = nullptr; s.user_dist = nullptr;
-        HIP_CHECK(hipMemcpyAsync(s.d_q, s.h_q, (size_t)t->dim * 4, hipMemcpyHostToDevice, p->search));
+        HIP_CHECK(hipMemcpyAsync(s.d_q, s.h_q.p, (size_t)t->dim * 4, hipMemcpyHostToDevice, p->search));
         t->writes.begin(p->search);
         t->reads.begin(p->search);
         auto& sp = span_begin(p, p->scan, &p->n_scan, 1, p->search);

@@ -19,9 +19,8 @@ void run(int device, const uint8_t* src, uint32_t w, uint32_t h, uint32_t nw, ui
     const size_t in_b = (size_t)w * h * 3, out_n = (size_t)nw * nh * 3;
     Scratch scratch;
     void *d_src = scratch.get(in_b), *d_tmp = scratch.get((size_t)nh * w * 3 * 4), *d_out = scratch.get(out_n * (TO_CHW ? 4 : 1));
-    hipStream_t s = nullptr;
-    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
+    Stream own;   // declared behind the device memory: the stream goes first, as the call's own guard had it
+    hipStream_t s = own.get(hipStreamNonBlocking);
     HIP_CHECK(hipMemcpyAsync(d_src, src, in_b, hipMemcpyHostToDevice, s));
     resize_catmullrom_launch<TO_CHW>((const uint8_t*)d_src, w, h, nw, nh, (float*)d_tmp, TO_CHW ? nullptr : (uint8_t*)d_out,
                                      TO_CHW ? (float*)d_out : nullptr, s);

@@ -88,26 +88,12 @@ void free_sharded(mi_knn_sharded* t) {
         (void)hipSetDevice(t->devices[s]);
         (void)hipDeviceSynchronize();
     }
-    for (auto& sl : t->slots) {
-        for (size_t s = 0; s < t->shard.size(); ++s) {
-            (void)hipSetDevice(t->devices[s]);
-            for (std::vector<DevBuf>* v : {&sl.d_q, &sl.d_rec, &sl.g_rec})
-                if (s < v->size() && (*v)[s].p) (void)hipFree((*v)[s].p);
-            if (s < sl.ev.size() && sl.ev[s]) (void)hipEventDestroy(sl.ev[s]);
-        }
-        if (!t->devices.empty()) (void)hipSetDevice(t->devices[0]);
-        for (DevBuf* b : {&sl.m_rec})
-            if (b->p) (void)hipFree(b->p);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    }
-    for (hipEvent_t e : t->ev_src)
-        if (e) (void)hipEventDestroy(e);
     for (size_t s = 0; s < t->shard.size(); ++s) {
         (void)hipSetDevice(t->devices[s]);
         if (s < t->comms.size() && t->comms[s] && rccl().ok) (void)rccl().CommDestroy(t->comms[s]);
         mi_knn_free(t->shard[s]);
     }
-    delete t;
+    delete t;   // the slots' buffers and events and ev_src go with their owners
 }
 
 // run fn(lo, n, shard, local) over the maximal runs of [first, first + n) that are contiguous inside one shard
@@ -130,7 +116,8 @@ void roll_back(mi_knn_sharded* t) {
     for (uint32_t s = 0; s < t->n(); ++s) knn_truncate(t->shard[s], sharded_rows_of(t, t->rows, s));
 }
 
-void grow_buf(DevBuf& b, size_t bytes, hipStream_t in_flight_on) {
+// caller has the device selected
+void grow_buf(DevArray<unsigned char>& b, size_t bytes, hipStream_t in_flight_on) {
     if (bytes <= b.cap) return;
     if (b.p && in_flight_on) HIP_CHECK(hipStreamSynchronize(in_flight_on));  // an older search of this slot may still use it
     b.reserve(bytes);
@@ -179,7 +166,7 @@ void append_device_locked(mi_knn_sharded* t, const float* d_rows, uint64_t n, in
         // a search of a shard must wait for these copies: same device -> the shard's write event is recorded on the
         // producer's stream; another device -> an event of the source device, waited for on the shard's own stream, which
         // then carries the shard's write event (events are recorded only on streams of their own device)
-        hipEvent_t& es = t->ev_src[(size_t)src_device];
+        Event& es = t->ev_src[(size_t)src_device];
         bool recorded = false;
         for (uint32_t s = 0; s < t->n(); ++s) {
             if (!touched[s]) continue;
@@ -192,8 +179,7 @@ void append_device_locked(mi_knn_sharded* t, const float* d_rows, uint64_t n, in
             }
             if (!recorded) {
                 DeviceGuard g(src_device);
-                if (!es) HIP_CHECK(hipEventCreateWithFlags(&es, hipEventDisableTiming));
-                HIP_CHECK(hipEventRecord(es, st));
+                HIP_CHECK(hipEventRecord(es.get(hipEventDisableTiming), st));
                 recorded = true;
             }
             DeviceGuard g(sh->device);
@@ -265,7 +251,7 @@ void sharded_search_enqueue(mi_knn_sharded* t, const float* q, uint32_t nq, uint
     deliver(sl);  // the ring is full only when N_SLOTS searches are pending: finish the oldest
     if (sl.d_q.empty()) {
         sl.d_q.resize(n); sl.d_rec.resize(n); sl.g_rec.resize(n);
-        sl.ev.assign(n, nullptr);
+        sl.ev.resize(n);
     }
     sl.nq = nq; sl.k = k; sl.user_idx = idx; sl.user_dist = dist;
     sl.h_q.reserve((size_t)nq * t->dim * 4);
@@ -324,8 +310,7 @@ void sharded_search_enqueue(mi_knn_sharded* t, const float* q, uint32_t nq, uint
                 else HIP_CHECK(hipMemcpyPeerAsync(dst, first->device, sl.d_rec[s].p, sh->device, rec, sh->stream));
                 ++t->stats.copies;
                 if (s == 0) continue;
-                if (!sl.ev[s]) HIP_CHECK(hipEventCreateWithFlags(&sl.ev[s], hipEventDisableTiming));
-                HIP_CHECK(hipEventRecord(sl.ev[s], sh->stream));
+                HIP_CHECK(hipEventRecord(sl.ev[s].get(hipEventDisableTiming), sh->stream));
             }
             DeviceGuard g(first->device);
             for (uint32_t s = 1; s < n; ++s) HIP_CHECK(hipStreamWaitEvent(first->stream, sl.ev[s], 0));
@@ -340,8 +325,7 @@ void sharded_search_enqueue(mi_knn_sharded* t, const float* q, uint32_t nq, uint
     }
     DeviceGuard g(first->device);
     HIP_CHECK(hipMemcpyAsync(sl.h_rec.p, result, per * 12, hipMemcpyDeviceToHost, first->stream));
-    if (!sl.done) HIP_CHECK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    HIP_CHECK(hipEventRecord(sl.done, first->stream));
+    HIP_CHECK(hipEventRecord(sl.done.get(hipEventDisableTiming), first->stream));
     sl.busy = true;
 }
 
@@ -366,7 +350,7 @@ int mi_knn_sharded_create(uint32_t dim, const int* devices, int n_dev, uint32_t 
             h->cyc_block = block_rows; h->cyc_n = (uint32_t)n_dev; h->cyc_rank = (uint32_t)s;
             t->shard.push_back(h);
         }
-        t->ev_src.assign((size_t)std::max(1, mi_device_count()), nullptr);
+        t->ev_src.resize((size_t)std::max(1, mi_device_count()));
         // RCCL only between distinct devices (a communicator refuses one GPU twice); n_dev == 1 gathers nothing
         bool distinct = true;
         for (int a = 0; a < n_dev; ++a)

@@ -43,10 +43,7 @@ struct SumShard : KmPart {
     const uint32_t* d_labels = nullptr;
     float *d_flag = nullptr, *d_dist = nullptr;
     unsigned long long *d_slots = nullptr, *d_words = nullptr;
-    hipEvent_t ev_slots = nullptr;             // shard >= 1: its slots hold global ids
-    ~SumShard() {
-        if (ev_slots) (void)hipEventDestroy(ev_slots);
-    }
+    Event ev_slots;                            // shard >= 1: its slots hold global ids
 };
 
 // every shard's stream idle before the call's device memory goes, on every way out
@@ -90,8 +87,8 @@ void sharded_summary_run(ShardedCall& call, const uint32_t* labels, uint32_t C, 
         sh->writes.begin(x.s);
         sh->reads.begin(x.s);
         const uint32_t n = x.n_rows;
-        HIP_CHECK(hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&x.ev_slots, hipEventDisableTiming));
+        x.ev.get(hipEventDisableTiming);
+        x.ev_slots.get(hipEventDisableTiming);
         x.d_vec = (float*)x.scratch.get(cbytes);
         x.d_slots = (unsigned long long*)x.scratch.get(sbytes);
         HIP_CHECK(hipMemsetAsync(x.d_slots, 0xFF, (size_t)C * sizeof(unsigned long long), x.s));

@@ -56,17 +56,14 @@ bool qkv_head_major(const mi_clip* m) {
 }
 
 
+// n elements (one at least) among the handle's weights
 template <typename T>
-T* dalloc(mi_clip* m, size_t n, std::vector<void*>& bag) {
-    void* p = nullptr;
-    HIP_CHECK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-    bag.push_back(p);
-    (void)m;
-    return static_cast<T*>(p);
+T* dalloc(mi_clip* m, size_t n) {
+    return static_cast<T*>(m->allocs.exact(std::max<size_t>(n, 1) * sizeof(T)));
 }
 
 float* upload_f32(mi_clip* m, const std::vector<float>& h) {
-    float* d = dalloc<float>(m, h.size(), m->allocs);
+    float* d = dalloc<float>(m, h.size());
     HIP_CHECK(hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
     return d;
 }
@@ -81,7 +78,7 @@ void* upload_mat(mi_clip* m, const std::vector<float>& h, size_t dup_k = 0) {
             for (size_t c = 0; c < dup_k; ++c) b[r * 2 * dup_k + c] = b[r * 2 * dup_k + dup_k + c] = f32_to_bf16_host(h[r * dup_k + c]);
     } else
     for (size_t i = 0; i < h.size(); ++i) b[i] = f32_to_bf16_host(h[i]);
-    uint16_t* d = dalloc<uint16_t>(m, b.size(), m->allocs);
+    uint16_t* d = dalloc<uint16_t>(m, b.size());
     HIP_CHECK(hipMemcpy(d, b.data(), b.size() * 2, hipMemcpyHostToDevice));
     return d;
 }
@@ -106,7 +103,7 @@ std::vector<uint16_t> split_rows_x3(const float* h, size_t rows, size_t k, size_
 // an encoder linear of a MI_PRECISION_BF16X3 handle: W [N][k] as rows [W_hi | W_lo] (4 bytes per weight, as fp32)
 void* upload_x3(mi_clip* m, const std::vector<float>& h, size_t k) {
     const std::vector<uint16_t> b = split_rows_x3(h.data(), h.size() / k, k, h.size() / k);
-    uint16_t* d = dalloc<uint16_t>(m, b.size(), m->allocs);
+    uint16_t* d = dalloc<uint16_t>(m, b.size());
     HIP_CHECK(hipMemcpy(d, b.data(), b.size() * 2, hipMemcpyHostToDevice));
     return d;
 }
@@ -183,7 +180,7 @@ void fold_ln(mi_clip* m, const std::vector<float>& w, const std::vector<float>& 
         cv[n] = (float)cs;
         bv[n] = (float)bs;
     }
-    uint16_t* d = dalloc<uint16_t>(m, w16.size(), m->allocs);
+    uint16_t* d = dalloc<uint16_t>(m, w16.size());
     HIP_CHECK(hipMemcpy(d, w16.data(), w16.size() * 2, hipMemcpyHostToDevice));
     *wf = d;
     *c = upload_f32(m, cv);
@@ -273,7 +270,7 @@ void load_weights(mi_clip* m, const char* path) {
     m->fold_ready = m->precision == MI_PRECISION_BF16 && !m->split_ln && m->D % 256 == 0 && m->FF % 256 == 0 && m->L >= 2;
     m->ln_center = m->fold_ready && m->ln_center;
     if (m->fold_ready) {
-        m->d_fold_offset_rows = dalloc<unsigned long long>(m, 1, m->allocs);
+        m->d_fold_offset_rows = dalloc<unsigned long long>(m, 1);
         HIP_CHECK(hipMemset(m->d_fold_offset_rows, 0, sizeof(unsigned long long)));
     }
     load_layers(m, st, v);
@@ -331,25 +328,25 @@ void load_layers(mi_clip* m, WeightFile& st, const std::string& v) {
 
 
 hipStream_t own_stream(mi_clip* m) {
-    if (!m->stream) HIP_CHECK(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-    return m->stream;
+    return m->stream.get(hipStreamNonBlocking);
+}
+
+// The workspace goes: enqueued forwards still use it, and a captured text query holds its addresses.  An image handle has no
+// graph and no text_cap, a text handle no cap: what this does beyond a caller's own need is a no-op there.
+void drop_workspace(mi_clip* m) {
+    m->order.sync();
+    m->text_graph.drop();
+    m->ws.clear();
+    m->cap = 0;
+    m->text_cap = 0;
 }
 
 void ensure_workspace(mi_clip* m, size_t n) {
     if (n <= m->cap) return;
     own_stream(m);
-    m->order.sync();  // enqueued forwards still use the buffers freed below
-    for (void* p : m->ws) HIP_CHECK(hipFree(p));
-    m->ws.clear();
-    m->cap = 0;
-    const size_t es = esize(m), Mp = pad256(n * m->S), Pp = pad256(n * (m->S - 1));
-    auto bytes = [&](size_t b) {
-        void* p = nullptr;
-        HIP_CHECK(hipMalloc(&p, b));
-        HIP_CHECK(hipMemsetAsync(p, 0, b, m->stream));
-        m->ws.push_back(p);
-        return p;
-    };
+    drop_workspace(m);
+    const size_t es = esize(m);
+    auto bytes = [&](size_t b) { return m->ws.zeroed(b, m->stream); };
     const size_t px = (size_t)m->image * m->image * 3;
     m->d_in = (float*)bytes(n * px * 4);
     m->d_in2 = (float*)bytes(n * px * 4);  // mi_clip_embed: upload of chunk i+1 under the forward of chunk i
@@ -384,7 +381,6 @@ void ensure_workspace(mi_clip* m, size_t n) {
             m->act[a].c_stats = (float*)bytes(Ca * 8);
         }
     }
-    (void)Mp; (void)Pp;
     m->d_out = (float*)bytes(n * m->E * 4);
     m->d_out2 = (float*)bytes(n * m->E * 4);
     HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -676,8 +672,7 @@ void forward(mi_clip* m, const float* d_img, size_t n, float* d_out, hipStream_t
         const size_t np = n / parts + (p < n % parts ? 1 : 0);
         hipStream_t st = s0;
         if (p > 0) {
-            if (!m->aux[p - 1]) HIP_CHECK(hipStreamCreateWithFlags(&m->aux[p - 1], hipStreamNonBlocking));
-            st = m->aux[p - 1];
+            st = m->aux[p - 1].get(hipStreamNonBlocking);
         }
         pt[p] = {np, np * S, np * (S - 1), d_img + first * px, d_out + first * m->E, st, &m->act[p], nullptr, nullptr,
                  x24 ? pad256(np * S) * (size_t)D * 2 : (size_t)0};   // the lo plane lies behind a hi plane of the part's padded rows
@@ -691,10 +686,8 @@ void forward(mi_clip* m, const float* d_img, size_t n, float* d_out, hipStream_t
         Part& q = pt[p];
         hipStream_t es_ = q.s;                 // embed_ln and everything behind it
         hipStream_t fs = front ? front : q.s;  // the front
-        if (!m->ev_embed[p]) {
-            HIP_CHECK(hipEventCreateWithFlags(&m->ev_embed[p], hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&m->ev_front[p], hipEventDisableTiming));
-        }
+        m->ev_embed[p].get(hipEventDisableTiming);
+        m->ev_front[p].get(hipEventDisableTiming);
         if (front && m->ev_embed_set[p]) HIP_CHECK(hipStreamWaitEvent(front, m->ev_embed[p], 0));
         // patch embedding: gather -> GEMM [P,Kp] x [D,Kp]^T -> f32
         const size_t total = q.P * 3 * (size_t)m->patch;  // one thread per patch-row segment
@@ -848,38 +841,20 @@ void forward(mi_clip* m, const float* d_img, size_t n, float* d_out, hipStream_t
 }
 
 void ensure_copy_stream(mi_clip* m) {
-    if (m->copy_stream) return;
-    HIP_CHECK(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking));
+    m->copy_stream.get(hipStreamNonBlocking);
     for (int b = 0; b < 2; ++b) {
-        HIP_CHECK(hipEventCreateWithFlags(&m->ev_up[b], hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&m->ev_used[b], hipEventDisableTiming));
+        m->ev_up[b].get(hipEventDisableTiming);
+        m->ev_used[b].get(hipEventDisableTiming);
     }
 }
 
 // ---- text tower: workspace and forward (fp32) -------------------------------------------
-void drop_text_graph(mi_clip* m) {
-    if (m->text_graph_exec) (void)hipGraphExecDestroy(m->text_graph_exec);
-    if (m->text_graph) (void)hipGraphDestroy(m->text_graph);
-    m->text_graph_exec = nullptr; m->text_graph = nullptr;
-    m->text_graph_state = 0;
-}
-
 void ensure_text_workspace(mi_clip* m, size_t n) {
     if (n <= m->text_cap) return;
     own_stream(m);
-    m->order.sync();
-    drop_text_graph(m);  // it holds the addresses of the buffers freed here
-    for (void* p : m->ws) HIP_CHECK(hipFree(p));
-    m->ws.clear();
-    m->text_cap = 0;
+    drop_workspace(m);
     const size_t Ma = pad256(n * m->S);
-    auto bytes = [&](size_t b) {
-        void* p = nullptr;
-        HIP_CHECK(hipMalloc(&p, b));
-        HIP_CHECK(hipMemsetAsync(p, 0, b, m->stream));
-        m->ws.push_back(p);
-        return p;
-    };
+    auto bytes = [&](size_t b) { return m->ws.zeroed(b, m->stream); };
     const size_t es = esize(m);
     m->act[0].x = (float*)bytes(Ma * m->D * 4);
     m->act[0].y = bytes(Ma * m->D * es);
@@ -910,7 +885,7 @@ void forward_text_one(mi_clip* m, hipStream_t s) {
     const int D = m->D, S = m->S, FF = m->FF;
     mi_clip::Act& a = m->act[0];
     // the ids come from, and the embedding goes to, pinned staging: both copies are nodes of the captured graph
-    HIP_CHECK(hipMemcpyAsync(m->d_ids, m->h_ids_pin, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(m->d_ids, m->h_ids_pin.p, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, s));
     bf16_t *y = (bf16_t*)a.y, *qkv = (bf16_t*)a.qkv, *h = (bf16_t*)a.h;
     float* slabs = a.patch;  // [4][SKINNY_ROWS][D] fp32
     const unsigned lb = (unsigned)((S + 3) / 4);
@@ -948,45 +923,41 @@ void forward_text_one(mi_clip* m, hipStream_t s) {
     hipLaunchKernelGGL((text_head_one_kernel<VEC, NT>), dim3((unsigned)((m->E + 3) / 4)), dim3(256), 0, s, a.x, d1, slabs, n_slabs, b2, m->post_w,
                        m->post_b, m->proj, m->d_out, m->d_ids, S, m->E, m->eps);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(m->h_out_pin, m->d_out, (size_t)m->E * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(m->h_out_pin.p, m->d_out, (size_t)m->E * sizeof(float), hipMemcpyDeviceToHost, s));
 }
 
 // ... replayed as ONE graph launch from the third call on (first call: eager, which also sets the kernels' function
 // attributes; second: captured while it is enqueued; `s` must be the handle's own stream)
 void forward_text_one_graphed(mi_clip* m, hipStream_t s) {
-    if (m->text_graph_state == 2) {
-        HIP_CHECK(hipGraphLaunch(m->text_graph_exec, s));
+    mi_clip::TextGraph& tg = m->text_graph;
+    if (tg.state == 2) {
+        HIP_CHECK(hipGraphLaunch(tg.exec, s));
         return;
     }
-    if (m->text_graph_state == 0) {
+    if (tg.state == 0) {
         forward_text_one(m, s);
-        m->text_graph_state = 1;
+        tg.state = 1;
         return;
     }
+    // captured straight into the handle's owner (empty in this state).  A capture or an instantiation that fails leaves
+    // nothing behind: the query is answered eagerly and the next call tries again from this state
+    auto give_up = [&] { tg.drop(); tg.state = 1; };
     HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     try {
         forward_text_one(m, s);
     } catch (...) {
-        hipGraph_t dead = nullptr;
-        (void)hipStreamEndCapture(s, &dead);
-        if (dead) (void)hipGraphDestroy(dead);
+        (void)hipStreamEndCapture(s, &tg.graph);
+        give_up();
         throw;
     }
-    // a capture or an instantiation that fails leaves nothing behind: the query is answered eagerly and the next call
-    // tries again from a clean state
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    if (hipStreamEndCapture(s, &g) != hipSuccess || !g || hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) {
+    if (hipStreamEndCapture(s, &tg.graph) != hipSuccess || !tg.graph || hipGraphInstantiate(&tg.exec, tg.graph, nullptr, nullptr, 0) != hipSuccess) {
         (void)hipGetLastError();
-        if (ge) (void)hipGraphExecDestroy(ge);
-        if (g) (void)hipGraphDestroy(g);
+        give_up();
         forward_text_one(m, s);
         return;
     }
-    m->text_graph = g;
-    m->text_graph_exec = ge;
-    m->text_graph_state = 2;
-    HIP_CHECK(hipGraphLaunch(m->text_graph_exec, s));
+    tg.state = 2;
+    HIP_CHECK(hipGraphLaunch(tg.exec, s));
 }
 
 // n sequences whose ids are in m->d_ids -> m->d_out [n,E]
@@ -1021,28 +992,14 @@ void forward_text(mi_clip* m, size_t n, hipStream_t s) {
     HIP_CHECK(hipGetLastError());
 }
 
+// the streams idle and gone with their device selected; everything else goes with the handle, whatever device is current
 void free_model(mi_clip* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    if (m->stream) { (void)hipStreamSynchronize(m->stream); (void)hipStreamDestroy(m->stream); }
-    for (auto& a : m->aux) if (a) { (void)hipStreamSynchronize(a); (void)hipStreamDestroy(a); }
-    m->order.destroy();
-    if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
-    for (auto& e : m->ev_embed) if (e) (void)hipEventDestroy(e);
-    for (auto& e : m->ev_front) if (e) (void)hipEventDestroy(e);
-    for (auto& e : m->ev_join) if (e) (void)hipEventDestroy(e);
-    if (m->copy_stream) { (void)hipStreamSynchronize(m->copy_stream); (void)hipStreamDestroy(m->copy_stream); }
-    for (int b = 0; b < 2; ++b) {
-        if (m->ev_up[b]) (void)hipEventDestroy(m->ev_up[b]);
-        if (m->ev_used[b]) (void)hipEventDestroy(m->ev_used[b]);
-        if (m->d_img_src[b]) (void)hipFree(m->d_img_src[b]);
+    for (Stream* s : {&m->stream, &m->aux[0], &m->aux[1], &m->aux[2], &m->copy_stream}) {
+        if (*s) (void)hipStreamSynchronize(*s);
+        s->reset();
     }
-    if (m->d_img_tmp) (void)hipFree(m->d_img_tmp);
-    drop_text_graph(m);
-    if (m->h_ids_pin) (void)hipHostFree(m->h_ids_pin);
-    if (m->h_out_pin) (void)hipHostFree(m->h_out_pin);
-    for (void* p : m->allocs) (void)hipFree(p);
-    for (void* p : m->ws) (void)hipFree(p);
     delete m;
 }
 
@@ -1085,7 +1042,7 @@ int mi_clip_set_option(mi_clip* m, const char* key, int value) {
         DeviceGuard g(m->device);
         const std::string k(key);
         // a captured text query has kernel arguments and launch choices baked in: any option may change them
-        if (m->text) { m->order.sync(); drop_text_graph(m); }
+        if (m->text) { m->order.sync(); m->text_graph.drop(); }
         if (k == "full_last") m->full_last = value != 0;
         else if (k == "attn_shift") m->attn_shift = value != 0;
         else if (k == "front_overlap") m->front_overlap = value != 0;
@@ -1095,10 +1052,7 @@ int mi_clip_set_option(mi_clip* m, const char* key, int value) {
             if (value < 0 || value > 1024 || value % 64) fail(MI_ERR_INVALID, "qkv_pad must be a multiple of 64 in 0..1024");
             if (m->text) fail(MI_ERR_INVALID, "the text tower's qkv rows are dense");
             if (value != m->qkv_pad) {
-                m->order.sync();
-                for (void* p : m->ws) HIP_CHECK(hipFree(p));
-                m->ws.clear();
-                m->cap = 0;
+                drop_workspace(m);
                 m->qkv_pad = value;
             }
         } else if (k == "qkv_layout") {   // takes effect with the next forward (every forward rewrites q|k|v)
@@ -1136,10 +1090,7 @@ int mi_clip_set_option(mi_clip* m, const char* key, int value) {
             if (value < 1 || value > 4) fail(MI_ERR_INVALID, "parts must be 1..4");
             if (m->text) fail(MI_ERR_INVALID, "the text tower runs as one stream");
             if (value != m->parts) {  // the activation sets are sized per part: rebuild on next use
-                m->order.sync();
-                for (void* p : m->ws) HIP_CHECK(hipFree(p));
-                m->ws.clear();
-                m->cap = 0;
+                drop_workspace(m);
                 m->parts = value;
             }
         } else fail(MI_ERR_INVALID, "unknown option '%s' (full_last, front_overlap, attn_shift, attn_nt, store_nt, attn_order, qkv_pad, qkv_layout, split_tail, gemm_order, im2col_rows, ln_nt, x24, ln_fold, text_fast, text_fuse, attn_f32_mfma, max_batch, parts)", key);
@@ -1163,8 +1114,8 @@ int mi_clip_load(const char* weights_path, int device, int precision, mi_clip** 
         if (const char* e = std::getenv("MI_CLIP_MAX_BATCH")) m->max_batch = std::max(1, std::atoi(e));
         // aux streams are created on first use: HIP multiplexes streams onto 4 hardware queues
         // (GPU_MAX_HW_QUEUES), and two streams that share a queue do not overlap
-        HIP_CHECK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
-        for (auto& e : m->ev_join) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        m->ev_fork.get(hipEventDisableTiming);
+        for (auto& e : m->ev_join) e.get(hipEventDisableTiming);
         if (const char* e = std::getenv("MI_CLIP_PARTS")) m->parts = std::min(4, std::max(1, std::atoi(e)));
         if (const char* e = std::getenv("MI_CLIP_FULL_LAST")) m->full_last = std::atoi(e) != 0;
         if (const char* e = std::getenv("MI_CLIP_ATTN")) m->attn_ver = std::atoi(e) == 1 ? 1 : 2;  // fixed at load: decides the q scale
@@ -1229,16 +1180,14 @@ int mi_clip_embed_text(mi_clip* m, const int32_t* input_ids, size_t n, float* ou
         const size_t chunk = std::min(n, m->max_batch);
         ensure_text_workspace(m, chunk);
         if (text_one_applies(m, n)) {  // one query: pinned staging, the copies ride in the graph
-            if (!m->h_ids_pin) {
-                HIP_CHECK(hipHostMalloc((void**)&m->h_ids_pin, (size_t)m->S * sizeof(int32_t), hipHostMallocDefault));
-                HIP_CHECK(hipHostMalloc((void**)&m->h_out_pin, (size_t)m->E * sizeof(float), hipHostMallocDefault));
-            }
-            std::memcpy(m->h_ids_pin, input_ids, (size_t)m->S * sizeof(int32_t));
+            m->h_ids_pin.reserve((size_t)m->S * sizeof(int32_t));
+            m->h_out_pin.reserve((size_t)m->E * sizeof(float));
+            std::memcpy(m->h_ids_pin.p, input_ids, (size_t)m->S * sizeof(int32_t));
             m->order.begin(m->stream);
             forward_text_one_graphed(m, m->stream);
             HIP_CHECK(hipStreamSynchronize(m->stream));
             m->order.pending = false;
-            std::memcpy(out, m->h_out_pin, (size_t)m->E * sizeof(float));
+            std::memcpy(out, m->h_out_pin.p, (size_t)m->E * sizeof(float));
             return;
         }
         for (size_t i = 0; i < n; i += chunk) {
@@ -1383,7 +1332,7 @@ int mi_clip_embed_images(mi_clip* m, const uint8_t* const* rgb8, const uint32_t*
             if (!resize_supported(widths[i], heights[i], (uint32_t)m->image, (uint32_t)m->image, &why))
                 fail(MI_ERR_UNSUPPORTED, "image %zu (%ux%u): %s", i, widths[i], heights[i], why);
             max_src = std::max(max_src, (size_t)widths[i] * heights[i] * 3);
-            max_tmp = std::max(max_tmp, (size_t)m->image * widths[i] * 3 * 4);
+            max_tmp = std::max(max_tmp, (size_t)m->image * widths[i] * 3);   // floats
         }
         std::lock_guard<std::mutex> l(m->mu);
         DeviceGuard g(m->device);
@@ -1391,20 +1340,9 @@ int mi_clip_embed_images(mi_clip* m, const uint8_t* const* rgb8, const uint32_t*
         const size_t chunk = std::min(n, m->max_batch);
         ensure_workspace(m, chunk);
         // two source buffers: the upload of image i+1 overlaps the resize of image i
-        if (max_src > m->img_src_cap) {
-            for (int b = 0; b < 2; ++b) {
-                if (m->d_img_src[b]) HIP_CHECK(hipFree(m->d_img_src[b]));
-                m->d_img_src[b] = nullptr;
-                HIP_CHECK(hipMalloc((void**)&m->d_img_src[b], max_src));
-            }
-            m->img_src_cap = max_src;
-        }
-        if (max_tmp > m->img_tmp_cap) {
-            if (m->d_img_tmp) HIP_CHECK(hipFree(m->d_img_tmp));
-            m->d_img_tmp = nullptr;
-            HIP_CHECK(hipMalloc((void**)&m->d_img_tmp, max_tmp));
-            m->img_tmp_cap = max_tmp;
-        }
+        // (every earlier call has waited for its stream: nothing in flight reads the old buffers)
+        for (auto& src : m->d_img_src) src.reserve(max_src);
+        m->d_img_tmp.reserve(max_tmp);
         ensure_copy_stream(m);
         m->order.begin(m->stream);
         for (size_t i0 = 0; i0 < n; i0 += chunk) {
@@ -1433,28 +1371,29 @@ int mi_clip_embed_images(mi_clip* m, const uint8_t* const* rgb8, const uint32_t*
 // ---- op-level entry points (include/mi355clip_ops.h): host buffers in fp32, the op runs
 // on the device in `precision`; used by the per-op parity tests.
 namespace {
-struct OpScratch {
-    std::vector<void*> p;
-    ~OpScratch() { for (void* q : p) (void)hipFree(q); }
-    void* bytes(size_t b) { void* q = nullptr; HIP_CHECK(hipMalloc(&q, std::max<size_t>(b, 16))); HIP_CHECK(hipMemset(q, 0, std::max<size_t>(b, 16))); p.push_back(q); return q; }
-    // host f32 [rows][cols] -> device T [rows_pad][cols]
-    void* up(int precision, const float* h, size_t rows, size_t cols, size_t rows_pad) {
-        void* d = bytes(rows_pad * cols * (precision == MI_PRECISION_F32 ? 4 : 2));
-        if (precision == MI_PRECISION_F32) HIP_CHECK(hipMemcpy(d, h, rows * cols * 4, hipMemcpyHostToDevice));
-        else {
-            std::vector<uint16_t> b(rows * cols);
-            for (size_t i = 0; i < b.size(); ++i) b[i] = f32_to_bf16_host(h[i]);
-            HIP_CHECK(hipMemcpy(d, b.data(), b.size() * 2, hipMemcpyHostToDevice));
-        }
-        return d;
+// an op's device memory, zero-filled by a blocking hipMemset: the ops copy in with blocking copies and launch on the null stream
+void* op_bytes(Scratch& sc, size_t b) {
+    void* q = sc.get(b);
+    HIP_CHECK(hipMemset(q, 0, std::max<size_t>(b, 16)));
+    return q;
+}
+// host f32 [rows][cols] -> device T [rows_pad][cols]
+void* op_up(Scratch& sc, int precision, const float* h, size_t rows, size_t cols, size_t rows_pad) {
+    void* d = op_bytes(sc, rows_pad * cols * (precision == MI_PRECISION_F32 ? 4 : 2));
+    if (precision == MI_PRECISION_F32) HIP_CHECK(hipMemcpy(d, h, rows * cols * 4, hipMemcpyHostToDevice));
+    else {
+        std::vector<uint16_t> b(rows * cols);
+        for (size_t i = 0; i < b.size(); ++i) b[i] = f32_to_bf16_host(h[i]);
+        HIP_CHECK(hipMemcpy(d, b.data(), b.size() * 2, hipMemcpyHostToDevice));
     }
-    void down(int precision, const void* d, float* h, size_t n) {
-        if (precision == MI_PRECISION_F32) { HIP_CHECK(hipMemcpy(h, d, n * 4, hipMemcpyDeviceToHost)); return; }
-        std::vector<uint16_t> b(n);
-        HIP_CHECK(hipMemcpy(b.data(), d, n * 2, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; ++i) { uint32_t u = (uint32_t)b[i] << 16; std::memcpy(&h[i], &u, 4); }
-    }
-};
+    return d;
+}
+void op_down(int precision, const void* d, float* h, size_t n) {
+    if (precision == MI_PRECISION_F32) { HIP_CHECK(hipMemcpy(h, d, n * 4, hipMemcpyDeviceToHost)); return; }
+    std::vector<uint16_t> b(n);
+    HIP_CHECK(hipMemcpy(b.data(), d, n * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) { uint32_t u = (uint32_t)b[i] << 16; std::memcpy(&h[i], &u, 4); }
+}
 }  // namespace
 
 namespace {
@@ -1468,14 +1407,14 @@ void op_linear_x3(int device, int epilogue, const float* x, const float* w, cons
     if (!pp_shape_ok(mp, n, k, pair ? 2 * n : n, 4, pair ? 2 : 4))
         fail(MI_ERR_UNSUPPORTED, "MI_PRECISION_BF16X3: shape [%zu x %d x %d] is not one of the persistent GEMM's", m_rows, n, k);
     DeviceGuard g(device);
-    OpScratch sc;
+    Scratch sc;
     const std::vector<uint16_t> xs = split_rows_x3(x, m_rows, (size_t)k, mp), ws = split_rows_x3(w, (size_t)n, (size_t)k, (size_t)n);
-    void* dx = sc.bytes(xs.size() * 2);
-    void* dw = sc.bytes(ws.size() * 2);
+    void* dx = op_bytes(sc, xs.size() * 2);
+    void* dw = op_bytes(sc, ws.size() * 2);
     HIP_CHECK(hipMemcpy(dx, xs.data(), xs.size() * 2, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(dw, ws.data(), ws.size() * 2, hipMemcpyHostToDevice));
-    float* db = (float*)sc.up(MI_PRECISION_F32, bias, 1, n, 1);
-    void* dout = pair ? sc.bytes(mp * (size_t)n * 4) : sc.up(MI_PRECISION_F32, out, m_rows, n, mp);
+    float* db = (float*)op_up(sc, MI_PRECISION_F32, bias, 1, n, 1);
+    void* dout = pair ? op_bytes(sc, mp * (size_t)n * 4) : op_up(sc, MI_PRECISION_F32, out, m_rows, n, mp);
     mi_clip mm;
     mm.precision = MI_PRECISION_BF16X3;
     hipDeviceProp_t prop;
@@ -1515,13 +1454,13 @@ int mi_op_linear(int device, int precision, int epilogue, const float* x, const 
         if (epilogue != EPI_STORE_F32 && !bias) fail(MI_ERR_INVALID, "bias is null");
         if (precision == MI_PRECISION_BF16X3) { op_linear_x3(device, epilogue, x, w, bias, out, m_rows, n, k); return; }
         DeviceGuard g(device);
-        OpScratch sc;
+        Scratch sc;
         const size_t mp = pad256(m_rows);
-        void* dx = sc.up(precision, x, m_rows, k, mp);
-        void* dw = sc.up(precision, w, n, k, n);
-        float* db = bias ? (float*)sc.up(MI_PRECISION_F32, bias, 1, n, 1) : nullptr;
+        void* dx = op_up(sc, precision, x, m_rows, k, mp);
+        void* dw = op_up(sc, precision, w, n, k, n);
+        float* db = bias ? (float*)op_up(sc, MI_PRECISION_F32, bias, 1, n, 1) : nullptr;
         const bool f32_out = epilogue == EPI_STORE_F32 || epilogue == EPI_BIAS_RESID;
-        void* dout = f32_out ? sc.up(MI_PRECISION_F32, out, m_rows, n, mp) : sc.bytes(mp * n * 4);
+        void* dout = f32_out ? op_up(sc, MI_PRECISION_F32, out, m_rows, n, mp) : op_bytes(sc, mp * n * 4);
         // same dispatcher as the tower (persistent 256x256 kernel when the shape allows);
         // MI_OP_GRID overrides the CU count so that small test shapes exercise several tiles
         // per workgroup and the split last round
@@ -1540,7 +1479,7 @@ int mi_op_linear(int device, int precision, int epilogue, const float* x, const 
             default: fail(MI_ERR_INVALID, "epilogue %d", epilogue);
         }
         HIP_CHECK(hipDeviceSynchronize());
-        sc.down(f32_out ? MI_PRECISION_F32 : precision, dout, out, m_rows * n);
+        op_down(f32_out ? MI_PRECISION_F32 : precision, dout, out, m_rows * n);
     });
 }
 
@@ -1566,20 +1505,20 @@ int mi_op_linear_lnf(int device, int epilogue, const float* x, const float* w, c
         const size_t mp = pad256(m_rows);
         if (!pp_shape_ok(mp, n, k, n)) fail(MI_ERR_UNSUPPORTED, "shape [%zu x %d x %d] is not one of the persistent GEMM's", m_rows, n, k);
         DeviceGuard g(device);
-        OpScratch sc;
-        void* dx = sc.up(MI_PRECISION_BF16, x, m_rows, k, mp);
-        void* dw = sc.up(MI_PRECISION_BF16, w, n, k, n);
-        float* db = (float*)sc.up(MI_PRECISION_F32, bias, 1, n, 1);
+        Scratch sc;
+        void* dx = op_up(sc, MI_PRECISION_BF16, x, m_rows, k, mp);
+        void* dw = op_up(sc, MI_PRECISION_BF16, w, n, k, n);
+        float* db = (float*)op_up(sc, MI_PRECISION_F32, bias, 1, n, 1);
         PpFold f;
-        f.cvec = (float*)sc.up(MI_PRECISION_F32, c, 1, n, 1);
-        f.stats = (float*)sc.up(MI_PRECISION_F32, stats, m_rows, 2, mp);
-        void* dout = sc.bytes(mp * n * 2);
+        f.cvec = (float*)op_up(sc, MI_PRECISION_F32, c, 1, n, 1);
+        f.stats = (float*)op_up(sc, MI_PRECISION_F32, stats, m_rows, 2, mp);
+        void* dout = op_bytes(sc, mp * n * 2);
         mi_clip mm;
         op_pp_model(mm, device);
         if (epilogue == EPI_LNF) launch_pp<EPI_LNF>(&mm, dx, dw, db, dout, mp, n, k, n, f, nullptr);
         else launch_pp<EPI_LNF_QGELU>(&mm, dx, dw, db, dout, mp, n, k, n, f, nullptr);
         HIP_CHECK(hipDeviceSynchronize());
-        sc.down(MI_PRECISION_BF16, dout, out, m_rows * n);
+        op_down(MI_PRECISION_BF16, dout, out, m_rows * n);
     });
 }
 
@@ -1591,10 +1530,10 @@ int mi_op_linear_resid24(int device, const float* x, const float* w, const float
         if (!pp_shape_ok(mp, n, k, n) || mp * (size_t)(n / 32) * 8 >= (1ull << 32))
             fail(MI_ERR_UNSUPPORTED, "shape [%zu x %d x %d] is not one of the persistent GEMM's", m_rows, n, k);
         DeviceGuard g(device);
-        OpScratch sc;
-        void* dx = sc.up(MI_PRECISION_BF16, x, m_rows, k, mp);
-        void* dw = sc.up(MI_PRECISION_BF16, w, n, k, n);
-        float* db = (float*)sc.up(MI_PRECISION_F32, bias, 1, n, 1);
+        Scratch sc;
+        void* dx = op_up(sc, MI_PRECISION_BF16, x, m_rows, k, mp);
+        void* dw = op_up(sc, MI_PRECISION_BF16, w, n, k, n);
+        float* db = (float*)op_up(sc, MI_PRECISION_F32, bias, 1, n, 1);
         // the residual rows as the two planes: b' = bits + 0x8080, hi = b' >> 16, lo = (b' >> 8) & 0xFF; padding rows = 0.0
         const size_t cnt = mp * (size_t)n;
         std::vector<uint16_t> hi(cnt, 0);
@@ -1606,15 +1545,15 @@ int mi_op_linear_resid24(int device, const float* x, const float* w, const float
             hi[i] = (uint16_t)(u >> 16);
             lo[i] = (uint8_t)(u >> 8);
         }
-        uint16_t* dhi = (uint16_t*)sc.bytes(cnt * 2);
-        uint8_t* dlo = (uint8_t*)sc.bytes(cnt);
+        uint16_t* dhi = (uint16_t*)op_bytes(sc, cnt * 2);
+        uint8_t* dlo = (uint8_t*)op_bytes(sc, cnt);
         HIP_CHECK(hipMemcpy(dhi, hi.data(), cnt * 2, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(dlo, lo.data(), cnt, hipMemcpyHostToDevice));
         const int nb = n / 32;
         PpFold f;
         f.xlo = dlo;
-        f.part = (float*)sc.bytes(mp * nb * 8);
-        float* dstats = (float*)sc.bytes(mp * 8);
+        f.part = (float*)op_bytes(sc, mp * nb * 8);
+        float* dstats = (float*)op_bytes(sc, mp * 8);
         mi_clip mm;
         op_pp_model(mm, device);
         launch_pp<EPI_RESID24>(&mm, dx, dw, db, dhi, mp, n, k, n, f, nullptr);
@@ -1639,7 +1578,7 @@ int mi_op_attention(int device, int precision, const float* qkv, float* ctx, siz
         if (d != heads * 64) fail(MI_ERR_UNSUPPORTED, "head_dim must be 64");
         if (precision == MI_PRECISION_BF16X3) fail(MI_ERR_UNSUPPORTED, "no attention op for MI_PRECISION_BF16X3 (the tower's is the fp32 kernel)");
         DeviceGuard g(device);
-        OpScratch sc;
+        Scratch sc;
         mi_clip m;
         m.precision = precision; m.S = s_tok; m.D = d; m.H = heads;
         if (const char* e = std::getenv("MI_OP_ATTN")) m.attn_ver = std::atoi(e) == 1 ? 1 : 2;   // test hook: which bf16 kernel
@@ -1648,14 +1587,14 @@ int mi_op_attention(int device, int precision, const float* qkv, float* ctx, siz
         if (const char* e = std::getenv("MI_OP_ATTN_NT")) m.attn_nt = std::atoi(e) != 0;         // test hook: cache policy of the K / V / q stream
         if (const char* e = std::getenv("MI_OP_ATTN_F32_MFMA")) m.attn_f32_mfma = std::atoi(e) != 0;   // test hook: 0 = the one-thread-per-query fp32 kernel
         const size_t rows = n_img * s_tok;
-        void* dq = sc.up(precision, qkv, rows, 3 * (size_t)d, pad256(rows));
-        void* dc = sc.bytes(pad256(rows) * d * 4);
+        void* dq = op_up(sc, precision, qkv, rows, 3 * (size_t)d, pad256(rows));
+        void* dc = op_bytes(sc, pad256(rows) * d * 4);
         int ldq = 3 * d;
         if (const char* e = std::getenv("MI_OP_ATTN_QKV_PAD")) {   // test hook: the padded row pitch the tower gives q|k|v where attn32 runs
             const int pad = std::atoi(e);
             if (pad > 0 && attn32_applies(&m)) {
                 ldq = 3 * d + pad;
-                void* padded = sc.bytes(pad256(rows) * (size_t)ldq * 2);
+                void* padded = op_bytes(sc, pad256(rows) * (size_t)ldq * 2);
                 HIP_CHECK(hipMemset(padded, 0xFF, pad256(rows) * (size_t)ldq * 2));   // NaN patterns between the rows: a stray read shows
                 HIP_CHECK(hipMemcpy2D(padded, (size_t)ldq * 2, dq, (size_t)3 * d * 2, (size_t)3 * d * 2, rows, hipMemcpyDeviceToDevice));
                 dq = padded;
@@ -1671,13 +1610,13 @@ int mi_op_attention(int device, int precision, const float* qkv, float* ctx, siz
                         const size_t sel = c / d, hh = (c % d) / 64, el = c % 64;
                         planes[((sel * heads + hh) * hm_rows + r) * 64 + el] = f32_to_bf16_host(qkv[r * 3 * (size_t)d + c]);
                     }
-                dq = sc.bytes(planes.size() * 2);
+                dq = op_bytes(sc, planes.size() * 2);
                 HIP_CHECK(hipMemcpy(dq, planes.data(), planes.size() * 2, hipMemcpyHostToDevice));
             }
         }
         attention(&m, dq, dc, n_img, nullptr, false, ldq, hm_rows);
         HIP_CHECK(hipDeviceSynchronize());
-        sc.down(precision, dc, ctx, rows * d);
+        op_down(precision, dc, ctx, rows * d);
     });
 }
 
@@ -1685,14 +1624,12 @@ int mi_op_clock_probe(int device, void* stream, float* mhz) {
     return guarded([&] {
         if (!mhz) fail(MI_ERR_INVALID, "null argument");
         DeviceGuard g(device);
-        unsigned long long* d = nullptr;
-        HIP_CHECK(hipMalloc((void**)&d, 4 * sizeof(unsigned long long)));
+        Scratch sc;
+        unsigned long long* d = (unsigned long long*)sc.get(4 * sizeof(unsigned long long));
         hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d);
         unsigned long long h[4] = {0, 0, 0, 0};
-        const hipError_t e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, (hipStream_t)stream);
-        const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize((hipStream_t)stream) : e;
-        (void)hipFree(d);
-        HIP_CHECK(e2);
+        HIP_CHECK(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
         *mhz = h[1] ? (float)((double)h[0] / (double)h[1] * 100.0) : 0.0f;  // shader cycles per 100 MHz reference tick
     });
 }
@@ -1703,16 +1640,16 @@ int mi_op_layernorm(int device, int precision, const float* x, const float* w, c
         if (!x || !w || !b || !y) fail(MI_ERR_INVALID, "null buffer");
         if (precision == MI_PRECISION_BF16X3) fail(MI_ERR_UNSUPPORTED, "no LayerNorm op for MI_PRECISION_BF16X3");
         DeviceGuard g(device);
-        OpScratch sc;
+        Scratch sc;
         mi_clip m;
         m.precision = precision; m.D = d; m.eps = eps;
-        float* dx = (float*)sc.up(MI_PRECISION_F32, x, rows, d, rows);
-        float* dw = (float*)sc.up(MI_PRECISION_F32, w, 1, d, 1);
-        float* db = (float*)sc.up(MI_PRECISION_F32, b, 1, d, 1);
-        void* dy = sc.bytes(rows * d * 4);
+        float* dx = (float*)op_up(sc, MI_PRECISION_F32, x, rows, d, rows);
+        float* dw = (float*)op_up(sc, MI_PRECISION_F32, w, 1, d, 1);
+        float* db = (float*)op_up(sc, MI_PRECISION_F32, b, 1, d, 1);
+        void* dy = op_bytes(sc, rows * d * 4);
         layer_norm(&m, dx, nullptr, nullptr, true, dy, dw, db, rows, nullptr);
         HIP_CHECK(hipDeviceSynchronize());
-        sc.down(precision, dy, y, rows * d);
+        op_down(precision, dy, y, rows * d);
     });
 }
 
